@@ -2,8 +2,15 @@
 """bench.py -- headline benchmark: 2-opt delta evaluations per second and wall-clock to the
 2-opt local optimum on the n=4096 uniform-random EUC_2D instance (BASELINE.json `metric`).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints one short JSON line (the headline figures below).
+--dump-outputs DIR writes what the last timed step computed (rank 0): DIR/path.npy (the local optimum's successor
+array; N > 1: the winner after the exchange), DIR/cost.npy (its tour cost) and DIR/sweeps.npy (sweeps of rank 0's
+descent), all float64 -- 8(n + 2) bytes, far below 64 MB at any n the engine takes.  The instance is drawn from
+(--n, --seed) with the reference's generator, so the same arguments give the same inputs in every run.
+--full adds everything else the line used to carry: the parity gate and the auxiliary legs listed below.
 
 One STEP = one full best-improvement 2-opt local search on the device: the nearest-
 neighbour tour (already resident in HBM, next to the cost matrix) is copied into a work
@@ -19,7 +26,7 @@ clock after tsp_compute_costs) and SURVEY 8(d).
                  h_greedy_2opt, heuristics.c:82-111, sharded), then ONE RCCL MIN
                  all-reduce picks the best tour and its owner broadcasts it (4n bytes).
 
-Objects on the same JSON line (rank 0; the auxiliary legs run after the timed region):
+Objects on the same JSON line with --full (rank 0; the auxiliary legs run after the timed region):
   roofline               dominant kernel (the sweep): algorithmic bytes per launch / mean launch duration from HIP events
                          on the engine's stream, against the 8 TB/s HBM peak
   roofline_build         K1 (k_build_costs): bytes stored / launch duration against the same peak
@@ -250,26 +257,46 @@ def main():
     ap.add_argument("--no-otf", action="store_true", help="skip the matrix-free (pla85900) leg")
     ap.add_argument("--no-cpu-multistart", action="store_true", help="skip the all-cores CPU multi-start baseline")
     ap.add_argument("--no-host-c", action="store_true", help="skip the `tsp` binary (C host layer, multi-device) leg")
-    ap.add_argument("--lean", action="store_true", help="headline + roofline only (profiling runs)")
+    ap.add_argument("--lean", action="store_true", help="--full with the headline's rooflines only (profiling runs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the parity gate, the rooflines and the auxiliary legs (the options above select among them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float64)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.lean:
+        args.full = True
         args.no_other = args.no_sizes = args.no_otf = args.no_cpu_multistart = args.no_host_c = True
         args.cpu_sweeps = 0
         args.batch_starts = 0
     if args.job_starts is None:
         args.job_starts = 0 if args.lean else 512
 
-    draw_points([(args.n, args.seed), (1024, 1), (16384, 123), (1024, 123), (3584, 123), (4096, 123)])
-    global _VNS_RAND
-    _VNS_RAND = libc_rand_values(1, 64 * 1000 + 4096)          # the VNS leg's numbers: also before HIP is initialised
-    import torch
-    import torch.distributed as dist
-    import travellingsalesmanoptimization_amd as T
-    from travellingsalesmanoptimization_amd import multistart
-
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
+
+    if args.full:
+        draw_points([(args.n, args.seed), (1024, 1), (16384, 123), (1024, 123), (3584, 123), (4096, 123)])
+        global _VNS_RAND
+        _VNS_RAND = libc_rand_values(1, 64 * 1000 + 4096)      # the VNS leg's numbers: also before HIP is initialised
+    else:
+        draw_points([(args.n, args.seed)])
+    import travellingsalesmanoptimization_amd as T
+    # torch is the process group of N > 1 and the device synchronise of the --full legs.  A plain single-rank run does
+    # not import it: every engine call on its path ends in a synchronise of the engine's stream (build_costs,
+    # tour_two_opt's sweep count, tour_store's read-back), so the host clock around the steps needs nothing more.
+    use_torch = world > 1 or args.full
+    if use_torch:
+        import torch
+        import torch.distributed as dist
+        from travellingsalesmanoptimization_amd import multistart
+
+    def device_sync():
+        if use_torch:
+            torch.cuda.synchronize()
+
     if world > 1:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         torch.cuda.set_device(local % max(torch.cuda.device_count(), 1))
@@ -278,9 +305,9 @@ def main():
         dist.init_process_group(os.environ.get("TSPGPU_BENCH_BACKEND", "nccl"))
     assert world == args.gpus, f"--gpus {args.gpus} but WORLD_SIZE={world}"
     backend = dist.get_backend() if world > 1 else None
-    local = local % max(torch.cuda.device_count(), 1)
-    dev = torch.device("cuda", local) if backend != "gloo" else torch.device("cpu")
-    aux = rank == 0 and world == 1          # the auxiliary single-GPU legs
+    local = local % max(int(T._lib.load().tspgpu_device_count()), 1)
+    dev = (torch.device("cuda", local) if backend != "gloo" else torch.device("cpu")) if use_torch else None
+    aux = rank == 0 and world == 1 and args.full          # the auxiliary single-GPU legs
 
     ELEMS = {"auto": T.ELEM_AUTO, "u16": T.ELEM_U16, "i32": T.ELEM_I32, "f64": T.ELEM_F64}
     NAMES = {T.ELEM_U16: "u16", T.ELEM_I32: "i32", T.ELEM_F64: "f64"}
@@ -504,9 +531,9 @@ def main():
     xy = reference_points(n, seed)
     eng.set_points(xy)
     eng.build_costs()
-    broof = build_roofline(eng) if rank == 0 else None
+    broof = build_roofline(eng) if rank == 0 and args.full else None
     start = rank % n                       # rank r = the r-th iteration of h_greedy_2opt's loop
-    torch.cuda.synchronize()
+    device_sync()
     t0 = time.perf_counter()
     eng.tour_nn(0, start)
     _, nn_cost, _ = eng.tour_store(0, want_path=False)
@@ -521,7 +548,7 @@ def main():
     def sync_all():
         if world > 1:
             dist.barrier()
-        torch.cuda.synchronize()
+        device_sync()
 
     for _ in range(args.warmup):
         step()
@@ -529,14 +556,21 @@ def main():
     t0 = time.perf_counter()
     my_sweeps = 0
     for _ in range(args.steps):
-        my_sweeps += step()
+        last_sweeps = step()
+        my_sweeps += last_sweeps
         if world > 1:
             # the exchange step of the sharded multi-start: one MIN all-reduce + winner broadcast
             path, cost, _ = eng.tour_store(1)
-            multistart.select_best(cost, start, path, device=dev)
+            best = multistart.select_best(cost, start, path, device=dev)
     sync_all()
     dt = time.perf_counter() - t0
     path, final_cost, _ = eng.tour_store(1)
+
+    if args.dump_outputs and rank == 0:
+        out_cost, out_path = (best[0], best[2]) if world > 1 else (final_cost, path)
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in (("path", out_path), ("cost", [out_cost]), ("sweeps", [last_sweeps])):
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), np.asarray(a, dtype=np.float64))
 
     tot_sweeps, tmax = my_sweeps, dt
     if world > 1:
@@ -547,7 +581,7 @@ def main():
         tmax, tot_sweeps = float(t.item()), int(s.item())
 
     info_main = eng.info()                 # (the path the timed steps took)
-    gate = parity(n, seed, my_sweeps // max(args.steps, 1), final_cost, path) if rank == 0 and start == 0 else None
+    gate = parity(n, seed, my_sweeps // max(args.steps, 1), final_cost, path) if args.full and rank == 0 and start == 0 else None
     if gate and gate.get("golden") and not gate["ok"]:
         raise SystemExit(f"parity gate failed: {gate}")        # a fast kernel whose result differs is not a result
 
@@ -556,7 +590,7 @@ def main():
     # shard one batched call of the HIP engine, ONE MIN all-reduce + ONE broadcast (RCCL) to select the winner.  Timed at
     # every N including 1, so the driver's N = 1, 2, 4, 8 runs give the strong-scaling curve of the same job.
     job = None
-    if args.job_starts > 0:
+    if args.full and args.job_starts > 0:
         jstarts = np.arange(min(args.job_starts, n), dtype=np.int32)
 
         def solve_local(mine):
@@ -603,7 +637,7 @@ def main():
         eng.tour_nn(0, start)        # (the job used the slots: the legs below expect the NN tour in slot 0 again)
 
     roof = roof_fused = None
-    if rank == 0:
+    if rank == 0 and args.full:
         roof = timed_search(eng, evals)
         roof["kernel_ms_back_to_back"] = eng.time_sweep(1, 50)   # the sweep part alone (no move applied between launches)
         if eng.info().get("persist"):
@@ -856,7 +890,7 @@ def main():
     # ---- the drop-in binary: C host layer, multi-start sharded in C over the N devices of this run, RCCL exchange.
     # A child process (its own HIP context); at N > 1 the other ranks have left and released their devices.
     host_c = None
-    if not args.no_host_c:
+    if args.full and not args.no_host_c:
         def host_c_leg():
             tsp = os.path.join(ROOT, "travellingsalesmanoptimization_amd", "host", "tsp")
             ndev = min(world, int(T._lib.load().tspgpu_device_count()))
@@ -913,7 +947,7 @@ def main():
                    "parallelism": f"multistart-shard{world}"},
         "wall_clock_to_local_optimum_ms": 1e3 * tmax / args.steps,
         "final_cost_rank0": final_cost, "nn_cost_rank0": nn_cost, "parity": gate,
-        "matrix_build_ms": broof["kernel_ms_mean"], "nn_tour_ms": nn_ms,
+        "matrix_build_ms": broof["kernel_ms_mean"] if broof else None, "nn_tour_ms": nn_ms,
         "roofline": roof, "roofline_one_launch_per_sweep": roof_fused, "roofline_build": broof, "cpu_baseline": base,
         "other_matrix_storage": other, "sizes": sizes, "multistart_batch": batch, "multistart_job": job, "otf": otf, "cpu_multistart_baseline": cpu_ms, "host_c_path": host_c,
         "tabu_walk": tabu, "vns_walk": vns, "config2_fnl4461": cfg2,

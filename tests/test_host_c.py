@@ -264,7 +264,7 @@ def test_bench_line_contract():
     """bench.py prints ONE JSON line carrying the driver's contract fields, the roofline object and
     the parity gate (final cost of the headline workload)"""
     import json, subprocess, sys
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--cpu-sweeps", "3",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--cpu-sweeps", "3",
                           "--no-other", "--batch-starts", "8", "--job-starts", "16", "--no-sizes", "--no-otf", "--no-cpu-multistart", "--no-host-c"],
                          capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-2000:]
@@ -315,6 +315,31 @@ def test_bench_line_contract():
 
 
 @pytest.mark.gpu
+def test_bench_plain_run_and_dumped_outputs(tmp_path, O, golden):
+    """a plain run (no --full) times only the headline: one short JSON line with the driver's fields, no auxiliary leg;
+    --dump-outputs writes the last timed step's local optimum, which is the compiled reference's (golden n4096_s123)"""
+    import json, subprocess, sys
+    import numpy as np
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert out.returncode == 0, out.stderr[-2000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1 and len(lines[0]) < 4096, len(lines[0])
+    d = json.loads(lines[0])
+    assert d["steps"] == 3 and d["warmup"] == 1 and d["higher_is_better"] is True and d["unit"] == "evals/s"
+    assert d["metric"].startswith("2-opt delta evals/sec") and d["dtype"] == "uint16 costs, int32 deltas"
+    assert abs(d["value"] - 609 * 8382464 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-6
+    for k in ("parity", "roofline", "roofline_build", "cpu_baseline", "multistart_job", "multistart_batch", "sizes", "otf", "host_c_path"):
+        assert d[k] is None, k
+    g = golden["random"]["n4096_s123"]["two_opt"]
+    path, cost, sweeps = (np.load(tmp_path / f"{k}.npy") for k in ("path", "cost", "sweeps"))
+    assert path.dtype == cost.dtype == sweeps.dtype == np.float64 and path.shape == (4096,)
+    succ = path.astype(np.int32)
+    assert np.array_equal(succ, path) and O.valid_tour(succ) and f"{O.fnv1a(succ):016x}" == g["final_fnv"]
+    assert cost.tolist() == [g["final_cost"]] == [d["final_cost_rank0"]] and sweeps.tolist() == [g["sweeps"]]
+
+
+@pytest.mark.gpu
 def test_bench_two_ranks_gloo_on_one_gpu():
     """the N > 1 branch of bench.py (torch.distributed launch, barrier, per-step exchange, MAX over ranks,
     SUM of sweeps, rank 0's host_c_path leg) rehearsed as two gloo ranks sharing device 0 -- collectives on CPU tensors,
@@ -325,7 +350,7 @@ def test_bench_two_ranks_gloo_on_one_gpu():
         sk.bind(("127.0.0.1", 0)); port = sk.getsockname()[1]
     env = dict(os.environ, TSPGPU_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                          "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+                          "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "2", "--warmup", "1",
                           "--size", "1024", "--seed", "1"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert out.returncode == 0, (out.stdout[-1000:], out.stderr[-3000:])

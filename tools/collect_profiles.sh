@@ -6,10 +6,10 @@ set -o pipefail
 out=gpurun_out/${1:-prof}
 rm -rf "$out"; mkdir -p "$out"
 export TMPDIR=/tmp
-B="--cpu-sweeps 0 --no-other --batch-starts 0"
-timeout -k 10 300 python3 bench.py --steps 5 > "$out/bench_n4096.json" || exit 1
-timeout -k 10 200 python3 bench.py --n 1024 --steps 5 --cpu-sweeps 168 > "$out/bench_n1024.json" || exit 1
-timeout -k 10 400 python3 bench.py --n 16384 --steps 2 --warmup 1 --cpu-sweeps 25 --batch-starts 8 > "$out/bench_n16384.json" || exit 1
+B="--full --cpu-sweeps 0 --no-other --batch-starts 0"
+timeout -k 10 300 python3 bench.py --full --steps 5 > "$out/bench_n4096.json" || exit 1
+timeout -k 10 200 python3 bench.py --full --n 1024 --steps 5 --cpu-sweeps 168 > "$out/bench_n1024.json" || exit 1
+timeout -k 10 400 python3 bench.py --full --n 16384 --steps 2 --warmup 1 --cpu-sweeps 25 --batch-starts 8 > "$out/bench_n16384.json" || exit 1
 for tag in auto f64 i32 auto@16384; do
   e=${tag%@*}; n=4096; [[ $tag == *@* ]] && n=${tag#*@}
   st=3; [[ $n -gt 8000 ]] && st=1

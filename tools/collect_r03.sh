@@ -1,6 +1,6 @@
 #!/bin/bash
 # Runs ON THE GPU BOX (through gpurun): round 3's evidence --
-#   bench_default.json                      the default bench line (steps 20, warmup 5)
+#   bench_default.json                      the full bench line (--full, steps 20, warmup 5)
 #   trace_n4096 / trace_fnl4461             rocprofv3 --kernel-trace --stats of the headline (k_lds2opt) and of BASELINE config 3
 #                                           (k_lds2opt_w): ONE launch per descent
 #   fetch_* / write_*                       rocprofv3 --pmc FETCH_SIZE | WRITE_SIZE (separate passes, nothing else traced)
@@ -16,7 +16,7 @@ run() {   # name, then the rocprofv3 arguments
   echo "$name rc=$rc"
   if [ $rc -ge 124 ]; then echo "timeout/kill: stopping"; exit 1; fi
 }
-timeout -k 10 600 python3 bench.py --steps 20 --warmup 5 > "$out/bench_default.json" 2> "$out/bench_default.err" || { echo "bench failed"; tail -5 "$out/bench_default.err"; exit 1; }
+timeout -k 10 600 python3 bench.py --full --steps 20 --warmup 5 > "$out/bench_default.json" 2> "$out/bench_default.err" || { echo "bench failed"; tail -5 "$out/bench_default.err"; exit 1; }
 run trace_n4096 --kernel-trace --stats --output-format csv -d "$out/trace_n4096" -- python3 bench.py --steps 5 --warmup 1 --lean
 run trace_fnl4461 --kernel-trace --stats --output-format csv -d "$out/trace_fnl4461" -- python3 tools/run_instance.py fnl4461 5
 find "$out" -name "*_kernel_trace.csv" -delete

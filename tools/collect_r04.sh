@@ -1,6 +1,6 @@
 #!/bin/bash
 # Runs ON THE GPU BOX (through gpurun): round 4's evidence --
-#   bench_default.json                 the default bench line (steps 20, warmup 5)
+#   bench_default.json                 the full bench line (--full, steps 20, warmup 5)
 #   trace_*                            rocprofv3 --kernel-trace --stats (kernel stats only) of: the headline (k_lds2opt, bench --lean),
 #                                      the batched multi-start n=4096 x 64 (k_sweep_pipe), the streamed persistent descent at
 #                                      n = 5600 / 8192 (k_str2opt), pla85900 matrix-free (k_sweep_otf8: the final kernel)
@@ -17,7 +17,7 @@ run() {   # name, then the rocprofv3 arguments
   echo "$name rc=$rc"
   if [ $rc -ge 124 ]; then echo "timeout/kill: stopping"; exit 1; fi
 }
-timeout -k 10 600 python3 bench.py --steps 20 --warmup 5 > "$out/bench_default.json" 2> "$out/bench_default.err" || { echo "bench failed"; tail -5 "$out/bench_default.err"; exit 1; }
+timeout -k 10 600 python3 bench.py --full --steps 20 --warmup 5 > "$out/bench_default.json" 2> "$out/bench_default.err" || { echo "bench failed"; tail -5 "$out/bench_default.err"; exit 1; }
 run trace_n4096 --kernel-trace --stats --output-format csv -d "$out/trace_n4096" -- python3 bench.py --steps 5 --warmup 1 --lean
 run trace_batch --kernel-trace --stats --output-format csv -d "$out/trace_batch" -- python3 tools/multistart_rate.py n4096 64
 run trace_n5600 --kernel-trace --stats --output-format csv -d "$out/trace_n5600" -- python3 tools/run_instance.py 5600 3
