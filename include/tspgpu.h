@@ -57,8 +57,10 @@ enum {
     TSPGPU_OPT_DEPTH = 10,      /* matrix rows in flight per workgroup in the pipelined sweep (0 = auto) */
     TSPGPU_OPT_FUSED = 12,      /* one launch per sweep (resident kernel): 1 (default) when <= 4 tours are in flight,
                                    2 always, 0 never (separate sweep + apply launches) */
-    TSPGPU_OPT_MATRIX_FREE = 11,/* 0 auto (matrix-free when a matrix row cannot sit in LDS), 1 always, 2 never;
-                                   takes effect at the next tspgpu_build_costs */
+    TSPGPU_OPT_MATRIX_FREE = 11,/* 0 auto (matrix-free when a matrix row cannot sit in LDS or n exceeds the matrix-mode
+                                   limit of 65 536 nodes), 1 always, 2 never (tspgpu_build_costs then fails with code 8
+                                   past either limit, before any matrix is allocated); takes effect at the next
+                                   tspgpu_build_costs.  Matrix-free mode needs costs below 2^27 (else code 8) and n <= 131 072 */
     TSPGPU_OPT_PIPE2 = 15,      /* one-launch-per-sweep kernel over streamed rows: 1 (default) two tour edges per barrier
                                    interval where four rows fit LDS, 0 one edge per barrier over three row buffers */
     TSPGPU_OPT_NN_KERNEL = 14,  /* nearest-neighbour construction: 0 auto (the grid kernel whenever the weights come from
@@ -103,7 +105,10 @@ int  tspgpu_set_option(tspgpu_ctx *ctx, int option, long value);
  * single-tour descent began LDS-resident and was finished one launch per sweep (the grid lost its co-residency), 22 sweeps run by the last
  * LDS-resident descent / tabu walk / VNS walk, 23 how the last tspgpu_vns_search ran (1 resident throughout, 2 one device local
  * search per iteration with the kicks on the host, 3 resident launches first, then -- the grid lost its co-residency -- host kicks),
- * 24 the last single-tour descent ran in the streamed persistent kernel (TSPGPU_OPT_STREAM_PERSIST) */
+ * 24 the last single-tour descent ran in the streamed persistent kernel (TSPGPU_OPT_STREAM_PERSIST), 25 the matrix-free sweep
+ * kernel of the current plan (0 not matrix-free / no plan yet, 1 k_sweep_otf: costs from 2^25 or n = 131 072, 2 k_sweep_otf8,
+ * 3 k_sweep_otf8 with the exact early-out), 26 CEIL_2D weights come from the exact integer ceil-sqrt of integer coordinates
+ * (cost bound below 2^22; 0: the generic double form, or another kind) */
 long tspgpu_info(const tspgpu_ctx *ctx, int what);
 
 /* ---- instance / cost matrix ------------------------------------------- */

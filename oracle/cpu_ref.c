@@ -423,18 +423,40 @@ double orc_two_opt_scan_xy(const double *xy, int n, int kind, const int *succ, i
     return best;
 }
 
+/* one pair's delta, the arithmetic of the scan above (kept = c[a][succ a] + c[b][succ b], made = c[a][b] + c[succ a][succ b],
+ * delta = made - kept); a and b as the scan orders them (a < b) */
+double orc_move_delta_xy(const double *xy, int n, int kind, const int *succ, int a, int b)
+{
+    (void)n;
+    const int sa = succ[a], sb = succ[b];
+    const double kept = edge_weight(xy[2 * a], xy[2 * a + 1], xy[2 * sa], xy[2 * sa + 1], kind) +
+                        edge_weight(xy[2 * b], xy[2 * b + 1], xy[2 * sb], xy[2 * sb + 1], kind);
+    const double made = edge_weight(xy[2 * a], xy[2 * a + 1], xy[2 * b], xy[2 * b + 1], kind) +
+                        edge_weight(xy[2 * sa], xy[2 * sa + 1], xy[2 * sb], xy[2 * sb + 1], kind);
+    return made - kept;
+}
+
+/* the move (a, b) as ref_2opt_once applies its choice (refinment.c:71-91): prev is filled from succ when NULL, else it must
+ * be succ's inverse and is kept so.  Returns the number of nodes whose order it reversed. */
+int orc_apply_move(int *succ, int *prev, int n, int a, int b)
+{
+    int *p = prev ? prev : (int *)malloc(sizeof(int) * (size_t)n);
+    if (!prev) fill_prev(succ, n, p);
+    int len = 1;                                  /* nodes on the reversed path succ a .. b */
+    for (int cur = b; cur != succ[a] && len <= n; cur = p[cur]) len++;
+    orc_reverse_path(a, succ[a], b, succ[b], p, succ, n);
+    if (!prev) free(p);
+    return len;
+}
+
 double orc_two_opt_once_xy(const double *xy, int n, int kind, int *succ, double *cost, int *move_ab)
 {
     int ab[2];
     const double best = orc_two_opt_scan_xy(xy, n, kind, succ, 0, n - 1, ab);
-    const int ba = ab[0], bb = ab[1];
-    if (move_ab) { move_ab[0] = ba; move_ab[1] = bb; }
+    if (move_ab) { move_ab[0] = ab[0]; move_ab[1] = ab[1]; }
     if (best < ORC_EPS) {
-        int *prev = (int *)malloc(sizeof(int) * (size_t)n);
-        fill_prev(succ, n, prev);
-        orc_reverse_path(ba, succ[ba], bb, succ[bb], prev, succ, n);
+        orc_apply_move(succ, NULL, n, ab[0], ab[1]);
         *cost += best;
-        free(prev);
     }
     return best;
 }

@@ -97,6 +97,12 @@ double orc_two_opt_once_xy(const double *xy, int n, int kind, int *succ, double 
 /* the scan of one sweep for a in [a_lo, a_hi), read-only (refinment.c:49-69) */
 double orc_two_opt_scan_xy(const double *xy, int n, int kind, const int *succ, int a_lo, int a_hi, int *move_ab);
 
+/* one pair's delta, computed as orc_two_opt_scan_xy computes it (made - kept) */
+double orc_move_delta_xy(const double *xy, int n, int kind, const int *succ, int a, int b);
+/* applies the move (a, b) exactly as orc_two_opt_once_xy applies its choice; prev: succ's inverse (kept so), or NULL;
+ * returns the length of the reversed path */
+int orc_apply_move(int *succ, int *prev, int n, int a, int b);
+
 /* src/tsp.c:642-667 + :687-728  tsp_validate_solution / tsp_is_tour. */
 int orc_valid_tour(const int *succ, int n);
 

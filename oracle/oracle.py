@@ -63,6 +63,9 @@ def lib():
         L.orc_two_opt_once_xy.restype = C.c_double
         L.orc_two_opt_scan_xy.argtypes = [_dp, C.c_int, C.c_int, _ip, C.c_int, C.c_int, _ip]
         L.orc_two_opt_scan_xy.restype = C.c_double
+        L.orc_move_delta_xy.argtypes = [_dp, C.c_int, C.c_int, _ip, C.c_int, C.c_int]
+        L.orc_move_delta_xy.restype = C.c_double
+        L.orc_apply_move.argtypes = [_ip, C.c_void_p, C.c_int, C.c_int, C.c_int]
         L.orc_valid_tour.argtypes = [_ip, C.c_int]
         L.orc_fnv1a.argtypes = [_ip, C.c_int]
         L.orc_fnv1a.restype = C.c_uint64
@@ -238,6 +241,65 @@ def two_opt_best_move_xy(xy, kind, succ, threads=8):
         if d < best[0]:
             best = (d, a, b)
     return best[0], (best[1], best[2])
+
+
+def move_delta_xy(xy, kind, succ, a, b):
+    """the delta of the move (a, b) on the tour succ, computed as the scan of two_opt_once_xy computes it"""
+    xy = np.ascontiguousarray(xy, dtype=np.float64).reshape(-1)
+    return lib().orc_move_delta_xy(xy, len(xy) // 2, kind, np.ascontiguousarray(succ, np.int32), int(a), int(b))
+
+
+def apply_move(succ, prev, a, b):
+    """In-place on succ (int32, contiguous): the move (a, b) as two_opt_once_xy applies its choice.  prev: succ's inverse,
+    kept so (or None: filled for this call).  Returns the number of nodes on the reversed path."""
+    assert succ.dtype == np.int32 and succ.flags.c_contiguous
+    if prev is not None:
+        assert prev.dtype == np.int32 and prev.flags.c_contiguous and len(prev) == len(succ)
+    return lib().orc_apply_move(succ, None if prev is None else prev.ctypes.data, len(succ), int(a), int(b))
+
+
+def replay(xy, kind, succ0, cost0, hist, checkpoints=(), final=None, threads=16, keep=()):
+    """Walk an engine history of (a, b, delta) -- one entry per sweep, (-1, -1, .) for a sweep that found nothing, which
+    can only be the last -- from (succ0, cost0) with the oracle, and check it:
+      - every move's delta equals move_delta_xy of that pair on the current tour, bit for bit, and improves;
+      - at each checkpoint sweep k, two_opt_best_move_xy of the current tour is the engine's move k: the same pair under
+        the reference's tie order and the same delta (a no-move entry: the oracle finds nothing either);
+      - the running cost equals tour_cost_xy at the end; and the final tour equals `final` when given.
+    keep: sweep indices whose tours (before that sweep's move) are returned.  Returns (succ, cost, {k: tour}, lens) with
+    lens[k] the length of move k's reversed path."""
+    ha, hb, hd = (np.asarray(v) for v in hist)
+    m = len(ha)
+    assert len(hb) == m and len(hd) == m
+    cps, keep = set(int(k) for k in checkpoints), set(int(k) for k in keep)
+    assert all(0 <= k < m for k in cps), (sorted(cps), m)
+    succ = np.array(succ0, dtype=np.int32)
+    prev = np.empty_like(succ)
+    prev[succ] = np.arange(len(succ), dtype=np.int32)
+    cost, kept, lens = float(cost0), {}, []
+    for k in range(m):
+        a, b, d = int(ha[k]), int(hb[k]), float(hd[k])
+        if k in keep:
+            kept[k] = succ.copy()
+        if a < 0:
+            assert k == m - 1 and b < 0 and d >= -1e-7, ("a no-move entry before the end", k, a, b, d)
+            if k in cps:
+                od, omv = two_opt_best_move_xy(xy, kind, succ, threads)
+                assert od >= -1e-7, ("the oracle still improves where the engine stopped", k, od, omv)
+            break
+        lo, hi = min(a, b), max(a, b)
+        assert 0 <= lo < hi < len(succ) and succ[lo] != hi and succ[hi] != lo and succ[lo] != succ[hi], \
+            ("degenerate pair", k, lo, hi)
+        od = move_delta_xy(xy, kind, succ, lo, hi)
+        assert od == d and d < -1e-7, ("delta", k, lo, hi, d, od)
+        if k in cps:
+            bd, bmv = two_opt_best_move_xy(xy, kind, succ, threads)
+            assert (bd, bmv) == (d, (lo, hi)), ("checkpoint", k, (d, lo, hi), (bd, bmv))
+        lens.append(apply_move(succ, prev, lo, hi))
+        cost += d
+    assert cost == tour_cost_xy(xy, kind, succ), ("running cost", cost, tour_cost_xy(xy, kind, succ))
+    if final is not None:
+        assert np.array_equal(succ, np.asarray(final, dtype=np.int32)), "final tour"
+    return succ, cost, kept, lens
 
 
 def valid_tour(succ):

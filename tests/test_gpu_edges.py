@@ -1,0 +1,470 @@
+"""The sweep kernels where they change representation, and deep in the two large descents (on an MI355X).
+
+- weight width: instances whose bounding box puts cost_bound (include/tspgpu.h: the largest weight the points can
+  produce) on each side of every threshold the engine switches at -- 65 534 (uint16 -> int32 cells), 2^22 (CEIL_2D's
+  integer ceil-sqrt -> the generic double form), 2^25 (k_sweep_otf8 -> k_sweep_otf), 2^27 (int32 -> f64 cells; the
+  matrix-free mode refuses) -- through every path that admits them, move by move against the oracle;
+- label width: n = 65 535 / 65 536 (the largest matrix-mode instances), n past 65 536 in the automatic mode, n = 131 071 /
+  131 072 at the top of the matrix-free 17-bit labels and of the NN grid's 32-bit key, n = 131 073 refused;
+- the whole descents of BASELINE configs 4 (d18512) and 5 (pla85900), replayed move by move with oracle scans at
+  checkpoints (oracle.replay).
+Every expectation comes from the oracle (oracle/) or from tests/golden."""
+import ctypes
+import json
+import math
+import os
+
+import numpy as np
+import pytest
+
+from conftest import GOLDEN_DIR, data_path
+
+pytestmark = pytest.mark.gpu
+
+U16_MAX, CEIL_INT_BOUND, OTF8_BOUND, I32_BOUND = 65534.0, 4194304.0, 33554432.0, 134217728.0
+
+
+@pytest.fixture(scope="module")
+def eng():
+    import travellingsalesmanoptimization_amd as T
+    e = T.Engine(0)
+    yield e
+    e.close()
+
+
+@pytest.fixture(scope="module")
+def T():
+    import travellingsalesmanoptimization_amd as T
+    return T
+
+
+@pytest.fixture
+def clean(eng, T):
+    """every test starts and ends on the engine's defaults"""
+    def reset():
+        for opt, v in ((T.OPT_ELEM, 0), (T.OPT_KERNEL, 0), (T.OPT_MATRIX_FREE, 0), (91, 0), (T.OPT_PERSIST, 1), (T.OPT_FUSED, 1),
+                       (T.OPT_HISTORY, 0), (T.OPT_SWEEP_CAP, -1), (T.OPT_PERSIST_WINDOW, 0)):
+            eng.set_option(opt, v)
+    reset()
+    yield eng
+    reset()
+
+
+def fx(O, v):
+    return f"{O.fnv1a(v):016x}"
+
+
+def _libc_draws(O, seed, count):
+    libc = ctypes.CDLL(None)
+    O.libc_srand(seed)
+    return np.array([libc.rand() for _ in range(count)], dtype=np.int32)
+
+
+def _cost_bound(xy, kind):
+    """the engine's cost_bound (tspgpu_set_points): the bounding box's diagonal (ATT: over sqrt 10) + 2"""
+    x0, y0 = xy.min(0)
+    x1, y1 = xy.max(0)
+    diag = math.sqrt((x1 - x0) * (x1 - x0) + (y1 - y0) * (y1 - y0))
+    return (diag / math.sqrt(10.0) if kind == 1 else diag) + 2.0
+
+
+def _history(eng, cap):
+    a, b, d = eng.history(cap)
+    return np.array(a), np.array(b), np.array(d)
+
+
+# ------------------------------------------------------------------ weight width
+# regime -> (threshold, side): cost_bound just below / just above it
+REGIMES = {"u16_top": (U16_MAX, -1), "i32_bottom": (U16_MAX, +1), "ceil_int_top": (CEIL_INT_BOUND, -1),
+           "ceil_generic": (CEIL_INT_BOUND, +1), "otf8_top": (OTF8_BOUND, -1), "otf_bottom": (OTF8_BOUND, +1),
+           "i32_top": (I32_BOUND, -1), "f64_bottom": (I32_BOUND, +1)}
+KINDS = ["EUC_2D", "CEIL_2D", "ATT"]
+
+
+def _edge_instance(inst, kind, regime):
+    """points whose cost_bound lies on the regime's side of its threshold, within a few units of it for the lattices and the
+    boxes (the corner-to-corner edge is a real weight of the instance)"""
+    thr, side = REGIMES[regime]
+    att = math.sqrt(10.0) if kind == 1 else 1.0
+    if side < 0:
+        want = (thr - 2.0 - (0.0 if thr == U16_MAX else 0.5)) * att       # u16: bound <= 65534; else bound < thr
+    else:
+        want = (thr - 2.0 + 0.5) * att
+    if inst in ("lattice", "lattice_frac"):        # grid20 scaled: ties everywhere, kept by the scaling
+        g = np.arange(20, dtype=np.float64)
+        base = np.stack(np.meshgrid(g, g), -1).reshape(-1, 2)
+        f = want / (19 * math.sqrt(2.0))
+        if inst == "lattice":
+            f = math.floor(f) if side < 0 else math.ceil(f)
+        else:
+            f = f * (1 - 1e-9) if side < 0 else f * (1 + 1e-9)
+        xy = base * f
+    elif inst == "dups":                           # every point twice + a collinear run, scaled by an integer
+        r = np.random.RandomState(9)
+        base = r.randint(0, 50, size=(150, 2)).astype(np.float64)
+        base = np.concatenate([base, base, np.stack([np.arange(60.0), np.zeros(60)], -1), [[0.0, 0.0], [59.0, 49.0]]])
+        d = math.hypot(59.0, 49.0)
+        f = math.floor(want / d) if side < 0 else math.ceil(want / d)
+        xy = base * f
+    else:                                          # a square box, corners included
+        s = want / math.sqrt(2.0)
+        if inst == "rand_int":                     # odd n
+            s = math.floor(s) if side < 0 else math.ceil(s)
+            r = np.random.RandomState(int(thr) % 1000 + 7)
+            xy = np.concatenate([[[0.0, 0.0], [s, s]], r.randint(0, int(s) + 1, size=(999, 2)).astype(np.float64)])
+        else:
+            s = s * (1 - 1e-9) if side < 0 else s * (1 + 1e-9)
+            r = np.random.RandomState(int(thr) % 1000 + 8)
+            xy = np.concatenate([[[0.0, 0.0], [s, s]], r.uniform(0, s, size=(698, 2))])
+    xy = np.ascontiguousarray(xy, dtype=np.float64)
+    b = _cost_bound(xy, kind)
+    assert (b <= thr if thr == U16_MAX else b < thr) if side < 0 else (b > thr if thr == U16_MAX else b >= thr), (inst, regime, b)
+    return xy
+
+
+def _edge_cases():
+    out = []
+    for i, regime in enumerate(REGIMES):
+        out += [(regime, "EUC_2D", "lattice"), (regime, "CEIL_2D", "rand_int"), (regime, "ATT", "rand_frac"),
+                (regime, KINDS[i % 3], "dups"), (regime, KINDS[(i + 1) % 3], "lattice_frac")]
+        if regime.startswith("ceil"):
+            out.append((regime, "CEIL_2D", "lattice"))          # the integer ceil-sqrt on both sides of 2^22, with ties
+    return out
+
+
+# path -> options (matrix paths: cells stored; matrix-free paths: weights from the points)
+PATHS = {"default": {}, "one_launch": {16: 0}, "split": {16: 0, 12: 0},
+         "mf_auto": {11: 1}, "mf_early_out": {11: 1, 91: 1}}
+
+
+@pytest.mark.parametrize("regime,kind,inst", _edge_cases())
+def test_weight_width_edges(clean, T, O, regime, kind, inst):
+    """one instance on one side of one threshold: on every admissible path the NN tour, every move of the 2-opt descent from
+    it, a 150-move tabu walk from the oracle's optimum -- against the oracle's matrix of the same kind --, info() naming the
+    storage and the sweep kernel that ran; one matrix-free VNS walk on the glibc stream; the matrix-free mode refuses past
+    2^27 with code 8"""
+    eng = clean
+    k = getattr(O, kind)
+    xy = _edge_instance(inst, k, regime)
+    n = len(xy)
+    bound = _cost_bound(xy, k)
+    c = O.cost_matrix(xy, k)
+    succ0, cost0 = O.nn_tour(c, 0)
+    want, succ, cost = [], succ0.copy(), cost0
+    while True:
+        d, cost, mv = O.two_opt_once(c, succ, cost)
+        want.append((mv[0], mv[1], d) if d < -1e-7 else None)
+        if d >= -1e-7:
+            break
+    opt, opt_cost = succ, cost
+    tabu_k = 150
+    otabu = O.tabu_search(c, opt.copy(), opt_cost, tabu_k)
+    elem = 3 if bound <= U16_MAX else 2 if bound < I32_BOUND else 1
+    ran = []
+    for path, opts in PATHS.items():
+        mf = path.startswith("mf")
+        for o, v in opts.items():
+            eng.set_option(o, v)
+        try:
+            eng.set_points(xy, k)
+            if mf and bound >= I32_BOUND:
+                with pytest.raises(T.TspGpuError) as ei:
+                    eng.build_costs()
+                assert ei.value.code == 8 and "2^27" in str(ei.value)
+                continue
+            eng.build_costs()
+            g, gcost = eng.nn_tour(0)
+            assert gcost == cost0 and np.array_equal(g, succ0), path
+            ceil_int = kind == "CEIL_2D" and inst in ("lattice", "rand_int", "dups") and bound < CEIL_INT_BOUND
+            assert eng.info()["ceil_int"] == int(ceil_int), (path, eng.info()["ceil_int"])    # which side of 2^22 ran
+            # the descent, every move
+            eng.set_option(T.OPT_HISTORY, 8192)
+            eng.tour_load(0, succ0)
+            sw, rc = eng.tour_two_opt(0)
+            ha, hb, hd = _history(eng, 8192)
+            got, gcost, _ = eng.tour_store(0)
+            eng.set_option(T.OPT_HISTORY, 0)
+            info = eng.info()
+            assert rc == 0 and sw == len(want), (path, sw, len(want))
+            for i, w in enumerate(want):
+                h = (int(min(ha[i], hb[i])), int(max(ha[i], hb[i])), float(hd[i]))
+                assert (w is None and h[0] == -1) or h == w, (path, i, h, w)
+            assert gcost == opt_cost and np.array_equal(got, opt), path
+            if mf:
+                otf = 1 if bound >= OTF8_BOUND else 3 if path == "mf_early_out" else 2
+                assert (info["matrix_free"], info["kernel"], info["otf_kernel"]) == (1, 4, otf), (path, info)
+            else:
+                assert info["matrix_free"] == 0 and info["elem"] == elem and info["otf_kernel"] == 0, (path, info)
+                if path == "default" and elem == 3:
+                    assert info["persist"] == 1, info          # k_lds2opt
+                if path == "split":
+                    assert info["fused"] == 0, info
+            # the tabu walk
+            s = opt.copy()
+            best, best_cost, final, trace = eng.tabu_search(s, opt_cost, tabu_k, want_trace=True)
+            bad = np.nonzero(trace != otabu[3])[0]
+            assert len(bad) == 0, (path, bad[:5], trace[bad[:5]], otabu[3][bad[:5]])
+            assert final == otabu[2] and best_cost == otabu[1] and np.array_equal(best, otabu[0]), path
+            if mf:
+                info = eng.info()
+                assert info["otf_kernel"] == (1 if bound >= OTF8_BOUND else 2), (path, info)   # the tabu form: never early-out
+            ran.append(path)
+        finally:
+            for o in opts:
+                eng.set_option(o, {16: 1, 12: 1, 11: 0, 91: 0}[o])
+    assert len(ran) == (3 if bound >= I32_BOUND else 5)
+    if bound >= I32_BOUND:
+        return
+    # one matrix-free VNS walk (mh_VNS's loop, host kicks) against the oracle on the glibc stream
+    vk = 6
+    eng.set_option(T.OPT_MATRIX_FREE, 1)
+    eng.set_points(xy, k); eng.build_costs()
+    rv = _libc_draws(O, 5, 64 * vk + 4096)
+    O.libc_srand(5)
+    s = succ0.copy()
+    obest, obc = O.vns(c, s, cost0, vk)
+    used = int(np.nonzero(rv == ctypes.CDLL(None).rand())[0][0])
+    path, best = succ0.copy(), succ0.copy()
+    r = eng.vns_search(path, vk, rv, best, cost0)
+    assert (r["rc"], r["iterations"], r["kick_pending"]) == (0, vk, 0)
+    assert r["best_cost"] == obc and np.array_equal(best, obest) and np.array_equal(path, s) and r["consumed"] == used
+    assert eng.info()["matrix_free"] == 1
+
+
+# ------------------------------------------------------------------ label width
+def _box(n, side, seed):
+    """n integer points in [0, side]^2 (corners included): EUC_2D bound = side * sqrt 2 + 2"""
+    r = np.random.RandomState(seed)
+    return np.ascontiguousarray(np.concatenate([[[0.0, 0.0], [side, side]], r.randint(0, side + 1, size=(n - 2, 2))]).astype(np.float64))
+
+
+@pytest.mark.parametrize("n", [65535, 65536])
+def test_matrix_mode_at_the_matrix_limit(clean, T, O, n):
+    """n = 65 535 / 65 536 with uint16 cells, the largest instances matrix mode takes.  A row is 128 KB: only the simple sweep
+    (k_sweep_simple, (a << 32 | b) keys) + k_apply plan there -- the packed 16-bit keys of the resident, pipelined and fused
+    forms are confined to the sizes whose rows they can hold.  From a random permutation (long, wrapping reversals) and from
+    NN(n-1), the engine's descents replayed against the oracle (every delta, the reference's best move at checkpoints); the
+    batched multi-start (6 tours in flight) records the same slot-0 history as the single tour"""
+    eng = clean
+    xy = _box(n, 40000, n)
+    eng.set_points(xy); eng.build_costs()
+    info = eng.info()
+    assert (info["matrix_free"], info["elem"], info["n"]) == (0, 3, n)
+    perm = np.random.RandomState(n + 1).permutation(n).astype(np.int32)
+    succ0 = np.empty(n, dtype=np.int32)
+    succ0[perm] = np.roll(perm, -1)
+    cost0 = O.tour_cost_xy(xy, O.EUC_2D, succ0)
+    eng.set_option(T.OPT_HISTORY, 8192)
+    eng.tour_load(0, succ0)
+    sw, rc = eng.tour_two_opt(0, max_sweeps=300)
+    hist = _history(eng, 8192)
+    got, gcost, _ = eng.tour_store(0)
+    assert rc == 0 and sw == 300 and len(hist[0]) == 300 and eng.info()["kernel"] == 1
+    assert max(hist[1].max(), hist[0].max()) >= 60000                  # labels in the top bits were chosen
+    _, cost, _, lens = O.replay(xy, O.EUC_2D, succ0, cost0, hist, checkpoints=(0, 1, 2, 3, 150, 299), final=got)
+    assert cost == gcost and max(lens) > n // 4
+    # NN(n-1): single tour, then the batch
+    eng.tour_nn(0, n - 1)
+    nn, nn_cost, _ = eng.tour_store(0)
+    assert O.valid_tour(nn) and O.tour_cost_xy(xy, O.EUC_2D, nn) == nn_cost
+    sw, rc = eng.tour_two_opt(0, max_sweeps=200)
+    single = _history(eng, 8192)
+    got, gcost, _ = eng.tour_store(0)
+    assert sw == 200 and len(single[0]) == 200
+    O.replay(xy, O.EUC_2D, nn, nn_cost, single, checkpoints=(0, 1, 199), final=got)
+    eng.set_option(T.OPT_SWEEP_CAP, 200)
+    starts = np.array([n - 1, 0, 1, 2, 3, n // 2], dtype=np.int32)
+    res = eng.multistart_nn_2opt(starts)
+    batch = _history(eng, 8192)
+    assert res["rc"] == 0 and eng.info()["kernel"] == 1
+    for x, y in zip(batch, single):
+        assert np.array_equal(x, y)
+    s0, c0, _ = eng.tour_store(0)
+    assert c0 == gcost and np.array_equal(s0, got)
+
+
+@pytest.mark.parametrize("n", [65537, 80000])
+def test_auto_mode_goes_matrix_free_past_the_matrix_limit(clean, T, O, n):
+    """small coordinates (a uint16 row of n cells still fits LDS) but n past the matrix sweeps' 65 536 labels: the automatic
+    mode builds no matrix and runs matrix-free; the first moves from NN(0) against the oracle; matrix mode forced at that
+    size fails in tspgpu_build_costs with code 8 and the matrix-mode limit named (that this refusal comes before the matrix is
+    allocated is the order of tspgpu_build_costs, not something this test observes)"""
+    eng = clean
+    xy = _box(n, 40000, n)
+    eng.set_points(xy); eng.build_costs()
+    info = eng.info()
+    assert info["matrix_free"] == 1 and info["n"] == n
+    eng.tour_nn(0, 0)
+    nn, nn_cost, _ = eng.tour_store(0)
+    assert O.valid_tour(nn) and O.tour_cost_xy(xy, O.EUC_2D, nn) == nn_cost
+    eng.set_option(T.OPT_HISTORY, 16)
+    sw, rc = eng.tour_two_opt(0, max_sweeps=3)
+    hist = _history(eng, 16)
+    got, _, _ = eng.tour_store(0)
+    assert sw == 3 and eng.info()["kernel"] == 4 and eng.info()["otf_kernel"] in (2, 3)
+    O.replay(xy, O.EUC_2D, nn, nn_cost, hist, checkpoints=(0, 2) if n > 70000 else (0, 1, 2), final=got)
+    eng.set_option(T.OPT_MATRIX_FREE, 2)
+    eng.set_points(xy)
+    with pytest.raises(T.TspGpuError) as ei:
+        eng.build_costs()
+    assert ei.value.code == 8 and "matrix-mode limit" in str(ei.value)
+
+
+# ------------------------------------------------------------------ deep trajectories: BASELINE config 5 (pla85900)
+def test_pla85900_whole_descent_replayed(clean, T, O, capsys):
+    """pla85900 (CEIL_2D, matrix-free, the exact early-out k_sweep_otf8<., false, true>): NN(0) -> local optimum, the whole
+    history replayed -- every move's delta, oracle scans at sweeps 0 and 1, spread over the descent, after the three longest
+    reversals and at the end (the certificate) --; at 150 of the replayed tours one sweep of the full evaluation (hook 91 = 2)
+    picks the recorded move.  Then one VNS iteration whose repair descent (seed found by search) ends on a different cost:
+    the kicks against the oracle's, that descent replayed and certified."""
+    import time
+    g = json.load(open(os.path.join(GOLDEN_DIR, "golden_large.json")))["pla85900"]
+    xy, _ = O.read_tsplib(data_path("pla85900"))
+    K = O.CEIL_2D
+    eng = clean
+    eng.set_points(xy, K); eng.build_costs()
+    n = eng.n
+    eng.tour_nn(0, 0)
+    nn, nn_cost, _ = eng.tour_store(0)
+    assert nn_cost == g["nn_cost"] and fx(O, nn) == g["nn_fnv"]
+    eng.set_option(T.OPT_HISTORY, 8192)
+    sw, rc = eng.tour_two_opt(0)
+    hist = _history(eng, 8192)
+    opt, cost, _ = eng.tour_store(0)
+    info = eng.info()
+    assert rc == 0 and (info["matrix_free"], info["kernel"], info["otf_kernel"]) == (1, 4, 3)
+    m = len(hist[0])
+    assert m == sw and hist[0][-1] == -1 and (hist[0][:-1] >= 0).all()
+    for i, mv in enumerate(g["moves"]):
+        assert (int(hist[0][i]), int(hist[1][i]), float(hist[2][i])) == (mv["a"], mv["b"], mv["delta"])
+    t0 = time.time()
+    d, _ = O.two_opt_best_move_xy(xy, K, nn, threads=16)
+    scan_s = time.time() - t0
+    # pass 1: every delta, the running cost, the final tour; 150 tours kept; the reversal lengths
+    keep = sorted(set(np.linspace(0, m - 2, 150).astype(int).tolist()))
+    _, fcost, kept, lens = O.replay(xy, K, nn, nn_cost, hist, final=opt, keep=keep)
+    assert fcost == cost
+    # one sweep of the full evaluation (no early-out) from each kept tour picks the recorded move
+    eng.set_option(91, 2)
+    for kk in keep:
+        eng.tour_load(0, kept[kk])
+        s1, _ = eng.tour_two_opt(0, max_sweeps=1)
+        a1, b1, d1 = _history(eng, 1)
+        assert s1 == 1 and (int(a1[0]), int(b1[0]), float(d1[0])) == (int(hist[0][kk]), int(hist[1][kk]), float(hist[2][kk])), kk
+    assert eng.info()["otf_kernel"] == 2
+    eng.set_option(91, 0)
+    del kept
+    # pass 2: the oracle's best move at the checkpoints (one scan ~ scan_s)
+    longest = np.argsort(lens)[-3:] + 1
+    cps = sorted({0, 1, m // 5, 2 * m // 5, 3 * m // 5, 4 * m // 5, m - 1} | set(int(x) for x in longest))
+    O.replay(xy, K, nn, nn_cost, hist, checkpoints=cps, final=opt)
+    with capsys.disabled():
+        print(f"\n[pla85900] {m} sweeps replayed, {len(cps)} checkpoints at {cps}, one oracle scan {scan_s:.2f} s, "
+              f"longest reversals {sorted(lens)[-3:]}")
+    # ---- one VNS iteration whose repair descent lands elsewhere.  The seed of the glibc stream was found by search: the first
+    # seed whose draw r = rand() % 9 - 2 kicks (r >= 2), whose next draw does not (r <= 0), and whose kicked tour's repair
+    # descent ends on another cost than the first optimum (seeds 1, 2, ... each: the kicks on the host, the descent on the engine)
+    seed = 380
+    libc = ctypes.CDLL(None)
+    O.libc_srand(seed)
+    r0 = libc.rand() % 9 - 2
+    kicked = opt.copy()
+    for _ in range(r0):
+        O.vns_kick(kicked)
+    assert r0 >= 2 and libc.rand() % 9 - 2 <= 0 and O.valid_tour(kicked) and not np.array_equal(kicked, opt)
+    eng.set_option(T.OPT_HISTORY, 0)
+    rv = _libc_draws(O, seed, 4096)
+    path, best = opt.copy(), opt.copy()
+    r = eng.vns_search(path, 1, rv, best, cost)
+    assert (r["rc"], r["iterations"]) == (0, 1) and np.array_equal(path, kicked)
+    used0 = r["consumed"]
+    r = eng.vns_search(path, 2, rv[used0:], best, r["best_cost"], iterations=1)
+    assert r["rc"] == 0 and r["cost"] != cost
+    kcost = O.tour_cost_xy(xy, K, kicked)
+    eng.set_option(T.OPT_HISTORY, 8192)
+    eng.tour_load(0, kicked)
+    sw, rc = eng.tour_two_opt(0)
+    rh = _history(eng, 8192)
+    rep, rcost, _ = eng.tour_store(0)
+    assert rcost == r["cost"] and np.array_equal(rep, path)
+    mr = len(rh[0])
+    O.replay(xy, K, kicked, kcost, rh, checkpoints=(0, mr - 1), final=rep)
+    with capsys.disabled():
+        print(f"[pla85900] VNS seed {seed}: {r0} kicks, repair descent {mr} sweeps -> {rcost:.0f} (first optimum {cost:.0f})")
+
+
+# ------------------------------------------------------------------ deep trajectories: BASELINE config 4 (d18512)
+def test_d18512_whole_descent_three_paths_and_batch(clean, T, O, golden):
+    """d18512 NN(0) -> local optimum (~2 400 sweeps) on the matrix default path, matrix-free auto (k_sweep_otf8) and
+    matrix-free with the early-out forced onto double points (hook 91 = 1): three identical histories, replayed once with
+    40 oracle checkpoints; the batched multi-start of 8 starts to convergence records the same slot-0 history and leaves
+    every slot on a certified local optimum"""
+    xy, _ = O.read_tsplib(data_path("d18512"))
+    g = golden["instances"]["d18512"]["two_opt"]
+    eng = clean
+    hists, finals = [], []
+    for path, opts, otf in (("matrix", {}, 0), ("mf_auto", {11: 1}, 2), ("mf_early_out", {11: 1, 91: 1}, 3)):
+        for o, v in opts.items():
+            eng.set_option(o, v)
+        eng.set_points(xy); eng.build_costs()
+        eng.tour_nn(0, 0)
+        nn, nn_cost, _ = eng.tour_store(0)
+        assert nn_cost == g["nn_cost"] and fx(O, nn) == g["nn_fnv"]
+        eng.set_option(T.OPT_HISTORY, 8192)
+        sw, rc = eng.tour_two_opt(0)
+        hists.append(_history(eng, 8192))
+        finals.append(eng.tour_store(0))
+        info = eng.info()
+        assert rc == 0 and sw == len(hists[-1][0]) and info["otf_kernel"] == otf and info["matrix_free"] == (otf > 0), (path, info)
+        eng.set_option(T.OPT_HISTORY, 0); eng.set_option(11, 0); eng.set_option(91, 0)
+    for h, f in zip(hists[1:], finals[1:]):
+        assert all(np.array_equal(x, y) for x, y in zip(h, hists[0]))
+        assert f[1] == finals[0][1] and np.array_equal(f[0], finals[0][0])
+    m = len(hists[0][0])
+    cps = sorted(set(np.linspace(0, m - 1, 40).astype(int).tolist()))
+    O.replay(xy, O.EUC_2D, nn, nn_cost, hists[0], checkpoints=cps, final=finals[0][0])
+    # the batch (more than 4 tours: k_sweep_pipe + k_apply), uncapped
+    eng.set_points(xy); eng.build_costs()
+    eng.set_option(T.OPT_HISTORY, 8192)
+    res = eng.multistart_nn_2opt(np.arange(8, dtype=np.int32))
+    batch = _history(eng, 8192)
+    assert res["rc"] == 0 and eng.info()["kernel"] == 2
+    assert all(np.array_equal(x, y) for x, y in zip(batch, hists[0]))
+    for i in range(8):
+        succ, c, _ = eng.tour_store(i)
+        assert O.valid_tour(succ) and O.tour_cost_xy(xy, O.EUC_2D, succ) == c
+        d, mv = O.two_opt_best_move_xy(xy, O.EUC_2D, succ, threads=16)
+        assert d >= -1e-7, (i, d, mv)
+    s0, c0, _ = eng.tour_store(0)
+    assert c0 == finals[0][1] and np.array_equal(s0, finals[0][0])
+
+
+# ------------------------------------------------------------------ the top of the matrix-free label range
+@pytest.mark.parametrize("n", [131071, 131072])
+def test_matrix_free_at_the_largest_n(clean, T, O, n):
+    """n = 131 071 (k_sweep_otf8: 17-bit labels up to 0x1fffe) and 131 072 (the engine's largest n: k_sweep_otf), integer
+    points with weights below 32 767 so that the NN grid kernel packs (weight << 17 | node) into its 32-bit key, node 131 071
+    next to the "none" key: the NN(0) tour and the first 3 moves equal the oracle's (tests/golden/golden_edges.json,
+    oracle/make_golden_edges.py); n = 131 073 is refused with code 3"""
+    g = json.load(open(os.path.join(GOLDEN_DIR, "golden_edges.json")))[f"n{n}"]
+    eng = clean
+    xy = _box(n, g["side"], g["seed"])
+    assert _cost_bound(xy, O.EUC_2D) < 32767.0
+    eng.set_points(xy); eng.build_costs()
+    info = eng.info()
+    assert (info["n"], info["matrix_free"]) == (n, 1) and info["nn_grid"] > 0
+    eng.tour_nn(0, 0)
+    nn, nn_cost, _ = eng.tour_store(0)
+    assert nn_cost == g["nn_cost"] and fx(O, nn) == g["nn_fnv"]
+    eng.set_option(T.OPT_HISTORY, 8)
+    sw, rc = eng.tour_two_opt(0, max_sweeps=3)
+    a, b, d = _history(eng, 8)
+    succ, cost, _ = eng.tour_store(0)
+    assert rc == 0 and sw == 3 and eng.info()["otf_kernel"] == (2 if n < 131072 else 1)
+    for i, mv in enumerate(g["moves"]):
+        assert (int(min(a[i], b[i])), int(max(a[i], b[i])), float(d[i])) == (mv["a"], mv["b"], mv["delta"]), i
+    assert cost == g["moves"][-1]["cost"] and fx(O, succ) == g["moves"][-1]["fnv"]
+    if n == 131072:
+        with pytest.raises(T.TspGpuError) as ei:
+            eng.set_points(_box(n + 1, g["side"], g["seed"]))
+        assert ei.value.code == 3 and "131072" in str(ei.value)

@@ -1304,7 +1304,7 @@ __global__ void __launch_bounds__(1024) k_sweep_simple(SweepArgs A)
 // nodes around a (refinment.c:55: b == a, b == succ a, succ b == a).
 //
 // Argmin.  The reference keeps the first strictly smaller delta in (a asc, b asc) order, i.e.
-// it minimises (delta, min(a,b), max(a,b)).  Integer deltas (n < 65536): ONE signed 64-bit word,
+// it minimises (delta, min(a,b), max(a,b)).  Integer deltas (n <= 65536): ONE signed 64-bit word,
 // delta in the high half, so "better" is a single compare and ties need no special path.
 // uint16 cells go one step further: for a fixed a the labels of a thread's consecutive b's
 // ascend with the slot number v, so per pair a 32-bit (delta << 3 | v) and ONE v_min suffice;
@@ -1996,7 +1996,7 @@ __global__ void __launch_bounds__(1024) k_sweep_res(SweepArgs A)
 // nodes and its own cells of ord.  No separate apply launch, no gather, no inter-workgroup
 // communication inside a launch.  k_fused_begin / k_fused_end convert from / to the Tours form.
 // ---------------------------------------------------------------------------
-// PACKED (uint16 cells, n < 65536): the per-node records are 16-bit -- pos as uint16, (nl, nr) and
+// PACKED (uint16 cells, n <= 65536): the per-node records are 16-bit -- pos as uint16, (nl, nr) and
 // (dl, dr) as halves of one 32-bit word each, in the same buffers -- which halves what every
 // workgroup of every launch reads of them.
 template <typename AT, bool PACKED>
@@ -3371,6 +3371,9 @@ static int new_instance(tspgpu_ctx *ctx, int n)
     return E_OK;
 }
 
+// the matrix sweeps pack a pair as min(a,b) << 16 | max(a,b): labels 0..65535
+static const int MATRIX_MAX_N = 64 * 1024;
+
 static size_t elem_size(int elem) { return elem == TSPGPU_ELEM_F64 ? 8 : elem == TSPGPU_ELEM_I32 ? 4 : 2; }
 
 // run `...` with T bound to the storage type of `elem`
@@ -3610,7 +3613,7 @@ static int make_plan(tspgpu_ctx *ctx, int ntours)
         ctx->plan_lds = row + 16 * sizeof(Partial) + 64;
         nch = 0;
     }
-    if (n > 64 * 1024) return fail(ctx, E_EXHAUSTED, "n=%d exceeds the matrix-mode limit", n);
+    if (n > MATRIX_MAX_N) return fail(ctx, E_EXHAUSTED, "n=%d exceeds the matrix-mode limit", n);
     ctx->plan_kernel = kernel; ctx->plan_G = G; ctx->plan_P = P; ctx->plan_BT = BT; ctx->plan_NCH = nch; ctx->plan_T = ntours;
     if (kernel != 2) ctx->plan_pipe2 = ctx->plan_pipe2_sweep = false;
     ctx->plan_lds_fused = ctx->plan_lds + (ctx->plan_pipe2 ? row : 0);
@@ -4845,6 +4848,10 @@ long tspgpu_info(const tspgpu_ctx *ctx, int what)
     case 22: return ctx->lp_sweeps;
     case 23: return ctx->vns_mode;
     case 24: return ctx->sp_used ? 1 : 0;
+    case 25:   // the matrix-free sweep kernel of the current plan (see launch_sweep)
+        if (!ctx->otf || ctx->plan_kernel != 4) return 0;
+        return !(ctx->cost_bound < 33554432.0 && ctx->n < 131072) ? 1 : ctx->plan_otf_early ? 3 : 2;
+    case 26: return ctx->have_points && ctx->ceil_int() ? 1 : 0;   // CEIL_2D weights by the integer ceil-sqrt (edge_w<KIND_CEIL_INT>)
     case 12: return (ctx->built && ctx->grid_ok && ctx->opt_nn != 1 && ctx->cost_bound < 134217728.0) ? ctx->grid_G : 0;
     case 13: return ctx->grid_max_occ;
     }
@@ -4931,10 +4938,12 @@ int tspgpu_build_costs(tspgpu_ctx *ctx, double *host_out)
     if (ctx->opt_elem == TSPGPU_ELEM_I32 && !fits32) return fail(ctx, E_INVALID, "int32 storage requested but costs may reach %.0f", ctx->cost_bound);
     if (ctx->opt_elem != TSPGPU_ELEM_AUTO) ctx->elem = ctx->opt_elem;
     else ctx->elem = fits16 ? TSPGPU_ELEM_U16 : fits32 ? TSPGPU_ELEM_I32 : TSPGPU_ELEM_F64;
-    // matrix-free when asked for, or when one matrix row cannot sit in LDS (every matrix sweep
-    // gathers c[succ a][succ b] from an LDS row) -- e.g. pla85900: 343 KB per int32 row
+    // matrix-free when asked for, when one matrix row cannot sit in LDS (every matrix sweep
+    // gathers c[succ a][succ b] from an LDS row) -- e.g. pla85900: 343 KB per int32 row --, or when n
+    // is past the matrix sweeps' 16-bit labels (a uint16 row of up to ~80 900 cells still fits LDS)
     const bool row_fits = (size_t)ctx->ld * elem_size(ctx->elem) + 2048 <= ctx->lds_max;
-    ctx->otf = ctx->opt_otf == 1 || (ctx->opt_otf == 0 && !row_fits);
+    const bool labels_fit = ctx->n <= MATRIX_MAX_N;
+    ctx->otf = ctx->opt_otf == 1 || (ctx->opt_otf == 0 && (!row_fits || !labels_fit));
     if (ctx->otf) {
         if (!fits32) return fail(ctx, E_EXHAUSTED, "matrix-free mode needs integer costs below 2^27 (bound %.0f)", ctx->cost_bound);
         if (host_out) return fail(ctx, E_INVALID, "matrix-free mode: there is no n x n matrix to copy out (n = %d)", ctx->n);
@@ -4946,6 +4955,7 @@ int tspgpu_build_costs(tspgpu_ctx *ctx, double *host_out)
         return E_OK;
     }
     if (!row_fits) return fail(ctx, E_EXHAUSTED, "n = %d: a matrix row does not fit LDS and matrix-free mode is disabled", ctx->n);
+    if (!labels_fit) return fail(ctx, E_EXHAUSTED, "n = %d exceeds the matrix-mode limit of %d nodes and matrix-free mode is disabled", ctx->n, MATRIX_MAX_N);
     HIP_TRY(hipMalloc(&ctx->d_mat, cells * elem_size(ctx->elem)));
     int rc = launch_build(ctx);
     if (rc) return rc;

@@ -211,7 +211,9 @@ ERROR_CODE tsp_compute_costs(void)
      * past 46 340 and needs 59 GB for pla85900) or on request: no n x n array anywhere, the
      * device recomputes weights from the coordinates and tsp_inst.costs stays NULL. */
     const char *mf = getenv("TSP_MATRIX_FREE");
-    tsp_matrix_free = mf ? atoi(mf) != 0 : n > 32768;   /* an explicit 0 keeps the matrix at any size */
+    /* an explicit 0 leaves it to the engine's automatic choice, which still goes matrix-free where a matrix row cannot sit in
+     * LDS or n exceeds the matrix-mode limit of 65 536 nodes (a build that is to fill tsp_inst.costs then fails with code 3) */
+    tsp_matrix_free = mf ? atoi(mf) != 0 : n > 32768;
     int rc;
     if (m) {
         /* several devices: each builds its own matrix from the 16n-byte coordinate array (never shipped) */
