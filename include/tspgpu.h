@@ -86,7 +86,11 @@ enum {
                                    code 8 (and used from n = 1024 up) */
     TSPGPU_OPT_PERSIST_WINDOW = 18 /* rows of that kernel: 0 auto (whole rows where they fit the chip's LDS, else the half
                                    window of n/2 cells ahead of the workgroup's own edges), 1 half-window rows wherever they
-                                   apply, 2 whole rows only */
+                                   apply, 2 whole rows only */,
+    TSPGPU_OPT_EM_FORM = 21     /* Extra Mileage insertion loop (tspgpu_extra_mileage): 0 (default) and 2 one launch pair per
+                                   step, enqueued back to back (measured faster); 1 ONE launch for the whole construction
+                                   (one workgroup per CU, a grid barrier between phases), or fail with code 8 when the grid
+                                   does not come up co-resident */
 };
 
 int  tspgpu_device_count(void);
@@ -108,7 +112,8 @@ int  tspgpu_set_option(tspgpu_ctx *ctx, int option, long value);
  * 24 the last single-tour descent ran in the streamed persistent kernel (TSPGPU_OPT_STREAM_PERSIST), 25 the matrix-free sweep
  * kernel of the current plan (0 not matrix-free / no plan yet, 1 k_sweep_otf: costs from 2^25 or n = 131 072, 2 k_sweep_otf8,
  * 3 k_sweep_otf8 with the exact early-out), 26 CEIL_2D weights come from the exact integer ceil-sqrt of integer coordinates
- * (cost bound below 2^22; 0: the generic double form, or another kind) */
+ * (cost bound below 2^22; 0: the generic double form, or another kind), 27 how the last tspgpu_extra_mileage ran (1 one launch,
+ * 2 one launch pair per step), 28 / 29 its stale-node rescans / insertions */
 long tspgpu_info(const tspgpu_ctx *ctx, int what);
 
 /* ---- instance / cost matrix ------------------------------------------- */
@@ -175,6 +180,23 @@ int tspgpu_tabu_search(tspgpu_ctx *ctx, int *path, double *cost, int k,
 int tspgpu_vns_search(tspgpu_ctx *ctx, int *path, double *cost, int k, double time_left_s,
                       const int *rand_values, long nrand, long *consumed, int *iterations, int *kick_pending,
                       int *best_path, double *best_cost, double *trace);
+
+/* ---- Extra Mileage (h_ExtraMileage, src/algorithms/heuristics.c:156-210) --------
+ * Both need every off-diagonal cost an integer in [0, 2^27) -- true for every matrix tspgpu_build_costs makes, in
+ * matrix and matrix-free mode; a caller matrix (tspgpu_set_costs) that breaks it fails with FAILED_PRECONDITION (9). */
+
+/* The EM_MAX start of h_ExtraMileage (src/algorithms/heuristics.c:165-177): the first pair i < j in row-major order
+ * whose cost is strictly the largest (all costs 0: (0, 1)).  *cost = c[a][b]. */
+int tspgpu_farthest_pair(tspgpu_ctx *ctx, int *a, int *b, double *cost);
+
+/* h_extramileage_util (src/algorithms/heuristics.c:290-367) from the pair (a, b) as h_ExtraMileage starts it
+ * (:180-186: path[a] = b, path[b] = a, cost 2 c[a][b]): cheapest insertion, the first strict minimum of
+ * c[u][i] + c[i][v] - c[u][v] over unvisited i ascending, then edges in the reference's array order, until every
+ * node is in.  path receives the successor array, *cost = 2 c[a][b] + the inserted deltas.  3 when a, b are not two
+ * distinct nodes; time_left_s < 0 = no deadline, else checked before every insertion: 4 when it passes, and then path
+ * and *cost are left untouched (the reference's partial tour is rejected by tsp_update_best_solution).
+ * TSPGPU_OPT_EM_FORM chooses between the one-launch and the per-step form; tspgpu_info 27 says which ran. */
+int tspgpu_extra_mileage(tspgpu_ctx *ctx, int a, int b, double time_left_s, int *path, double *cost);
 
 /* ---- multi-start entry points ------------------------------------------ */
 

@@ -21,6 +21,8 @@ ELEM_AUTO, ELEM_F64, ELEM_I32, ELEM_U16 = 0, 1, 2, 3
 OPT_ELEM, OPT_KERNEL, OPT_BATCH, OPT_WGS_PER_TOUR, OPT_HISTORY = 1, 2, 3, 4, 5
 OPT_GRAPH, OPT_TIMING, OPT_BLOCK, OPT_MAX_TOURS, OPT_DEPTH, OPT_MATRIX_FREE, OPT_FUSED, OPT_SWEEP_CAP, OPT_NN_KERNEL, OPT_PIPE2 = 6, 7, 8, 9, 10, 11, 12, 13, 14, 15
 OPT_PERSIST, OPT_PERSIST_EDGES, OPT_PERSIST_WINDOW, OPT_BUILD_KERNEL, OPT_STREAM_PERSIST = 16, 17, 18, 19, 20
+OPT_EM_FORM = 21
+EM_FORM_AUTO, EM_FORM_RESIDENT, EM_FORM_PER_STEP = 0, 1, 2
 MOPT_EXCHANGE = 1000
 EXCHANGE_AUTO, EXCHANGE_HOST, EXCHANGE_RCCL = 0, 1, 2
 
@@ -49,6 +51,8 @@ SIGNATURES = {
     "tspgpu_tabu_move": (C.c_int, [_ctx, _ip, _pd, _ip, C.c_int, C.c_int]),
     "tspgpu_tabu_search": (C.c_int, [_ctx, _ip, _pd, C.c_int, _ip, _pd, C.c_void_p]),
     "tspgpu_vns_search": (C.c_int, [_ctx, _ip, _pd, C.c_int, C.c_double, _ip, C.c_long, _pl, _pi, _pi, _ip, _pd, C.c_void_p]),
+    "tspgpu_farthest_pair": (C.c_int, [_ctx, _pi, _pi, _pd]),
+    "tspgpu_extra_mileage": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_double, _ip, _pd]),
     "tspgpu_nn_all": (C.c_int, [_ctx, C.c_void_p, C.c_int, _ip, _pd, _pi]),
     "tspgpu_tour_sweep_part": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, _pd, _pi, _pi]),
     "tspgpu_tour_apply_move": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_double]),

@@ -3080,6 +3080,7 @@ __global__ void k_cap_now(Tours S, int slot0, int count)
 #include "tspgpu_lds2opt.inc"
 #include "tspgpu_lds2opt_win.inc"
 #include "tspgpu_str2opt.inc"
+#include "tspgpu_em.inc"
 
 // ===========================================================================
 // host side
@@ -3179,6 +3180,11 @@ struct tspgpu_ctx {
     bool lp_attr[6] = {false, false, false, false, false, false};
     bool max16k = false;       // every off-diagonal cell <= 16383 (packed 16-bit deltas cannot overflow)
     bool max8k = false;        // ... <= 8190 (the tabu form of the packed loop: a poisoned pair must exceed every valid delta)
+
+    // Extra Mileage (tspgpu_em.inc)
+    int opt_em_form = 0;       // 0 (default) and 2 one launch pair per step; 1 the one-launch form, or fail with code 8
+    int em_form = 0;           // how the last construction ran: 1 resident, 2 per step
+    long em_stale = 0, em_steps = 0;   // stale rescans and insertions of the last construction
 
     Fused F{};                 // fused path state (allocated on first use, capacity fcap)
     int fcap = 0;
@@ -4810,6 +4816,7 @@ int tspgpu_set_option(tspgpu_ctx *ctx, int option, long value)
     case TSPGPU_OPT_PERSIST_WINDOW: if (value < 0 || value > 2) return fail(ctx, E_INVALID, "bad window mode"); ctx->opt_persist_window = (int)value; break;
     case TSPGPU_OPT_PIPE2: if (value < 0 || value > 1) return fail(ctx, E_INVALID, "bad pipe2 mode"); ctx->opt_pipe2 = (int)value; ctx->plan_kernel = 0; drop_graphs(ctx); break;
     case TSPGPU_OPT_NN_KERNEL: if (value < 0 || value > 3) return fail(ctx, E_INVALID, "bad NN kernel id"); ctx->opt_nn = (int)value; break;
+    case TSPGPU_OPT_EM_FORM: if (value < 0 || value > 2) return fail(ctx, E_INVALID, "bad Extra Mileage form"); ctx->opt_em_form = (int)value; break;
     case TSPGPU_OPT_SWEEP_CAP: if (value < -1 || value > INT_MAX) return fail(ctx, E_INVALID, "bad sweep cap"); ctx->opt_sweep_cap = (int)value; break;
     default: return fail(ctx, E_INVALID, "unknown option %d", option);
     }
@@ -4852,6 +4859,9 @@ long tspgpu_info(const tspgpu_ctx *ctx, int what)
         if (!ctx->otf || ctx->plan_kernel != 4) return 0;
         return !(ctx->cost_bound < 33554432.0 && ctx->n < 131072) ? 1 : ctx->plan_otf_early ? 3 : 2;
     case 26: return ctx->have_points && ctx->ceil_int() ? 1 : 0;   // CEIL_2D weights by the integer ceil-sqrt (edge_w<KIND_CEIL_INT>)
+    case 27: return ctx->em_form;
+    case 28: return ctx->em_stale;
+    case 29: return ctx->em_steps;
     case 12: return (ctx->built && ctx->grid_ok && ctx->opt_nn != 1 && ctx->cost_bound < 134217728.0) ? ctx->grid_G : 0;
     case 13: return ctx->grid_max_occ;
     }
@@ -5557,6 +5567,148 @@ int tspgpu_history(tspgpu_ctx *ctx, int *a, int *b, double *delta, int capacity,
     }
     *count = m;
     return E_OK;
+}
+
+} // extern "C"
+
+// ---- Extra Mileage (tspgpu_em.inc) -----------------------------------------------------------------------------------
+
+// run `...` with WF bound to the weight functor of the context's matrix / matrix-free kind
+#define EM_WF_SWITCH(ctx, WF, ...)                                                                        \
+    do {                                                                                                  \
+        if ((ctx)->otf) {                                                                                 \
+            if ((ctx)->kind == TSPGPU_EUC_2D) { typedef EmPts<TSPGPU_EUC_2D> WF; __VA_ARGS__; }          \
+            else if ((ctx)->kind == TSPGPU_ATT) { typedef EmPts<TSPGPU_ATT> WF; __VA_ARGS__; }           \
+            else { typedef EmPts<TSPGPU_CEIL_2D> WF; __VA_ARGS__; }                                       \
+        } else if ((ctx)->elem == TSPGPU_ELEM_F64) { typedef EmMat<double> WF; __VA_ARGS__; }             \
+        else if ((ctx)->elem == TSPGPU_ELEM_I32) { typedef EmMat<int> WF; __VA_ARGS__; }                  \
+        else { typedef EmMat<u16> WF; __VA_ARGS__; }                                                      \
+    } while (0)
+
+// the held weights are integers in [0, 2^27) off the diagonal (every delta and key then is an exact integer)
+static int em_check(tspgpu_ctx *ctx)
+{
+    int rc = need_costs(ctx);
+    if (rc) return rc;
+    if (ctx->built) {
+        if (!(ctx->cost_bound < 134217728.0)) return fail(ctx, E_PRECOND, "Extra Mileage needs integer costs below 2^27 (bound %.0f)", ctx->cost_bound);
+        return E_OK;
+    }
+    const int n = ctx->n, ld = ctx->ld;
+    HIP_TRY(hipMemsetAsync(ctx->d_flags, 0, 4, ctx->stream));
+    const dim3 grid((n + 255) / 256, n);
+    if (ctx->elem == TSPGPU_ELEM_F64) hipLaunchKernelGGL((k_em_check<double>), grid, dim3(256), 0, ctx->stream, (const double *)ctx->d_mat, n, ld, ctx->d_flags);
+    else if (ctx->elem == TSPGPU_ELEM_I32) hipLaunchKernelGGL((k_em_check<int>), grid, dim3(256), 0, ctx->stream, (const int *)ctx->d_mat, n, ld, ctx->d_flags);
+    else hipLaunchKernelGGL((k_em_check<u16>), grid, dim3(256), 0, ctx->stream, (const u16 *)ctx->d_mat, n, ld, ctx->d_flags);
+    HIP_TRY(hipGetLastError());
+    int flag = 0;
+    HIP_TRY(hipMemcpyAsync(&flag, ctx->d_flags, 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (flag) return fail(ctx, E_PRECOND, "Extra Mileage needs every off-diagonal cost an integer in [0, 2^27)");
+    return E_OK;
+}
+
+static EmArgs em_args(const tspgpu_ctx *ctx)
+{
+    EmArgs A;
+    memset(&A, 0, sizeof A);
+    A.mat = ctx->d_mat; A.pts = ctx->d_pts; A.ld = ctx->ld; A.n = ctx->n; A.sym = ctx->symmetric;
+    return A;
+}
+
+extern "C" {
+
+int tspgpu_farthest_pair(tspgpu_ctx *ctx, int *a, int *b, double *cost)
+{
+    if (!ctx || !a || !b || !cost) return fail(ctx, E_INVALID, "null argument");
+    hipSetDevice(ctx->device);
+    int rc = em_check(ctx);
+    if (rc) return rc;
+    u64 *d_key = nullptr, key = 0;
+    HIP_TRY(hipMalloc(&d_key, 8));
+    EmArgs A = em_args(ctx);
+    hipError_t e = hipMemsetAsync(d_key, 0, 8, ctx->stream);
+    if (e == hipSuccess) {
+        EM_WF_SWITCH(ctx, WF, hipLaunchKernelGGL((k_em_farthest<WF>), dim3(ctx->n), dim3(EM_BT), 0, ctx->stream, A, d_key));
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&key, d_key, 8, hipMemcpyDeviceToHost, ctx->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    hipFree(d_key);
+    if (e != hipSuccess) return fail(ctx, E_INTERNAL, "farthest pair: %s", hipGetErrorString(e));
+    const u64 lin = ~key & EM_FMASK, n = (u64)ctx->n;
+    *a = (int)(lin / n); *b = (int)(lin % n);
+    *cost = (double)(key >> 35);
+    return E_OK;
+}
+
+int tspgpu_extra_mileage(tspgpu_ctx *ctx, int a, int b, double time_left_s, int *path, double *cost)
+{
+    if (!ctx || !path || !cost) return fail(ctx, E_INVALID, "null argument");
+    hipSetDevice(ctx->device);
+    int rc = em_check(ctx);
+    if (rc) return rc;
+    const int n = ctx->n;
+    if (a < 0 || a >= n || b < 0 || b >= n || a == b) return fail(ctx, E_INVALID, "starting pair (%d, %d) is not two distinct nodes of [0, %d)", a, b, n);
+    if (time_left_s >= 0 && time_left_s <= 0) return fail(ctx, E_DEADLINE, "time limit exceeded before the first insertion");
+    // one allocation: control block | skey[n] | eu, ev, ec, succ [n] | stale [3][n]
+    const size_t N = (size_t)n, bytes = sizeof(EmCtl) + N * 8 + N * 4 * 4 + N * 4 * 3;
+    unsigned char *mem = nullptr;
+    HIP_TRY(hipMalloc(&mem, bytes));
+    EmArgs A = em_args(ctx);
+    A.ctl = reinterpret_cast<EmCtl *>(mem);
+    A.skey = reinterpret_cast<u64 *>(mem + sizeof(EmCtl));
+    A.eu = reinterpret_cast<int *>(mem + sizeof(EmCtl) + N * 8);
+    A.ev = A.eu + N; A.ec = A.ev + N; A.succ = A.ec + N; A.stale = A.succ + N;
+    A.limit = time_left_s < 0 ? -1 : (long long)(time_left_s * 1e8);
+    A.hello = ctx->opt_lp_hello;            // 2 ms
+    A.spin = 100000000;                     // 1 s
+    const int W = ctx->cus;
+    EmCtl C;
+    memset(&C, 0, sizeof C);
+    auto run = [&](bool resident) -> int {
+        HIP_TRY(hipMemsetAsync(A.ctl, 0, sizeof(EmCtl), ctx->stream));
+        if (resident) {
+            EM_WF_SWITCH(ctx, WF, hipLaunchKernelGGL((k_em_resident<WF>), dim3(W), dim3(EM_BT), 0, ctx->stream, A, a, b));
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(&C, A.ctl, sizeof C, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+            return E_OK;
+        }
+        EM_WF_SWITCH(ctx, WF, hipLaunchKernelGGL((k_em_init<WF>), dim3(W), dim3(EM_BT), 0, ctx->stream, A, a, b));
+        HIP_TRY(hipGetLastError());
+        // every step's two launches back to back; the host looks at the stop word once per chunk of steps
+        for (int s0 = 0; s0 <= n - 3; s0 += 2048) {
+            for (int s = s0; s <= n - 3 && s < s0 + 2048; s++) {
+                EM_WF_SWITCH(ctx, WF, hipLaunchKernelGGL((k_em_a<WF>), dim3(W), dim3(EM_BT), 0, ctx->stream, A, s));
+                if (s < n - 3) EM_WF_SWITCH(ctx, WF, hipLaunchKernelGGL((k_em_b<WF>), dim3(W), dim3(EM_BT), 0, ctx->stream, A, s));
+            }
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync(&C, A.ctl, sizeof C, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+            if (C.stop) break;
+        }
+        return E_OK;
+    };
+    const int form = ctx->opt_em_form == 1 ? 1 : 2;    // (measured: the per-step form is faster)
+    rc = run(form == 1);
+    if (!rc && C.status == EM_ST_BROKEN) rc = fail(ctx, E_INTERNAL, "Extra Mileage: a step found no candidate (after %d insertions)", C.steps);
+    if (!rc && C.status != EM_ST_OK)
+        rc = fail(ctx, E_EXHAUSTED, "Extra Mileage: the resident grid of %d workgroups %s", W,
+                  C.status == EM_ST_NO_RENDEZVOUS ? "did not come up co-resident" : "lost its co-residency");
+    if (!rc) {
+        ctx->em_form = form; ctx->em_stale = C.stale; ctx->em_steps = C.steps;
+        if (C.stop) rc = fail(ctx, E_DEADLINE, "time limit exceeded after %d of %d insertions", C.steps, n - 2);
+        else if (C.steps != n - 2) rc = fail(ctx, E_INTERNAL, "Extra Mileage ended after %d of %d insertions", C.steps, n - 2);
+        else {
+            hipError_t e = hipMemcpyAsync(path, A.succ, N * 4, hipMemcpyDeviceToHost, ctx->stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+            if (e != hipSuccess) rc = fail(ctx, E_INTERNAL, "tour download: %s", hipGetErrorString(e));
+            else *cost = 2.0 * (double)C.cab + (double)C.dsum;     // heuristics.c:184 then :362, exact in integers
+        }
+    }
+    hipFree(mem);
+    return rc;
 }
 
 } // extern "C"

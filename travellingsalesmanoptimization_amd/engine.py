@@ -50,7 +50,7 @@ class Engine:
         names = ["n", "ld", "elem", "kernel", "wgs_per_tour", "lds_bytes", "block", "symmetric", "cus", "depth", "matrix_free", "fused",
                  "nn_grid", "nn_grid_max_cell", "pipe2", "persist", "persist_wgs", "persist_edges", "persist_lds", "persist_window_cells",
                  "persist_window", "persist_handed", "persist_sweeps", "vns_mode", "stream_persist",
-                 "otf_kernel", "ceil_int"]
+                 "otf_kernel", "ceil_int", "em_form", "em_stale", "em_steps"]
         return {k: int(self.L.tspgpu_info(self.ctx, i)) for i, k in enumerate(names)}
 
     # ---- instance
@@ -86,6 +86,25 @@ class Engine:
         cost = C.c_double()
         self._ck(self.L.tspgpu_nn_tour(self.ctx, int(start), path, C.byref(cost)))
         return path, cost.value
+
+    def farthest_pair(self):
+        """The EM_MAX start of h_ExtraMileage (heuristics.c:165-177) -> (a, b, cost)."""
+        a, b, c = C.c_int(), C.c_int(), C.c_double()
+        self._ck(self.L.tspgpu_farthest_pair(self.ctx, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
+    def extra_mileage(self, a=None, b=None, time_left_s=-1.0):
+        """h_extramileage_util (heuristics.c:290-367) from (a, b), by default the farthest pair -> (succ, cost, rc).
+        rc is DEADLINE_EXCEEDED when the time ran out; succ is then None and cost None."""
+        if a is None or b is None:
+            a, b, _ = self.farthest_pair()
+        path = np.empty(self.n, dtype=np.int32)
+        cost = C.c_double()
+        rc = self._ck(self.L.tspgpu_extra_mileage(self.ctx, int(a), int(b), float(time_left_s), path, C.byref(cost)),
+                      ok=(T_OK, DEADLINE_EXCEEDED))
+        if rc != T_OK:
+            return None, None, rc
+        return path, cost.value, rc
 
     def two_opt_once(self, path, cost):
         """ref_2opt_once (refinment.c:39-93); path modified in place -> (delta, cost)."""

@@ -328,10 +328,84 @@ ERROR_CODE h_Greedy_2opt_mod_costs(tsp_solution *solution, double *costs)
     return from_rc(rc);
 }
 
+/* heuristics.c:156-210.  The farthest pair (EM_MAX) and the insertion loop run on the device.  EM_RANDOM draws the pair
+ * from the program's rand() stream exactly as the reference does; the draws with which the reference would read outside
+ * its arrays or build a broken tour (A == n, B == n, A == B) -- and instances of fewer than 2 nodes -- return
+ * INVALID_ARGUMENT with the incumbent untouched.  A deadline that passes before the last insertion returns
+ * DEADLINE_EXCEEDED, also with the incumbent untouched (the reference's partial tour fails tsp_update_best_solution). */
 ERROR_CODE h_ExtraMileage(void)
 {
-    log_error("Extra Mileage is not part of the accelerated heuristic path");
-    return UNIMPLEMENTED;
+    log_info("running Extra Mileage");
+    const int n = tsp_inst.nnodes;
+    double max_distance = 0.0;
+    int nodeA = 0, nodeB = 1;
+    switch (tsp_env.mileage_init) {
+    case EM_MAX:
+        if (n >= 2) {
+            tspgpu_ctx *g = tsp_gpu();
+            if (!g) return UNAVAILABLE;
+            const int rc = tspgpu_farthest_pair(g, &nodeA, &nodeB, &max_distance);
+            if (rc != 0) { log_error("tspgpu_farthest_pair: %s", tspgpu_last_error(g)); return from_rc(rc); }
+        }
+        break;
+    case EM_RANDOM:
+        nodeA = tsp_rand() % (n + 1);
+        nodeB = tsp_rand() % (n - nodeA + 1) + nodeA;
+        break;
+    default:
+        log_warn("aborted");
+        return ABORTED;
+    }
+    log_debug("max edge : (%d, %d) with distance %f", nodeA, nodeB, max_distance);
+    if (n < 2 || nodeA >= n || nodeB >= n || nodeA == nodeB) {
+        log_error("extra mileage: starting pair (%d, %d) is not two distinct nodes of the %d", nodeA, nodeB, n);
+        return INVALID_ARGUMENT;
+    }
+    tsp_solution solution;
+    tsp_init_solution(n, &solution);
+    solution.cost = 2 * tsp_get_cost(nodeA, nodeB);
+    solution.path[nodeA] = nodeB;
+    solution.path[nodeB] = nodeA;
+    log_debug("initial cost: %f", solution.cost);
+    ERROR_CODE error = h_extramileage_util(&solution, nodeA, nodeB);
+    if (error == T_OK) {
+        ERROR_CODE u = tsp_update_best_solution(&solution);
+        if (!err_ok(u)) log_error("code %d : error in updating solution for extra mileage", u);
+    } else if (error == DEADLINE_EXCEEDED) {
+        log_warn("time limit exceeded in extra mileage");
+    }
+    free(solution.path); free(solution.comp);
+    return error;
+}
+
+/* heuristics.c:290-367: cheapest insertion from the pair (nodeA, nodeB) on the device.  As in the reference, the
+ * deltas are ADDED to the caller's solution->cost (h_ExtraMileage starts it at 2 c(A, B)) and the successor array is
+ * written into solution->path.  DEADLINE_EXCEEDED (checked before every insertion) leaves *solution untouched. */
+ERROR_CODE h_extramileage_util(tsp_solution *solution, int nodeA, int nodeB)
+{
+    const int n = tsp_inst.nnodes;
+    if (n < 2 || nodeA < 0 || nodeA >= n || nodeB < 0 || nodeB >= n || nodeA == nodeB) {
+        log_error("extra mileage: starting pair (%d, %d) is not two distinct nodes of the %d", nodeA, nodeB, n);
+        return INVALID_ARGUMENT;
+    }
+    if (past_deadline()) return DEADLINE_EXCEEDED;
+    tspgpu_ctx *g = tsp_gpu();
+    if (!g) return UNAVAILABLE;
+    int *path = (int *)malloc((size_t)n * sizeof(int));
+    if (!path) return RESOURCE_EXHAUSTED;
+    double cost = 0;
+    const int rc = tspgpu_extra_mileage(g, nodeA, nodeB, time_left(), path, &cost);
+    if (rc == 0) {
+        memcpy(solution->path, path, (size_t)n * sizeof(int));
+        solution->cost += cost - 2 * tsp_get_cost(nodeA, nodeB);     /* the inserted deltas: integers, exact */
+        log_debug("current cost: %f", solution->cost);
+    } else if (rc == DEADLINE_EXCEEDED) {
+        log_info("extra mileage: %s", tspgpu_last_error(g));      /* the device's count of the insertions made */
+    } else {
+        log_error("tspgpu_extra_mileage: %s", tspgpu_last_error(g));
+    }
+    free(path);
+    return from_rc(rc);
 }
 
 /* ===================================================================== metaheuristic.c */

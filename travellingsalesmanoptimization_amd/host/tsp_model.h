@@ -135,7 +135,8 @@ ERROR_CODE h_Greedy_iterative(void);                         /* heuristics.c:34-
 ERROR_CODE h_greedy_2opt(void);                              /* heuristics.c:74-116 -> device, all starts batched */
 ERROR_CODE h_Greedy_2opt_mod_costs(tsp_solution *solution, double *costs); /* heuristics.c:118-149 -> device */
 ERROR_CODE h_greedyutil(int starting_node, tsp_solution *solution, double *costs); /* heuristics.c:216-288 -> device */
-ERROR_CODE h_ExtraMileage(void);                             /* heuristics.c:156-210: not on the hot path, UNIMPLEMENTED */
+ERROR_CODE h_ExtraMileage(void);                             /* heuristics.c:156-210 -> device (farthest pair, insertion) */
+ERROR_CODE h_extramileage_util(tsp_solution *solution, int nodeA, int nodeB); /* heuristics.c:290-367 -> device */
 
 /* ---- src/algorithms/metaheuristic.h ---------------------------------------------- */
 #define UPPER 10
