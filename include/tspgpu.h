@@ -198,6 +198,34 @@ int tspgpu_farthest_pair(tspgpu_ctx *ctx, int *a, int *b, double *cost);
  * TSPGPU_OPT_EM_FORM chooses between the one-launch and the per-step form; tspgpu_info 27 says which ran. */
 int tspgpu_extra_mileage(tspgpu_ctx *ctx, int a, int b, double time_left_s, int *path, double *cost);
 
+/* ---- Or-opt and the 2-opt + Or-opt descent (an extension: the reference has no Or-opt) ----------------------------
+ * A candidate (s, L, q, rev) moves the L in {1, 2, 3} consecutive tour nodes s .. t (t = L - 1 steps after s) between
+ * q and q' = path[q]; q is any node outside the segment other than p = pred(s) (q = x = path[t] is allowed), rev = 1
+ * (L >= 2 only) inserts the segment the other way round: (h, e) = (s, t), or (t, s) when rev.
+ *     delta = ((c[p][x] + c[q][h]) + c[e][q']) - ((c[p][s] + c[t][x]) + c[q][q'])
+ * evaluated in this order (bit-exact for double cells).  A sweep finds the first strict minimum over s ascending, then
+ * L = 1, 2, 3, then q ascending, then rev = 0 before 1 -- the lexicographic minimum of (delta, s, L, q, rev) -- and applies
+ * it iff delta < -1e-7 (TWO_OPT_EPS, src/algorithms/refinment.c): path[p] = x, path[q] = h, the segment's inner links
+ * reversed when rev, path[e] = q', *cost += delta.
+ * Preconditions: n >= 8 (else 3), a symmetric matrix (tspgpu_info 7, else 9), MATRIX MODE ONLY -- in matrix-free mode
+ * every entry point of this section returns UNIMPLEMENTED (12) --, and four matrix rows of ld = n rounded up to 32 cells
+ * plus 3072 bytes in one workgroup's 160 KiB of LDS: n <= 20 096 with uint16 cells, 10 048 with int32, 5 024 with
+ * doubles, else RESOURCE_EXHAUSTED (8) with the limit in the error text.  Without a context (no device): 14. */
+
+/* one Or-opt sweep on a host tour; applies the move when delta < -1e-7.  *cost is the caller's running cost (as
+ * tspgpu_two_opt_once).  move[4] = {s, L, q, rev} of the applied move (all -1 and *delta = 0 when nothing improves) */
+int tspgpu_or_opt_once(tspgpu_ctx *ctx, int *path, double *cost, double *delta, int move[4]);
+/* Or-opt sweeps until none improves; *cost is the caller's running cost plus the applied deltas in order; *moves (may be
+ * NULL) counts applied moves.  time_left_s < 0 = no deadline, else polled before every sweep: 4 once it has passed */
+int tspgpu_or_opt(tspgpu_ctx *ctx, int *path, double *cost, double time_left_s, long *moves);
+/* Variable-neighbourhood descent: *cost recomputed as ref_2opt does (src/algorithms/refinment.c:6-9), then
+ * { the 2-opt descent of tspgpu_two_opt to its local optimum; Or-opt sweeps until none improves } until the Or-opt
+ * phase applies no move: the result is locally optimal for both neighbourhoods.  *two_opt_sweeps counts every round's
+ * final non-improving sweep too, *rounds the 2-opt descents run (each may be NULL).  The deadline is polled between
+ * Or-opt sweeps and handed on to the 2-opt descent; once it passes: 4, with a valid tour and its cost. */
+int tspgpu_local_search(tspgpu_ctx *ctx, int *path, double *cost, double time_left_s,
+                        long *two_opt_sweeps, long *or_moves, int *rounds);
+
 /* ---- multi-start entry points ------------------------------------------ */
 
 /* h_Greedy_iterative (src/algorithms/heuristics.c:34-72): NN from every listed
@@ -277,6 +305,15 @@ int tspgpu_tour_nn(tspgpu_ctx *ctx, int slot, int start);
 int tspgpu_tour_copy(tspgpu_ctx *ctx, int dst, int src);
 /* sweep slot to its local optimum (max_sweeps < 0: no cap) */
 int tspgpu_tour_two_opt(tspgpu_ctx *ctx, int slot, long max_sweeps, double time_left_s, long *sweeps);
+/* Or-opt on a slot (the section "Or-opt" above): at most max_moves moves (< 0: until no sweep improves); the slot's
+ * cost and last delta follow, and every later slot call (2-opt sweeps included) sees the rewritten tour */
+int tspgpu_tour_or_opt(tspgpu_ctx *ctx, int slot, long max_moves, double time_left_s, long *moves);
+/* the descent of tspgpu_local_search on a slot (its cost is taken as it stands) */
+int tspgpu_tour_local_search(tspgpu_ctx *ctx, int slot, double time_left_s,
+                             long *two_opt_sweeps, long *or_moves, int *rounds);
+/* a measurement aid (tools/oropt_rate.py), the Or-opt counterpart of tspgpu_time_sweep: launch the Or-opt sweep kernel
+ * alone `reps` times on slot (no move applied) and return its mean duration in ms from HIP events on the engine's stream */
+int tspgpu_time_or_sweep(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean);
 /* Intra-sweep sharding ("optional, config 5": one sweep of a large instance split over
  * the GPUs of a node).  Every rank holds the same tour in `slot`; tspgpu_tour_sweep_part evaluates
  * the runs [part*G/nparts, (part+1)*G/nparts) of ONE sweep (refinment.c:49-69) and returns the best

@@ -53,6 +53,12 @@ SIGNATURES = {
     "tspgpu_vns_search": (C.c_int, [_ctx, _ip, _pd, C.c_int, C.c_double, _ip, C.c_long, _pl, _pi, _pi, _ip, _pd, C.c_void_p]),
     "tspgpu_farthest_pair": (C.c_int, [_ctx, _pi, _pi, _pd]),
     "tspgpu_extra_mileage": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_double, _ip, _pd]),
+    "tspgpu_or_opt_once": (C.c_int, [_ctx, _ip, _pd, _pd, _ip]),
+    "tspgpu_or_opt": (C.c_int, [_ctx, _ip, _pd, C.c_double, _pl]),
+    "tspgpu_local_search": (C.c_int, [_ctx, _ip, _pd, C.c_double, _pl, _pl, _pi]),
+    "tspgpu_tour_or_opt": (C.c_int, [_ctx, C.c_int, C.c_long, C.c_double, _pl]),
+    "tspgpu_tour_local_search": (C.c_int, [_ctx, C.c_int, C.c_double, _pl, _pl, _pi]),
+    "tspgpu_time_or_sweep": (C.c_int, [_ctx, C.c_int, C.c_int, C.POINTER(C.c_float)]),
     "tspgpu_nn_all": (C.c_int, [_ctx, C.c_void_p, C.c_int, _ip, _pd, _pi]),
     "tspgpu_tour_sweep_part": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, _pd, _pi, _pi]),
     "tspgpu_tour_apply_move": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_double]),

@@ -3081,6 +3081,7 @@ __global__ void k_cap_now(Tours S, int slot0, int count)
 #include "tspgpu_lds2opt_win.inc"
 #include "tspgpu_str2opt.inc"
 #include "tspgpu_em.inc"
+#include "tspgpu_oropt.inc"
 
 // ===========================================================================
 // host side
@@ -3185,6 +3186,10 @@ struct tspgpu_ctx {
     int opt_em_form = 0;       // 0 (default) and 2 one launch pair per step; 1 the one-launch form, or fail with code 8
     int em_form = 0;           // how the last construction ran: 1 resident, 2 per step
     long em_stale = 0, em_steps = 0;   // stale rescans and insertions of the last construction
+
+    // Or-opt (tspgpu_oropt.inc)
+    OrCtl *d_or = nullptr;     // control block, allocated on first use
+    bool or_attr[9] = {false, false, false, false, false, false, false, false, false};
 
     Fused F{};                 // fused path state (allocated on first use, capacity fcap)
     int fcap = 0;
@@ -4759,6 +4764,7 @@ void tspgpu_destroy(tspgpu_ctx *ctx)
     if (ctx->d_stamps) hipFree(ctx->d_stamps);
     if (ctx->d_spts) hipFree(ctx->d_spts);
     if (ctx->d_ipts) hipFree(ctx->d_ipts);
+    if (ctx->d_or) hipFree(ctx->d_or);
     free_grid(ctx);
     if (ctx->hist.a) { hipFree(ctx->hist.a); hipFree(ctx->hist.b); hipFree(ctx->hist.d); }
     for (auto e : ctx->ev) hipEventDestroy(e);
@@ -5709,6 +5715,243 @@ int tspgpu_extra_mileage(tspgpu_ctx *ctx, int a, int b, double time_left_s, int 
     }
     hipFree(mem);
     return rc;
+}
+
+} // extern "C"
+
+// ---- Or-opt and the 2-opt + Or-opt descent (tspgpu_oropt.inc) -------------------------------------------------------
+
+// largest n the Or-opt sweep takes with cells of `esz` bytes: four rows of ld cells and OR_EXTRA bytes in one workgroup's LDS
+static int or_max_n(const tspgpu_ctx *ctx, size_t esz) { return (int)((ctx->lds_max - OR_EXTRA) / (4 * esz)) & ~31; }
+
+static int or_check(tspgpu_ctx *ctx)
+{
+    int rc = need_costs(ctx);
+    if (rc) return rc;
+    if (ctx->otf) return fail(ctx, E_UNIMPL, "Or-opt needs the resident cost matrix: it is not implemented in matrix-free mode");
+    if (ctx->n < 8) return fail(ctx, E_INVALID, "Or-opt needs at least 8 nodes, got %d", ctx->n);
+    if (!ctx->symmetric) return fail(ctx, E_PRECOND, "Or-opt needs a symmetric cost matrix");
+    const int lim = or_max_n(ctx, elem_size(ctx->elem));
+    if (ctx->ld > lim)
+        return fail(ctx, E_EXHAUSTED, "Or-opt keeps four matrix rows in LDS: n = %d is past the limit of %d nodes for %d-byte cells",
+                    ctx->n, lim, (int)elem_size(ctx->elem));
+    if (!ctx->d_or) HIP_TRY(hipMalloc(&ctx->d_or, sizeof(OrCtl)));
+    return E_OK;
+}
+
+// geometry of a sweep launch: threads, 16-byte vectors per thread and row, positions per workgroup, workgroups, LDS bytes
+struct OrPlan { int BT, NCH, R, W; size_t lds; const void *fn; int fi; };
+
+template <typename T> static const void *or_sweep_fn(int nch)
+{
+    return nch == 1 ? (const void *)k_oropt_sweep<T, 1> : nch == 2 ? (const void *)k_oropt_sweep<T, 2> : (const void *)k_oropt_sweep<T, 3>;
+}
+
+static OrPlan or_plan(const tspgpu_ctx *ctx)
+{
+    OrPlan P;
+    const size_t esz = elem_size(ctx->elem);
+    const int nvec = ctx->ld / (int)(16 / esz), n = ctx->n;
+    P.BT = nvec <= 256 ? 256 : nvec <= 1024 ? 512 : 1024;
+    P.NCH = (nvec + P.BT - 1) / P.BT;                       // <= 3 below every LDS limit
+    P.lds = 4 * (size_t)ctx->ld * esz + OR_EXTRA;
+    const int occ = (int)std::max<size_t>(1, std::min<size_t>(ctx->lds_max / P.lds, (size_t)(2048 / P.BT)));
+    const int target = ctx->cus * occ;                      // one wave of workgroups over the chip
+    int R = (n + target - 1) / target;
+    R = std::max(R, (n + MAX_WGS_PER_TOUR - 1) / MAX_WGS_PER_TOUR);    // the partial slots of a tour
+    P.R = std::min(std::max(R, 2), OR_RMAX);
+    P.W = (n + P.R - 1) / P.R;
+    ELEM_SWITCH(ctx->elem, T, P.fn = or_sweep_fn<T>(P.NCH));
+    P.fi = (ctx->elem == TSPGPU_ELEM_F64 ? 0 : ctx->elem == TSPGPU_ELEM_I32 ? 3 : 6) + P.NCH - 1;
+    return P;
+}
+
+static int or_launch_sweep(tspgpu_ctx *ctx, int slot, const OrPlan &P)
+{
+    if (!ctx->or_attr[P.fi]) {
+        HIP_TRY(hipFuncSetAttribute(P.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->lds_max));
+        ctx->or_attr[P.fi] = true;
+    }
+#define OR_SWEEP(T, N) hipLaunchKernelGGL((k_oropt_sweep<T, N>), dim3(P.W), dim3(P.BT), P.lds, ctx->stream, ctx->S, (const T *)ctx->d_mat, \
+                                          ctx->n, ctx->ld, slot, P.R, (const OrCtl *)ctx->d_or)
+    ELEM_SWITCH(ctx->elem, T, { if (P.NCH == 1) OR_SWEEP(T, 1); else if (P.NCH == 2) OR_SWEEP(T, 2); else OR_SWEEP(T, 3); });
+#undef OR_SWEEP
+    HIP_TRY(hipGetLastError());
+    return E_OK;
+}
+
+static int or_launch_apply(tspgpu_ctx *ctx, int slot, const OrPlan &P)
+{
+    const int BT = std::min(1024, std::max(64, pow2_ceil(ctx->n / 8)));
+    ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_oropt_apply<T>), dim3(1), dim3(BT), 0, ctx->stream, ctx->S, (const T *)ctx->d_mat,
+                                                 ctx->n, ctx->ld, slot, P.W, ctx->d_or));
+    HIP_TRY(hipGetLastError());
+    return E_OK;
+}
+
+// Or-opt moves on `slot` until a sweep finds nothing improving, max_moves (< 0: no cap) are applied or t_end (< 0: none) passes;
+// one sweep launch and one apply launch per move, eight pairs between looks at the control block (one under a deadline)
+static int or_run(tspgpu_ctx *ctx, int slot, long max_moves, double t_end, long *moves, bool *late, OrCtl *last)
+{
+    OrCtl C;
+    memset(&C, 0, sizeof C);
+    C.move[0] = C.move[1] = C.move[2] = C.move[3] = -1;
+    C.budget = max_moves;
+    if (late) *late = false;
+    if (moves) *moves = 0;
+    if (last) *last = C;
+    if (max_moves == 0) return E_OK;
+    HIP_TRY(hipMemcpyAsync(ctx->d_or, &C, sizeof C, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));       // (C is on the stack)
+    const OrPlan P = or_plan(ctx);
+    for (;;) {
+        if (t_end >= 0 && now_s() >= t_end) { if (late) *late = true; break; }
+        const int K = t_end >= 0 ? 1 : 8;
+        for (int i = 0; i < K; i++) {
+            int rc = or_launch_sweep(ctx, slot, P);
+            if (!rc) rc = or_launch_apply(ctx, slot, P);
+            if (rc) return rc;
+        }
+        HIP_TRY(hipMemcpyAsync(&C, ctx->d_or, sizeof C, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if (C.stop) break;
+    }
+    if (moves) *moves = (long)C.moves;
+    if (last) *last = C;
+    return E_OK;
+}
+
+// the descent of tspgpu_local_search on a slot: { 2-opt to its local optimum; Or-opt until nothing improves } until Or-opt applies nothing
+static int or_descent(tspgpu_ctx *ctx, int slot, double time_left_s, long *two_opt_sweeps, long *or_moves, int *rounds, bool *late)
+{
+    const double t_end = time_left_s >= 0 ? now_s() + time_left_s : -1;
+    long tw = 0, om = 0;
+    int nr = 0, rc = E_OK;
+    *late = false;
+    for (;;) {
+        double left = -1;
+        if (t_end >= 0 && (left = t_end - now_s()) <= 0) { *late = true; break; }
+        hipLaunchKernelGGL(k_rearm, dim3(1), dim3(64), 0, ctx->stream, ctx->S, slot, 1, -1);
+        HIP_TRY(hipGetLastError());
+        if ((rc = run_sweeps(ctx, slot, 1, false, -1, left, late))) break;
+        int ns = 0;
+        HIP_TRY(hipMemcpyAsync(&ns, ctx->S.nsweeps + slot, 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        tw += ns; nr++;
+        if (*late) break;
+        long m = 0;
+        if ((rc = or_run(ctx, slot, -1, t_end, &m, late, nullptr))) break;
+        om += m;
+        if (*late || m == 0) break;
+    }
+    if (two_opt_sweeps) *two_opt_sweeps = tw;
+    if (or_moves) *or_moves = om;
+    if (rounds) *rounds = nr;
+    return rc;
+}
+
+extern "C" {
+
+int tspgpu_tour_or_opt(tspgpu_ctx *ctx, int slot, long max_moves, double time_left_s, long *moves)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    hipSetDevice(ctx->device);
+    int rc = or_check(ctx);
+    if (rc) return rc;
+    if ((rc = need_slot(ctx, slot))) return rc;
+    bool late = false;
+    if ((rc = or_run(ctx, slot, max_moves, time_left_s >= 0 ? now_s() + time_left_s : -1, moves, &late, nullptr))) return rc;
+    return late ? E_DEADLINE : E_OK;
+}
+
+int tspgpu_tour_local_search(tspgpu_ctx *ctx, int slot, double time_left_s, long *two_opt_sweeps, long *or_moves, int *rounds)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    hipSetDevice(ctx->device);
+    int rc = or_check(ctx);
+    if (rc) return rc;
+    if ((rc = need_slot(ctx, slot))) return rc;
+    bool late = false;
+    if ((rc = or_descent(ctx, slot, time_left_s, two_opt_sweeps, or_moves, rounds, &late))) return rc;
+    return late ? E_DEADLINE : E_OK;
+}
+
+int tspgpu_time_or_sweep(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    if (!ms_mean || reps <= 0) return fail(ctx, E_INVALID, "bad argument");
+    hipSetDevice(ctx->device);
+    int rc = or_check(ctx);
+    if (rc) return rc;
+    if ((rc = need_slot(ctx, slot))) return rc;
+    HIP_TRY(hipMemsetAsync(ctx->d_or, 0, sizeof(OrCtl), ctx->stream));
+    const OrPlan P = or_plan(ctx);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    float ms = 0;
+    // (the events are destroyed on every way out)
+    auto timed = [&]() -> int {
+        int r;
+        HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
+        if ((r = or_launch_sweep(ctx, slot, P))) return r; // warm
+        HIP_TRY(hipEventRecord(e0, ctx->stream));
+        for (int i = 0; i < reps; i++) if ((r = or_launch_sweep(ctx, slot, P))) return r;
+        HIP_TRY(hipEventRecord(e1, ctx->stream));
+        HIP_TRY(hipEventSynchronize(e1));
+        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+        return E_OK;
+    };
+    rc = timed();
+    if (e0) hipEventDestroy(e0);
+    if (e1) hipEventDestroy(e1);
+    if (rc) return rc;
+    *ms_mean = ms / reps;
+    return E_OK;
+}
+
+int tspgpu_or_opt_once(tspgpu_ctx *ctx, int *path, double *cost, double *delta, int move[4])
+{
+    if (!ctx) return E_UNAVAILABLE;
+    if (!path || !cost) return fail(ctx, E_INVALID, "null argument");
+    hipSetDevice(ctx->device);
+    int rc = or_check(ctx);
+    if (rc) return rc;
+    if ((rc = load_path(ctx, 0, path, -1))) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->S.cost, cost, 8, hipMemcpyHostToDevice, ctx->stream));     // the caller's running cost, as ref_2opt_once
+    OrCtl C;
+    if ((rc = or_run(ctx, 0, 1, -1, nullptr, nullptr, &C))) return rc;
+    if ((rc = store_path(ctx, 0, path, cost, nullptr))) return rc;
+    if (delta) *delta = C.applied ? C.d : 0.0;
+    if (move) for (int i = 0; i < 4; i++) move[i] = C.applied ? C.move[i] : -1;
+    return E_OK;
+}
+
+int tspgpu_or_opt(tspgpu_ctx *ctx, int *path, double *cost, double time_left_s, long *moves)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    if (!path || !cost) return fail(ctx, E_INVALID, "null argument");
+    hipSetDevice(ctx->device);
+    int rc = or_check(ctx);
+    if (rc) return rc;
+    if ((rc = load_path(ctx, 0, path, -1))) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->S.cost, cost, 8, hipMemcpyHostToDevice, ctx->stream));
+    bool late = false;
+    if ((rc = or_run(ctx, 0, -1, time_left_s >= 0 ? now_s() + time_left_s : -1, moves, &late, nullptr))) return rc;
+    if ((rc = store_path(ctx, 0, path, cost, nullptr))) return rc;
+    return late ? E_DEADLINE : E_OK;
+}
+
+int tspgpu_local_search(tspgpu_ctx *ctx, int *path, double *cost, double time_left_s, long *two_opt_sweeps, long *or_moves, int *rounds)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    if (!path || !cost) return fail(ctx, E_INVALID, "null argument");
+    hipSetDevice(ctx->device);
+    int rc = or_check(ctx);
+    if (rc) return rc;
+    if ((rc = load_path(ctx, 0, path, -1))) return rc;          // recomputes the cost, refinment.c:6-9
+    bool late = false;
+    if ((rc = or_descent(ctx, 0, time_left_s, two_opt_sweeps, or_moves, rounds, &late))) return rc;
+    if ((rc = store_path(ctx, 0, path, cost, nullptr))) return rc;
+    return late ? E_DEADLINE : E_OK;
 }
 
 } // extern "C"

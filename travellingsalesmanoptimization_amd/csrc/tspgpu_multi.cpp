@@ -369,6 +369,10 @@ void tspgpu_multi_destroy(tspgpu_multi *m)
     if (m->comm_ready)
         for (ncclComm_t c : m->comm) if (c) m->R.CommDestroy(c);
     for (int i = 0; i < m->G; i++) {
+        // no context: tspgpu_multi_create stopped at or before this device and nothing lives on it. Selecting a device
+        // that does not exist would also leave "invalid device ordinal" pending on the calling thread, where the next
+        // launch check of an unrelated context (HIP_TRY(hipGetLastError())) would report it
+        if (!m->ctx[i]) continue;
         hipSetDevice(m->dev[i]);
         if (m->d_key[i]) hipFree(m->d_key[i]);
         if (m->d_path[i]) hipFree(m->d_path[i]);

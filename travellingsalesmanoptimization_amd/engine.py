@@ -119,6 +119,29 @@ class Engine:
                       ok=(T_OK, DEADLINE_EXCEEDED))
         return c.value, s.value, rc
 
+    def or_opt_once(self, path, cost):
+        """one Or-opt sweep (include/tspgpu.h "Or-opt"); path in place -> (delta, cost, (s, L, q, rev));
+        delta 0 and (-1, -1, -1, -1) when nothing improves."""
+        c, d = C.c_double(cost), C.c_double()
+        mv = np.empty(4, dtype=np.int32)
+        self._ck(self.L.tspgpu_or_opt_once(self.ctx, path, C.byref(c), C.byref(d), mv))
+        return d.value, c.value, tuple(int(v) for v in mv)
+
+    def or_opt(self, path, cost, time_left_s=-1.0):
+        """Or-opt sweeps until none improves; path in place -> (cost, moves, rc)."""
+        c, m = C.c_double(cost), C.c_long()
+        rc = self._ck(self.L.tspgpu_or_opt(self.ctx, path, C.byref(c), float(time_left_s), C.byref(m)),
+                      ok=(T_OK, DEADLINE_EXCEEDED))
+        return c.value, m.value, rc
+
+    def local_search(self, path, time_left_s=-1.0):
+        """2-opt and Or-opt in turn until neither improves; path in place ->
+        dict(cost, two_opt_sweeps, or_moves, rounds, rc)."""
+        c, sw, om, nr = C.c_double(), C.c_long(), C.c_long(), C.c_int()
+        rc = self._ck(self.L.tspgpu_local_search(self.ctx, path, C.byref(c), float(time_left_s), C.byref(sw), C.byref(om), C.byref(nr)),
+                      ok=(T_OK, DEADLINE_EXCEEDED))
+        return {"cost": c.value, "two_opt_sweeps": sw.value, "or_moves": om.value, "rounds": nr.value, "rc": rc}
+
     def tabu_move(self, path, cost, tabu_list, tenure, it):
         """tabu_best_move (metaheuristic.c:188-245); path and tabu_list in place -> cost."""
         c = C.c_double(cost)
@@ -201,6 +224,25 @@ class Engine:
         rc = self._ck(self.L.tspgpu_tour_two_opt(self.ctx, slot, int(max_sweeps), float(time_left_s), C.byref(s)),
                       ok=(T_OK, DEADLINE_EXCEEDED))
         return s.value, rc
+
+    def tour_or_opt(self, slot, max_moves=-1, time_left_s=-1.0):
+        """Or-opt moves on a slot -> (moves, rc)."""
+        m = C.c_long()
+        rc = self._ck(self.L.tspgpu_tour_or_opt(self.ctx, int(slot), int(max_moves), float(time_left_s), C.byref(m)),
+                      ok=(T_OK, DEADLINE_EXCEEDED))
+        return m.value, rc
+
+    def tour_local_search(self, slot, time_left_s=-1.0):
+        """the descent of local_search on a slot -> dict(two_opt_sweeps, or_moves, rounds, rc)."""
+        sw, om, nr = C.c_long(), C.c_long(), C.c_int()
+        rc = self._ck(self.L.tspgpu_tour_local_search(self.ctx, int(slot), float(time_left_s), C.byref(sw), C.byref(om), C.byref(nr)),
+                      ok=(T_OK, DEADLINE_EXCEEDED))
+        return {"two_opt_sweeps": sw.value, "or_moves": om.value, "rounds": nr.value, "rc": rc}
+
+    def time_or_sweep(self, slot, reps):
+        ms = C.c_float()
+        self._ck(self.L.tspgpu_time_or_sweep(self.ctx, slot, reps, C.byref(ms)))
+        return ms.value
 
     def tour_sweep_part(self, slot, part, nparts):
         """one sweep's runs [part*G/nparts, (part+1)*G/nparts) -> (delta, a, b); (0, 0, 0): nothing improving there"""

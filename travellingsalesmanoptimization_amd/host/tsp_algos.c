@@ -12,6 +12,7 @@
 #include "tsp_model.h"
 
 #include <math.h>
+#include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
 
@@ -669,20 +670,83 @@ ERROR_CODE mh_VNS(void)
     return e;
 }
 
+/* ===================================================================== Or-opt polish (an extension: no reference counterpart) */
+
+/* 2-opt and Or-opt in turn until neither improves (tspgpu_local_search), on the instance's own matrix, under
+ * tsp_env.timelimit.  DEADLINE_EXCEEDED leaves a valid tour and its cost in *solution, like ref_2opt. */
+/* the codes with which tspgpu_local_search refuses an instance it is not built for (fewer than 8 nodes, rows past the LDS
+ * limit, an asymmetric matrix, matrix-free mode): the tour is untouched */
+static int or_opt_refusal(ERROR_CODE e)
+{
+    return e == INVALID_ARGUMENT || e == RESOURCE_EXHAUSTED || e == FAILED_PRECONDITION || e == UNIMPLEMENTED;
+}
+
+ERROR_CODE tsp_or_opt_polish(tsp_solution *solution)
+{
+    if (!solution || !solution->path) return INVALID_ARGUMENT;
+    thread_ctx *lease;
+    tspgpu_ctx *g = ctx_for(tsp_inst.costs, &lease);
+    if (!g) return UNAVAILABLE;
+    long sweeps = 0, moves = 0;
+    int rounds = 0;
+    const int rc = tspgpu_local_search(g, solution->path, &solution->cost, time_left(), &sweeps, &moves, &rounds);
+    if (or_opt_refusal(from_rc(rc))) log_warn("tspgpu_local_search: %s", tspgpu_last_error(g));
+    else if (rc != 0 && rc != DEADLINE_EXCEEDED) log_error("tspgpu_local_search: %s", tspgpu_last_error(g));
+    else log_debug("Or-opt polish: %d rounds, %ld 2-opt sweeps, %ld Or-opt moves, cost %f", rounds, sweeps, moves, solution->cost);
+    thread_done(lease);
+    return from_rc(rc);
+}
+
+/* TSP_OR_OPT: unset or 0 = off, 1 = polish the incumbent after the heuristic; anything else is an error (-1) */
+static int or_opt_switch(void)
+{
+    const char *v = getenv("TSP_OR_OPT");
+    if (!v || !strcmp(v, "0")) return 0;
+    if (!strcmp(v, "1")) return 1;
+    fprintf(stderr, "tsp: TSP_OR_OPT=\"%s\": expected 0 or 1\n", v);     /* (shown under -q too: a mistyped switch must not pass silently) */
+    return -1;
+}
+
 /* ===================================================================== main.c:4-87 */
 ERROR_CODE tsp_run_algorithm(void)
 {
+    const int polish = or_opt_switch();
+    if (polish < 0) return INVALID_ARGUMENT;
     free(tsp_inst.best_solution.path);
     tsp_inst.best_solution.path = (int *)calloc((size_t)tsp_inst.nnodes, sizeof(int));
+    ERROR_CODE e;
     switch (tsp_inst.alg) {
-    case ALG_GREEDY: return h_Greedy();
-    case ALG_GREEDY_ITER: return h_Greedy_iterative();
-    case ALG_2OPT_GREEDY: return h_greedy_2opt();
-    case ALG_TABU_SEARCH: return mh_TabuSearch();
-    case ALG_VNS: return mh_VNS();
-    case ALG_EXTRAMILEAGE: return h_ExtraMileage();
+    case ALG_GREEDY: e = h_Greedy(); break;
+    case ALG_GREEDY_ITER: e = h_Greedy_iterative(); break;
+    case ALG_2OPT_GREEDY: e = h_greedy_2opt(); break;
+    case ALG_TABU_SEARCH: e = mh_TabuSearch(); break;
+    case ALG_VNS: e = mh_VNS(); break;
+    case ALG_EXTRAMILEAGE: e = h_ExtraMileage(); break;
     default:
         log_error("algorithm %d belongs to the CPLEX path, which this library leaves to the reference build", tsp_inst.alg);
         return UNIMPLEMENTED;
     }
+    if (!polish || (e != T_OK && e != DEADLINE_EXCEEDED)) return e;
+    if (tsp_matrix_free) {
+        log_warn("TSP_OR_OPT=1: Or-opt needs the cost matrix and the instance runs matrix-free; the polish is skipped");
+        return e;
+    }
+    /* the polish works on a copy: tsp_update_best_solution takes it only if it is a tour and strictly better */
+    tsp_solution s;
+    const int n = tsp_inst.nnodes;
+    tsp_init_solution(n, &s);
+    memcpy(s.path, tsp_inst.best_solution.path, (size_t)n * sizeof(int));
+    s.cost = tsp_inst.best_solution.cost;
+    const ERROR_CODE pe = tsp_or_opt_polish(&s);
+    if (pe == T_OK || pe == DEADLINE_EXCEEDED) {
+        const ERROR_CODE u = tsp_update_best_solution(&s);
+        if (!err_ok(u)) log_error("code %d : error in updating the best solution after the Or-opt polish", u);
+    }
+    free(s.path); free(s.comp);
+    if (or_opt_refusal(pe)) {       /* as in matrix-free mode: the heuristic's result stands */
+        log_warn("TSP_OR_OPT=1: Or-opt does not take this instance (code %d); the polish is skipped", pe);
+        return e;
+    }
+    if (pe != T_OK && pe != DEADLINE_EXCEEDED) return pe;
+    return pe == DEADLINE_EXCEEDED ? pe : e;
 }
