@@ -113,7 +113,8 @@ int  tspgpu_set_option(tspgpu_ctx *ctx, int option, long value);
  * kernel of the current plan (0 not matrix-free / no plan yet, 1 k_sweep_otf: costs from 2^25 or n = 131 072, 2 k_sweep_otf8,
  * 3 k_sweep_otf8 with the exact early-out), 26 CEIL_2D weights come from the exact integer ceil-sqrt of integer coordinates
  * (cost bound below 2^22; 0: the generic double form, or another kind), 27 how the last tspgpu_extra_mileage ran (1 one launch,
- * 2 one launch pair per step), 28 / 29 its stale-node rescans / insertions */
+ * 2 one launch pair per step), 28 / 29 its stale-node rescans / insertions, 30 tour positions per Or-opt sweep workgroup (R) in
+ * the first Or-opt round of the last batched descent (tspgpu_tours_local_search and the calls built on it; 0: none ran), 31 the R of a single-tour Or-opt sweep on this instance (0: no matrix) */
 long tspgpu_info(const tspgpu_ctx *ctx, int what);
 
 /* ---- instance / cost matrix ------------------------------------------- */
@@ -249,6 +250,17 @@ int tspgpu_multistart_nn_2opt(tspgpu_ctx *ctx, const int *starts, int nstarts,
                               int *best_start, long *total_sweeps,
                               int *last_path, double *last_cost);
 
+/* NN + the 2-opt + Or-opt descent of tspgpu_local_search (the section "Or-opt" above, its preconditions and codes) from every
+ * listed start (starts == NULL: 0..nstarts-1), the tours of a chunk of TSPGPU_OPT_MAX_TOURS starts descending together
+ * (tspgpu_tours_local_search).  The winner is the lowest cost, ties to the earliest entry of `starts` (strict <); it is in
+ * general NOT the tour tspgpu_multistart_nn_2opt + tspgpu_local_search on its winner gives.  costs_out (may be NULL) receives
+ * every start's final cost in list order, the totals (each may be NULL) the sums over the starts.  A TSPGPU_OPT_SWEEP_CAP
+ * other than -1 is refused with 3: a capped 2-opt phase is not this descent.  Once the deadline passes: 4, with the best of
+ * the chunks begun so far (the entries of costs_out behind them are left as they were). */
+int tspgpu_multistart_local_search(tspgpu_ctx *ctx, const int *starts, int nstarts, double time_left_s,
+                                   int *best_path, double *best_cost, int *best_start,
+                                   long *total_two_opt_sweeps, long *total_or_moves, double *costs_out);
+
 /* ---- multi-device multi-start (csrc/tspgpu_multi.cpp) ------------------------
  * The reference's multi-start loops (h_greedy_2opt, src/algorithms/heuristics.c:82-111; h_Greedy_iterative, :43-66)
  * are sequential C; their iterations are independent except for the incumbent minimum (src/tsp.c:669-676, strict <).
@@ -287,6 +299,11 @@ int  tspgpu_multi_build_costs(tspgpu_multi *m);                 /* tsp_compute_c
  * tspgpu_multistart_nn_2opt over the whole list when no deadline is set */
 int  tspgpu_multi_multistart_nn_2opt(tspgpu_multi *m, const int *starts, int nstarts, double time_left_s,
                                      int *best_path, double *best_cost, int *best_start, long *total_sweeps);
+/* tspgpu_multistart_local_search sharded the same way (entry p of the list on device p mod G, the same exchange);
+ * without a handle: 14 */
+int  tspgpu_multi_multistart_local_search(tspgpu_multi *m, const int *starts, int nstarts, double time_left_s,
+                                          int *best_path, double *best_cost, int *best_start,
+                                          long *total_two_opt_sweeps, long *total_or_moves);
 /* h_Greedy_iterative (src/algorithms/heuristics.c:34-72) sharded the same way */
 int  tspgpu_multi_nn_all(tspgpu_multi *m, const int *starts, int nstarts, double time_left_s,
                          int *best_path, double *best_cost, int *best_start, int *done_starts);
@@ -311,6 +328,12 @@ int tspgpu_tour_or_opt(tspgpu_ctx *ctx, int slot, long max_moves, double time_le
 /* the descent of tspgpu_local_search on a slot (its cost is taken as it stands) */
 int tspgpu_tour_local_search(tspgpu_ctx *ctx, int slot, double time_left_s,
                              long *two_opt_sweeps, long *or_moves, int *rounds);
+/* the descent of tspgpu_tour_local_search on slots slot0 .. slot0+count-1 at once: one Or-opt sweep launch and one apply
+ * launch per round serve every tour still descending, and each slot ends exactly as tspgpu_tour_local_search would leave
+ * it.  Per-slot outputs, [count] each (each may be NULL).  A slot of the range that holds no tour: 9, nothing is run.
+ * Once the deadline passes: 4, every slot holding a valid tour and its cost. */
+int tspgpu_tours_local_search(tspgpu_ctx *ctx, int slot0, int count, double time_left_s,
+                              long *two_opt_sweeps, long *or_moves, int *rounds);
 /* a measurement aid (tools/oropt_rate.py), the Or-opt counterpart of tspgpu_time_sweep: launch the Or-opt sweep kernel
  * alone `reps` times on slot (no move applied) and return its mean duration in ms from HIP events on the engine's stream */
 int tspgpu_time_or_sweep(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean);

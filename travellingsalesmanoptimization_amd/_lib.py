@@ -58,6 +58,8 @@ SIGNATURES = {
     "tspgpu_local_search": (C.c_int, [_ctx, _ip, _pd, C.c_double, _pl, _pl, _pi]),
     "tspgpu_tour_or_opt": (C.c_int, [_ctx, C.c_int, C.c_long, C.c_double, _pl]),
     "tspgpu_tour_local_search": (C.c_int, [_ctx, C.c_int, C.c_double, _pl, _pl, _pi]),
+    "tspgpu_tours_local_search": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tspgpu_multistart_local_search": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_double, _ip, _pd, _pi, _pl, _pl, C.c_void_p]),
     "tspgpu_time_or_sweep": (C.c_int, [_ctx, C.c_int, C.c_int, C.POINTER(C.c_float)]),
     "tspgpu_nn_all": (C.c_int, [_ctx, C.c_void_p, C.c_int, _ip, _pd, _pi]),
     "tspgpu_tour_sweep_part": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, _pd, _pi, _pi]),
@@ -77,6 +79,7 @@ SIGNATURES = {
     "tspgpu_multi_set_points": (C.c_int, [_ctx, _dp, C.c_int, C.c_int]),
     "tspgpu_multi_build_costs": (C.c_int, [_ctx]),
     "tspgpu_multi_multistart_nn_2opt": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_double, _ip, _pd, _pi, _pl]),
+    "tspgpu_multi_multistart_local_search": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_double, _ip, _pd, _pi, _pl, _pl]),
     "tspgpu_multi_nn_all": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_double, _ip, _pd, _pi, _pi]),
     "tspgpu_tour_load": (C.c_int, [_ctx, C.c_int, _ip]),
     "tspgpu_tour_nn": (C.c_int, [_ctx, C.c_int, C.c_int]),

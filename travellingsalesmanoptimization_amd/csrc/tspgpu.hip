@@ -3069,6 +3069,13 @@ __global__ void k_rearm(Tours S, int slot0, int count, int cap)
     if (i < count) { S.done[slot0 + i] = 0; S.nsweeps[slot0 + i] = 0; S.cap_sweeps[slot0 + i] = cap; }
 }
 
+// the masked form: only the listed slots (a batch descent re-arms the tours still in it; a finished tour keeps done = 1)
+__global__ void k_rearm_list(Tours S, const int *__restrict__ list, int count, int cap)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < count) { const int t = list[i]; S.done[t] = 0; S.nsweeps[t] = 0; S.cap_sweeps[t] = cap; }
+}
+
 // deadline drain of the one-launch-per-sweep path: the sweep cap of every unfinished tour := the sweeps it has
 // completed, so that the next launch applies the pending move and stops (refinment.c:17-26: a sweep that ran is applied)
 __global__ void k_cap_now(Tours S, int slot0, int count)
@@ -3190,6 +3197,11 @@ struct tspgpu_ctx {
     // Or-opt (tspgpu_oropt.inc)
     OrCtl *d_or = nullptr;     // control block, allocated on first use
     bool or_attr[9] = {false, false, false, false, false, false, false, false, false};
+    // ... over a batch of tours: one control block per slot, the list of slots a launch works on (device, and its pinned staging)
+    OrCtl *d_or_ctl = nullptr;
+    int *d_or_live = nullptr, *h_or_live = nullptr;
+    bool or_battr[9] = {false, false, false, false, false, false, false, false, false};
+    int or_batch_R = 0;        // positions per sweep workgroup in the first Or-opt round of the last batched descent
 
     Fused F{};                 // fused path state (allocated on first use, capacity fcap)
     int fcap = 0;
@@ -3259,7 +3271,11 @@ static void free_tour_scratch(tspgpu_ctx *ctx)
     if (ctx->d_caps) hipFree(ctx->d_caps);
     if (ctx->h_status) hipHostFree(ctx->h_status);
     if (ctx->h_costs) hipHostFree(ctx->h_costs);
+    if (ctx->d_or_ctl) hipFree(ctx->d_or_ctl);
+    if (ctx->d_or_live) hipFree(ctx->d_or_live);
+    if (ctx->h_or_live) hipHostFree(ctx->h_or_live);
     ctx->d_starts = ctx->d_caps = nullptr; ctx->h_status = nullptr; ctx->h_costs = nullptr;
+    ctx->d_or_ctl = nullptr; ctx->d_or_live = ctx->h_or_live = nullptr;
 }
 
 static void free_grid(tspgpu_ctx *ctx)
@@ -3351,6 +3367,9 @@ static int ensure_tours(tspgpu_ctx *ctx, int want)
     }
     HIP_TRY(hipHostMalloc(&ctx->h_status, T * 4 * 2));
     HIP_TRY(hipHostMalloc(&ctx->h_costs, T * 8));
+    HIP_TRY(hipMalloc(&ctx->d_or_ctl, T * sizeof(OrCtl)));     // (armed at the start of every batched Or-opt phase)
+    HIP_TRY(hipMalloc(&ctx->d_or_live, T * 4));
+    HIP_TRY(hipHostMalloc(&ctx->h_or_live, T * 4));
     ctx->tcap = want;
     ctx->slot_valid.resize(T, 0);
     return E_OK;
@@ -4829,6 +4848,8 @@ int tspgpu_set_option(tspgpu_ctx *ctx, int option, long value)
     return E_OK;
 }
 
+static int or_single_R(const tspgpu_ctx *ctx);      // (tspgpu_oropt.inc's driver, below)
+
 long tspgpu_info(const tspgpu_ctx *ctx, int what)
 {
     if (!ctx) return -1;
@@ -4868,6 +4889,8 @@ long tspgpu_info(const tspgpu_ctx *ctx, int what)
     case 27: return ctx->em_form;
     case 28: return ctx->em_stale;
     case 29: return ctx->em_steps;
+    case 30: return ctx->or_batch_R;
+    case 31: return or_single_R(ctx);
     case 12: return (ctx->built && ctx->grid_ok && ctx->opt_nn != 1 && ctx->cost_bound < 134217728.0) ? ctx->grid_G : 0;
     case 13: return ctx->grid_max_occ;
     }
@@ -5766,6 +5789,8 @@ static OrPlan or_plan(const tspgpu_ctx *ctx)
     return P;
 }
 
+static int or_single_R(const tspgpu_ctx *ctx) { return ctx->have_costs && !ctx->otf && ctx->n >= 8 ? or_plan(ctx).R : 0; }
+
 static int or_launch_sweep(tspgpu_ctx *ctx, int slot, const OrPlan &P)
 {
     if (!ctx->or_attr[P.fi]) {
@@ -5850,7 +5875,199 @@ static int or_descent(tspgpu_ctx *ctx, int slot, double time_left_s, long *two_o
     return rc;
 }
 
+// ---- the same descent over a batch of slots ----
+
+template <typename T> static const void *or_sweep_batch_fn(int nch)
+{
+    return nch == 1 ? (const void *)k_oropt_sweep_batch<T, 1> : nch == 2 ? (const void *)k_oropt_sweep_batch<T, 2>
+                                                                         : (const void *)k_oropt_sweep_batch<T, 3>;
+}
+
+// or_plan sizes R so that ONE tour's workgroups fill the chip; with `live` tours in flight fewer workgroups per tour do, and a
+// workgroup of R positions streams R + 2 rows: the largest R at which live * W still gives every CU two workgroups (one to
+// compute while the other waits at its barrier), never below the single-tour R
+static OrPlan or_plan_batch(const tspgpu_ctx *ctx, int live)
+{
+    OrPlan P = or_plan(ctx);
+    const int n = ctx->n;
+    const int occ = (int)std::max<size_t>(1, std::min<size_t>(ctx->lds_max / P.lds, (size_t)(2048 / P.BT)));
+    const long target = (long)ctx->cus * std::min(occ, 2);
+    for (int R = OR_RMAX; R > P.R; R--)
+        if ((long)live * ((n + R - 1) / R) >= target) { P.R = R; break; }
+    P.W = (n + P.R - 1) / P.R;
+    ELEM_SWITCH(ctx->elem, T, P.fn = or_sweep_batch_fn<T>(P.NCH));
+    return P;
+}
+
+// the slot list of the next launches: staged in pinned memory, so the stream must have drained the previous list first
+static int or_set_live(tspgpu_ctx *ctx, const std::vector<int> &list)
+{
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    memcpy(ctx->h_or_live, list.data(), list.size() * 4);
+    HIP_TRY(hipMemcpyAsync(ctx->d_or_live, ctx->h_or_live, list.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    return E_OK;
+}
+
+// one Or-opt round on the first `live` slots of the list: a sweep launch and an apply launch (grid rows in runs of 65 535)
+static int or_launch_round(tspgpu_ctx *ctx, int live, const OrPlan &P)
+{
+    if (!ctx->or_battr[P.fi]) {
+        HIP_TRY(hipFuncSetAttribute(P.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->lds_max));
+        ctx->or_battr[P.fi] = true;
+    }
+    for (int off = 0; off < live; off += 65535) {
+        const int rows = std::min(65535, live - off);
+        const int *list = ctx->d_or_live + off;
+#define OR_SWEEP(T, N) hipLaunchKernelGGL((k_oropt_sweep_batch<T, N>), dim3(P.W, rows), dim3(P.BT), P.lds, ctx->stream, ctx->S, \
+                                          (const T *)ctx->d_mat, ctx->n, ctx->ld, list, P.R, (const OrCtl *)ctx->d_or_ctl)
+        ELEM_SWITCH(ctx->elem, T, { if (P.NCH == 1) OR_SWEEP(T, 1); else if (P.NCH == 2) OR_SWEEP(T, 2); else OR_SWEEP(T, 3); });
+#undef OR_SWEEP
+        HIP_TRY(hipGetLastError());
+    }
+    const int BT = std::min(1024, std::max(64, pow2_ceil(ctx->n / 8)));
+    ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_oropt_apply_batch<T>), dim3(live), dim3(BT), 0, ctx->stream, ctx->S, (const T *)ctx->d_mat,
+                                                 ctx->n, ctx->ld, (const int *)ctx->d_or_live, P.W, ctx->d_or_ctl));
+    HIP_TRY(hipGetLastError());
+    return E_OK;
+}
+
+// or_descent on the slots slot0 .. slot0 + count - 1 at once; every tour goes through exactly the sequence or_descent runs on it.
+// A tour is LIVE until one of its Or-opt phases applies nothing.  Per round: the live tours are re-armed (k_rearm_list: a
+// finished tour keeps done = 1 and is skipped by the sweep kernels, so it runs no extra sweep) and run_sweeps takes the whole
+// range to the 2-opt optimum; then Or-opt rounds -- one sweep and one apply launch for all tours still in the phase -- with the
+// control blocks read back every 8 rounds (every round under a deadline) and the list rebuilt from them.
+// tw / om / nr: per-slot 2-opt sweeps, Or-opt moves and 2-opt descents, [count].
+static int or_descent_batch(tspgpu_ctx *ctx, int slot0, int count, double time_left_s, long *tw, long *om, int *nr, bool *late)
+{
+    const double t_end = time_left_s >= 0 ? now_s() + time_left_s : -1;
+    std::vector<int> live(count), act;
+    std::vector<OrCtl> hc(count);
+    for (int i = 0; i < count; i++) { live[i] = slot0 + i; tw[i] = om[i] = 0; nr[i] = 0; }
+    *late = false;
+    ctx->or_batch_R = 0;
+    int rc;
+    auto read_ctl = [&]() -> int {
+        HIP_TRY(hipMemcpyAsync(hc.data(), ctx->d_or_ctl + slot0, (size_t)count * sizeof(OrCtl), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        return E_OK;
+    };
+    while (!live.empty()) {
+        double left = -1;
+        if (t_end >= 0 && (left = t_end - now_s()) <= 0) { *late = true; break; }
+        const int nl = (int)live.size();
+        if ((rc = or_set_live(ctx, live))) return rc;
+        hipLaunchKernelGGL(k_rearm_list, dim3((nl + 255) / 256), dim3(256), 0, ctx->stream, ctx->S, (const int *)ctx->d_or_live, nl, -1);
+        HIP_TRY(hipGetLastError());
+        if ((rc = run_sweeps(ctx, slot0, count, false, -1, left, late))) return rc;
+        HIP_TRY(hipMemcpyAsync(ctx->h_status, ctx->S.nsweeps + slot0, (size_t)count * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        for (int t : live) { tw[t - slot0] += ctx->h_status[t - slot0]; nr[t - slot0]++; }
+        if (*late) break;
+        // the Or-opt phase of the live tours (the list uploaded above is still theirs)
+        hipLaunchKernelGGL(k_or_arm, dim3((nl + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_or_ctl, (const int *)ctx->d_or_live, nl);
+        HIP_TRY(hipGetLastError());
+        act = live;
+        bool fresh = true;      // d_or_live holds `act`
+        while (!act.empty()) {
+            if (t_end >= 0 && now_s() >= t_end) { *late = true; break; }
+            if (!fresh && (rc = or_set_live(ctx, act))) return rc;
+            fresh = false;
+            const OrPlan P = or_plan_batch(ctx, (int)act.size());
+            if (!ctx->or_batch_R) ctx->or_batch_R = P.R;
+            const int K = t_end >= 0 ? 1 : 8;
+            for (int i = 0; i < K; i++)
+                if ((rc = or_launch_round(ctx, (int)act.size(), P))) return rc;
+            if ((rc = read_ctl())) return rc;
+            size_t k = 0;
+            for (int t : act) if (!hc[t - slot0].stop) act[k++] = t;
+            act.resize(k);
+        }
+        if (*late && (rc = read_ctl())) return rc;
+        size_t k = 0;
+        for (int t : live) {
+            const long m = (long)hc[t - slot0].moves;
+            om[t - slot0] += m;
+            if (m > 0) live[k++] = t;
+        }
+        live.resize(k);
+        if (*late) break;
+    }
+    return E_OK;
+}
+
+// the argument checks of the batched entry points: the slots exist and hold tours
+static int or_batch_args(tspgpu_ctx *ctx, int slot0, int count)
+{
+    if (slot0 < 0 || count <= 0 || slot0 > INT_MAX - count) return fail(ctx, E_INVALID, "bad slot range: slot0 %d, count %d", slot0, count);
+    for (int i = 0; i < count; i++) {
+        const int rc = need_slot(ctx, slot0 + i);
+        if (rc) return rc;
+    }
+    return E_OK;
+}
+
 extern "C" {
+
+int tspgpu_tours_local_search(tspgpu_ctx *ctx, int slot0, int count, double time_left_s, long *two_opt_sweeps, long *or_moves, int *rounds)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    hipSetDevice(ctx->device);
+    int rc = or_check(ctx);
+    if (rc) return rc;
+    if ((rc = or_batch_args(ctx, slot0, count))) return rc;
+    std::vector<long> tw(count), om(count);
+    std::vector<int> nr(count);
+    bool late = false;
+    if ((rc = or_descent_batch(ctx, slot0, count, time_left_s, tw.data(), om.data(), nr.data(), &late))) return rc;
+    if (two_opt_sweeps) std::copy(tw.begin(), tw.end(), two_opt_sweeps);
+    if (or_moves) std::copy(om.begin(), om.end(), or_moves);
+    if (rounds) std::copy(nr.begin(), nr.end(), rounds);
+    return late ? E_DEADLINE : E_OK;
+}
+
+int tspgpu_multistart_local_search(tspgpu_ctx *ctx, const int *starts, int nstarts, double time_left_s, int *best_path, double *best_cost,
+                                   int *best_start, long *total_two_opt_sweeps, long *total_or_moves, double *costs_out)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    if (!best_path || !best_cost || !best_start || nstarts <= 0) return fail(ctx, E_INVALID, "bad argument");
+    hipSetDevice(ctx->device);
+    int rc = or_check(ctx);
+    if (rc) return rc;
+    if (ctx->opt_sweep_cap != -1)
+        return fail(ctx, E_INVALID, "TSPGPU_OPT_SWEEP_CAP = %d: the 2-opt + Or-opt descent runs every 2-opt phase to its local optimum", ctx->opt_sweep_cap);
+    const double t_end = time_left_s >= 0 ? now_s() + time_left_s : -1;
+    const int chunk = std::min(nstarts, ctx->opt_max_tours);
+    if ((rc = ensure_tours(ctx, chunk))) return rc;
+    double best = DBL_MAX; int arg = -1; long sweeps = 0, moves = 0;
+    bool late = false;
+    std::vector<int> hs(chunk), nr(chunk);
+    std::vector<long> tw(chunk), om(chunk);
+    for (int base = 0; base < nstarts && !late; base += chunk) {
+        const int m = std::min(chunk, nstarts - base);
+        for (int i = 0; i < m; i++) hs[i] = starts ? starts[base + i] : base + i;
+        if ((rc = launch_nn(ctx, 0, hs.data(), m))) return rc;
+        if ((rc = init_slots(ctx, 0, m, -1))) return rc;
+        mark_slots(ctx, 0, m, true);
+        const double left = t_end >= 0 ? std::max(0.0, t_end - now_s()) : -1;
+        if ((rc = or_descent_batch(ctx, 0, m, left, tw.data(), om.data(), nr.data(), &late))) return rc;
+        HIP_TRY(hipMemcpyAsync(ctx->h_costs, ctx->S.cost, (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        int win = -1;
+        for (int i = 0; i < m; i++) {
+            sweeps += tw[i]; moves += om[i];
+            if (costs_out) costs_out[base + i] = ctx->h_costs[i];
+            if (ctx->h_costs[i] < best) { best = ctx->h_costs[i]; win = i; }    // strict <: ties to the earliest entry
+        }
+        if (win >= 0) {
+            arg = hs[win];
+            if ((rc = store_path(ctx, win, best_path, nullptr, nullptr))) return rc;
+        }
+    }
+    *best_cost = best; *best_start = arg;
+    if (total_two_opt_sweeps) *total_two_opt_sweeps = sweeps;
+    if (total_or_moves) *total_or_moves = moves;
+    return late ? E_DEADLINE : E_OK;
+}
 
 int tspgpu_tour_or_opt(tspgpu_ctx *ctx, int slot, long max_moves, double time_left_s, long *moves)
 {

@@ -28,7 +28,7 @@ static constexpr int OR_EXTRA = 3072;       // LDS beside the four rows: nodes, 
 static constexpr int OR_QB = 17;            // bits of a node id (n <= 131 072)
 static constexpr u64 OR_QM = (1ull << OR_QB) - 1;
 
-struct OrCtl {              // one per context; reset before every run
+struct OrCtl {              // one per context for the single-tour calls, one per slot for the batch; reset before every run
     double d;               // delta of the last applied move (0: the last sweep found nothing improving)
     int move[4];            // s, L, q, rev of it (-1: none)
     int applied;            // the last apply launch applied a move
@@ -159,8 +159,9 @@ __global__ void __launch_bounds__(1024) k_oropt_sweep(Tours S, const T *__restri
     }
 }
 
+// the body of the apply kernels: one workgroup, tour slot t, G partials, that tour's control block
 template <typename T>
-__global__ void __launch_bounds__(1024) k_oropt_apply(Tours S, const T *__restrict__ mat, int n, int ld, int t, int G, OrCtl *ctl)
+__device__ __forceinline__ void or_apply_tour(const Tours &S, const T *__restrict__ mat, int n, int ld, int t, int G, OrCtl *ctl)
 {
     typedef typename Elem<T>::acc AT;
     __shared__ Partial scratch[16];
@@ -248,4 +249,150 @@ __global__ void __launch_bounds__(1024) k_oropt_apply(Tours S, const T *__restri
         ctl->moves += 1;
         if (budget >= 0) { ctl->budget = budget - 1; if (budget - 1 <= 0) ctl->stop = 1; }
     }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(1024) k_oropt_apply(Tours S, const T *__restrict__ mat, int n, int ld, int t, int G, OrCtl *ctl)
+{
+    or_apply_tour<T>(S, mat, n, ld, t, G, ctl);
+}
+
+// ---------------------------------------------------------------------------
+// The batch: row y of the sweep grid (workgroup y of the apply grid) works on tour slot live[y] under that slot's own
+// control block ctl[slot]; a tour whose `stop` is up costs an early return until the host drops it from the list.
+// The sweep is k_oropt_sweep with one change: the q a thread visits are the same for every position of its workgroup,
+// so succ[q] and dnb[q] are loaded once into registers (NCH * V of each: n <= ld <= BT * NCH * V) and not per position.
+// ---------------------------------------------------------------------------
+template <typename T, int NCH>
+__global__ void __launch_bounds__(1024) k_oropt_sweep_batch(Tours S, const T *__restrict__ mat, int n, int ld, const int *__restrict__ live,
+                                                            int R, const OrCtl *ctl)
+{
+    typedef typename Elem<T>::acc AT;
+    typedef typename Elem<T>::vec VT;
+    constexpr int V = Elem<T>::V, QN = NCH * V;
+    extern __shared__ __attribute__((aligned(16))) unsigned char or_smem[];
+    const int t = live[blockIdx.y];
+    if (ctl[t].stop) return;
+    T *rows = reinterpret_cast<T *>(or_smem);                                         // as k_oropt_sweep
+    int *nodes = reinterpret_cast<int *>(or_smem + (size_t)4 * ld * sizeof(T));
+    double *dn8 = reinterpret_cast<double *>(nodes + OR_RMAX + 4);
+    AT *dn = reinterpret_cast<AT *>(dn8);
+    AT *pxc = reinterpret_cast<AT *>(dn8 + OR_RMAX + 4);
+    Partial *scratch = reinterpret_cast<Partial *>(dn8 + OR_RMAX + 4 + 3 * OR_RMAX);
+
+    const int tid = threadIdx.x, BT = blockDim.x;
+    const int k0 = (int)blockIdx.x * R, cnt = min(R, n - k0);
+    const int dir = S.dir[t];
+    const int *ord = S.ord + (size_t)t * n, *succ = S.succ + (size_t)t * n;
+    const AT *dnb = dnb_of<AT>(S, t, n);
+    const int nvec = ld / V;
+
+    for (int j = tid; j < cnt + 4; j += BT) {
+        const int v = ord[or_cell(k0 - 1 + j, n, dir)];
+        nodes[j] = v;
+        dn[j] = dnb[v];
+    }
+    int qnx[QN];
+    AT cqx[QN];
+#pragma unroll
+    for (int j = 0; j < QN; j++) {
+        const int q = tid + j * BT;
+        qnx[j] = q < n ? succ[q] : 0;
+        cqx[j] = q < n ? dnb[q] : (AT)0;
+    }
+    __syncthreads();
+    for (int j = tid; j < 3 * cnt; j += BT) {
+        const int i = j / 3, L = j % 3 + 1;
+        pxc[j] = (AT)mat[(size_t)nodes[i] * ld + nodes[i + 1 + L]];
+    }
+    for (int r = 0; r < 3; r++) {
+        const VT *src = reinterpret_cast<const VT *>(mat + (size_t)nodes[r + 1] * ld);
+        VT *dst = reinterpret_cast<VT *>(rows + (size_t)r * ld);
+#pragma unroll
+        for (int c = 0; c < NCH; c++) {
+            const int idx = tid + c * BT;
+            if (idx < nvec) dst[idx] = src[idx];
+        }
+    }
+    __syncthreads();
+
+    AT bd = Elem<T>::lim();
+    u64 bk = KEY_NONE;
+    for (int i = 0; i < cnt; i++) {
+        const bool more = i + 3 <= cnt + 1;
+        VT nxt[NCH];
+        if (more) {
+            const VT *src = reinterpret_cast<const VT *>(mat + (size_t)nodes[i + 4] * ld);
+#pragma unroll
+            for (int c = 0; c < NCH; c++) {
+                const int idx = tid + c * BT;
+                if (idx < nvec) nxt[c] = src[idx];
+            }
+        }
+        const int p = nodes[i], s = nodes[i + 1], n1 = nodes[i + 2], n2 = nodes[i + 3];
+        const T *rA = rows + (size_t)(i & 3) * ld, *rB = rows + (size_t)((i + 1) & 3) * ld, *rC = rows + (size_t)((i + 2) & 3) * ld;
+        const AT cps = dn[i];
+        const AT rem1 = cps + dn[i + 1], rem2 = cps + dn[i + 2], rem3 = cps + dn[i + 3];
+        const AT px1 = pxc[3 * i], px2 = pxc[3 * i + 1], px3 = pxc[3 * i + 2];
+        const u64 ks = (u64)s << (OR_QB + 3);
+#pragma unroll
+        for (int j = 0; j < QN; j++) {
+            const int q = tid + j * BT;
+            if (q < n) {
+                const int qn = qnx[j];
+                const AT cqq = cqx[j];
+                const AT aq = (AT)rA[q], bq = (AT)rB[q], cq = (AT)rC[q];
+                const AT an = (AT)rA[qn], bn = (AT)rB[qn], cn = (AT)rC[qn];
+                const bool ok1 = q != p && q != s, ok2 = ok1 && q != n1, ok3 = ok2 && q != n2;
+                const u64 kq = ks | (u64)q << 1;
+#define OR_CONSIDER(OK, HQ, EN, PX, REM, L, REV)                                                   \
+                {                                                                                  \
+                    const AT d_ = ((PX + HQ) + EN) - (REM + cqq);                                  \
+                    const u64 k_ = kq | (u64)(L) << (OR_QB + 1) | (u64)(REV);                      \
+                    if ((OK) && (d_ < bd || (d_ == bd && k_ < bk))) { bd = d_; bk = k_; }          \
+                }
+                OR_CONSIDER(ok1, aq, an, px1, rem1, 1, 0)
+                OR_CONSIDER(ok2, aq, bn, px2, rem2, 2, 0)
+                OR_CONSIDER(ok2, bq, an, px2, rem2, 2, 1)
+                OR_CONSIDER(ok3, aq, cn, px3, rem3, 3, 0)
+                OR_CONSIDER(ok3, cq, an, px3, rem3, 3, 1)
+#undef OR_CONSIDER
+            }
+        }
+        if (more) {
+            VT *dst = reinterpret_cast<VT *>(rows + (size_t)((i + 3) & 3) * ld);
+#pragma unroll
+            for (int c = 0; c < NCH; c++) {
+                const int idx = tid + c * BT;
+                if (idx < nvec) dst[idx] = nxt[c];
+            }
+        }
+        __syncthreads();
+    }
+    double d = bk == KEY_NONE ? DBL_MAX : (double)bd;
+    block_argmin(d, bk, scratch);
+    if (tid == 0) {
+        Partial *part = S.partial + (size_t)t * S.pstride;
+        part[blockIdx.x].d = d;
+        part[blockIdx.x].key = bk;
+    }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(1024) k_oropt_apply_batch(Tours S, const T *__restrict__ mat, int n, int ld, const int *__restrict__ live,
+                                                            int G, OrCtl *ctl)
+{
+    const int t = live[blockIdx.x];
+    or_apply_tour<T>(S, mat, n, ld, t, G, ctl + t);
+}
+
+// control blocks of the listed slots := "nothing applied yet, no move budget" (the start of a batch's Or-opt phase)
+__global__ void k_or_arm(OrCtl *ctl, const int *__restrict__ list, int count)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    OrCtl c;
+    c.d = 0.0; c.move[0] = c.move[1] = c.move[2] = c.move[3] = -1;
+    c.applied = 0; c.stop = 0; c.moves = 0; c.budget = -1;
+    ctl[list[i]] = c;
 }

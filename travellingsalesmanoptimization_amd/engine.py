@@ -50,7 +50,7 @@ class Engine:
         names = ["n", "ld", "elem", "kernel", "wgs_per_tour", "lds_bytes", "block", "symmetric", "cus", "depth", "matrix_free", "fused",
                  "nn_grid", "nn_grid_max_cell", "pipe2", "persist", "persist_wgs", "persist_edges", "persist_lds", "persist_window_cells",
                  "persist_window", "persist_handed", "persist_sweeps", "vns_mode", "stream_persist",
-                 "otf_kernel", "ceil_int", "em_form", "em_stale", "em_steps"]
+                 "otf_kernel", "ceil_int", "em_form", "em_stale", "em_steps", "or_batch_r", "or_single_r"]
         return {k: int(self.L.tspgpu_info(self.ctx, i)) for i, k in enumerate(names)}
 
     # ---- instance
@@ -209,6 +209,19 @@ class Engine:
         return {"path": best, "cost": c.value, "start": s.value, "sweeps": sw.value, "rc": rc,
                 "last_path": last, "last_cost": lc.value if want_last else None}
 
+    def multistart_local_search(self, starts=None, time_left_s=-1.0):
+        """NN + the 2-opt + Or-opt descent from every start, batched ->
+        dict(path, cost, start, two_opt_sweeps, or_moves, costs, rc); costs[i] is the final cost of list entry i."""
+        p, m, keep = self._starts(starts, self.n)
+        best = np.empty(self.n, dtype=np.int32)
+        c, s, sw, om = C.c_double(), C.c_int(), C.c_long(), C.c_long()
+        costs = np.full(m, np.nan, dtype=np.float64)
+        rc = self._ck(self.L.tspgpu_multistart_local_search(self.ctx, p, m, float(time_left_s), best, C.byref(c), C.byref(s),
+                                                            C.byref(sw), C.byref(om), costs.ctypes.data),
+                      ok=(T_OK, DEADLINE_EXCEEDED))
+        return {"path": best, "cost": c.value, "start": s.value, "two_opt_sweeps": sw.value, "or_moves": om.value,
+                "costs": costs, "rc": rc}
+
     # ---- device-resident
     def tour_load(self, slot, path):
         self._ck(self.L.tspgpu_tour_load(self.ctx, slot, np.ascontiguousarray(path, np.int32)))
@@ -238,6 +251,17 @@ class Engine:
         rc = self._ck(self.L.tspgpu_tour_local_search(self.ctx, int(slot), float(time_left_s), C.byref(sw), C.byref(om), C.byref(nr)),
                       ok=(T_OK, DEADLINE_EXCEEDED))
         return {"two_opt_sweeps": sw.value, "or_moves": om.value, "rounds": nr.value, "rc": rc}
+
+    def tours_local_search(self, slot0, count, time_left_s=-1.0):
+        """the descent of tour_local_search on slots slot0 .. slot0+count-1 at once ->
+        dict(two_opt_sweeps, or_moves, rounds: arrays of count entries, rc)."""
+        count = int(count)
+        sw, om = np.zeros(max(count, 0), dtype=np.int64), np.zeros(max(count, 0), dtype=np.int64)
+        nr = np.zeros(max(count, 0), dtype=np.int32)
+        rc = self._ck(self.L.tspgpu_tours_local_search(self.ctx, int(slot0), count, float(time_left_s),
+                                                       sw.ctypes.data, om.ctypes.data, nr.ctypes.data),
+                      ok=(T_OK, DEADLINE_EXCEEDED))
+        return {"two_opt_sweeps": sw, "or_moves": om, "rounds": nr, "rc": rc}
 
     def time_or_sweep(self, slot, reps):
         ms = C.c_float()
@@ -346,6 +370,16 @@ class MultiEngine:
         rc = self._ck(self.L.tspgpu_multi_multistart_nn_2opt(self.m, p, m, float(time_left_s), best, C.byref(c), C.byref(s), C.byref(sw)),
                       ok=(T_OK, DEADLINE_EXCEEDED))
         return {"path": best, "cost": c.value, "start": s.value, "sweeps": sw.value, "rc": rc}
+
+    def multistart_local_search(self, starts=None, time_left_s=-1.0):
+        """Engine.multistart_local_search over every device -> dict(path, cost, start, two_opt_sweeps, or_moves, rc)."""
+        p, m, keep = Engine._starts(starts, self.n)
+        best = np.empty(self.n, dtype=np.int32)
+        c, s, sw, om = C.c_double(), C.c_int(), C.c_long(), C.c_long()
+        rc = self._ck(self.L.tspgpu_multi_multistart_local_search(self.m, p, m, float(time_left_s), best, C.byref(c), C.byref(s),
+                                                                  C.byref(sw), C.byref(om)),
+                      ok=(T_OK, DEADLINE_EXCEEDED))
+        return {"path": best, "cost": c.value, "start": s.value, "two_opt_sweeps": sw.value, "or_moves": om.value, "rc": rc}
 
     def nn_all(self, starts=None, time_left_s=-1.0):
         """h_Greedy_iterative (heuristics.c:34-72) over every device -> (best_path, best_cost, best_start, done, rc)."""

@@ -697,28 +697,71 @@ ERROR_CODE tsp_or_opt_polish(tsp_solution *solution)
     return from_rc(rc);
 }
 
-/* TSP_OR_OPT: unset or 0 = off, 1 = polish the incumbent after the heuristic; anything else is an error (-1) */
-static int or_opt_switch(void)
+/* h_greedy_2opt with the 2-opt + Or-opt descent from EVERY start (tspgpu_multistart_local_search: the starts of a chunk
+ * descend together), not only as a polish of the 2-opt winner; the incumbent, starting_node and the deadline are handled as
+ * in h_greedy_2opt.  An instance the descent does not take (matrix-free, fewer than 8 nodes, rows past the LDS limit, an
+ * asymmetric matrix) gets a warning and the plain h_greedy_2opt. */
+ERROR_CODE h_greedy_local_search(void)
 {
-    const char *v = getenv("TSP_OR_OPT");
+    log_info("running All Nearest Neighbour + 2OPT + Or-opt");
+    if (past_deadline()) { log_warn("time limit exceeded in greedy local search"); return DEADLINE_EXCEEDED; }
+    tspgpu_ctx *g = tsp_gpu();
+    if (!g) return UNAVAILABLE;
+    if (tsp_matrix_free) {
+        log_warn("TSP_OR_OPT_EVERY_START=1: Or-opt needs the cost matrix and the instance runs matrix-free; running the plain multi-start");
+        return h_greedy_2opt();
+    }
+    tsp_solution s;
+    tsp_init_solution(tsp_inst.nnodes, &s);
+    int start = -1;
+    long sweeps = 0, moves = 0;
+    struct tspgpu_multi *m = tsp_gpu_multi();
+    const double t0 = utils_timeelapsed(&tsp_inst.c);
+    int rc = m ? tspgpu_multi_multistart_local_search(m, NULL, tsp_inst.nnodes, time_left(), s.path, &s.cost, &start, &sweeps, &moves)
+               : tspgpu_multistart_local_search(g, NULL, tsp_inst.nnodes, time_left(), s.path, &s.cost, &start, &sweeps, &moves, NULL);
+    ERROR_CODE e = from_rc(rc);
+    if (or_opt_refusal(e)) {
+        log_warn("TSP_OR_OPT_EVERY_START=1: %s; running the plain multi-start", m ? tspgpu_multi_last_error(m) : tspgpu_last_error(g));
+        free(s.path); free(s.comp);
+        return h_greedy_2opt();
+    }
+    multi_stats("h_greedy_local_search", m, tsp_inst.nnodes, sweeps, utils_timeelapsed(&tsp_inst.c) - t0, s.cost);
+    if (rc != 0 && rc != DEADLINE_EXCEEDED) {
+        log_error("tspgpu_multistart_local_search: %s", m ? tspgpu_multi_last_error(m) : tspgpu_last_error(g));
+    } else {
+        ERROR_CODE u = tsp_update_best_solution(&s);
+        if (!err_ok(u)) log_error("code %d : Error in local search solution update", u);
+        if (rc == 0) tsp_inst.starting_node = tsp_inst.nnodes - 1;
+        else log_warn("time limit exceeded in greedy local search");
+        log_debug("best start %d, cost %f, %ld 2-opt sweeps, %ld Or-opt moves", start, s.cost, sweeps, moves);
+    }
+    free(s.path); free(s.comp);
+    return e;
+}
+
+/* TSP_OR_OPT (1 = polish the incumbent after the heuristic) and TSP_OR_OPT_EVERY_START (1 = -alg 2OPT_GREEDY runs
+ * h_greedy_local_search): unset or 0 = off; anything else is an error (-1) */
+static int env_switch(const char *name)
+{
+    const char *v = getenv(name);
     if (!v || !strcmp(v, "0")) return 0;
     if (!strcmp(v, "1")) return 1;
-    fprintf(stderr, "tsp: TSP_OR_OPT=\"%s\": expected 0 or 1\n", v);     /* (shown under -q too: a mistyped switch must not pass silently) */
+    fprintf(stderr, "tsp: %s=\"%s\": expected 0 or 1\n", name, v);     /* (shown under -q too: a mistyped switch must not pass silently) */
     return -1;
 }
 
 /* ===================================================================== main.c:4-87 */
 ERROR_CODE tsp_run_algorithm(void)
 {
-    const int polish = or_opt_switch();
-    if (polish < 0) return INVALID_ARGUMENT;
+    const int polish = env_switch("TSP_OR_OPT"), every_start = env_switch("TSP_OR_OPT_EVERY_START");
+    if (polish < 0 || every_start < 0) return INVALID_ARGUMENT;
     free(tsp_inst.best_solution.path);
     tsp_inst.best_solution.path = (int *)calloc((size_t)tsp_inst.nnodes, sizeof(int));
     ERROR_CODE e;
     switch (tsp_inst.alg) {
     case ALG_GREEDY: e = h_Greedy(); break;
     case ALG_GREEDY_ITER: e = h_Greedy_iterative(); break;
-    case ALG_2OPT_GREEDY: e = h_greedy_2opt(); break;
+    case ALG_2OPT_GREEDY: e = every_start ? h_greedy_local_search() : h_greedy_2opt(); break;
     case ALG_TABU_SEARCH: e = mh_TabuSearch(); break;
     case ALG_VNS: e = mh_VNS(); break;
     case ALG_EXTRAMILEAGE: e = h_ExtraMileage(); break;

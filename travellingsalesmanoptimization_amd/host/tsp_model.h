@@ -159,6 +159,7 @@ ERROR_CODE tabu_make_move(int *prev, tsp_solution *solution, int bestCase, int i
                           int k, int succ_k);                /* metaheuristic.c:425-507 */
 
 /* ---- src/main.c ------------------------------------------------------------------ */
+ERROR_CODE h_greedy_local_search(void);                      /* extension: h_greedy_2opt with the 2-opt + Or-opt descent from every start (TSP_OR_OPT_EVERY_START=1) */
 ERROR_CODE tsp_or_opt_polish(tsp_solution *solution);         /* extension: 2-opt + Or-opt descent on the device (TSP_OR_OPT=1) */
 ERROR_CODE tsp_run_algorithm(void);                          /* main.c:4-87 (heuristic algorithms only) */
 
