@@ -114,7 +114,9 @@ int  tspgpu_set_option(tspgpu_ctx *ctx, int option, long value);
  * 3 k_sweep_otf8 with the exact early-out), 26 CEIL_2D weights come from the exact integer ceil-sqrt of integer coordinates
  * (cost bound below 2^22; 0: the generic double form, or another kind), 27 how the last tspgpu_extra_mileage ran (1 one launch,
  * 2 one launch pair per step), 28 / 29 its stale-node rescans / insertions, 30 tour positions per Or-opt sweep workgroup (R) in
- * the first Or-opt round of the last batched descent (tspgpu_tours_local_search and the calls built on it; 0: none ran), 31 the R of a single-tour Or-opt sweep on this instance (0: no matrix) */
+ * the first Or-opt round of the last batched descent (tspgpu_tours_local_search and the calls built on it; 0: none ran), 31 the R of a single-tour Or-opt sweep on this instance (0: no matrix),
+ * 32 / 33 threads per workgroup (256, 512 or 1024) and 16-byte vectors per thread and matrix row (1, 2 or 3) of an Or-opt sweep,
+ * single-tour or batched, on this instance (0 where 31 is 0) */
 long tspgpu_info(const tspgpu_ctx *ctx, int what);
 
 /* ---- instance / cost matrix ------------------------------------------- */

@@ -4849,6 +4849,7 @@ int tspgpu_set_option(tspgpu_ctx *ctx, int option, long value)
 }
 
 static int or_single_R(const tspgpu_ctx *ctx);      // (tspgpu_oropt.inc's driver, below)
+static int or_single_geom(const tspgpu_ctx *ctx, bool nch);
 
 long tspgpu_info(const tspgpu_ctx *ctx, int what)
 {
@@ -4891,6 +4892,8 @@ long tspgpu_info(const tspgpu_ctx *ctx, int what)
     case 29: return ctx->em_steps;
     case 30: return ctx->or_batch_R;
     case 31: return or_single_R(ctx);
+    case 32: return or_single_geom(ctx, false);
+    case 33: return or_single_geom(ctx, true);
     case 12: return (ctx->built && ctx->grid_ok && ctx->opt_nn != 1 && ctx->cost_bound < 134217728.0) ? ctx->grid_G : 0;
     case 13: return ctx->grid_max_occ;
     }
@@ -5790,6 +5793,13 @@ static OrPlan or_plan(const tspgpu_ctx *ctx)
 }
 
 static int or_single_R(const tspgpu_ctx *ctx) { return ctx->have_costs && !ctx->otf && ctx->n >= 8 ? or_plan(ctx).R : 0; }
+// threads per sweep workgroup, or -- nch -- 16-byte vectors per thread and row, of the same plan (0 where or_single_R is 0)
+static int or_single_geom(const tspgpu_ctx *ctx, bool nch)
+{
+    if (!or_single_R(ctx)) return 0;
+    const OrPlan P = or_plan(ctx);
+    return nch ? P.NCH : P.BT;
+}
 
 static int or_launch_sweep(tspgpu_ctx *ctx, int slot, const OrPlan &P)
 {
