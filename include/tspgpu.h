@@ -87,10 +87,12 @@ enum {
     TSPGPU_OPT_PERSIST_WINDOW = 18 /* rows of that kernel: 0 auto (whole rows where they fit the chip's LDS, else the half
                                    window of n/2 cells ahead of the workgroup's own edges), 1 half-window rows wherever they
                                    apply, 2 whole rows only */,
-    TSPGPU_OPT_EM_FORM = 21     /* Extra Mileage insertion loop (tspgpu_extra_mileage): 0 (default) and 2 one launch pair per
+    TSPGPU_OPT_EM_FORM = 21,    /* Extra Mileage insertion loop (tspgpu_extra_mileage): 0 (default) and 2 one launch pair per
                                    step, enqueued back to back (measured faster); 1 ONE launch for the whole construction
                                    (one workgroup per CU, a grid barrier between phases), or fail with code 8 when the grid
                                    does not come up co-resident */
+    TSPGPU_OPT_OR_MATRIX_FREE = 22 /* Or-opt in matrix-free mode (the section "Or-opt" below): 0 (default) refused with code 12,
+                                   1 the single-tour entry points run from the uploaded coordinates; any other value: 3 */
 };
 
 int  tspgpu_device_count(void);
@@ -116,7 +118,8 @@ int  tspgpu_set_option(tspgpu_ctx *ctx, int option, long value);
  * 2 one launch pair per step), 28 / 29 its stale-node rescans / insertions, 30 tour positions per Or-opt sweep workgroup (R) in
  * the first Or-opt round of the last batched descent (tspgpu_tours_local_search and the calls built on it; 0: none ran), 31 the R of a single-tour Or-opt sweep on this instance (0: no matrix),
  * 32 / 33 threads per workgroup (256, 512 or 1024) and 16-byte vectors per thread and matrix row (1, 2 or 3) of an Or-opt sweep,
- * single-tour or batched, on this instance (0 where 31 is 0) */
+ * single-tour or batched, on this instance (0 where 31 is 0), 34 how the last matrix-free Or-opt sweep ran (0 none, 1 every candidate
+ * evaluated, 2 with the exact early-out), 35 tour positions per workgroup of that sweep (0 where 34 is 0) */
 long tspgpu_info(const tspgpu_ctx *ctx, int what);
 
 /* ---- instance / cost matrix ------------------------------------------- */
@@ -213,7 +216,15 @@ int tspgpu_extra_mileage(tspgpu_ctx *ctx, int a, int b, double time_left_s, int 
  * Preconditions: n >= 8 (else 3), a symmetric matrix (tspgpu_info 7, else 9), MATRIX MODE ONLY -- in matrix-free mode
  * every entry point of this section returns UNIMPLEMENTED (12) --, and four matrix rows of ld = n rounded up to 32 cells
  * plus 3072 bytes in one workgroup's 160 KiB of LDS: n <= 20 096 with uint16 cells, 10 048 with int32, 5 024 with
- * doubles, else RESOURCE_EXHAUSTED (8) with the limit in the error text.  Without a context (no device): 14. */
+ * doubles, else RESOURCE_EXHAUSTED (8) with the limit in the error text.  Without a context (no device): 14.
+ * With TSPGPU_OPT_OR_MATRIX_FREE = 1 the single-tour entry points -- tspgpu_or_opt_once, tspgpu_or_opt,
+ * tspgpu_local_search, tspgpu_tour_or_opt, tspgpu_tour_local_search, tspgpu_time_or_sweep -- also run in matrix-free mode,
+ * with the costs matrix mode would hold for the same points and kind recomputed from the coordinates: the same move, tie
+ * order, outputs and deadline behaviour, so the whole descent equals the matrix-mode descent of the instance move for move.
+ * There the preconditions are n >= 8 (else 3) and what matrix-free mode itself guarantees (integer costs below 2^27,
+ * n <= 131 072, symmetry): there is no row-in-LDS limit.  The batch entry points (tspgpu_tours_local_search,
+ * tspgpu_multistart_local_search, tspgpu_multi_multistart_local_search) stay refused with 12 in matrix-free mode whatever
+ * the option says. */
 
 /* one Or-opt sweep on a host tour; applies the move when delta < -1e-7.  *cost is the caller's running cost (as
  * tspgpu_two_opt_once).  move[4] = {s, L, q, rev} of the applied move (all -1 and *delta = 0 when nothing improves) */

@@ -22,6 +22,8 @@ OPT_ELEM, OPT_KERNEL, OPT_BATCH, OPT_WGS_PER_TOUR, OPT_HISTORY = 1, 2, 3, 4, 5
 OPT_GRAPH, OPT_TIMING, OPT_BLOCK, OPT_MAX_TOURS, OPT_DEPTH, OPT_MATRIX_FREE, OPT_FUSED, OPT_SWEEP_CAP, OPT_NN_KERNEL, OPT_PIPE2 = 6, 7, 8, 9, 10, 11, 12, 13, 14, 15
 OPT_PERSIST, OPT_PERSIST_EDGES, OPT_PERSIST_WINDOW, OPT_BUILD_KERNEL, OPT_STREAM_PERSIST = 16, 17, 18, 19, 20
 OPT_EM_FORM = 21
+OPT_OR_MATRIX_FREE = 22
+INFO_OR_OTF, INFO_OR_OTF_R = 34, 35     # tspgpu_info: form (0 none, 1 full, 2 early-out) and R of the last matrix-free Or-opt sweep
 EM_FORM_AUTO, EM_FORM_RESIDENT, EM_FORM_PER_STEP = 0, 1, 2
 MOPT_EXCHANGE = 1000
 EXCHANGE_AUTO, EXCHANGE_HOST, EXCHANGE_RCCL = 0, 1, 2

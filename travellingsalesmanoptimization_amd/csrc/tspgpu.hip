@@ -3202,6 +3202,11 @@ struct tspgpu_ctx {
     int *d_or_live = nullptr, *h_or_live = nullptr;
     bool or_battr[9] = {false, false, false, false, false, false, false, false, false};
     int or_batch_R = 0;        // positions per sweep workgroup in the first Or-opt round of the last batched descent
+    // ... in matrix-free mode (k_oropt_sweep_otf): single tours only
+    int opt_or_otf = 0;        // TSPGPU_OPT_OR_MATRIX_FREE: 0 refuse Or-opt in matrix-free mode (code 12), 1 run it from the points
+    int opt_or_otf_early = 0;  // hook 90: 0 automatic, 1 the early-out form for every matrix-free Or-opt sweep, 2 never
+    int or_otf_form = 0;       // how the last matrix-free Or-opt sweep ran: 0 none, 1 every candidate, 2 with the early-out
+    int or_otf_R = 0;          // its tour positions per workgroup
 
     Fused F{};                 // fused path state (allocated on first use, capacity fcap)
     int fcap = 0;
@@ -3239,6 +3244,7 @@ static void free_matrix(tspgpu_ctx *ctx)
 {
     if (ctx->d_mat) hipFree(ctx->d_mat);
     ctx->d_mat = nullptr; ctx->have_costs = false;
+    ctx->or_otf_form = ctx->or_otf_R = 0;
     std::fill(ctx->slot_valid.begin(), ctx->slot_valid.end(), 0);   // the slots' edge costs belong to the old matrix
     drop_graphs(ctx);
 }
@@ -4819,6 +4825,7 @@ int tspgpu_set_option(tspgpu_ctx *ctx, int option, long value)
     case TSPGPU_OPT_BLOCK: if (value < 0 || value > 1024) return fail(ctx, E_INVALID, "bad block"); ctx->opt_block = (int)value; ctx->plan_kernel = 0; break;
     case TSPGPU_OPT_DEPTH: if (value < 0 || value > 8) return fail(ctx, E_INVALID, "bad depth"); ctx->opt_depth = (int)value; ctx->plan_kernel = 0; break;
     case 99: ctx->opt_ablate = (int)value; drop_graphs(ctx); break; // undocumented: kernel ablation for profiling
+    case 90: ctx->opt_or_otf_early = value == 1 || value == 2 ? (int)value : 0; break; // undocumented: see or_otf_early()
     case 91: ctx->opt_otf_early = value == 1 || value == 2 ? (int)value : 0; ctx->plan_kernel = 0; drop_graphs(ctx); break; // undocumented: see otf_early()
     case 92: ctx->opt_build_tile = (int)value; break; // undocumented: tile of the triangle build (tools/build_probe.py)
     case 93: ctx->opt_sp_nch = value == 1 || value == 2 ? (int)value : 0; break; // undocumented: vectors per thread of k_str2opt (tools/stream_probe.py)
@@ -4842,6 +4849,7 @@ int tspgpu_set_option(tspgpu_ctx *ctx, int option, long value)
     case TSPGPU_OPT_PIPE2: if (value < 0 || value > 1) return fail(ctx, E_INVALID, "bad pipe2 mode"); ctx->opt_pipe2 = (int)value; ctx->plan_kernel = 0; drop_graphs(ctx); break;
     case TSPGPU_OPT_NN_KERNEL: if (value < 0 || value > 3) return fail(ctx, E_INVALID, "bad NN kernel id"); ctx->opt_nn = (int)value; break;
     case TSPGPU_OPT_EM_FORM: if (value < 0 || value > 2) return fail(ctx, E_INVALID, "bad Extra Mileage form"); ctx->opt_em_form = (int)value; break;
+    case TSPGPU_OPT_OR_MATRIX_FREE: if (value < 0 || value > 1) return fail(ctx, E_INVALID, "bad matrix-free Or-opt mode"); ctx->opt_or_otf = (int)value; break;
     case TSPGPU_OPT_SWEEP_CAP: if (value < -1 || value > INT_MAX) return fail(ctx, E_INVALID, "bad sweep cap"); ctx->opt_sweep_cap = (int)value; break;
     default: return fail(ctx, E_INVALID, "unknown option %d", option);
     }
@@ -4894,6 +4902,8 @@ long tspgpu_info(const tspgpu_ctx *ctx, int what)
     case 31: return or_single_R(ctx);
     case 32: return or_single_geom(ctx, false);
     case 33: return or_single_geom(ctx, true);
+    case 34: return ctx->or_otf_form;
+    case 35: return ctx->or_otf_R;
     case 12: return (ctx->built && ctx->grid_ok && ctx->opt_nn != 1 && ctx->cost_bound < 134217728.0) ? ctx->grid_G : 0;
     case 13: return ctx->grid_max_occ;
     }
@@ -5750,11 +5760,24 @@ int tspgpu_extra_mileage(tspgpu_ctx *ctx, int a, int b, double time_left_s, int 
 // largest n the Or-opt sweep takes with cells of `esz` bytes: four rows of ld cells and OR_EXTRA bytes in one workgroup's LDS
 static int or_max_n(const tspgpu_ctx *ctx, size_t esz) { return (int)((ctx->lds_max - OR_EXTRA) / (4 * esz)) & ~31; }
 
-static int or_check(tspgpu_ctx *ctx)
+// batch: the entry points over several slots, which matrix-free mode refuses whatever TSPGPU_OPT_OR_MATRIX_FREE says
+static int or_check(tspgpu_ctx *ctx, bool batch = false)
 {
     int rc = need_costs(ctx);
     if (rc) return rc;
-    if (ctx->otf) return fail(ctx, E_UNIMPL, "Or-opt needs the resident cost matrix: it is not implemented in matrix-free mode");
+    if (ctx->otf && (batch || !ctx->opt_or_otf))
+        return fail(ctx, E_UNIMPL, "Or-opt needs the resident cost matrix: it is not implemented in matrix-free mode");
+    if (ctx->otf) {     // from the points: symmetric by construction, costs below 2^27, n <= 131 072 (new_instance), no row in LDS
+        if (ctx->n < 8) return fail(ctx, E_INVALID, "Or-opt needs at least 8 nodes, got %d", ctx->n);
+        if (ctx->spts_cap < (size_t)ctx->n) {       // the gathered successor points, sized as make_plan sizes them for one tour
+            if (ctx->d_spts) hipFree(ctx->d_spts);
+            ctx->d_spts = nullptr; ctx->spts_cap = 0;
+            HIP_TRY(hipMalloc(&ctx->d_spts, (size_t)ctx->n * sizeof(double2)));
+            ctx->spts_cap = (size_t)ctx->n;
+        }
+        if (!ctx->d_or) HIP_TRY(hipMalloc(&ctx->d_or, sizeof(OrCtl)));
+        return E_OK;
+    }
     if (ctx->n < 8) return fail(ctx, E_INVALID, "Or-opt needs at least 8 nodes, got %d", ctx->n);
     if (!ctx->symmetric) return fail(ctx, E_PRECOND, "Or-opt needs a symmetric cost matrix");
     const int lim = or_max_n(ctx, elem_size(ctx->elem));
@@ -5766,16 +5789,27 @@ static int or_check(tspgpu_ctx *ctx)
 }
 
 // geometry of a sweep launch: threads, 16-byte vectors per thread and row, positions per workgroup, workgroups, LDS bytes
-struct OrPlan { int BT, NCH, R, W; size_t lds; const void *fn; int fi; };
+// (matrix-free mode: BT = 256, NCH = 0, R = OR_OTF_RUN, no dynamic LDS; early = the early-out form)
+struct OrPlan { int BT, NCH, R, W; size_t lds; const void *fn; int fi; bool early; };
 
 template <typename T> static const void *or_sweep_fn(int nch)
 {
     return nch == 1 ? (const void *)k_oropt_sweep<T, 1> : nch == 2 ? (const void *)k_oropt_sweep<T, 2> : (const void *)k_oropt_sweep<T, 3>;
 }
 
+// the form of a matrix-free Or-opt sweep (hook 90).  Automatic is the full form: the early-out form is chosen only where
+// tools/oropt_otf_rate.py has measured it faster, and no such measurement is recorded yet
+static bool or_otf_early(const tspgpu_ctx *ctx) { return ctx->opt_or_otf_early == 1; }
+
 static OrPlan or_plan(const tspgpu_ctx *ctx)
 {
     OrPlan P;
+    P.early = false;
+    if (ctx->otf) {
+        P.BT = 256; P.NCH = 0; P.R = OR_OTF_RUN; P.W = (ctx->n + P.R - 1) / P.R; P.lds = 0; P.fn = nullptr; P.fi = 0;
+        P.early = or_otf_early(ctx);
+        return P;
+    }
     const size_t esz = elem_size(ctx->elem);
     const int nvec = ctx->ld / (int)(16 / esz), n = ctx->n;
     P.BT = nvec <= 256 ? 256 : nvec <= 1024 ? 512 : 1024;
@@ -5801,8 +5835,35 @@ static int or_single_geom(const tspgpu_ctx *ctx, bool nch)
     return nch ? P.NCH : P.BT;
 }
 
-static int or_launch_sweep(tspgpu_ctx *ctx, int slot, const OrPlan &P)
+// matrix-free mode: the gather of the successors' points (it must see the tour the previous apply left), then the sweep
+static int or_launch_sweep_otf(tspgpu_ctx *ctx, int slot, const OrPlan &P, bool gather)
 {
+    const int n = ctx->n;
+    const bool ip = ctx->ceil_int() && ctx->d_ipts;         // int2 points, as launch_sweep
+    const OrCtl *ctl = ctx->d_or;
+    if (gather) {
+        if (ip) hipLaunchKernelGGL((k_oropt_gather<int2>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->S, n, slot,
+                                   (const int2 *)ctx->d_ipts, reinterpret_cast<int2 *>(ctx->d_spts), ctl);
+        else hipLaunchKernelGGL((k_oropt_gather<double2>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->S, n, slot,
+                                (const double2 *)ctx->d_pts, ctx->d_spts, ctl);
+        HIP_TRY(hipGetLastError());
+    }
+#define OR_OTF(K, PTS, SPTS) do { if (P.early) hipLaunchKernelGGL((k_oropt_sweep_otf<K, true>), dim3(P.W), dim3(P.BT), 0, ctx->stream, ctx->S, PTS, SPTS, n, slot, ctl); \
+                                  else hipLaunchKernelGGL((k_oropt_sweep_otf<K, false>), dim3(P.W), dim3(P.BT), 0, ctx->stream, ctx->S, PTS, SPTS, n, slot, ctl); } while (0)
+    if (ip) OR_OTF(KIND_CEIL_INT, (const int2 *)ctx->d_ipts, reinterpret_cast<const int2 *>(ctx->d_spts));
+    else if (ctx->kind == TSPGPU_EUC_2D) OR_OTF(TSPGPU_EUC_2D, (const double2 *)ctx->d_pts, (const double2 *)ctx->d_spts);
+    else if (ctx->kind == TSPGPU_ATT) OR_OTF(TSPGPU_ATT, (const double2 *)ctx->d_pts, (const double2 *)ctx->d_spts);
+    else OR_OTF(TSPGPU_CEIL_2D, (const double2 *)ctx->d_pts, (const double2 *)ctx->d_spts);
+#undef OR_OTF
+    HIP_TRY(hipGetLastError());
+    ctx->or_otf_form = P.early ? 2 : 1;
+    ctx->or_otf_R = P.R;
+    return E_OK;
+}
+
+static int or_launch_sweep(tspgpu_ctx *ctx, int slot, const OrPlan &P, bool gather = true)
+{
+    if (ctx->otf) return or_launch_sweep_otf(ctx, slot, P, gather);
     if (!ctx->or_attr[P.fi]) {
         HIP_TRY(hipFuncSetAttribute(P.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->lds_max));
         ctx->or_attr[P.fi] = true;
@@ -5818,6 +5879,16 @@ static int or_launch_sweep(tspgpu_ctx *ctx, int slot, const OrPlan &P)
 static int or_launch_apply(tspgpu_ctx *ctx, int slot, const OrPlan &P)
 {
     const int BT = std::min(1024, std::max(64, pow2_ceil(ctx->n / 8)));
+    if (ctx->otf) {
+#define OR_APPLY_OTF(K, PTS) hipLaunchKernelGGL((k_oropt_apply_otf<K>), dim3(1), dim3(BT), 0, ctx->stream, ctx->S, PTS, ctx->n, slot, P.W, ctx->d_or)
+        if (ctx->ceil_int() && ctx->d_ipts) OR_APPLY_OTF(KIND_CEIL_INT, (const int2 *)ctx->d_ipts);
+        else if (ctx->kind == TSPGPU_EUC_2D) OR_APPLY_OTF(TSPGPU_EUC_2D, (const double2 *)ctx->d_pts);
+        else if (ctx->kind == TSPGPU_ATT) OR_APPLY_OTF(TSPGPU_ATT, (const double2 *)ctx->d_pts);
+        else OR_APPLY_OTF(TSPGPU_CEIL_2D, (const double2 *)ctx->d_pts);
+#undef OR_APPLY_OTF
+        HIP_TRY(hipGetLastError());
+        return E_OK;
+    }
     ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_oropt_apply<T>), dim3(1), dim3(BT), 0, ctx->stream, ctx->S, (const T *)ctx->d_mat,
                                                  ctx->n, ctx->ld, slot, P.W, ctx->d_or));
     HIP_TRY(hipGetLastError());
@@ -5825,7 +5896,8 @@ static int or_launch_apply(tspgpu_ctx *ctx, int slot, const OrPlan &P)
 }
 
 // Or-opt moves on `slot` until a sweep finds nothing improving, max_moves (< 0: no cap) are applied or t_end (< 0: none) passes;
-// one sweep launch and one apply launch per move, eight pairs between looks at the control block (one under a deadline)
+// one sweep launch and one apply launch per move (matrix-free mode: gather, sweep, apply), eight of them between looks at the
+// control block (one under a deadline)
 static int or_run(tspgpu_ctx *ctx, int slot, long max_moves, double t_end, long *moves, bool *late, OrCtl *last)
 {
     OrCtl C;
@@ -6022,7 +6094,7 @@ int tspgpu_tours_local_search(tspgpu_ctx *ctx, int slot0, int count, double time
 {
     if (!ctx) return E_UNAVAILABLE;
     hipSetDevice(ctx->device);
-    int rc = or_check(ctx);
+    int rc = or_check(ctx, true);
     if (rc) return rc;
     if ((rc = or_batch_args(ctx, slot0, count))) return rc;
     std::vector<long> tw(count), om(count);
@@ -6041,7 +6113,7 @@ int tspgpu_multistart_local_search(tspgpu_ctx *ctx, const int *starts, int nstar
     if (!ctx) return E_UNAVAILABLE;
     if (!best_path || !best_cost || !best_start || nstarts <= 0) return fail(ctx, E_INVALID, "bad argument");
     hipSetDevice(ctx->device);
-    int rc = or_check(ctx);
+    int rc = or_check(ctx, true);
     if (rc) return rc;
     if (ctx->opt_sweep_cap != -1)
         return fail(ctx, E_INVALID, "TSPGPU_OPT_SWEEP_CAP = %d: the 2-opt + Or-opt descent runs every 2-opt phase to its local optimum", ctx->opt_sweep_cap);
@@ -6119,9 +6191,9 @@ int tspgpu_time_or_sweep(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean)
     auto timed = [&]() -> int {
         int r;
         HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-        if ((r = or_launch_sweep(ctx, slot, P))) return r; // warm
+        if ((r = or_launch_sweep(ctx, slot, P))) return r; // warm (matrix-free mode: with its gather; the timed launches are the sweep kernel alone)
         HIP_TRY(hipEventRecord(e0, ctx->stream));
-        for (int i = 0; i < reps; i++) if ((r = or_launch_sweep(ctx, slot, P))) return r;
+        for (int i = 0; i < reps; i++) if ((r = or_launch_sweep(ctx, slot, P, false))) return r;
         HIP_TRY(hipEventRecord(e1, ctx->stream));
         HIP_TRY(hipEventSynchronize(e1));
         HIP_TRY(hipEventElapsedTime(&ms, e0, e1));

@@ -21,7 +21,8 @@
 // array the move is a rotation: the block x .. q moves L cells towards p, or the complementary block q' .. p moves L
 // cells the other way -- whichever is shorter (<= n / 2 cells) --, in chunks of one element per thread ordered so that
 // no cell is overwritten before it was read; the segment (held in registers) then lands in the L cells that became
-// free.  Edge costs travel with their cells; the three new edges are three matrix reads.
+// free.  Edge costs travel with their cells; the three new edges are three reads of the cost source: the matrix
+// (OrMatCost) or -- matrix-free mode, k_oropt_apply_otf -- the weight function over the points (OrPtsCost).
 // ---------------------------------------------------------------------------
 static constexpr int OR_RMAX = 64;          // tour positions per sweep workgroup, at most
 static constexpr int OR_EXTRA = 3072;       // LDS beside the four rows: nodes, their dnb, c[p][x], the reduction scratch
@@ -159,9 +160,29 @@ __global__ void __launch_bounds__(1024) k_oropt_sweep(Tours S, const T *__restri
     }
 }
 
+// where the apply takes its three new edge costs from: the resident matrix, or the points (matrix-free mode: the weights
+// matrix mode would hold for the same points and kind -- edge_w / edge_w_ceil_i are the arithmetic of the build kernels)
+template <typename T> struct OrMatCost {
+    const T *__restrict__ mat;
+    int ld;
+    __device__ __forceinline__ typename Elem<T>::acc operator()(int u, int v) const { return (typename Elem<T>::acc)mat[(size_t)u * ld + v]; }
+};
+template <int KIND> struct OrPt { typedef double2 type; };
+template <> struct OrPt<KIND_CEIL_INT> { typedef int2 type; };      // ceil_int(): the integer points of k_sweep_otf8<KIND_CEIL_INT>
+template <int KIND>
+__device__ __forceinline__ int or_weight(const typename OrPt<KIND>::type &u, const typename OrPt<KIND>::type &v)
+{
+    if constexpr (KIND == KIND_CEIL_INT) return edge_w_ceil_i(u.x, u.y, v.x, v.y);
+    else return edge_w<KIND>(u.x, u.y, v.x, v.y);
+}
+template <int KIND> struct OrPtsCost {
+    const typename OrPt<KIND>::type *__restrict__ pts;
+    __device__ __forceinline__ int operator()(int u, int v) const { return or_weight<KIND>(pts[u], pts[v]); }
+};
+
 // the body of the apply kernels: one workgroup, tour slot t, G partials, that tour's control block
-template <typename T>
-__device__ __forceinline__ void or_apply_tour(const Tours &S, const T *__restrict__ mat, int n, int ld, int t, int G, OrCtl *ctl)
+template <typename T, typename CS>
+__device__ __forceinline__ void or_apply_tour(const Tours &S, const CS cs, int n, int t, int G, OrCtl *ctl)
 {
     typedef typename Elem<T>::acc AT;
     __shared__ Partial scratch[16];
@@ -197,7 +218,7 @@ __device__ __forceinline__ void or_apply_tour(const Tours &S, const T *__restric
     const int p = ord[or_cell(a - 1, n, dir)], x = ord[or_cell(a + L, n, dir)], qn = ord[or_cell(b + 1, n, dir)];
     const int tn = L == 1 ? g0 : L == 2 ? g1 : g2;
     const int h = rev ? tn : s, e = rev ? s : tn;
-    const AT wpx = (AT)mat[(size_t)p * ld + x], wqh = (AT)mat[(size_t)q * ld + h], weq = (AT)mat[(size_t)e * ld + qn];
+    const AT wpx = cs(p, x), wqh = cs(q, h), weq = cs(e, qn);
     int m1 = (b - (a + L)) % n;
     if (m1 < 0) m1 += n;
     m1 += 1;                                // cells of the block x .. q
@@ -254,7 +275,186 @@ __device__ __forceinline__ void or_apply_tour(const Tours &S, const T *__restric
 template <typename T>
 __global__ void __launch_bounds__(1024) k_oropt_apply(Tours S, const T *__restrict__ mat, int n, int ld, int t, int G, OrCtl *ctl)
 {
-    or_apply_tour<T>(S, mat, n, ld, t, G, ctl);
+    or_apply_tour<T>(S, OrMatCost<T>{mat, ld}, n, t, G, ctl);
+}
+
+// ---------------------------------------------------------------------------
+// Matrix-free mode (TSPGPU_OPT_OR_MATRIX_FREE = 1, single tours): the sibling of k_sweep_otf8.  Per move three launches:
+// k_oropt_gather (P_succ(q) for every q, from the tour the previous apply left), k_oropt_sweep_otf, k_oropt_apply_otf.
+//
+// k_oropt_sweep_otf: workgroup g owns the tour positions [g R, g R + R), R = OR_OTF_RUN.  The nodes of positions
+// g R - 1 .. g R + R + 2, their points, their dnb and the three c[p][x] per position (computed here with the weight
+// function) sit in LDS.  A thread streams over q, OR_OTF_VQ consecutive q per pass, with coalesced loads of P_q,
+// P_succ(q) and c[q][q'] = dnb[q].  The five candidates of a (position, q) need w(q, .) and w(q', .) to the nodes at the
+// position and the two behind it: a three-deep register window of (w(q, node_j), w(q', node_j)) slides along the run,
+// so each weight is computed once per (q, j) and workgroup -- 2 (R + 2) weights for 5 R candidates -- and not per
+// candidate.  Exclusions, key and order are those of k_oropt_sweep; deltas are int32 (three costs below 2^27 minus three).
+//
+// EARLY: the exact early-out.  With G(s, L) = (c[p][s] + c[t][x]) - c[p][x] a candidate improves iff
+//     c[q][h] + c[e][q'] < G + c[q][q'],
+// weights are >= 0 and integers, so BOTH c[q][h] <= T and c[e][q'] <= T with T = Gmax + c[q][q'] - 1 are necessary,
+// Gmax the largest G of the run; h and e are nodes of the run's positions g R .. g R + R + 1.  A weight is a monotone
+// function of the squared distance, so w <= T bounds the squared distance d2 (T < 0: nothing passes):
+//     EUC_2D   w = (int)(c + 0.5), c = the f32 root of the f32-rounded d2:  c < T + 0.5, so d2 < (T + 0.5)^2 (1 + 2^-22)
+//     CEIL_2D  w = ceil(sqrt(d2)) (f64 root, or exact over integer points):  d2 <= T^2 (1 + 2^-52)
+//     ATT      w >= r = sqrt(d2 / 10) (f64):                                 d2 <= 10 T^2 (1 + 2^-51)
+// The test compares, in f32, a LOWER bound of d2 -- the squared distance from the point to the bounding box of the run's
+// nodes -- with that bound: the gaps lose 2^-24 each in the conversion, their squares and the fused sum 2^-22 in all, the
+// f32 bound ((float)T, + 0.5, the square, the factor 10) another 2^-22; the bound carries a factor 1.000004 (2^-18).
+// A pass of 64 x VQ q none of which is within the bound for q AND for q' holds no improving candidate for any position
+// of the run and skips its weights.  Only candidates with delta >= 0 are left out: the argmin of an improving sweep and
+// its tie order are unchanged, and a sweep without an improving candidate stops the descent in either form.
+// ---------------------------------------------------------------------------
+static constexpr int OR_OTF_RUN = 16;       // tour positions per workgroup (W = ceil(n / 16) <= the n / 8 + 8 partial slots of a tour)
+static constexpr int OR_OTF_VQ = 4;         // consecutive q per thread and pass
+
+// spts[q] = pts[succ q]; unlike k_gather_spts it does not look at the slot's 2-opt `done` flag (Or-opt runs on finished slots)
+template <typename PT>
+__global__ void __launch_bounds__(256) k_oropt_gather(Tours S, int n, int t, const PT *__restrict__ pts, PT *__restrict__ spts, const OrCtl *ctl)
+{
+    const int q = blockIdx.x * 256 + threadIdx.x;
+    if (q >= n || ctl->stop) return;
+    spts[q] = pts[S.succ[(size_t)t * n + q]];
+}
+
+template <int KIND>
+__device__ __forceinline__ float or_d2_bound(int T)
+{
+    if (T < 0) return -1.0f;
+    float tq = (float)T;
+    if constexpr (KIND == TSPGPU_EUC_2D) tq += 0.5f;
+    float b = tq * tq;
+    if constexpr (KIND == TSPGPU_ATT) b *= 10.0f;
+    return b * 1.000004f;
+}
+
+template <int KIND, bool EARLY>
+__global__ void __launch_bounds__(256) k_oropt_sweep_otf(Tours S, const typename OrPt<KIND>::type *__restrict__ pts,
+                                                         const typename OrPt<KIND>::type *__restrict__ spts, int n, int t, const OrCtl *ctl)
+{
+    typedef typename OrPt<KIND>::type PT;
+    constexpr int R = OR_OTF_RUN, VQ = OR_OTF_VQ;
+    __shared__ int nodes[R + 4];            // positions k0 - 1 .. k0 + R + 2
+    __shared__ PT npt[R + 4];
+    __shared__ int dn[R + 4];               // c[node][succ node]
+    __shared__ int pxc[3 * R];              // c[p][x] for L = 1, 2, 3
+    __shared__ Partial scratch[16];
+    if (ctl->stop) return;
+    const int tid = threadIdx.x, BT = blockDim.x;
+    const int k0 = (int)blockIdx.x * R, cnt = min(R, n - k0);
+    const int dir = S.dir[t];
+    const int *ord = S.ord + (size_t)t * n;
+    const int *dnb = dnb_of<int>(S, t, n);
+
+    if (tid < cnt + 4) {
+        const int v = ord[or_cell(k0 - 1 + tid, n, dir)];
+        nodes[tid] = v;
+        npt[tid] = pts[v];
+        dn[tid] = dnb[v];
+    }
+    __syncthreads();
+    if (tid < 3 * cnt) {
+        const int i = tid / 3, L = tid % 3 + 1;
+        pxc[tid] = or_weight<KIND>(npt[i], npt[i + 1 + L]);
+    }
+    __syncthreads();
+
+    // EARLY: the largest G of the run and the box of the nodes that can be h or e (positions k0 .. k0 + cnt + 1)
+    typedef typename std::conditional<KIND == KIND_CEIL_INT, int, double>::type CT;      // coordinate type
+    int gmax = 0;
+    CT bx0 = 0, bx1 = 0, by0 = 0, by1 = 0;
+    if constexpr (EARLY) {
+        gmax = INT_MIN;
+        for (int i = 0; i < cnt; i++)
+            for (int L = 1; L <= 3; L++) gmax = max(gmax, (dn[i] + dn[i + L]) - pxc[3 * i + L - 1]);
+        bx0 = bx1 = npt[1].x; by0 = by1 = npt[1].y;
+        for (int j = 2; j <= cnt + 2; j++) {
+            const PT c = npt[j];
+            bx0 = min(bx0, c.x); bx1 = max(bx1, c.x); by0 = min(by0, c.y); by1 = max(by1, c.y);
+        }
+    }
+    auto box_d2 = [&](const PT &c) __attribute__((always_inline)) {      // squared distance from c to the box, rounded to f32
+        float gx, gy;
+        if constexpr (KIND == KIND_CEIL_INT) { gx = (float)max(max(bx0 - c.x, c.x - bx1), 0); gy = (float)max(max(by0 - c.y, c.y - by1), 0); }
+        else { gx = (float)fmax(fmax(bx0 - c.x, c.x - bx1), 0.0); gy = (float)fmax(fmax(by0 - c.y, c.y - by1), 0.0); }
+        return __builtin_fmaf(gy, gy, gx * gx);
+    };
+
+    int bd = INT_MAX;
+    u64 bk = KEY_NONE;
+    for (int base = 0; base < n; base += BT * VQ) {
+        const int q0 = base + tid * VQ;
+        PT pq[VQ], pn[VQ];
+        int cqq[VQ];
+#pragma unroll
+        for (int v = 0; v < VQ; v++) {
+            const int qq = min(q0 + v, n - 1);
+            pq[v] = pts[qq];
+            pn[v] = spts[qq];
+            cqq[v] = dnb[qq];
+        }
+        if constexpr (EARLY) {
+            bool maybe = false;
+#pragma unroll
+            for (int v = 0; v < VQ; v++) {
+                const float b = or_d2_bound<KIND>(gmax + cqq[v] - 1);
+                maybe |= (q0 + v < n) & (box_d2(pq[v]) <= b) & (box_d2(pn[v]) <= b);
+            }
+            if (!__ballot(maybe)) continue;
+        }
+        // the window: A = the node at the position, B, C = the two behind it
+        int wqA[VQ], wnA[VQ], wqB[VQ], wnB[VQ];
+        {
+            const PT c1 = npt[1], c2 = npt[2];
+#pragma unroll
+            for (int v = 0; v < VQ; v++) {
+                wqA[v] = or_weight<KIND>(pq[v], c1); wnA[v] = or_weight<KIND>(pn[v], c1);
+                wqB[v] = or_weight<KIND>(pq[v], c2); wnB[v] = or_weight<KIND>(pn[v], c2);
+            }
+        }
+        for (int i = 0; i < cnt; i++) {
+            const PT c3 = npt[i + 3];
+            const int p = nodes[i], s = nodes[i + 1], n1 = nodes[i + 2], n2 = nodes[i + 3];
+            const int cps = dn[i];
+            const int rem1 = cps + dn[i + 1], rem2 = cps + dn[i + 2], rem3 = cps + dn[i + 3];
+            const int px1 = pxc[3 * i], px2 = pxc[3 * i + 1], px3 = pxc[3 * i + 2];
+            const u64 ks = (u64)s << (OR_QB + 3);
+#pragma unroll
+            for (int v = 0; v < VQ; v++) {
+                const int q = q0 + v;
+                const int aq = wqA[v], bq = wqB[v], cq = or_weight<KIND>(pq[v], c3);
+                const int an = wnA[v], bn = wnB[v], cn = or_weight<KIND>(pn[v], c3);
+                const bool ok1 = q < n && q != p && q != s, ok2 = ok1 && q != n1, ok3 = ok2 && q != n2;
+                const u64 kq = ks | (u64)q << 1;
+#define OR_CONSIDER(OK, HQ, EN, PX, REM, L, REV)                                                   \
+                {                                                                                  \
+                    const int d_ = ((PX + HQ) + EN) - (REM + cqq[v]);                              \
+                    const u64 k_ = kq | (u64)(L) << (OR_QB + 1) | (u64)(REV);                      \
+                    if ((OK) && (d_ < bd || (d_ == bd && k_ < bk))) { bd = d_; bk = k_; }          \
+                }
+                OR_CONSIDER(ok1, aq, an, px1, rem1, 1, 0)
+                OR_CONSIDER(ok2, aq, bn, px2, rem2, 2, 0)
+                OR_CONSIDER(ok2, bq, an, px2, rem2, 2, 1)
+                OR_CONSIDER(ok3, aq, cn, px3, rem3, 3, 0)
+                OR_CONSIDER(ok3, cq, an, px3, rem3, 3, 1)
+#undef OR_CONSIDER
+                wqA[v] = bq; wqB[v] = cq; wnA[v] = bn; wnB[v] = cn;
+            }
+        }
+    }
+    double d = bk == KEY_NONE ? DBL_MAX : (double)bd;
+    block_argmin(d, bk, scratch);
+    if (tid == 0) {
+        Partial *part = S.partial + (size_t)t * S.pstride;
+        part[blockIdx.x].d = d;
+        part[blockIdx.x].key = bk;
+    }
+}
+
+template <int KIND>
+__global__ void __launch_bounds__(1024) k_oropt_apply_otf(Tours S, const typename OrPt<KIND>::type *__restrict__ pts, int n, int t, int G, OrCtl *ctl)
+{
+    or_apply_tour<int>(S, OrPtsCost<KIND>{pts}, n, t, G, ctl);
 }
 
 // ---------------------------------------------------------------------------
@@ -383,7 +583,7 @@ __global__ void __launch_bounds__(1024) k_oropt_apply_batch(Tours S, const T *__
                                                             int G, OrCtl *ctl)
 {
     const int t = live[blockIdx.x];
-    or_apply_tour<T>(S, mat, n, ld, t, G, ctl + t);
+    or_apply_tour<T>(S, OrMatCost<T>{mat, ld}, n, t, G, ctl + t);
 }
 
 // control blocks of the listed slots := "nothing applied yet, no move budget" (the start of a batch's Or-opt phase)

@@ -51,7 +51,7 @@ class Engine:
                  "nn_grid", "nn_grid_max_cell", "pipe2", "persist", "persist_wgs", "persist_edges", "persist_lds", "persist_window_cells",
                  "persist_window", "persist_handed", "persist_sweeps", "vns_mode", "stream_persist",
                  "otf_kernel", "ceil_int", "em_form", "em_stale", "em_steps", "or_batch_r", "or_single_r",
-                 "or_block", "or_nch"]
+                 "or_block", "or_nch", "or_otf", "or_otf_R"]
         return {k: int(self.L.tspgpu_info(self.ctx, i)) for i, k in enumerate(names)}
 
     # ---- instance

@@ -739,8 +739,9 @@ ERROR_CODE h_greedy_local_search(void)
     return e;
 }
 
-/* TSP_OR_OPT (1 = polish the incumbent after the heuristic) and TSP_OR_OPT_EVERY_START (1 = -alg 2OPT_GREEDY runs
- * h_greedy_local_search): unset or 0 = off; anything else is an error (-1) */
+/* TSP_OR_OPT (1 = polish the incumbent after the heuristic), TSP_OR_OPT_EVERY_START (1 = -alg 2OPT_GREEDY runs
+ * h_greedy_local_search) and TSP_OR_OPT_MATRIX_FREE (1 = the TSP_OR_OPT polish also runs on a matrix-free instance,
+ * TSPGPU_OPT_OR_MATRIX_FREE): unset or 0 = off; anything else is an error (-1) */
 static int env_switch(const char *name)
 {
     const char *v = getenv(name);
@@ -754,7 +755,8 @@ static int env_switch(const char *name)
 ERROR_CODE tsp_run_algorithm(void)
 {
     const int polish = env_switch("TSP_OR_OPT"), every_start = env_switch("TSP_OR_OPT_EVERY_START");
-    if (polish < 0 || every_start < 0) return INVALID_ARGUMENT;
+    const int polish_mf = env_switch("TSP_OR_OPT_MATRIX_FREE");
+    if (polish < 0 || every_start < 0 || polish_mf < 0) return INVALID_ARGUMENT;
     free(tsp_inst.best_solution.path);
     tsp_inst.best_solution.path = (int *)calloc((size_t)tsp_inst.nnodes, sizeof(int));
     ERROR_CODE e;
@@ -770,9 +772,15 @@ ERROR_CODE tsp_run_algorithm(void)
         return UNIMPLEMENTED;
     }
     if (!polish || (e != T_OK && e != DEADLINE_EXCEEDED)) return e;
-    if (tsp_matrix_free) {
+    if (tsp_matrix_free && !polish_mf) {
         log_warn("TSP_OR_OPT=1: Or-opt needs the cost matrix and the instance runs matrix-free; the polish is skipped");
         return e;
+    }
+    if (tsp_matrix_free) {      /* TSP_OR_OPT_MATRIX_FREE=1: the single-tour descent from the coordinates */
+        tspgpu_ctx *g = tsp_gpu();
+        if (!g) return UNAVAILABLE;
+        const int rc = tspgpu_set_option(g, TSPGPU_OPT_OR_MATRIX_FREE, 1);
+        if (rc) { log_error("TSPGPU_OPT_OR_MATRIX_FREE: %s", tspgpu_last_error(g)); return from_rc(rc); }
     }
     /* the polish works on a copy: tsp_update_best_solution takes it only if it is a tour and strictly better */
     tsp_solution s;
