@@ -374,6 +374,49 @@ int tspgpu_debug_stamps(tspgpu_ctx *ctx, unsigned long long *out, int capacity_w
 /* with TSPGPU_OPT_HISTORY: the recorded moves of slot 0; returns count in *count */
 int tspgpu_history(tspgpu_ctx *ctx, int *a, int *b, double *delta, int capacity, int *count);
 
+/* ---- Parallel-move 2-opt (an extension: the reference applies one move per sweep) ---------------------------------
+ * A sweep keeps one candidate per tour edge and applies every candidate that beats all candidates it conflicts with.
+ * Preconditions: `path` a successor array, a symmetric cost matrix (or matrix-free mode), n >= 5.
+ *   1. Candidates.  For every node a, sa = path[a], every b, sb = path[b], the reference does not skip
+ *      (src/algorithms/refinment.c:55: sa == sb || a == sb || b == sa):
+ *          delta(a, b) = (c[a][b] + c[sa][sb]) - (c[a][sa] + c[b][sb])        (refinment.c:60-62, in this order)
+ *      cand(a) = the first strict minimum over b ascending, a candidate only if delta < -1e-7 (TWO_OPT_EPS).  A candidate
+ *      is the unordered pair {a, b} with the key (delta, lo, hi), lo < hi its labels; two nodes that choose each other
+ *      give one candidate.  The smallest key is the move ref_2opt_once makes.
+ *   2. Interval.  P(0) = 0, P(path[v]) = P(v) + 1; i = min(P(a), P(b)), j = max(P(a), P(b)): the candidate removes the
+ *      edges at positions i and j and reverses the nodes at positions i + 1 .. j.  Position 0 never moves.
+ *   3. Conflict.  Two different candidates conflict iff their closed ranges [i, j] intersect (shared edge, crossing, nesting).
+ *   4. Selection.  ONE round: a candidate is accepted iff its key is below the key of every candidate it conflicts with.
+ *      The smallest key is always accepted, so a sweep that finds an improving pair makes progress.
+ *   5. Apply.  Every accepted {a, b}, P(a) < P(b): path[a] = b, the links of sa .. b reversed, path[sa] = sb.  *cost grows
+ *      by the sum of the accepted deltas (exact for integer-valued costs; for other double cells the order of the sum is
+ *      not specified).
+ *   6. Descent.  *cost is recomputed from the matrix as ref_2opt does (refinment.c:6-9); sweeps run until one accepts
+ *      nothing, and that last sweep is counted as in tspgpu_two_opt.  The result is a local optimum of the full 2-opt
+ *      neighbourhood -- in general not the one tspgpu_two_opt reaches.
+ * Taken: every instance tspgpu_two_opt takes with a symmetric matrix (one matrix row in LDS: no tighter limit) and
+ * everything matrix-free mode takes.  Codes: no context 14, n < 5 3, no costs 9, an asymmetric matrix 9, a deadline that
+ * passed 4 (with a valid tour and its cost; it is polled between sweeps).  The candidate arrays (40 bytes per node) are
+ * allocated at the first call.
+ * tspgpu_info: 36 / 37 sweeps / moves of the last parallel-move descent (or single sweep), 38 the most moves one of its
+ * sweeps accepted, 39 / 40 tour positions / threads per workgroup of the candidate sweep on this instance (0: no
+ * symmetric costs of at least 5 nodes), 41 the 16-byte vectors of a matrix row one of its threads holds (1, 2, 4 or 10; 0 in
+ * matrix-free mode). */
+/* one sweep on a host tour.  *cost is the caller's running cost (as ref_2opt_once, refinment.c:83).  The accepted moves
+ * come back in ascending key order: moves_ab[2k], moves_ab[2k + 1] = a, b with P(a) < P(b), deltas[k]; *nmoves their
+ * number (0: nothing improves).  More accepted moves than `cap`: 8, nothing is applied and nothing written. */
+int tspgpu_two_opt_multi_once(tspgpu_ctx *ctx, int *path, double *cost, int *nmoves,
+                              int *moves_ab /* [2*cap] */, double *deltas /* [cap] */, int cap);
+/* the descent (rule 6); *sweeps and *moves (each may be NULL) the sweeps run and the moves applied */
+int tspgpu_two_opt_multi(tspgpu_ctx *ctx, int *path, double *cost, double time_left_s, long *sweeps, long *moves);
+/* the same on a slot, whose cost is taken as it stands: at most max_sweeps sweeps (< 0: until one accepts nothing).  The
+ * slot's cost, last delta (the smallest accepted delta of the last sweep, 0: none) and sweep count follow, and every later
+ * slot call sees the rewritten tour */
+int tspgpu_tour_two_opt_multi(tspgpu_ctx *ctx, int slot, long max_sweeps, double time_left_s, long *sweeps, long *moves);
+/* a measurement aid (tools/multi2opt_rate.py), the counterpart of tspgpu_time_or_sweep: the candidate sweep and the
+ * selection `reps` times on slot, nothing applied; mean duration in ms from HIP events on the engine's stream */
+int tspgpu_time_multi_sweep(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean);
+
 #ifdef __cplusplus
 }
 #endif

@@ -24,6 +24,8 @@ OPT_PERSIST, OPT_PERSIST_EDGES, OPT_PERSIST_WINDOW, OPT_BUILD_KERNEL, OPT_STREAM
 OPT_EM_FORM = 21
 OPT_OR_MATRIX_FREE = 22
 INFO_OR_OTF, INFO_OR_OTF_R = 34, 35     # tspgpu_info: form (0 none, 1 full, 2 early-out) and R of the last matrix-free Or-opt sweep
+# ... sweeps, moves and the largest move count of one sweep of the last parallel-move 2-opt descent; R and threads of its candidate sweep
+INFO_MULTI_SWEEPS, INFO_MULTI_MOVES, INFO_MULTI_MAX_MOVES, INFO_MULTI_R, INFO_MULTI_THREADS, INFO_MULTI_NCH = 36, 37, 38, 39, 40, 41
 EM_FORM_AUTO, EM_FORM_RESIDENT, EM_FORM_PER_STEP = 0, 1, 2
 MOPT_EXCHANGE = 1000
 EXCHANGE_AUTO, EXCHANGE_HOST, EXCHANGE_RCCL = 0, 1, 2
@@ -93,6 +95,10 @@ SIGNATURES = {
     "tspgpu_timing_read": (C.c_int, [_ctx, _pd, _pl, C.c_int]),
     "tspgpu_debug_stamps": (C.c_int, [_ctx, C.c_void_p, C.c_int]),
     "tspgpu_history": (C.c_int, [_ctx, _ip, _ip, _dp, C.c_int, _pi]),
+    "tspgpu_two_opt_multi_once": (C.c_int, [_ctx, _ip, _pd, _pi, _ip, _dp, C.c_int]),
+    "tspgpu_two_opt_multi": (C.c_int, [_ctx, _ip, _pd, C.c_double, _pl, _pl]),
+    "tspgpu_tour_two_opt_multi": (C.c_int, [_ctx, C.c_int, C.c_long, C.c_double, _pl, _pl]),
+    "tspgpu_time_multi_sweep": (C.c_int, [_ctx, C.c_int, C.c_int, C.POINTER(C.c_float)]),
 }
 
 _lib = None

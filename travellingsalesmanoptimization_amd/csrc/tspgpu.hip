@@ -3089,6 +3089,7 @@ __global__ void k_cap_now(Tours S, int slot0, int count)
 #include "tspgpu_str2opt.inc"
 #include "tspgpu_em.inc"
 #include "tspgpu_oropt.inc"
+#include "tspgpu_multi2opt.inc"
 
 // ===========================================================================
 // host side
@@ -3208,6 +3209,12 @@ struct tspgpu_ctx {
     int or_otf_form = 0;       // how the last matrix-free Or-opt sweep ran: 0 none, 1 every candidate, 2 with the early-out
     int or_otf_R = 0;          // its tour positions per workgroup
 
+    // parallel-move 2-opt (tspgpu_multi2opt.inc): control block and the candidate arrays of the slot a descent runs on, on first use
+    M2Ctl *d_m2 = nullptr;
+    M2Buf m2{};
+    bool m2_attr[12] = {false, false, false, false, false, false, false, false, false, false, false, false};
+    long m2_sweeps = 0, m2_moves = 0, m2_max_k = 0;    // the last parallel-move descent
+
     Fused F{};                 // fused path state (allocated on first use, capacity fcap)
     int fcap = 0;
     int opt_fused = 1;         // 1 = one launch per sweep where applicable
@@ -3292,9 +3299,17 @@ static void free_grid(tspgpu_ctx *ctx)
     ctx->grid_G = 0; ctx->grid_ok = false;
 }
 
+static void free_m2(tspgpu_ctx *ctx)
+{
+    void *ptrs[] = {ctx->m2.raw_d, ctx->m2.raw_b, ctx->m2.d, ctx->m2.a, ctx->m2.b, ctx->m2.i, ctx->m2.j, ctx->m2.acc};
+    for (void *p : ptrs) if (p) hipFree(p);
+    memset(&ctx->m2, 0, sizeof ctx->m2);
+}
+
 static void free_tours(tspgpu_ctx *ctx)
 {
     free_tour_arrays(ctx->S);
+    free_m2(ctx);              // sized by n
     free_tour_scratch(ctx);
     void *ptrs[] = {ctx->d_tabu_list, ctx->d_best_succ, ctx->d_tabu};
     for (void *p : ptrs) if (p) hipFree(p);
@@ -4790,6 +4805,7 @@ void tspgpu_destroy(tspgpu_ctx *ctx)
     if (ctx->d_spts) hipFree(ctx->d_spts);
     if (ctx->d_ipts) hipFree(ctx->d_ipts);
     if (ctx->d_or) hipFree(ctx->d_or);
+    if (ctx->d_m2) hipFree(ctx->d_m2);
     free_grid(ctx);
     if (ctx->hist.a) { hipFree(ctx->hist.a); hipFree(ctx->hist.b); hipFree(ctx->hist.d); }
     for (auto e : ctx->ev) hipEventDestroy(e);
@@ -4858,6 +4874,7 @@ int tspgpu_set_option(tspgpu_ctx *ctx, int option, long value)
 
 static int or_single_R(const tspgpu_ctx *ctx);      // (tspgpu_oropt.inc's driver, below)
 static int or_single_geom(const tspgpu_ctx *ctx, bool nch);
+static int m2_geom(const tspgpu_ctx *ctx, int what);       // (tspgpu_multi2opt.inc's driver, below)
 
 long tspgpu_info(const tspgpu_ctx *ctx, int what)
 {
@@ -4904,6 +4921,12 @@ long tspgpu_info(const tspgpu_ctx *ctx, int what)
     case 33: return or_single_geom(ctx, true);
     case 34: return ctx->or_otf_form;
     case 35: return ctx->or_otf_R;
+    case 36: return ctx->m2_sweeps;
+    case 37: return ctx->m2_moves;
+    case 38: return ctx->m2_max_k;
+    case 39: return m2_geom(ctx, 0);
+    case 40: return m2_geom(ctx, 1);
+    case 41: return m2_geom(ctx, 2);
     case 12: return (ctx->built && ctx->grid_ok && ctx->opt_nn != 1 && ctx->cost_bound < 134217728.0) ? ctx->grid_G : 0;
     case 13: return ctx->grid_max_occ;
     }
@@ -6251,6 +6274,301 @@ int tspgpu_local_search(tspgpu_ctx *ctx, int *path, double *cost, double time_le
     if ((rc = or_descent(ctx, 0, time_left_s, two_opt_sweeps, or_moves, rounds, &late))) return rc;
     if ((rc = store_path(ctx, 0, path, cost, nullptr))) return rc;
     return late ? E_DEADLINE : E_OK;
+}
+
+} // extern "C"
+
+// ---- parallel-move 2-opt (tspgpu_multi2opt.inc) ------------------------------------------------------------------------
+
+static int m2_check(tspgpu_ctx *ctx)
+{
+    int rc = need_costs(ctx);
+    if (rc) return rc;
+    const int n = ctx->n;
+    if (n < 5) return fail(ctx, E_INVALID, "parallel-move 2-opt needs at least 5 nodes, got %d", n);
+    if (!ctx->symmetric) return fail(ctx, E_PRECOND, "parallel-move 2-opt needs a symmetric cost matrix");
+    if (!ctx->otf && (size_t)ctx->ld * elem_size(ctx->elem) + M2_EXTRA > ctx->lds_max)     // (the matrix 2-opt's own limit: tspgpu_build_costs)
+        return fail(ctx, E_EXHAUSTED, "n = %d: a matrix row of %d-byte cells does not fit LDS (at most %d nodes)", n,
+                    (int)elem_size(ctx->elem), (int)((ctx->lds_max - M2_EXTRA) / elem_size(ctx->elem)) & ~31);
+    if (ctx->otf && ctx->spts_cap < (size_t)n) {    // the gathered successor points, sized as make_plan sizes them for one tour
+        if (ctx->d_spts) hipFree(ctx->d_spts);
+        ctx->d_spts = nullptr; ctx->spts_cap = 0;
+        HIP_TRY(hipMalloc(&ctx->d_spts, (size_t)n * sizeof(double2)));
+        ctx->spts_cap = (size_t)n;
+    }
+    if (!ctx->d_m2) HIP_TRY(hipMalloc(&ctx->d_m2, sizeof(M2Ctl)));
+    if (!ctx->m2.raw_d) {
+        M2Buf &B = ctx->m2;
+        const size_t N = (size_t)n;
+        void **ptrs[] = {(void **)&B.raw_d, (void **)&B.raw_b, (void **)&B.d, (void **)&B.a, (void **)&B.b, (void **)&B.i, (void **)&B.j,
+                         (void **)&B.acc};
+        const size_t bytes[] = {8, 4, 8, 4, 4, 4, 4, 4};
+        for (int k = 0; k < 8; k++) {
+            const hipError_t e = hipMalloc(ptrs[k], N * bytes[k]);
+            if (e != hipSuccess) {          // all eight or none: a later call must not find half of them
+                free_m2(ctx);
+                HIP_TRY(e);
+            }
+        }
+    }
+    return E_OK;
+}
+
+// geometry of a candidate sweep: threads, 16-byte vectors per thread and row (the template's: 1, 2, 4 or 10), positions per
+// workgroup, workgroups, LDS bytes (matrix-free mode: BT = 256, NCH = 0, R = M2_OTF_RUN, no dynamic LDS)
+struct M2Plan { int BT, NCH, R, W; size_t lds; int fi; };
+
+static M2Plan m2_plan(const tspgpu_ctx *ctx)
+{
+    M2Plan P;
+    const int n = ctx->n;
+    if (ctx->otf) {
+        P.BT = 256; P.NCH = 0; P.R = M2_OTF_RUN; P.W = (n + P.R - 1) / P.R; P.lds = 0; P.fi = 0;
+        return P;
+    }
+    const size_t esz = elem_size(ctx->elem);
+    const int nvec = ctx->ld / (int)(16 / esz);
+    P.BT = nvec <= 256 ? 256 : nvec <= 1024 ? 512 : 1024;
+    const int need = (nvec + P.BT - 1) / P.BT;              // <= 10: a row fits LDS (need_costs), 10 240 vectors at most
+    P.NCH = need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : 10;
+    P.lds = (size_t)ctx->ld * esz + M2_EXTRA;
+    const int occ = (int)std::max<size_t>(1, std::min<size_t>(ctx->lds_max / P.lds, (size_t)(2048 / P.BT)));
+    const int target = ctx->cus * occ;                      // one wave of workgroups over the chip
+    P.R = std::min(std::max((n + target - 1) / target, M2_RMIN), M2_RMAX);
+    P.W = (n + P.R - 1) / P.R;
+    P.fi = (ctx->elem == TSPGPU_ELEM_F64 ? 0 : ctx->elem == TSPGPU_ELEM_I32 ? 4 : 8) + (P.NCH == 1 ? 0 : P.NCH == 2 ? 1 : P.NCH == 4 ? 2 : 3);
+    return P;
+}
+
+// what = 0 / 1 / 2: positions per workgroup / threads per workgroup / 16-byte vectors per thread and row of the candidate sweep
+// (0: no symmetric costs of >= 5 nodes; the vectors also in matrix-free mode)
+static int m2_geom(const tspgpu_ctx *ctx, int what)
+{
+    if (!ctx->have_costs || !ctx->symmetric || ctx->n < 5) return 0;
+    const M2Plan P = m2_plan(ctx);
+    return what == 0 ? P.R : what == 1 ? P.BT : P.NCH;
+}
+
+template <typename T> static const void *m2_sweep_fn(int nch)
+{
+    return nch == 1 ? (const void *)k_m2_sweep<T, 1> : nch == 2 ? (const void *)k_m2_sweep<T, 2>
+         : nch == 4 ? (const void *)k_m2_sweep<T, 4> : (const void *)k_m2_sweep<T, 10>;
+}
+
+// the candidate sweep and the selection of one sweep (matrix-free mode: behind the gather of the successors' points)
+static int m2_launch_select(tspgpu_ctx *ctx, int slot, const M2Plan &P, bool gather = true)
+{
+    const int n = ctx->n;
+    const M2Ctl *ctl = ctx->d_m2;
+    if (ctx->otf) {
+        const bool ip = ctx->ceil_int() && ctx->d_ipts;     // int2 points, as launch_sweep
+        if (gather) {
+            if (ip) hipLaunchKernelGGL((k_m2_gather<int2>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->S, n, slot,
+                                       (const int2 *)ctx->d_ipts, reinterpret_cast<int2 *>(ctx->d_spts), ctl);
+            else hipLaunchKernelGGL((k_m2_gather<double2>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->S, n, slot,
+                                    (const double2 *)ctx->d_pts, ctx->d_spts, ctl);
+            HIP_TRY(hipGetLastError());
+        }
+#define M2_OTF(K, PTS, SPTS) hipLaunchKernelGGL((k_m2_sweep_otf<K>), dim3(P.W), dim3(P.BT), 0, ctx->stream, ctx->S, PTS, SPTS, n, slot, ctx->m2, ctl)
+        if (ip) M2_OTF(KIND_CEIL_INT, (const int2 *)ctx->d_ipts, reinterpret_cast<const int2 *>(ctx->d_spts));
+        else if (ctx->kind == TSPGPU_EUC_2D) M2_OTF(TSPGPU_EUC_2D, (const double2 *)ctx->d_pts, (const double2 *)ctx->d_spts);
+        else if (ctx->kind == TSPGPU_ATT) M2_OTF(TSPGPU_ATT, (const double2 *)ctx->d_pts, (const double2 *)ctx->d_spts);
+        else M2_OTF(TSPGPU_CEIL_2D, (const double2 *)ctx->d_pts, (const double2 *)ctx->d_spts);
+#undef M2_OTF
+    } else {
+        if (!ctx->m2_attr[P.fi]) {
+            const void *fn = nullptr;
+            ELEM_SWITCH(ctx->elem, T, fn = m2_sweep_fn<T>(P.NCH));
+            HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->lds_max));
+            ctx->m2_attr[P.fi] = true;
+        }
+#define M2_SWEEP(T, N) hipLaunchKernelGGL((k_m2_sweep<T, N>), dim3(P.W), dim3(P.BT), P.lds, ctx->stream, ctx->S, (const T *)ctx->d_mat, \
+                                          n, ctx->ld, slot, P.R, ctx->m2, ctl)
+        ELEM_SWITCH(ctx->elem, T, { if (P.NCH == 1) M2_SWEEP(T, 1); else if (P.NCH == 2) M2_SWEEP(T, 2);
+                                    else if (P.NCH == 4) M2_SWEEP(T, 4); else M2_SWEEP(T, 10); });
+#undef M2_SWEEP
+    }
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_m2_compact, dim3(1), dim3(1024), 0, ctx->stream, ctx->S, n, slot, ctx->m2, ctx->d_m2);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_m2_select, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->m2, ctl);
+    HIP_TRY(hipGetLastError());
+    return E_OK;
+}
+
+static int m2_launch_apply(tspgpu_ctx *ctx, int slot)
+{
+    const int n = ctx->n, G = std::min(M2_APPLY_WGS, (n + 1) / 2);
+    if (ctx->otf) {
+#define M2_APPLY_OTF(K, PTS) hipLaunchKernelGGL((k_m2_apply_otf<K>), dim3(G), dim3(256), 0, ctx->stream, ctx->S, PTS, n, slot, ctx->m2, ctx->d_m2)
+        if (ctx->ceil_int() && ctx->d_ipts) M2_APPLY_OTF(KIND_CEIL_INT, (const int2 *)ctx->d_ipts);
+        else if (ctx->kind == TSPGPU_EUC_2D) M2_APPLY_OTF(TSPGPU_EUC_2D, (const double2 *)ctx->d_pts);
+        else if (ctx->kind == TSPGPU_ATT) M2_APPLY_OTF(TSPGPU_ATT, (const double2 *)ctx->d_pts);
+        else M2_APPLY_OTF(TSPGPU_CEIL_2D, (const double2 *)ctx->d_pts);
+#undef M2_APPLY_OTF
+    } else {
+        ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_m2_apply<T>), dim3(G), dim3(256), 0, ctx->stream, ctx->S, (const T *)ctx->d_mat,
+                                                     n, ctx->ld, slot, ctx->m2, ctx->d_m2));
+    }
+    HIP_TRY(hipGetLastError());
+    return E_OK;
+}
+
+// the control block of a run := nothing done yet, `budget` sweeps allowed (< 0: no cap); the slot's sweep counter and flag re-armed
+static int m2_arm(tspgpu_ctx *ctx, int slot, long budget)
+{
+    M2Ctl C;
+    memset(&C, 0, sizeof C);
+    C.budget = budget;
+    HIP_TRY(hipMemcpyAsync(ctx->d_m2, &C, sizeof C, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));       // (C is on the stack)
+    hipLaunchKernelGGL(k_rearm, dim3(1), dim3(64), 0, ctx->stream, ctx->S, slot, 1, -1);
+    HIP_TRY(hipGetLastError());
+    return E_OK;
+}
+
+static void m2_record(tspgpu_ctx *ctx, const M2Ctl &C)
+{
+    ctx->m2_sweeps = (long)C.sweeps; ctx->m2_moves = (long)C.moves; ctx->m2_max_k = C.max_k;
+}
+
+// sweeps on `slot` until one accepts nothing, max_sweeps (< 0: no cap) have run or t_end (< 0: none) passes; per sweep the
+// launches of m2_launch_select and m2_launch_apply, four sweeps between looks at the control block (one under a deadline)
+static int m2_run(tspgpu_ctx *ctx, int slot, long max_sweeps, double t_end, long *sweeps, long *moves, bool *late)
+{
+    M2Ctl C;
+    memset(&C, 0, sizeof C);
+    *late = false;
+    if (sweeps) *sweeps = 0;
+    if (moves) *moves = 0;
+    m2_record(ctx, C);
+    if (max_sweeps == 0) return E_OK;
+    int rc = m2_arm(ctx, slot, max_sweeps);
+    if (rc) return rc;
+    const M2Plan P = m2_plan(ctx);
+    for (;;) {
+        if (t_end >= 0 && now_s() >= t_end) { *late = true; break; }
+        const int K = t_end >= 0 ? 1 : 4;
+        for (int i = 0; i < K; i++) {
+            if ((rc = m2_launch_select(ctx, slot, P))) return rc;
+            if ((rc = m2_launch_apply(ctx, slot))) return rc;
+        }
+        HIP_TRY(hipMemcpyAsync(&C, ctx->d_m2, sizeof C, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if (C.stop) break;
+    }
+    if (*late) {
+        HIP_TRY(hipMemcpyAsync(&C, ctx->d_m2, sizeof C, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    if (sweeps) *sweeps = (long)C.sweeps;
+    if (moves) *moves = (long)C.moves;
+    m2_record(ctx, C);
+    return E_OK;
+}
+
+extern "C" {
+
+int tspgpu_tour_two_opt_multi(tspgpu_ctx *ctx, int slot, long max_sweeps, double time_left_s, long *sweeps, long *moves)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    hipSetDevice(ctx->device);
+    int rc = m2_check(ctx);
+    if (rc) return rc;
+    if ((rc = need_slot(ctx, slot))) return rc;
+    bool late = false;
+    if ((rc = m2_run(ctx, slot, max_sweeps, time_left_s >= 0 ? now_s() + time_left_s : -1, sweeps, moves, &late))) return rc;
+    return late ? E_DEADLINE : E_OK;
+}
+
+int tspgpu_two_opt_multi(tspgpu_ctx *ctx, int *path, double *cost, double time_left_s, long *sweeps, long *moves)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    if (!path || !cost) return fail(ctx, E_INVALID, "null argument");
+    hipSetDevice(ctx->device);
+    int rc = m2_check(ctx);
+    if (rc) return rc;
+    if ((rc = load_path(ctx, 0, path, -1))) return rc;          // recomputes the cost, refinment.c:6-9
+    bool late = false;
+    if ((rc = m2_run(ctx, 0, -1, time_left_s >= 0 ? now_s() + time_left_s : -1, sweeps, moves, &late))) return rc;
+    if ((rc = store_path(ctx, 0, path, cost, nullptr))) return rc;
+    return late ? E_DEADLINE : E_OK;
+}
+
+int tspgpu_two_opt_multi_once(tspgpu_ctx *ctx, int *path, double *cost, int *nmoves, int *moves_ab, double *deltas, int cap)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    if (!path || !cost || cap < 0 || (cap > 0 && (!moves_ab || !deltas))) return fail(ctx, E_INVALID, "bad argument");
+    hipSetDevice(ctx->device);
+    int rc = m2_check(ctx);
+    if (rc) return rc;
+    if ((rc = load_path(ctx, 0, path, -1))) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->S.cost, cost, 8, hipMemcpyHostToDevice, ctx->stream));     // the caller's running cost, as ref_2opt_once
+    if ((rc = m2_arm(ctx, 0, 1))) return rc;
+    if ((rc = m2_launch_select(ctx, 0, m2_plan(ctx)))) return rc;
+    // the accepted list comes back before anything is applied: a list longer than `cap` leaves the tour as it is
+    M2Ctl C;
+    HIP_TRY(hipMemcpyAsync(&C, ctx->d_m2, sizeof C, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    const size_t m = (size_t)C.m;
+    std::vector<int> acc(m), a(m), b(m);
+    std::vector<double> d(m);
+    if (m) {
+        HIP_TRY(hipMemcpyAsync(acc.data(), ctx->m2.acc, m * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(a.data(), ctx->m2.a, m * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(b.data(), ctx->m2.b, m * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(d.data(), ctx->m2.d, m * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    }
+    std::vector<int> idx;
+    for (size_t x = 0; x < m; x++) if (acc[x]) idx.push_back((int)x);
+    if ((int)idx.size() > cap)
+        return fail(ctx, E_EXHAUSTED, "the sweep accepts %d moves, the caller's arrays hold %d: nothing was applied", (int)idx.size(), cap);
+    std::sort(idx.begin(), idx.end(), [&](int x, int y) {
+        if (d[x] != d[y]) return d[x] < d[y];
+        const int lx = std::min(a[x], b[x]), ly = std::min(a[y], b[y]);
+        return lx != ly ? lx < ly : std::max(a[x], b[x]) < std::max(a[y], b[y]);
+    });
+    for (size_t k = 0; k < idx.size(); k++) { moves_ab[2 * k] = a[idx[k]]; moves_ab[2 * k + 1] = b[idx[k]]; deltas[k] = d[idx[k]]; }
+    if (nmoves) *nmoves = (int)idx.size();
+    if ((rc = m2_launch_apply(ctx, 0))) return rc;
+    if ((rc = store_path(ctx, 0, path, cost, nullptr))) return rc;
+    HIP_TRY(hipMemcpyAsync(&C, ctx->d_m2, sizeof C, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    m2_record(ctx, C);
+    return E_OK;
+}
+
+int tspgpu_time_multi_sweep(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    if (!ms_mean || reps <= 0) return fail(ctx, E_INVALID, "bad argument");
+    hipSetDevice(ctx->device);
+    int rc = m2_check(ctx);
+    if (rc) return rc;
+    if ((rc = need_slot(ctx, slot))) return rc;
+    HIP_TRY(hipMemsetAsync(ctx->d_m2, 0, sizeof(M2Ctl), ctx->stream));
+    const M2Plan P = m2_plan(ctx);
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    float ms = 0;
+    // (the events are destroyed on every way out)
+    auto timed = [&]() -> int {
+        int r;
+        HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
+        if ((r = m2_launch_select(ctx, slot, P))) return r; // warm (matrix-free mode: with its gather; the timed launches go without)
+        HIP_TRY(hipEventRecord(e0, ctx->stream));
+        for (int i = 0; i < reps; i++) if ((r = m2_launch_select(ctx, slot, P, false))) return r;
+        HIP_TRY(hipEventRecord(e1, ctx->stream));
+        HIP_TRY(hipEventSynchronize(e1));
+        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+        return E_OK;
+    };
+    rc = timed();
+    if (e0) hipEventDestroy(e0);
+    if (e1) hipEventDestroy(e1);
+    if (rc) return rc;
+    *ms_mean = ms / reps;
+    return E_OK;
 }
 
 } // extern "C"

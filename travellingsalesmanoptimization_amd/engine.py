@@ -51,7 +51,8 @@ class Engine:
                  "nn_grid", "nn_grid_max_cell", "pipe2", "persist", "persist_wgs", "persist_edges", "persist_lds", "persist_window_cells",
                  "persist_window", "persist_handed", "persist_sweeps", "vns_mode", "stream_persist",
                  "otf_kernel", "ceil_int", "em_form", "em_stale", "em_steps", "or_batch_r", "or_single_r",
-                 "or_block", "or_nch", "or_otf", "or_otf_R"]
+                 "or_block", "or_nch", "or_otf", "or_otf_R",
+                 "multi_sweeps", "multi_moves", "multi_max_moves", "multi_r", "multi_block", "multi_nch"]
         return {k: int(self.L.tspgpu_info(self.ctx, i)) for i, k in enumerate(names)}
 
     # ---- instance
@@ -134,6 +135,24 @@ class Engine:
         rc = self._ck(self.L.tspgpu_or_opt(self.ctx, path, C.byref(c), float(time_left_s), C.byref(m)),
                       ok=(T_OK, DEADLINE_EXCEEDED))
         return c.value, m.value, rc
+
+    def two_opt_multi_once(self, path, cost, cap=None):
+        """one parallel-move 2-opt sweep (include/tspgpu.h "Parallel-move 2-opt"); path in place ->
+        (cost, moves, deltas): moves an array [k][2] of a, b with P(a) < P(b) in ascending key order, deltas [k]
+        (k = 0: nothing improves).  More than `cap` (default n) accepted moves: RESOURCE_EXHAUSTED, nothing applied."""
+        cap = self.n if cap is None else int(cap)
+        c, k = C.c_double(cost), C.c_int()
+        mv = np.empty(2 * max(cap, 1), dtype=np.int32)
+        dl = np.empty(max(cap, 1), dtype=np.float64)
+        self._ck(self.L.tspgpu_two_opt_multi_once(self.ctx, path, C.byref(c), C.byref(k), mv, dl, cap))
+        return c.value, mv[:2 * k.value].reshape(-1, 2).copy(), dl[:k.value].copy()
+
+    def two_opt_multi(self, path, time_left_s=-1.0):
+        """parallel-move 2-opt sweeps until one accepts nothing; path in place -> (cost, sweeps, moves, rc)."""
+        c, s, m = C.c_double(), C.c_long(), C.c_long()
+        rc = self._ck(self.L.tspgpu_two_opt_multi(self.ctx, path, C.byref(c), float(time_left_s), C.byref(s), C.byref(m)),
+                      ok=(T_OK, DEADLINE_EXCEEDED))
+        return c.value, s.value, m.value, rc
 
     def local_search(self, path, time_left_s=-1.0):
         """2-opt and Or-opt in turn until neither improves; path in place ->
@@ -263,6 +282,18 @@ class Engine:
                                                        sw.ctypes.data, om.ctypes.data, nr.ctypes.data),
                       ok=(T_OK, DEADLINE_EXCEEDED))
         return {"two_opt_sweeps": sw, "or_moves": om, "rounds": nr, "rc": rc}
+
+    def tour_two_opt_multi(self, slot, max_sweeps=-1, time_left_s=-1.0):
+        """parallel-move 2-opt sweeps on a slot -> (sweeps, moves, rc)."""
+        s, m = C.c_long(), C.c_long()
+        rc = self._ck(self.L.tspgpu_tour_two_opt_multi(self.ctx, int(slot), int(max_sweeps), float(time_left_s), C.byref(s), C.byref(m)),
+                      ok=(T_OK, DEADLINE_EXCEEDED))
+        return s.value, m.value, rc
+
+    def time_multi_sweep(self, slot, reps):
+        ms = C.c_float()
+        self._ck(self.L.tspgpu_time_multi_sweep(self.ctx, slot, reps, C.byref(ms)))
+        return ms.value
 
     def time_or_sweep(self, slot, reps):
         ms = C.c_float()

@@ -153,6 +153,10 @@ static void multi_stats(const char *what, struct tspgpu_multi *m, int starts, lo
 
 /* ===================================================================== refinment.c */
 
+/* TSP_2OPT_MULTI=1 (tsp_run_algorithm): ref_2opt runs the parallel-move descent (tspgpu_two_opt_multi, an extension: a 2-opt
+ * local optimum by another trajectory than the reference's) */
+static int two_opt_multi_on = 0;
+
 /* refinment.c:3-37.  Cost recompute, sweep loop and stop rule run on the device
  * (tspgpu_two_opt); the deadline is polled once per batch of sweeps instead of per sweep. */
 ERROR_CODE ref_2opt(tsp_solution *solution, double *costs, bool update_incumbent)
@@ -170,7 +174,15 @@ ERROR_CODE ref_2opt(tsp_solution *solution, double *costs, bool update_incumbent
         log_debug("time limit exceeded in 2opt");
         e = DEADLINE_EXCEEDED;
     } else {
-        int rc = tspgpu_two_opt(g, solution->path, &solution->cost, time_left(), NULL);
+        int rc = -1;
+        if (two_opt_multi_on) {
+            rc = tspgpu_two_opt_multi(g, solution->path, &solution->cost, time_left(), NULL, NULL);
+            if (rc == FAILED_PRECONDITION || rc == RESOURCE_EXHAUSTED) {   /* an asymmetric matrix, a size limit: the tour is untouched */
+                log_warn("TSP_2OPT_MULTI=1: %s; running tspgpu_two_opt", tspgpu_last_error(g));
+                rc = -1;
+            }
+        }
+        if (rc < 0) rc = tspgpu_two_opt(g, solution->path, &solution->cost, time_left(), NULL);
         if (rc != 0 && rc != DEADLINE_EXCEEDED) {
             log_error("tspgpu_two_opt: %s", tspgpu_last_error(g));
             thread_done(lease);
@@ -617,7 +629,7 @@ ERROR_CODE mh_VNS(void)
     FILE *f = fopen("results/VNSResults.dat", "w+");
     e = T_OK;
     const char *on_host = getenv("TSP_VNS_HOST");
-    if (on_host && atoi(on_host)) {
+    if ((on_host && atoi(on_host)) || two_opt_multi_on) {      /* (the resident loop's local search is the reference's descent) */
         for (int it = 0; it < tsp_env.k; it++) {
             if (past_deadline()) { e = DEADLINE_EXCEEDED; break; }
             e = ref_2opt(&s, tsp_inst.costs, true);
@@ -741,7 +753,8 @@ ERROR_CODE h_greedy_local_search(void)
 
 /* TSP_OR_OPT (1 = polish the incumbent after the heuristic), TSP_OR_OPT_EVERY_START (1 = -alg 2OPT_GREEDY runs
  * h_greedy_local_search) and TSP_OR_OPT_MATRIX_FREE (1 = the TSP_OR_OPT polish also runs on a matrix-free instance,
- * TSPGPU_OPT_OR_MATRIX_FREE): unset or 0 = off; anything else is an error (-1) */
+ * TSPGPU_OPT_OR_MATRIX_FREE), TSP_2OPT_MULTI (1 = ref_2opt, and with it every iteration of mh_VNS's host loop, runs the
+ * parallel-move descent tspgpu_two_opt_multi): unset or 0 = off; anything else is an error (-1) */
 static int env_switch(const char *name)
 {
     const char *v = getenv(name);
@@ -756,7 +769,10 @@ ERROR_CODE tsp_run_algorithm(void)
 {
     const int polish = env_switch("TSP_OR_OPT"), every_start = env_switch("TSP_OR_OPT_EVERY_START");
     const int polish_mf = env_switch("TSP_OR_OPT_MATRIX_FREE");
-    if (polish < 0 || every_start < 0 || polish_mf < 0) return INVALID_ARGUMENT;
+    const int multi = env_switch("TSP_2OPT_MULTI");
+    if (polish < 0 || every_start < 0 || polish_mf < 0 || multi < 0) return INVALID_ARGUMENT;
+    two_opt_multi_on = multi;
+    if (multi) log_warn("TSP_2OPT_MULTI=1: ref_2opt runs the parallel-move descent; results differ from the reference's trajectory");
     free(tsp_inst.best_solution.path);
     tsp_inst.best_solution.path = (int *)calloc((size_t)tsp_inst.nnodes, sizeof(int));
     ERROR_CODE e;
