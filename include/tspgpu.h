@@ -417,6 +417,50 @@ int tspgpu_tour_two_opt_multi(tspgpu_ctx *ctx, int slot, long max_sweeps, double
  * selection `reps` times on slot, nothing applied; mean duration in ms from HIP events on the engine's stream */
 int tspgpu_time_multi_sweep(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean);
 
+/* ---- Neighbour-list 2-opt (an extension: the candidates of a parallel-move sweep from K-nearest-neighbour lists) ------
+ * A sweep evaluates at most 2 K pairs per node instead of all n, and then selects and applies as the section above does.
+ * Preconditions: those of "Parallel-move 2-opt", and lists built for the cost source in place.
+ *   Lists.  For 1 <= K <= 16, K' = min(K, n - 1): N(v) = the K' nodes u != v with the smallest key (c[v][u], u), in
+ *      ascending key order.  Costs are compared exactly: as integers for uint16 / int32 cells and in matrix-free mode
+ *      (whose weights are the ones matrix mode would hold), as doubles for f64 cells.
+ *   Candidates (in place of rule 1 above; rules 2-5 -- interval, conflict, one selection round, apply -- are taken over
+ *      unchanged).  For node a, sa = path[a]:
+ *          B(a) = N(a) + { pred(x) : x in N(sa) }, minus every b the reference skips
+ *                 (src/algorithms/refinment.c:55: sa == sb || a == sb || b == sa)
+ *      delta(a, b) as in rule 1 (refinment.c:60-62, in this order: bit-exact for doubles); cand(a) = the lexicographic
+ *      minimum of (delta(a, b), b) over B(a), a candidate only if delta < -1e-7.  Two nodes that choose each other give
+ *      the pair once.
+ *   Membership.  A pair {a, b} is in B(a) or B(b) iff one of its two new edges (a, b), (sa, sb) joins a node to a member of
+ *      its own list, in either direction.
+ *   Local optimum.  The descent ends in a tour with no improving 2-opt move of that kind: a local optimum of the
+ *      neighbour-list neighbourhood, not of full 2-opt.
+ *   Equality with the full rule.  With K' = n - 1 (n <= 17 at K = 16) B(a) is everything rule 1 looks at: a sweep equals a
+ *      sweep of tspgpu_two_opt_multi_once move for move.
+ *   Descent (rule 6 with these candidates).  *cost is recomputed as ref_2opt does (refinment.c:6-9); sweeps run until one
+ *      accepts nothing, and that sweep is counted.  polish != 0: the parallel-move descent above then continues on the same
+ *      slot, without recomputing the cost, until it accepts nothing -- the result is a local optimum of full 2-opt.
+ * Codes: no context 14, n < 5 3, no costs 9, an asymmetric matrix 9, lists not built -- or invalidated by a later
+ * tspgpu_build_costs, tspgpu_set_costs or tspgpu_set_points -- 9 with the reason in tspgpu_last_error, a deadline that
+ * passed 4 (with a valid tour and its cost), more accepted moves than `cap` in _once 8 (nothing applied).
+ * The lists (12 bytes per entry: node and weight) stay on the device and are allocated all or none.
+ * tspgpu_info: 42 K' in effect (0: no lists), 43 / 44 sweeps / moves of the last neighbour-list phase (or single sweep),
+ * 45 sweeps of the last polish phase, 46 nodes per workgroup of the candidate sweep. */
+/* K in 1..16 builds the lists of the cost source in place; 0 drops them; any other K: 3 */
+int tspgpu_neighbours_build(tspgpu_ctx *ctx, int K);
+/* the lists, row v at nodes[v * K'] .. ; weights (may be NULL) the costs c[v][nodes[..]] */
+int tspgpu_neighbours_get(tspgpu_ctx *ctx, int *nodes /* [n*K'] */, double *weights /* [n*K'] or NULL */);
+/* one sweep on a host tour: arguments and results as tspgpu_two_opt_multi_once */
+int tspgpu_two_opt_nl_once(tspgpu_ctx *ctx, int *path, double *cost, int *nmoves,
+                           int *moves_ab /* [2*cap] */, double *deltas /* [cap] */, int cap);
+/* the descent; *sweeps / *moves of the neighbour-list phase, *polish_sweeps / *polish_moves of the polish (0 without);
+ * each may be NULL */
+int tspgpu_two_opt_nl(tspgpu_ctx *ctx, int *path, double *cost, double time_left_s, int polish,
+                      long *sweeps, long *moves, long *polish_sweeps, long *polish_moves);
+/* neighbour-list sweeps on a slot, as tspgpu_tour_two_opt_multi (no polish) */
+int tspgpu_tour_two_opt_nl(tspgpu_ctx *ctx, int slot, long max_sweeps, double time_left_s, long *sweeps, long *moves);
+/* a measurement aid (tools/nl2opt_rate.py): the candidate sweep and the selection `reps` times on slot, nothing applied */
+int tspgpu_time_nl_sweep(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,8 @@ OPT_OR_MATRIX_FREE = 22
 INFO_OR_OTF, INFO_OR_OTF_R = 34, 35     # tspgpu_info: form (0 none, 1 full, 2 early-out) and R of the last matrix-free Or-opt sweep
 # ... sweeps, moves and the largest move count of one sweep of the last parallel-move 2-opt descent; R and threads of its candidate sweep
 INFO_MULTI_SWEEPS, INFO_MULTI_MOVES, INFO_MULTI_MAX_MOVES, INFO_MULTI_R, INFO_MULTI_THREADS, INFO_MULTI_NCH = 36, 37, 38, 39, 40, 41
+# ... K' of the neighbour lists in place, sweeps / moves of the last neighbour-list 2-opt phase, sweeps of its polish, nodes per workgroup
+INFO_NL_K, INFO_NL_SWEEPS, INFO_NL_MOVES, INFO_NL_POLISH_SWEEPS, INFO_NL_NODES = 42, 43, 44, 45, 46
 EM_FORM_AUTO, EM_FORM_RESIDENT, EM_FORM_PER_STEP = 0, 1, 2
 MOPT_EXCHANGE = 1000
 EXCHANGE_AUTO, EXCHANGE_HOST, EXCHANGE_RCCL = 0, 1, 2
@@ -99,6 +101,12 @@ SIGNATURES = {
     "tspgpu_two_opt_multi": (C.c_int, [_ctx, _ip, _pd, C.c_double, _pl, _pl]),
     "tspgpu_tour_two_opt_multi": (C.c_int, [_ctx, C.c_int, C.c_long, C.c_double, _pl, _pl]),
     "tspgpu_time_multi_sweep": (C.c_int, [_ctx, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "tspgpu_neighbours_build": (C.c_int, [_ctx, C.c_int]),
+    "tspgpu_neighbours_get": (C.c_int, [_ctx, _ip, C.c_void_p]),
+    "tspgpu_two_opt_nl_once": (C.c_int, [_ctx, _ip, _pd, _pi, _ip, _dp, C.c_int]),
+    "tspgpu_two_opt_nl": (C.c_int, [_ctx, _ip, _pd, C.c_double, C.c_int, _pl, _pl, _pl, _pl]),
+    "tspgpu_tour_two_opt_nl": (C.c_int, [_ctx, C.c_int, C.c_long, C.c_double, _pl, _pl]),
+    "tspgpu_time_nl_sweep": (C.c_int, [_ctx, C.c_int, C.c_int, C.POINTER(C.c_float)]),
 }
 
 _lib = None

@@ -3090,6 +3090,7 @@ __global__ void k_cap_now(Tours S, int slot0, int count)
 #include "tspgpu_em.inc"
 #include "tspgpu_oropt.inc"
 #include "tspgpu_multi2opt.inc"
+#include "tspgpu_nl2opt.inc"
 
 // ===========================================================================
 // host side
@@ -3215,6 +3216,11 @@ struct tspgpu_ctx {
     bool m2_attr[12] = {false, false, false, false, false, false, false, false, false, false, false, false};
     long m2_sweeps = 0, m2_moves = 0, m2_max_k = 0;    // the last parallel-move descent
 
+    // neighbour-list 2-opt (tspgpu_nl2opt.inc): the lists of the cost source in place (tspgpu_neighbours_build)
+    NlBuf nl{};
+    bool nl_dropped = false;   // a new cost source took the lists away (the refusal says so)
+    long nl_sweeps = 0, nl_moves = 0, nl_polish_sweeps = 0;     // the last neighbour-list phase and its polish
+
     Fused F{};                 // fused path state (allocated on first use, capacity fcap)
     int fcap = 0;
     int opt_fused = 1;         // 1 = one launch per sweep where applicable
@@ -3247,8 +3253,17 @@ static void drop_graphs(tspgpu_ctx *ctx)
     ctx->graphs.clear();
 }
 
+static void free_nl(tspgpu_ctx *ctx)
+{
+    if (ctx->nl.node) hipFree(ctx->nl.node);
+    if (ctx->nl.w) hipFree(ctx->nl.w);
+    memset(&ctx->nl, 0, sizeof ctx->nl);
+}
+
 static void free_matrix(tspgpu_ctx *ctx)
 {
+    if (ctx->nl.K) ctx->nl_dropped = true;  // the neighbour lists belong to the old costs
+    free_nl(ctx);
     if (ctx->d_mat) hipFree(ctx->d_mat);
     ctx->d_mat = nullptr; ctx->have_costs = false;
     ctx->or_otf_form = ctx->or_otf_R = 0;
@@ -4806,6 +4821,7 @@ void tspgpu_destroy(tspgpu_ctx *ctx)
     if (ctx->d_ipts) hipFree(ctx->d_ipts);
     if (ctx->d_or) hipFree(ctx->d_or);
     if (ctx->d_m2) hipFree(ctx->d_m2);
+    free_nl(ctx);
     free_grid(ctx);
     if (ctx->hist.a) { hipFree(ctx->hist.a); hipFree(ctx->hist.b); hipFree(ctx->hist.d); }
     for (auto e : ctx->ev) hipEventDestroy(e);
@@ -4927,6 +4943,11 @@ long tspgpu_info(const tspgpu_ctx *ctx, int what)
     case 39: return m2_geom(ctx, 0);
     case 40: return m2_geom(ctx, 1);
     case 41: return m2_geom(ctx, 2);
+    case 42: return ctx->nl.K;
+    case 43: return ctx->nl_sweeps;
+    case 44: return ctx->nl_moves;
+    case 45: return ctx->nl_polish_sweeps;
+    case 46: return NL_NODES;
     case 12: return (ctx->built && ctx->grid_ok && ctx->opt_nn != 1 && ctx->cost_bound < 134217728.0) ? ctx->grid_G : 0;
     case 13: return ctx->grid_max_occ;
     }
@@ -6355,12 +6376,18 @@ template <typename T> static const void *m2_sweep_fn(int nch)
          : nch == 4 ? (const void *)k_m2_sweep<T, 4> : (const void *)k_m2_sweep<T, 10>;
 }
 
-// the candidate sweep and the selection of one sweep (matrix-free mode: behind the gather of the successors' points)
-static int m2_launch_select(tspgpu_ctx *ctx, int slot, const M2Plan &P, bool gather = true)
+static int nl_launch_sweep(tspgpu_ctx *ctx, int slot);      // (tspgpu_nl2opt.inc's driver, below)
+
+// the candidate sweep and the selection of one sweep (matrix-free mode: behind the gather of the successors' points);
+// nl: the candidates come from the neighbour lists (k_nl_sweep) instead
+static int m2_launch_select(tspgpu_ctx *ctx, int slot, const M2Plan &P, bool gather = true, bool nl = false)
 {
     const int n = ctx->n;
     const M2Ctl *ctl = ctx->d_m2;
-    if (ctx->otf) {
+    if (nl) {
+        const int rc = nl_launch_sweep(ctx, slot);
+        if (rc) return rc;
+    } else if (ctx->otf) {
         const bool ip = ctx->ceil_int() && ctx->d_ipts;     // int2 points, as launch_sweep
         if (gather) {
             if (ip) hipLaunchKernelGGL((k_m2_gather<int2>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->S, n, slot,
@@ -6427,21 +6454,22 @@ static int m2_arm(tspgpu_ctx *ctx, int slot, long budget)
     return E_OK;
 }
 
-static void m2_record(tspgpu_ctx *ctx, const M2Ctl &C)
+static void m2_record(tspgpu_ctx *ctx, const M2Ctl &C, bool nl = false)
 {
-    ctx->m2_sweeps = (long)C.sweeps; ctx->m2_moves = (long)C.moves; ctx->m2_max_k = C.max_k;
+    if (nl) { ctx->nl_sweeps = (long)C.sweeps; ctx->nl_moves = (long)C.moves; }
+    else { ctx->m2_sweeps = (long)C.sweeps; ctx->m2_moves = (long)C.moves; ctx->m2_max_k = C.max_k; }
 }
 
 // sweeps on `slot` until one accepts nothing, max_sweeps (< 0: no cap) have run or t_end (< 0: none) passes; per sweep the
 // launches of m2_launch_select and m2_launch_apply, four sweeps between looks at the control block (one under a deadline)
-static int m2_run(tspgpu_ctx *ctx, int slot, long max_sweeps, double t_end, long *sweeps, long *moves, bool *late)
+static int m2_run(tspgpu_ctx *ctx, int slot, long max_sweeps, double t_end, long *sweeps, long *moves, bool *late, bool nl = false)
 {
     M2Ctl C;
     memset(&C, 0, sizeof C);
     *late = false;
     if (sweeps) *sweeps = 0;
     if (moves) *moves = 0;
-    m2_record(ctx, C);
+    m2_record(ctx, C, nl);
     if (max_sweeps == 0) return E_OK;
     int rc = m2_arm(ctx, slot, max_sweeps);
     if (rc) return rc;
@@ -6450,7 +6478,7 @@ static int m2_run(tspgpu_ctx *ctx, int slot, long max_sweeps, double t_end, long
         if (t_end >= 0 && now_s() >= t_end) { *late = true; break; }
         const int K = t_end >= 0 ? 1 : 4;
         for (int i = 0; i < K; i++) {
-            if ((rc = m2_launch_select(ctx, slot, P))) return rc;
+            if ((rc = m2_launch_select(ctx, slot, P, true, nl))) return rc;
             if ((rc = m2_launch_apply(ctx, slot))) return rc;
         }
         HIP_TRY(hipMemcpyAsync(&C, ctx->d_m2, sizeof C, hipMemcpyDeviceToHost, ctx->stream));
@@ -6463,7 +6491,7 @@ static int m2_run(tspgpu_ctx *ctx, int slot, long max_sweeps, double t_end, long
     }
     if (sweeps) *sweeps = (long)C.sweeps;
     if (moves) *moves = (long)C.moves;
-    m2_record(ctx, C);
+    m2_record(ctx, C, nl);
     return E_OK;
 }
 
@@ -6495,17 +6523,22 @@ int tspgpu_two_opt_multi(tspgpu_ctx *ctx, int *path, double *cost, double time_l
     return late ? E_DEADLINE : E_OK;
 }
 
-int tspgpu_two_opt_multi_once(tspgpu_ctx *ctx, int *path, double *cost, int *nmoves, int *moves_ab, double *deltas, int cap)
+} // extern "C"
+
+static int nl_check(tspgpu_ctx *ctx);
+
+// one sweep on a host tour (tspgpu_two_opt_multi_once; nl: tspgpu_two_opt_nl_once)
+static int m2_once(tspgpu_ctx *ctx, int *path, double *cost, int *nmoves, int *moves_ab, double *deltas, int cap, bool nl)
 {
     if (!ctx) return E_UNAVAILABLE;
     if (!path || !cost || cap < 0 || (cap > 0 && (!moves_ab || !deltas))) return fail(ctx, E_INVALID, "bad argument");
     hipSetDevice(ctx->device);
-    int rc = m2_check(ctx);
+    int rc = nl ? nl_check(ctx) : m2_check(ctx);
     if (rc) return rc;
     if ((rc = load_path(ctx, 0, path, -1))) return rc;
     HIP_TRY(hipMemcpyAsync(ctx->S.cost, cost, 8, hipMemcpyHostToDevice, ctx->stream));     // the caller's running cost, as ref_2opt_once
     if ((rc = m2_arm(ctx, 0, 1))) return rc;
-    if ((rc = m2_launch_select(ctx, 0, m2_plan(ctx)))) return rc;
+    if ((rc = m2_launch_select(ctx, 0, m2_plan(ctx), true, nl))) return rc;
     // the accepted list comes back before anything is applied: a list longer than `cap` leaves the tour as it is
     M2Ctl C;
     HIP_TRY(hipMemcpyAsync(&C, ctx->d_m2, sizeof C, hipMemcpyDeviceToHost, ctx->stream));
@@ -6535,16 +6568,17 @@ int tspgpu_two_opt_multi_once(tspgpu_ctx *ctx, int *path, double *cost, int *nmo
     if ((rc = store_path(ctx, 0, path, cost, nullptr))) return rc;
     HIP_TRY(hipMemcpyAsync(&C, ctx->d_m2, sizeof C, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
-    m2_record(ctx, C);
+    m2_record(ctx, C, nl);
     return E_OK;
 }
 
-int tspgpu_time_multi_sweep(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean)
+// the candidate sweep and the selection `reps` times, nothing applied (tspgpu_time_multi_sweep; nl: tspgpu_time_nl_sweep)
+static int m2_time(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean, bool nl)
 {
     if (!ctx) return E_UNAVAILABLE;
     if (!ms_mean || reps <= 0) return fail(ctx, E_INVALID, "bad argument");
     hipSetDevice(ctx->device);
-    int rc = m2_check(ctx);
+    int rc = nl ? nl_check(ctx) : m2_check(ctx);
     if (rc) return rc;
     if ((rc = need_slot(ctx, slot))) return rc;
     HIP_TRY(hipMemsetAsync(ctx->d_m2, 0, sizeof(M2Ctl), ctx->stream));
@@ -6555,9 +6589,9 @@ int tspgpu_time_multi_sweep(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean)
     auto timed = [&]() -> int {
         int r;
         HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-        if ((r = m2_launch_select(ctx, slot, P))) return r; // warm (matrix-free mode: with its gather; the timed launches go without)
+        if ((r = m2_launch_select(ctx, slot, P, true, nl))) return r;   // warm (matrix-free mode: with its gather; the timed launches go without)
         HIP_TRY(hipEventRecord(e0, ctx->stream));
-        for (int i = 0; i < reps; i++) if ((r = m2_launch_select(ctx, slot, P, false))) return r;
+        for (int i = 0; i < reps; i++) if ((r = m2_launch_select(ctx, slot, P, false, nl))) return r;
         HIP_TRY(hipEventRecord(e1, ctx->stream));
         HIP_TRY(hipEventSynchronize(e1));
         HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
@@ -6569,6 +6603,162 @@ int tspgpu_time_multi_sweep(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean)
     if (rc) return rc;
     *ms_mean = ms / reps;
     return E_OK;
+}
+
+extern "C" {
+
+int tspgpu_two_opt_multi_once(tspgpu_ctx *ctx, int *path, double *cost, int *nmoves, int *moves_ab, double *deltas, int cap)
+{
+    return m2_once(ctx, path, cost, nmoves, moves_ab, deltas, cap, false);
+}
+
+int tspgpu_time_multi_sweep(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean)
+{
+    return m2_time(ctx, slot, reps, ms_mean, false);
+}
+
+} // extern "C"
+
+// ---- neighbour-list 2-opt (tspgpu_nl2opt.inc) --------------------------------------------------------------------------
+
+// everything the parallel-move descent needs (the polish runs it on the same slot), and the lists
+static int nl_check(tspgpu_ctx *ctx)
+{
+    const int rc = m2_check(ctx);
+    if (rc) return rc;
+    if (!ctx->nl.K)
+        return fail(ctx, E_PRECOND, ctx->nl_dropped ? "the neighbour lists were invalidated by a new cost source: call tspgpu_neighbours_build again"
+                                                    : "no neighbour lists: call tspgpu_neighbours_build first");
+    return E_OK;
+}
+
+static int nl_launch_sweep(tspgpu_ctx *ctx, int slot)
+{
+    const int n = ctx->n;
+    const dim3 grid((n + NL_NODES - 1) / NL_NODES), block(NL_NODES * 32);
+    const M2Ctl *ctl = ctx->d_m2;
+    if (ctx->otf) {
+#define NL_OTF(K, PTS) hipLaunchKernelGGL((k_nl_sweep_otf<K>), grid, block, 0, ctx->stream, ctx->S, PTS, n, slot, ctx->nl, ctx->m2, ctl)
+        if (ctx->ceil_int() && ctx->d_ipts) NL_OTF(KIND_CEIL_INT, (const int2 *)ctx->d_ipts);
+        else if (ctx->kind == TSPGPU_EUC_2D) NL_OTF(TSPGPU_EUC_2D, (const double2 *)ctx->d_pts);
+        else if (ctx->kind == TSPGPU_ATT) NL_OTF(TSPGPU_ATT, (const double2 *)ctx->d_pts);
+        else NL_OTF(TSPGPU_CEIL_2D, (const double2 *)ctx->d_pts);
+#undef NL_OTF
+    } else {
+        ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_nl_sweep<T>), grid, block, 0, ctx->stream, ctx->S, (const T *)ctx->d_mat, n, ctx->ld, slot,
+                                                     ctx->nl, ctx->m2, ctl));
+    }
+    HIP_TRY(hipGetLastError());
+    return E_OK;
+}
+
+extern "C" {
+
+int tspgpu_neighbours_build(tspgpu_ctx *ctx, int K)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    hipSetDevice(ctx->device);
+    if (K == 0) { free_nl(ctx); ctx->nl_dropped = false; return E_OK; }
+    if (K < 0 || K > NL_KMAX) return fail(ctx, E_INVALID, "neighbour lists hold 1 to %d nodes, got K = %d", NL_KMAX, K);
+    int rc = need_costs(ctx);
+    if (rc) return rc;
+    if (!ctx->symmetric) return fail(ctx, E_PRECOND, "neighbour lists need a symmetric cost matrix");
+    const int n = ctx->n, Kp = std::min(K, n - 1);
+    free_nl(ctx);
+    ctx->nl_dropped = false;
+    NlBuf L{};
+    const hipError_t e0 = hipMalloc(&L.node, (size_t)n * Kp * 4), e1 = e0 == hipSuccess ? hipMalloc(&L.w, (size_t)n * Kp * 8) : e0;
+    if (e1 != hipSuccess) {                 // both or none
+        if (L.node) hipFree(L.node);
+        HIP_TRY(e1);
+    }
+    L.K = Kp;
+    const dim3 grid((n + NL_BUILD_ROWS - 1) / NL_BUILD_ROWS), block(NL_BUILD_ROWS * 64);
+    if (ctx->otf) {
+#define NL_BUILD_OTF(KD, PTS) hipLaunchKernelGGL((k_nl_build_otf<KD>), grid, block, 0, ctx->stream, PTS, n, L)
+        if (ctx->ceil_int() && ctx->d_ipts) NL_BUILD_OTF(KIND_CEIL_INT, (const int2 *)ctx->d_ipts);
+        else if (ctx->kind == TSPGPU_EUC_2D) NL_BUILD_OTF(TSPGPU_EUC_2D, (const double2 *)ctx->d_pts);
+        else if (ctx->kind == TSPGPU_ATT) NL_BUILD_OTF(TSPGPU_ATT, (const double2 *)ctx->d_pts);
+        else NL_BUILD_OTF(TSPGPU_CEIL_2D, (const double2 *)ctx->d_pts);
+#undef NL_BUILD_OTF
+    } else {
+        ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_nl_build<T>), grid, block, 0, ctx->stream, (const T *)ctx->d_mat, n, ctx->ld, L));
+    }
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+    if (e != hipSuccess) { hipFree(L.node); hipFree(L.w); HIP_TRY(e); }
+    ctx->nl = L;
+    return E_OK;
+}
+
+int tspgpu_neighbours_get(tspgpu_ctx *ctx, int *nodes, double *weights)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    if (!nodes) return fail(ctx, E_INVALID, "null argument");
+    hipSetDevice(ctx->device);
+    int rc = need_costs(ctx);
+    if (rc) return rc;
+    if (!ctx->nl.K) return nl_check(ctx);   // (the refusal's text)
+    const size_t cnt = (size_t)ctx->n * ctx->nl.K;
+    HIP_TRY(hipMemcpyAsync(nodes, ctx->nl.node, cnt * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if (!weights) return E_OK;
+    if (ctx->elem == TSPGPU_ELEM_F64) {
+        HIP_TRY(hipMemcpyAsync(weights, ctx->nl.w, cnt * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+    } else {                                // integer modes keep 4-byte weights
+        std::vector<int> w(cnt);
+        HIP_TRY(hipMemcpyAsync(w.data(), ctx->nl.w, cnt * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        for (size_t i = 0; i < cnt; i++) weights[i] = (double)w[i];
+    }
+    return E_OK;
+}
+
+int tspgpu_two_opt_nl_once(tspgpu_ctx *ctx, int *path, double *cost, int *nmoves, int *moves_ab, double *deltas, int cap)
+{
+    return m2_once(ctx, path, cost, nmoves, moves_ab, deltas, cap, true);
+}
+
+int tspgpu_tour_two_opt_nl(tspgpu_ctx *ctx, int slot, long max_sweeps, double time_left_s, long *sweeps, long *moves)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    hipSetDevice(ctx->device);
+    int rc = nl_check(ctx);
+    if (rc) return rc;
+    if ((rc = need_slot(ctx, slot))) return rc;
+    bool late = false;
+    if ((rc = m2_run(ctx, slot, max_sweeps, time_left_s >= 0 ? now_s() + time_left_s : -1, sweeps, moves, &late, true))) return rc;
+    return late ? E_DEADLINE : E_OK;
+}
+
+int tspgpu_two_opt_nl(tspgpu_ctx *ctx, int *path, double *cost, double time_left_s, int polish,
+                      long *sweeps, long *moves, long *polish_sweeps, long *polish_moves)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    if (!path || !cost) return fail(ctx, E_INVALID, "null argument");
+    hipSetDevice(ctx->device);
+    int rc = nl_check(ctx);
+    if (rc) return rc;
+    if ((rc = load_path(ctx, 0, path, -1))) return rc;          // recomputes the cost, refinment.c:6-9
+    const double t_end = time_left_s >= 0 ? now_s() + time_left_s : -1;
+    bool late = false;
+    long ps = 0, pm = 0;
+    ctx->nl_polish_sweeps = 0;
+    if ((rc = m2_run(ctx, 0, -1, t_end, sweeps, moves, &late, true))) return rc;
+    if (polish && !late) {                  // the parallel-move descent goes on from the slot as it stands
+        if ((rc = m2_run(ctx, 0, -1, t_end, &ps, &pm, &late))) return rc;
+        ctx->nl_polish_sweeps = ps;
+    }
+    if (polish_sweeps) *polish_sweeps = ps;
+    if (polish_moves) *polish_moves = pm;
+    if ((rc = store_path(ctx, 0, path, cost, nullptr))) return rc;
+    return late ? E_DEADLINE : E_OK;
+}
+
+int tspgpu_time_nl_sweep(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean)
+{
+    return m2_time(ctx, slot, reps, ms_mean, true);
 }
 
 } // extern "C"

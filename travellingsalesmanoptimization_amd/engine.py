@@ -52,7 +52,8 @@ class Engine:
                  "persist_window", "persist_handed", "persist_sweeps", "vns_mode", "stream_persist",
                  "otf_kernel", "ceil_int", "em_form", "em_stale", "em_steps", "or_batch_r", "or_single_r",
                  "or_block", "or_nch", "or_otf", "or_otf_R",
-                 "multi_sweeps", "multi_moves", "multi_max_moves", "multi_r", "multi_block", "multi_nch"]
+                 "multi_sweeps", "multi_moves", "multi_max_moves", "multi_r", "multi_block", "multi_nch",
+                 "nl_k", "nl_sweeps", "nl_moves", "nl_polish_sweeps", "nl_nodes"]
         return {k: int(self.L.tspgpu_info(self.ctx, i)) for i, k in enumerate(names)}
 
     # ---- instance
@@ -153,6 +154,35 @@ class Engine:
         rc = self._ck(self.L.tspgpu_two_opt_multi(self.ctx, path, C.byref(c), float(time_left_s), C.byref(s), C.byref(m)),
                       ok=(T_OK, DEADLINE_EXCEEDED))
         return c.value, s.value, m.value, rc
+
+    def neighbours_build(self, K):
+        """neighbour lists of K nodes (1..16; 0 drops them) for the cost source in place (include/tspgpu.h "Neighbour-list 2-opt")."""
+        self._ck(self.L.tspgpu_neighbours_build(self.ctx, int(K)))
+
+    def neighbours_get(self):
+        """-> (nodes [n][K'], weights [n][K']) of the lists in place."""
+        k = int(self.L.tspgpu_info(self.ctx, 42))
+        nodes = np.empty((self.n, max(k, 1)), dtype=np.int32)
+        w = np.empty((self.n, max(k, 1)), dtype=np.float64)
+        self._ck(self.L.tspgpu_neighbours_get(self.ctx, nodes, w.ctypes.data))
+        return nodes, w
+
+    def two_opt_nl_once(self, path, cost, cap=None):
+        """one neighbour-list 2-opt sweep; arguments and results as two_opt_multi_once."""
+        cap = self.n if cap is None else int(cap)
+        c, k = C.c_double(cost), C.c_int()
+        mv = np.empty(2 * max(cap, 1), dtype=np.int32)
+        dl = np.empty(max(cap, 1), dtype=np.float64)
+        self._ck(self.L.tspgpu_two_opt_nl_once(self.ctx, path, C.byref(c), C.byref(k), mv, dl, cap))
+        return c.value, mv[:2 * k.value].reshape(-1, 2).copy(), dl[:k.value].copy()
+
+    def two_opt_nl(self, path, time_left_s=-1.0, polish=True):
+        """neighbour-list 2-opt sweeps until one accepts nothing, then (polish) the parallel-move descent on the result;
+        path in place -> dict(cost, sweeps, moves, polish_sweeps, polish_moves, rc)."""
+        c, s, m, ps, pm = C.c_double(), C.c_long(), C.c_long(), C.c_long(), C.c_long()
+        rc = self._ck(self.L.tspgpu_two_opt_nl(self.ctx, path, C.byref(c), float(time_left_s), 1 if polish else 0, C.byref(s), C.byref(m),
+                                               C.byref(ps), C.byref(pm)), ok=(T_OK, DEADLINE_EXCEEDED))
+        return {"cost": c.value, "sweeps": s.value, "moves": m.value, "polish_sweeps": ps.value, "polish_moves": pm.value, "rc": rc}
 
     def local_search(self, path, time_left_s=-1.0):
         """2-opt and Or-opt in turn until neither improves; path in place ->
@@ -289,6 +319,18 @@ class Engine:
         rc = self._ck(self.L.tspgpu_tour_two_opt_multi(self.ctx, int(slot), int(max_sweeps), float(time_left_s), C.byref(s), C.byref(m)),
                       ok=(T_OK, DEADLINE_EXCEEDED))
         return s.value, m.value, rc
+
+    def tour_two_opt_nl(self, slot, max_sweeps=-1, time_left_s=-1.0):
+        """neighbour-list 2-opt sweeps on a slot -> (sweeps, moves, rc)."""
+        s, m = C.c_long(), C.c_long()
+        rc = self._ck(self.L.tspgpu_tour_two_opt_nl(self.ctx, int(slot), int(max_sweeps), float(time_left_s), C.byref(s), C.byref(m)),
+                      ok=(T_OK, DEADLINE_EXCEEDED))
+        return s.value, m.value, rc
+
+    def time_nl_sweep(self, slot, reps):
+        ms = C.c_float()
+        self._ck(self.L.tspgpu_time_nl_sweep(self.ctx, slot, reps, C.byref(ms)))
+        return ms.value
 
     def time_multi_sweep(self, slot, reps):
         ms = C.c_float()

@@ -156,6 +156,10 @@ static void multi_stats(const char *what, struct tspgpu_multi *m, int starts, lo
 /* TSP_2OPT_MULTI=1 (tsp_run_algorithm): ref_2opt runs the parallel-move descent (tspgpu_two_opt_multi, an extension: a 2-opt
  * local optimum by another trajectory than the reference's) */
 static int two_opt_multi_on = 0;
+/* TSP_2OPT_NEIGHBOURS=K, K in 1..16 (tsp_run_algorithm): ref_2opt runs the neighbour-list descent over lists of K nodes
+ * (tspgpu_two_opt_nl), followed by the parallel-move descent as a polish unless TSP_2OPT_NEIGHBOURS_POLISH=0.  It goes
+ * before TSP_2OPT_MULTI. */
+static int two_opt_nl_k = 0, two_opt_nl_polish = 1;
 
 /* refinment.c:3-37.  Cost recompute, sweep loop and stop rule run on the device
  * (tspgpu_two_opt); the deadline is polled once per batch of sweeps instead of per sweep. */
@@ -175,7 +179,17 @@ ERROR_CODE ref_2opt(tsp_solution *solution, double *costs, bool update_incumbent
         e = DEADLINE_EXCEEDED;
     } else {
         int rc = -1;
-        if (two_opt_multi_on) {
+        if (two_opt_nl_k) {
+            /* the lists belong to the costs in place: built at the first call, and again behind every new matrix (ctx_for) */
+            const int kp = two_opt_nl_k < tsp_inst.nnodes - 1 ? two_opt_nl_k : tsp_inst.nnodes - 1;
+            rc = tspgpu_info(g, 42) == kp ? 0 : tspgpu_neighbours_build(g, two_opt_nl_k);
+            if (rc == 0)
+                rc = tspgpu_two_opt_nl(g, solution->path, &solution->cost, time_left(), two_opt_nl_polish, NULL, NULL, NULL, NULL);
+            if (rc == FAILED_PRECONDITION || rc == RESOURCE_EXHAUSTED) {   /* an asymmetric matrix, a size limit: the tour is untouched */
+                log_warn("TSP_2OPT_NEIGHBOURS=%d: %s; running tspgpu_two_opt", two_opt_nl_k, tspgpu_last_error(g));
+                rc = -1;
+            }
+        } else if (two_opt_multi_on) {
             rc = tspgpu_two_opt_multi(g, solution->path, &solution->cost, time_left(), NULL, NULL);
             if (rc == FAILED_PRECONDITION || rc == RESOURCE_EXHAUSTED) {   /* an asymmetric matrix, a size limit: the tour is untouched */
                 log_warn("TSP_2OPT_MULTI=1: %s; running tspgpu_two_opt", tspgpu_last_error(g));
@@ -629,7 +643,7 @@ ERROR_CODE mh_VNS(void)
     FILE *f = fopen("results/VNSResults.dat", "w+");
     e = T_OK;
     const char *on_host = getenv("TSP_VNS_HOST");
-    if ((on_host && atoi(on_host)) || two_opt_multi_on) {      /* (the resident loop's local search is the reference's descent) */
+    if ((on_host && atoi(on_host)) || two_opt_multi_on || two_opt_nl_k) {      /* (the resident loop's local search is the reference's descent) */
         for (int it = 0; it < tsp_env.k; it++) {
             if (past_deadline()) { e = DEADLINE_EXCEEDED; break; }
             e = ref_2opt(&s, tsp_inst.costs, true);
@@ -764,15 +778,34 @@ static int env_switch(const char *name)
     return -1;
 }
 
+/* TSP_2OPT_NEIGHBOURS: unset or 0 = off, 1..16 = the list length; anything else is an error (-1) */
+static int env_neighbours(void)
+{
+    const char *v = getenv("TSP_2OPT_NEIGHBOURS");
+    if (!v) return 0;
+    char *end = NULL;
+    const long k = strtol(v, &end, 10);
+    if (*v && !*end && k >= 0 && k <= 16) return (int)k;
+    fprintf(stderr, "tsp: TSP_2OPT_NEIGHBOURS=\"%s\": expected a list length from 1 to 16 (or 0: off)\n", v);
+    return -1;
+}
+
 /* ===================================================================== main.c:4-87 */
 ERROR_CODE tsp_run_algorithm(void)
 {
     const int polish = env_switch("TSP_OR_OPT"), every_start = env_switch("TSP_OR_OPT_EVERY_START");
     const int polish_mf = env_switch("TSP_OR_OPT_MATRIX_FREE");
     const int multi = env_switch("TSP_2OPT_MULTI");
-    if (polish < 0 || every_start < 0 || polish_mf < 0 || multi < 0) return INVALID_ARGUMENT;
+    const int nl_k = env_neighbours();
+    const char *nl_polish_set = getenv("TSP_2OPT_NEIGHBOURS_POLISH");
+    const int nl_polish = nl_polish_set ? env_switch("TSP_2OPT_NEIGHBOURS_POLISH") : 1;
+    if (polish < 0 || every_start < 0 || polish_mf < 0 || multi < 0 || nl_k < 0 || nl_polish < 0) return INVALID_ARGUMENT;
     two_opt_multi_on = multi;
-    if (multi) log_warn("TSP_2OPT_MULTI=1: ref_2opt runs the parallel-move descent; results differ from the reference's trajectory");
+    two_opt_nl_k = nl_k;
+    two_opt_nl_polish = nl_polish;
+    if (nl_k) log_warn("TSP_2OPT_NEIGHBOURS=%d: ref_2opt runs the neighbour-list descent%s; results differ from the reference's trajectory",
+                       nl_k, nl_polish ? " and the parallel-move polish" : ", no polish: a local optimum of the list neighbourhood only");
+    else if (multi) log_warn("TSP_2OPT_MULTI=1: ref_2opt runs the parallel-move descent; results differ from the reference's trajectory");
     free(tsp_inst.best_solution.path);
     tsp_inst.best_solution.path = (int *)calloc((size_t)tsp_inst.nnodes, sizeof(int));
     ERROR_CODE e;
