@@ -3198,11 +3198,9 @@ struct tspgpu_ctx {
 
     // Or-opt (tspgpu_oropt.inc)
     OrCtl *d_or = nullptr;     // control block, allocated on first use
-    bool or_attr[9] = {false, false, false, false, false, false, false, false, false};
     // ... over a batch of tours: one control block per slot, the list of slots a launch works on (device, and its pinned staging)
     OrCtl *d_or_ctl = nullptr;
     int *d_or_live = nullptr, *h_or_live = nullptr;
-    bool or_battr[9] = {false, false, false, false, false, false, false, false, false};
     int or_batch_R = 0;        // positions per sweep workgroup in the first Or-opt round of the last batched descent
     // ... in matrix-free mode (k_oropt_sweep_otf): single tours only
     int opt_or_otf = 0;        // TSPGPU_OPT_OR_MATRIX_FREE: 0 refuse Or-opt in matrix-free mode (code 12), 1 run it from the points
@@ -3213,7 +3211,6 @@ struct tspgpu_ctx {
     // parallel-move 2-opt (tspgpu_multi2opt.inc): control block and the candidate arrays of the slot a descent runs on, on first use
     M2Ctl *d_m2 = nullptr;
     M2Buf m2{};
-    bool m2_attr[12] = {false, false, false, false, false, false, false, false, false, false, false, false};
     long m2_sweeps = 0, m2_moves = 0, m2_max_k = 0;    // the last parallel-move descent
 
     // neighbour-list 2-opt (tspgpu_nl2opt.inc): the lists of the cost source in place (tspgpu_neighbours_build)
@@ -3226,6 +3223,7 @@ struct tspgpu_ctx {
     int opt_fused = 1;         // 1 = one launch per sweep where applicable
 
     std::vector<GraphEntry> graphs;
+    std::vector<const void *> max_lds_fns;     // kernels whose maximum dynamic LDS is set already (ensure_max_lds)
 
     // timing
     std::vector<hipEvent_t> ev;
@@ -3450,6 +3448,103 @@ static size_t elem_size(int elem) { return elem == TSPGPU_ELEM_F64 ? 8 : elem ==
         else { typedef u16 T; __VA_ARGS__; }                                  \
     } while (0)
 
+// f(kind, pts, spts) for the point kind of a matrix-free instance: `kind` a compile-time constant (kind()), pts the points and
+// spts the gathered successor points, typed for it -- the int2 points of ceil_int() where they exist, as launch_sweep
+template <typename F> static void kind_switch(const tspgpu_ctx *ctx, F &&f)
+{
+    double2 *const pts = ctx->d_pts, *const spts = ctx->d_spts;
+    if (ctx->ceil_int() && ctx->d_ipts) f(std::integral_constant<int, KIND_CEIL_INT>{}, ctx->d_ipts, reinterpret_cast<int2 *>(spts));
+    else if (ctx->kind == TSPGPU_EUC_2D) f(std::integral_constant<int, TSPGPU_EUC_2D>{}, pts, spts);
+    else if (ctx->kind == TSPGPU_ATT) f(std::integral_constant<int, TSPGPU_ATT>{}, pts, spts);
+    else f(std::integral_constant<int, TSPGPU_CEIL_2D>{}, pts, spts);
+}
+
+// room for `points` gathered successor points
+static int ensure_spts(tspgpu_ctx *ctx, size_t points)
+{
+    if (ctx->spts_cap >= points) return E_OK;
+    if (ctx->d_spts) hipFree(ctx->d_spts);
+    ctx->d_spts = nullptr; ctx->spts_cap = 0;
+    HIP_TRY(hipMalloc(&ctx->d_spts, points * sizeof(double2)));
+    ctx->spts_cap = points;
+    return E_OK;
+}
+
+// the kernel `fn` may use all of a workgroup's LDS as dynamic LDS: set at the first launch of each kernel
+static int ensure_max_lds(tspgpu_ctx *ctx, const void *fn)
+{
+    std::vector<const void *> &seen = ctx->max_lds_fns;
+    if (std::find(seen.begin(), seen.end(), fn) != seen.end()) return E_OK;
+    HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->lds_max));
+    seen.push_back(fn);
+    return E_OK;
+}
+
+// a control block to the device / `count` of them back, the stream drained (the host copy may sit on the caller's stack)
+template <typename C> static int ctl_put(tspgpu_ctx *ctx, C *dev, const C &host)
+{
+    HIP_TRY(hipMemcpyAsync(dev, &host, sizeof(C), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return E_OK;
+}
+template <typename C> static int ctl_get(tspgpu_ctx *ctx, C *host, const C *dev, size_t count = 1)
+{
+    HIP_TRY(hipMemcpyAsync(host, dev, count * sizeof(C), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    return E_OK;
+}
+
+// the mean time in ms of `reps` calls of body() on the engine's stream, behind one call of warm(); either returns a code, and
+// any failure ends the measurement with it.  The events are destroyed on every way out
+template <typename W, typename B> static int time_launches(tspgpu_ctx *ctx, int reps, W &&warm, B &&body, float *ms_mean)
+{
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    float ms = 0;
+    auto timed = [&]() -> int {
+        int rc;
+        HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
+        if ((rc = warm())) return rc;
+        HIP_TRY(hipEventRecord(e0, ctx->stream));
+        for (int i = 0; i < reps; i++) if ((rc = body())) return rc;
+        HIP_TRY(hipEventRecord(e1, ctx->stream));
+        HIP_TRY(hipEventSynchronize(e1));
+        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+        return E_OK;
+    };
+    const int rc = timed();
+    if (e0) hipEventDestroy(e0);
+    if (e1) hipEventDestroy(e1);
+    if (!rc) *ms_mean = ms / reps;
+    return rc;
+}
+
+// geometry of a candidate sweep: threads, 16-byte vectors per thread and row, tour positions per workgroup, workgroups, the
+// workgroups a CU holds, dynamic LDS bytes, and the kernel (the caller's to fill in)
+struct SweepGeom { int BT, NCH, R, W, occ; size_t lds; const void *fn; };
+
+// ... for a kernel that keeps `rows` matrix rows and `extra` more bytes in LDS: R is one wave of workgroups over the chip,
+// clamped to [rmin, rmax]; NCH is the first of `nchs` (ascending) that covers a row.  Matrix-free mode: BT = 256, NCH = 0,
+// R = otf_run, no dynamic LDS
+static SweepGeom sweep_geom(const tspgpu_ctx *ctx, int rows, size_t extra, int rmin, int rmax, std::initializer_list<int> nchs, int otf_run)
+{
+    SweepGeom P{};
+    const int n = ctx->n;
+    if (ctx->otf) {
+        P.BT = 256; P.R = otf_run; P.W = (n + P.R - 1) / P.R;
+        return P;
+    }
+    const size_t esz = elem_size(ctx->elem);
+    const int nvec = ctx->ld / (int)(16 / esz);
+    P.BT = nvec <= 256 ? 256 : nvec <= 1024 ? 512 : 1024;
+    for (int c : nchs) { P.NCH = c; if (c * P.BT >= nvec) break; }
+    P.lds = rows * (size_t)ctx->ld * esz + extra;
+    P.occ = (int)std::max<size_t>(1, std::min<size_t>(ctx->lds_max / P.lds, (size_t)(2048 / P.BT)));
+    const int target = ctx->cus * P.occ;
+    P.R = std::min(std::max((n + target - 1) / target, rmin), rmax);
+    P.W = (n + P.R - 1) / P.R;
+    return P;
+}
+
 // --------------------------------------------------------------- launch plan
 template <typename T, int NCH, int D, bool TABU> static const void *pipe_fn() { return (const void *)k_sweep_pipe<T, NCH, D, TABU>; }
 
@@ -3572,12 +3667,7 @@ static int make_plan(tspgpu_ctx *ctx, int ntours)
     int G = 1, P = n;
     if (ctx->otf) {
         // matrix-free: 8 tour edges per workgroup, the whole b range per workgroup
-        if (ctx->spts_cap < (size_t)ntours * n) {
-            if (ctx->d_spts) hipFree(ctx->d_spts);
-            ctx->d_spts = nullptr; ctx->spts_cap = 0;
-            HIP_TRY(hipMalloc(&ctx->d_spts, (size_t)ntours * n * sizeof(double2)));
-            ctx->spts_cap = (size_t)ntours * n;
-        }
+        if (const int rc = ensure_spts(ctx, (size_t)ntours * n)) return rc;
         P = (ctx->cost_bound < 33554432.0 && n < 131072) ? (ctx->plan_otf_early ? OTF8_RUN_INT : OTF8_RUN) : 8;     // (k_sweep_otf8 / k_sweep_otf: see launch_sweep)
         G = (n + P - 1) / P;
         if (G > ctx->S.pstride) return fail(ctx, E_INTERNAL, "partial stride %d < %d workgroups", ctx->S.pstride, G);
@@ -3789,6 +3879,10 @@ static double now_s()
 {
     return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
+
+// the entry points' time limit as a point in time (< 0: none), and what they answer when it passed
+static double deadline_of(double time_left_s) { return time_left_s >= 0 ? now_s() + time_left_s : -1; }
+static int done_code(bool late) { return late ? E_DEADLINE : E_OK; }
 
 static int ensure_fused(tspgpu_ctx *ctx)
 {
@@ -5580,18 +5674,8 @@ int tspgpu_time_sweep(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean)
     if ((rc = need_slot(ctx, slot))) return rc;
     if ((rc = ensure_plan(ctx, 1, false))) return rc;
     hipLaunchKernelGGL(k_rearm, dim3(1), dim3(64), 0, ctx->stream, ctx->S, slot, 1, -1);
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-    if ((rc = launch_sweep(ctx, slot, 1, false))) return rc; // warm
-    HIP_TRY(hipEventRecord(e0, ctx->stream));
-    for (int i = 0; i < reps; i++) if ((rc = launch_sweep(ctx, slot, 1, false))) return rc;
-    HIP_TRY(hipEventRecord(e1, ctx->stream));
-    HIP_TRY(hipEventSynchronize(e1));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    hipEventDestroy(e0); hipEventDestroy(e1);
-    *ms_mean = ms / reps;
-    return E_OK;
+    auto sweep = [&] { return launch_sweep(ctx, slot, 1, false); };
+    return time_launches(ctx, reps, sweep, sweep, ms_mean);
 }
 
 int tspgpu_time_build(tspgpu_ctx *ctx, int reps, float *ms_mean)
@@ -5602,18 +5686,8 @@ int tspgpu_time_build(tspgpu_ctx *ctx, int reps, float *ms_mean)
     if (rc) return rc;
     if (!ctx->have_points) return fail(ctx, E_PRECOND, "no points");
     if (ctx->otf) { *ms_mean = 0; return E_OK; }
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-    if ((rc = launch_build(ctx))) return rc;
-    HIP_TRY(hipEventRecord(e0, ctx->stream));
-    for (int i = 0; i < reps; i++) if ((rc = launch_build(ctx))) return rc;
-    HIP_TRY(hipEventRecord(e1, ctx->stream));
-    HIP_TRY(hipEventSynchronize(e1));
-    float ms = 0;
-    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    hipEventDestroy(e0); hipEventDestroy(e1);
-    *ms_mean = ms / reps;
-    return E_OK;
+    auto build = [&] { return launch_build(ctx); };
+    return time_launches(ctx, reps, build, build, ms_mean);
 }
 
 int tspgpu_timing_read(tspgpu_ctx *ctx, double *sweep_ms_total, long *sweep_launches, int reset)
@@ -5811,30 +5885,19 @@ static int or_check(tspgpu_ctx *ctx, bool batch = false)
     if (rc) return rc;
     if (ctx->otf && (batch || !ctx->opt_or_otf))
         return fail(ctx, E_UNIMPL, "Or-opt needs the resident cost matrix: it is not implemented in matrix-free mode");
-    if (ctx->otf) {     // from the points: symmetric by construction, costs below 2^27, n <= 131 072 (new_instance), no row in LDS
-        if (ctx->n < 8) return fail(ctx, E_INVALID, "Or-opt needs at least 8 nodes, got %d", ctx->n);
-        if (ctx->spts_cap < (size_t)ctx->n) {       // the gathered successor points, sized as make_plan sizes them for one tour
-            if (ctx->d_spts) hipFree(ctx->d_spts);
-            ctx->d_spts = nullptr; ctx->spts_cap = 0;
-            HIP_TRY(hipMalloc(&ctx->d_spts, (size_t)ctx->n * sizeof(double2)));
-            ctx->spts_cap = (size_t)ctx->n;
-        }
-        if (!ctx->d_or) HIP_TRY(hipMalloc(&ctx->d_or, sizeof(OrCtl)));
-        return E_OK;
-    }
     if (ctx->n < 8) return fail(ctx, E_INVALID, "Or-opt needs at least 8 nodes, got %d", ctx->n);
-    if (!ctx->symmetric) return fail(ctx, E_PRECOND, "Or-opt needs a symmetric cost matrix");
-    const int lim = or_max_n(ctx, elem_size(ctx->elem));
-    if (ctx->ld > lim)
-        return fail(ctx, E_EXHAUSTED, "Or-opt keeps four matrix rows in LDS: n = %d is past the limit of %d nodes for %d-byte cells",
-                    ctx->n, lim, (int)elem_size(ctx->elem));
+    if (ctx->otf) {     // from the points: symmetric by construction, costs below 2^27, n <= 131 072 (new_instance), no row in LDS
+        if ((rc = ensure_spts(ctx, (size_t)ctx->n))) return rc;     // sized as make_plan sizes them for one tour
+    } else {
+        if (!ctx->symmetric) return fail(ctx, E_PRECOND, "Or-opt needs a symmetric cost matrix");
+        const int lim = or_max_n(ctx, elem_size(ctx->elem));
+        if (ctx->ld > lim)
+            return fail(ctx, E_EXHAUSTED, "Or-opt keeps four matrix rows in LDS: n = %d is past the limit of %d nodes for %d-byte cells",
+                        ctx->n, lim, (int)elem_size(ctx->elem));
+    }
     if (!ctx->d_or) HIP_TRY(hipMalloc(&ctx->d_or, sizeof(OrCtl)));
     return E_OK;
 }
-
-// geometry of a sweep launch: threads, 16-byte vectors per thread and row, positions per workgroup, workgroups, LDS bytes
-// (matrix-free mode: BT = 256, NCH = 0, R = OR_OTF_RUN, no dynamic LDS; early = the early-out form)
-struct OrPlan { int BT, NCH, R, W; size_t lds; const void *fn; int fi; bool early; };
 
 template <typename T> static const void *or_sweep_fn(int nch)
 {
@@ -5845,28 +5908,12 @@ template <typename T> static const void *or_sweep_fn(int nch)
 // tools/oropt_otf_rate.py has measured it faster, and no such measurement is recorded yet
 static bool or_otf_early(const tspgpu_ctx *ctx) { return ctx->opt_or_otf_early == 1; }
 
-static OrPlan or_plan(const tspgpu_ctx *ctx)
+// four rows in LDS, at most three vectors per thread and row below every LDS limit, R at least 2 and the partial slots of a tour
+static SweepGeom or_plan(const tspgpu_ctx *ctx)
 {
-    OrPlan P;
-    P.early = false;
-    if (ctx->otf) {
-        P.BT = 256; P.NCH = 0; P.R = OR_OTF_RUN; P.W = (ctx->n + P.R - 1) / P.R; P.lds = 0; P.fn = nullptr; P.fi = 0;
-        P.early = or_otf_early(ctx);
-        return P;
-    }
-    const size_t esz = elem_size(ctx->elem);
-    const int nvec = ctx->ld / (int)(16 / esz), n = ctx->n;
-    P.BT = nvec <= 256 ? 256 : nvec <= 1024 ? 512 : 1024;
-    P.NCH = (nvec + P.BT - 1) / P.BT;                       // <= 3 below every LDS limit
-    P.lds = 4 * (size_t)ctx->ld * esz + OR_EXTRA;
-    const int occ = (int)std::max<size_t>(1, std::min<size_t>(ctx->lds_max / P.lds, (size_t)(2048 / P.BT)));
-    const int target = ctx->cus * occ;                      // one wave of workgroups over the chip
-    int R = (n + target - 1) / target;
-    R = std::max(R, (n + MAX_WGS_PER_TOUR - 1) / MAX_WGS_PER_TOUR);    // the partial slots of a tour
-    P.R = std::min(std::max(R, 2), OR_RMAX);
-    P.W = (n + P.R - 1) / P.R;
-    ELEM_SWITCH(ctx->elem, T, P.fn = or_sweep_fn<T>(P.NCH));
-    P.fi = (ctx->elem == TSPGPU_ELEM_F64 ? 0 : ctx->elem == TSPGPU_ELEM_I32 ? 3 : 6) + P.NCH - 1;
+    const int rmin = std::max(2, (ctx->n + MAX_WGS_PER_TOUR - 1) / MAX_WGS_PER_TOUR);
+    SweepGeom P = sweep_geom(ctx, 4, OR_EXTRA, rmin, OR_RMAX, {1, 2, 3}, OR_OTF_RUN);
+    if (!ctx->otf) ELEM_SWITCH(ctx->elem, T, P.fn = or_sweep_fn<T>(P.NCH));
     return P;
 }
 
@@ -5875,43 +5922,47 @@ static int or_single_R(const tspgpu_ctx *ctx) { return ctx->have_costs && !ctx->
 static int or_single_geom(const tspgpu_ctx *ctx, bool nch)
 {
     if (!or_single_R(ctx)) return 0;
-    const OrPlan P = or_plan(ctx);
+    const SweepGeom P = or_plan(ctx);
     return nch ? P.NCH : P.BT;
 }
 
-// matrix-free mode: the gather of the successors' points (it must see the tour the previous apply left), then the sweep
-static int or_launch_sweep_otf(tspgpu_ctx *ctx, int slot, const OrPlan &P, bool gather)
+// spts := the points of the successors in `slot`, unless *stop (a control block's, on the device) says the descent is over
+static int launch_spts_gather(tspgpu_ctx *ctx, int slot, const int *stop)
 {
     const int n = ctx->n;
-    const bool ip = ctx->ceil_int() && ctx->d_ipts;         // int2 points, as launch_sweep
+    kind_switch(ctx, [&](auto kind, auto *pts, auto *spts) {
+        hipLaunchKernelGGL((k_spts_gather<typename OrPt<kind()>::type>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->S, n, slot,
+                           pts, spts, stop);
+    });
+    HIP_TRY(hipGetLastError());
+    return E_OK;
+}
+
+// matrix-free mode: the gather of the successors' points (it must see the tour the previous apply left), then the sweep
+static int or_launch_sweep_otf(tspgpu_ctx *ctx, int slot, const SweepGeom &P, bool gather)
+{
+    const int n = ctx->n;
+    const bool early = or_otf_early(ctx);
     const OrCtl *ctl = ctx->d_or;
     if (gather) {
-        if (ip) hipLaunchKernelGGL((k_oropt_gather<int2>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->S, n, slot,
-                                   (const int2 *)ctx->d_ipts, reinterpret_cast<int2 *>(ctx->d_spts), ctl);
-        else hipLaunchKernelGGL((k_oropt_gather<double2>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->S, n, slot,
-                                (const double2 *)ctx->d_pts, ctx->d_spts, ctl);
-        HIP_TRY(hipGetLastError());
+        const int rc = launch_spts_gather(ctx, slot, &ctl->stop);
+        if (rc) return rc;
     }
-#define OR_OTF(K, PTS, SPTS) do { if (P.early) hipLaunchKernelGGL((k_oropt_sweep_otf<K, true>), dim3(P.W), dim3(P.BT), 0, ctx->stream, ctx->S, PTS, SPTS, n, slot, ctl); \
-                                  else hipLaunchKernelGGL((k_oropt_sweep_otf<K, false>), dim3(P.W), dim3(P.BT), 0, ctx->stream, ctx->S, PTS, SPTS, n, slot, ctl); } while (0)
-    if (ip) OR_OTF(KIND_CEIL_INT, (const int2 *)ctx->d_ipts, reinterpret_cast<const int2 *>(ctx->d_spts));
-    else if (ctx->kind == TSPGPU_EUC_2D) OR_OTF(TSPGPU_EUC_2D, (const double2 *)ctx->d_pts, (const double2 *)ctx->d_spts);
-    else if (ctx->kind == TSPGPU_ATT) OR_OTF(TSPGPU_ATT, (const double2 *)ctx->d_pts, (const double2 *)ctx->d_spts);
-    else OR_OTF(TSPGPU_CEIL_2D, (const double2 *)ctx->d_pts, (const double2 *)ctx->d_spts);
-#undef OR_OTF
+    kind_switch(ctx, [&](auto kind, auto *pts, auto *spts) {
+        if (early) hipLaunchKernelGGL((k_oropt_sweep_otf<kind(), true>), dim3(P.W), dim3(P.BT), 0, ctx->stream, ctx->S, pts, spts, n, slot, ctl);
+        else hipLaunchKernelGGL((k_oropt_sweep_otf<kind(), false>), dim3(P.W), dim3(P.BT), 0, ctx->stream, ctx->S, pts, spts, n, slot, ctl);
+    });
     HIP_TRY(hipGetLastError());
-    ctx->or_otf_form = P.early ? 2 : 1;
+    ctx->or_otf_form = early ? 2 : 1;
     ctx->or_otf_R = P.R;
     return E_OK;
 }
 
-static int or_launch_sweep(tspgpu_ctx *ctx, int slot, const OrPlan &P, bool gather = true)
+static int or_launch_sweep(tspgpu_ctx *ctx, int slot, const SweepGeom &P, bool gather = true)
 {
     if (ctx->otf) return or_launch_sweep_otf(ctx, slot, P, gather);
-    if (!ctx->or_attr[P.fi]) {
-        HIP_TRY(hipFuncSetAttribute(P.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->lds_max));
-        ctx->or_attr[P.fi] = true;
-    }
+    const int rc = ensure_max_lds(ctx, P.fn);
+    if (rc) return rc;
 #define OR_SWEEP(T, N) hipLaunchKernelGGL((k_oropt_sweep<T, N>), dim3(P.W), dim3(P.BT), P.lds, ctx->stream, ctx->S, (const T *)ctx->d_mat, \
                                           ctx->n, ctx->ld, slot, P.R, (const OrCtl *)ctx->d_or)
     ELEM_SWITCH(ctx->elem, T, { if (P.NCH == 1) OR_SWEEP(T, 1); else if (P.NCH == 2) OR_SWEEP(T, 2); else OR_SWEEP(T, 3); });
@@ -5920,21 +5971,16 @@ static int or_launch_sweep(tspgpu_ctx *ctx, int slot, const OrPlan &P, bool gath
     return E_OK;
 }
 
-static int or_launch_apply(tspgpu_ctx *ctx, int slot, const OrPlan &P)
+static int or_launch_apply(tspgpu_ctx *ctx, int slot, const SweepGeom &P)
 {
     const int BT = std::min(1024, std::max(64, pow2_ceil(ctx->n / 8)));
-    if (ctx->otf) {
-#define OR_APPLY_OTF(K, PTS) hipLaunchKernelGGL((k_oropt_apply_otf<K>), dim3(1), dim3(BT), 0, ctx->stream, ctx->S, PTS, ctx->n, slot, P.W, ctx->d_or)
-        if (ctx->ceil_int() && ctx->d_ipts) OR_APPLY_OTF(KIND_CEIL_INT, (const int2 *)ctx->d_ipts);
-        else if (ctx->kind == TSPGPU_EUC_2D) OR_APPLY_OTF(TSPGPU_EUC_2D, (const double2 *)ctx->d_pts);
-        else if (ctx->kind == TSPGPU_ATT) OR_APPLY_OTF(TSPGPU_ATT, (const double2 *)ctx->d_pts);
-        else OR_APPLY_OTF(TSPGPU_CEIL_2D, (const double2 *)ctx->d_pts);
-#undef OR_APPLY_OTF
-        HIP_TRY(hipGetLastError());
-        return E_OK;
-    }
-    ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_oropt_apply<T>), dim3(1), dim3(BT), 0, ctx->stream, ctx->S, (const T *)ctx->d_mat,
-                                                 ctx->n, ctx->ld, slot, P.W, ctx->d_or));
+    if (ctx->otf)
+        kind_switch(ctx, [&](auto kind, auto *pts, auto *) {
+            hipLaunchKernelGGL((k_oropt_apply_otf<kind()>), dim3(1), dim3(BT), 0, ctx->stream, ctx->S, pts, ctx->n, slot, P.W, ctx->d_or);
+        });
+    else
+        ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_oropt_apply<T>), dim3(1), dim3(BT), 0, ctx->stream, ctx->S, (const T *)ctx->d_mat,
+                                                     ctx->n, ctx->ld, slot, P.W, ctx->d_or));
     HIP_TRY(hipGetLastError());
     return E_OK;
 }
@@ -5952,19 +5998,17 @@ static int or_run(tspgpu_ctx *ctx, int slot, long max_moves, double t_end, long 
     if (moves) *moves = 0;
     if (last) *last = C;
     if (max_moves == 0) return E_OK;
-    HIP_TRY(hipMemcpyAsync(ctx->d_or, &C, sizeof C, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));       // (C is on the stack)
-    const OrPlan P = or_plan(ctx);
+    int rc = ctl_put(ctx, ctx->d_or, C);
+    if (rc) return rc;
+    const SweepGeom P = or_plan(ctx);
     for (;;) {
         if (t_end >= 0 && now_s() >= t_end) { if (late) *late = true; break; }
         const int K = t_end >= 0 ? 1 : 8;
         for (int i = 0; i < K; i++) {
-            int rc = or_launch_sweep(ctx, slot, P);
-            if (!rc) rc = or_launch_apply(ctx, slot, P);
-            if (rc) return rc;
+            if ((rc = or_launch_sweep(ctx, slot, P))) return rc;
+            if ((rc = or_launch_apply(ctx, slot, P))) return rc;
         }
-        HIP_TRY(hipMemcpyAsync(&C, ctx->d_or, sizeof C, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if ((rc = ctl_get(ctx, &C, ctx->d_or))) return rc;
         if (C.stop) break;
     }
     if (moves) *moves = (long)C.moves;
@@ -5975,7 +6019,7 @@ static int or_run(tspgpu_ctx *ctx, int slot, long max_moves, double t_end, long 
 // the descent of tspgpu_local_search on a slot: { 2-opt to its local optimum; Or-opt until nothing improves } until Or-opt applies nothing
 static int or_descent(tspgpu_ctx *ctx, int slot, double time_left_s, long *two_opt_sweeps, long *or_moves, int *rounds, bool *late)
 {
-    const double t_end = time_left_s >= 0 ? now_s() + time_left_s : -1;
+    const double t_end = deadline_of(time_left_s);
     long tw = 0, om = 0;
     int nr = 0, rc = E_OK;
     *late = false;
@@ -6012,12 +6056,11 @@ template <typename T> static const void *or_sweep_batch_fn(int nch)
 // or_plan sizes R so that ONE tour's workgroups fill the chip; with `live` tours in flight fewer workgroups per tour do, and a
 // workgroup of R positions streams R + 2 rows: the largest R at which live * W still gives every CU two workgroups (one to
 // compute while the other waits at its barrier), never below the single-tour R
-static OrPlan or_plan_batch(const tspgpu_ctx *ctx, int live)
+static SweepGeom or_plan_batch(const tspgpu_ctx *ctx, int live)
 {
-    OrPlan P = or_plan(ctx);
+    SweepGeom P = or_plan(ctx);
     const int n = ctx->n;
-    const int occ = (int)std::max<size_t>(1, std::min<size_t>(ctx->lds_max / P.lds, (size_t)(2048 / P.BT)));
-    const long target = (long)ctx->cus * std::min(occ, 2);
+    const long target = (long)ctx->cus * std::min(P.occ, 2);
     for (int R = OR_RMAX; R > P.R; R--)
         if ((long)live * ((n + R - 1) / R) >= target) { P.R = R; break; }
     P.W = (n + P.R - 1) / P.R;
@@ -6035,12 +6078,10 @@ static int or_set_live(tspgpu_ctx *ctx, const std::vector<int> &list)
 }
 
 // one Or-opt round on the first `live` slots of the list: a sweep launch and an apply launch (grid rows in runs of 65 535)
-static int or_launch_round(tspgpu_ctx *ctx, int live, const OrPlan &P)
+static int or_launch_round(tspgpu_ctx *ctx, int live, const SweepGeom &P)
 {
-    if (!ctx->or_battr[P.fi]) {
-        HIP_TRY(hipFuncSetAttribute(P.fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->lds_max));
-        ctx->or_battr[P.fi] = true;
-    }
+    const int rc = ensure_max_lds(ctx, P.fn);
+    if (rc) return rc;
     for (int off = 0; off < live; off += 65535) {
         const int rows = std::min(65535, live - off);
         const int *list = ctx->d_or_live + off;
@@ -6065,18 +6106,14 @@ static int or_launch_round(tspgpu_ctx *ctx, int live, const OrPlan &P)
 // tw / om / nr: per-slot 2-opt sweeps, Or-opt moves and 2-opt descents, [count].
 static int or_descent_batch(tspgpu_ctx *ctx, int slot0, int count, double time_left_s, long *tw, long *om, int *nr, bool *late)
 {
-    const double t_end = time_left_s >= 0 ? now_s() + time_left_s : -1;
+    const double t_end = deadline_of(time_left_s);
     std::vector<int> live(count), act;
     std::vector<OrCtl> hc(count);
     for (int i = 0; i < count; i++) { live[i] = slot0 + i; tw[i] = om[i] = 0; nr[i] = 0; }
     *late = false;
     ctx->or_batch_R = 0;
     int rc;
-    auto read_ctl = [&]() -> int {
-        HIP_TRY(hipMemcpyAsync(hc.data(), ctx->d_or_ctl + slot0, (size_t)count * sizeof(OrCtl), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        return E_OK;
-    };
+    auto read_ctl = [&] { return ctl_get(ctx, hc.data(), ctx->d_or_ctl + slot0, (size_t)count); };
     while (!live.empty()) {
         double left = -1;
         if (t_end >= 0 && (left = t_end - now_s()) <= 0) { *late = true; break; }
@@ -6098,7 +6135,7 @@ static int or_descent_batch(tspgpu_ctx *ctx, int slot0, int count, double time_l
             if (t_end >= 0 && now_s() >= t_end) { *late = true; break; }
             if (!fresh && (rc = or_set_live(ctx, act))) return rc;
             fresh = false;
-            const OrPlan P = or_plan_batch(ctx, (int)act.size());
+            const SweepGeom P = or_plan_batch(ctx, (int)act.size());
             if (!ctx->or_batch_R) ctx->or_batch_R = P.R;
             const int K = t_end >= 0 ? 1 : 8;
             for (int i = 0; i < K; i++)
@@ -6148,7 +6185,7 @@ int tspgpu_tours_local_search(tspgpu_ctx *ctx, int slot0, int count, double time
     if (two_opt_sweeps) std::copy(tw.begin(), tw.end(), two_opt_sweeps);
     if (or_moves) std::copy(om.begin(), om.end(), or_moves);
     if (rounds) std::copy(nr.begin(), nr.end(), rounds);
-    return late ? E_DEADLINE : E_OK;
+    return done_code(late);
 }
 
 int tspgpu_multistart_local_search(tspgpu_ctx *ctx, const int *starts, int nstarts, double time_left_s, int *best_path, double *best_cost,
@@ -6161,7 +6198,7 @@ int tspgpu_multistart_local_search(tspgpu_ctx *ctx, const int *starts, int nstar
     if (rc) return rc;
     if (ctx->opt_sweep_cap != -1)
         return fail(ctx, E_INVALID, "TSPGPU_OPT_SWEEP_CAP = %d: the 2-opt + Or-opt descent runs every 2-opt phase to its local optimum", ctx->opt_sweep_cap);
-    const double t_end = time_left_s >= 0 ? now_s() + time_left_s : -1;
+    const double t_end = deadline_of(time_left_s);
     const int chunk = std::min(nstarts, ctx->opt_max_tours);
     if ((rc = ensure_tours(ctx, chunk))) return rc;
     double best = DBL_MAX; int arg = -1; long sweeps = 0, moves = 0;
@@ -6192,7 +6229,7 @@ int tspgpu_multistart_local_search(tspgpu_ctx *ctx, const int *starts, int nstar
     *best_cost = best; *best_start = arg;
     if (total_two_opt_sweeps) *total_two_opt_sweeps = sweeps;
     if (total_or_moves) *total_or_moves = moves;
-    return late ? E_DEADLINE : E_OK;
+    return done_code(late);
 }
 
 int tspgpu_tour_or_opt(tspgpu_ctx *ctx, int slot, long max_moves, double time_left_s, long *moves)
@@ -6203,8 +6240,8 @@ int tspgpu_tour_or_opt(tspgpu_ctx *ctx, int slot, long max_moves, double time_le
     if (rc) return rc;
     if ((rc = need_slot(ctx, slot))) return rc;
     bool late = false;
-    if ((rc = or_run(ctx, slot, max_moves, time_left_s >= 0 ? now_s() + time_left_s : -1, moves, &late, nullptr))) return rc;
-    return late ? E_DEADLINE : E_OK;
+    if ((rc = or_run(ctx, slot, max_moves, deadline_of(time_left_s), moves, &late, nullptr))) return rc;
+    return done_code(late);
 }
 
 int tspgpu_tour_local_search(tspgpu_ctx *ctx, int slot, double time_left_s, long *two_opt_sweeps, long *or_moves, int *rounds)
@@ -6216,7 +6253,7 @@ int tspgpu_tour_local_search(tspgpu_ctx *ctx, int slot, double time_left_s, long
     if ((rc = need_slot(ctx, slot))) return rc;
     bool late = false;
     if ((rc = or_descent(ctx, slot, time_left_s, two_opt_sweeps, or_moves, rounds, &late))) return rc;
-    return late ? E_DEADLINE : E_OK;
+    return done_code(late);
 }
 
 int tspgpu_time_or_sweep(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean)
@@ -6228,27 +6265,9 @@ int tspgpu_time_or_sweep(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean)
     if (rc) return rc;
     if ((rc = need_slot(ctx, slot))) return rc;
     HIP_TRY(hipMemsetAsync(ctx->d_or, 0, sizeof(OrCtl), ctx->stream));
-    const OrPlan P = or_plan(ctx);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    float ms = 0;
-    // (the events are destroyed on every way out)
-    auto timed = [&]() -> int {
-        int r;
-        HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-        if ((r = or_launch_sweep(ctx, slot, P))) return r; // warm (matrix-free mode: with its gather; the timed launches are the sweep kernel alone)
-        HIP_TRY(hipEventRecord(e0, ctx->stream));
-        for (int i = 0; i < reps; i++) if ((r = or_launch_sweep(ctx, slot, P, false))) return r;
-        HIP_TRY(hipEventRecord(e1, ctx->stream));
-        HIP_TRY(hipEventSynchronize(e1));
-        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-        return E_OK;
-    };
-    rc = timed();
-    if (e0) hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
-    if (rc) return rc;
-    *ms_mean = ms / reps;
-    return E_OK;
+    const SweepGeom P = or_plan(ctx);
+    // warm: in matrix-free mode with its gather; the timed launches are the sweep kernel alone
+    return time_launches(ctx, reps, [&] { return or_launch_sweep(ctx, slot, P); }, [&] { return or_launch_sweep(ctx, slot, P, false); }, ms_mean);
 }
 
 int tspgpu_or_opt_once(tspgpu_ctx *ctx, int *path, double *cost, double *delta, int move[4])
@@ -6278,9 +6297,9 @@ int tspgpu_or_opt(tspgpu_ctx *ctx, int *path, double *cost, double time_left_s, 
     if ((rc = load_path(ctx, 0, path, -1))) return rc;
     HIP_TRY(hipMemcpyAsync(ctx->S.cost, cost, 8, hipMemcpyHostToDevice, ctx->stream));
     bool late = false;
-    if ((rc = or_run(ctx, 0, -1, time_left_s >= 0 ? now_s() + time_left_s : -1, moves, &late, nullptr))) return rc;
+    if ((rc = or_run(ctx, 0, -1, deadline_of(time_left_s), moves, &late, nullptr))) return rc;
     if ((rc = store_path(ctx, 0, path, cost, nullptr))) return rc;
-    return late ? E_DEADLINE : E_OK;
+    return done_code(late);
 }
 
 int tspgpu_local_search(tspgpu_ctx *ctx, int *path, double *cost, double time_left_s, long *two_opt_sweeps, long *or_moves, int *rounds)
@@ -6294,7 +6313,7 @@ int tspgpu_local_search(tspgpu_ctx *ctx, int *path, double *cost, double time_le
     bool late = false;
     if ((rc = or_descent(ctx, 0, time_left_s, two_opt_sweeps, or_moves, rounds, &late))) return rc;
     if ((rc = store_path(ctx, 0, path, cost, nullptr))) return rc;
-    return late ? E_DEADLINE : E_OK;
+    return done_code(late);
 }
 
 } // extern "C"
@@ -6311,12 +6330,7 @@ static int m2_check(tspgpu_ctx *ctx)
     if (!ctx->otf && (size_t)ctx->ld * elem_size(ctx->elem) + M2_EXTRA > ctx->lds_max)     // (the matrix 2-opt's own limit: tspgpu_build_costs)
         return fail(ctx, E_EXHAUSTED, "n = %d: a matrix row of %d-byte cells does not fit LDS (at most %d nodes)", n,
                     (int)elem_size(ctx->elem), (int)((ctx->lds_max - M2_EXTRA) / elem_size(ctx->elem)) & ~31);
-    if (ctx->otf && ctx->spts_cap < (size_t)n) {    // the gathered successor points, sized as make_plan sizes them for one tour
-        if (ctx->d_spts) hipFree(ctx->d_spts);
-        ctx->d_spts = nullptr; ctx->spts_cap = 0;
-        HIP_TRY(hipMalloc(&ctx->d_spts, (size_t)n * sizeof(double2)));
-        ctx->spts_cap = (size_t)n;
-    }
+    if (ctx->otf && (rc = ensure_spts(ctx, (size_t)n))) return rc;     // sized as make_plan sizes them for one tour
     if (!ctx->d_m2) HIP_TRY(hipMalloc(&ctx->d_m2, sizeof(M2Ctl)));
     if (!ctx->m2.raw_d) {
         M2Buf &B = ctx->m2;
@@ -6335,29 +6349,18 @@ static int m2_check(tspgpu_ctx *ctx)
     return E_OK;
 }
 
-// geometry of a candidate sweep: threads, 16-byte vectors per thread and row (the template's: 1, 2, 4 or 10), positions per
-// workgroup, workgroups, LDS bytes (matrix-free mode: BT = 256, NCH = 0, R = M2_OTF_RUN, no dynamic LDS)
-struct M2Plan { int BT, NCH, R, W; size_t lds; int fi; };
-
-static M2Plan m2_plan(const tspgpu_ctx *ctx)
+template <typename T> static const void *m2_sweep_fn(int nch)
 {
-    M2Plan P;
-    const int n = ctx->n;
-    if (ctx->otf) {
-        P.BT = 256; P.NCH = 0; P.R = M2_OTF_RUN; P.W = (n + P.R - 1) / P.R; P.lds = 0; P.fi = 0;
-        return P;
-    }
-    const size_t esz = elem_size(ctx->elem);
-    const int nvec = ctx->ld / (int)(16 / esz);
-    P.BT = nvec <= 256 ? 256 : nvec <= 1024 ? 512 : 1024;
-    const int need = (nvec + P.BT - 1) / P.BT;              // <= 10: a row fits LDS (need_costs), 10 240 vectors at most
-    P.NCH = need <= 1 ? 1 : need <= 2 ? 2 : need <= 4 ? 4 : 10;
-    P.lds = (size_t)ctx->ld * esz + M2_EXTRA;
-    const int occ = (int)std::max<size_t>(1, std::min<size_t>(ctx->lds_max / P.lds, (size_t)(2048 / P.BT)));
-    const int target = ctx->cus * occ;                      // one wave of workgroups over the chip
-    P.R = std::min(std::max((n + target - 1) / target, M2_RMIN), M2_RMAX);
-    P.W = (n + P.R - 1) / P.R;
-    P.fi = (ctx->elem == TSPGPU_ELEM_F64 ? 0 : ctx->elem == TSPGPU_ELEM_I32 ? 4 : 8) + (P.NCH == 1 ? 0 : P.NCH == 2 ? 1 : P.NCH == 4 ? 2 : 3);
+    return nch == 1 ? (const void *)k_m2_sweep<T, 1> : nch == 2 ? (const void *)k_m2_sweep<T, 2>
+         : nch == 4 ? (const void *)k_m2_sweep<T, 4> : (const void *)k_m2_sweep<T, 10>;
+}
+
+// one row in LDS; the vectors per thread and row are the template's 1, 2, 4 or 10 (a row fits LDS -- need_costs --, 10 240
+// vectors at most)
+static SweepGeom m2_plan(const tspgpu_ctx *ctx)
+{
+    SweepGeom P = sweep_geom(ctx, 1, M2_EXTRA, M2_RMIN, M2_RMAX, {1, 2, 4, 10}, M2_OTF_RUN);
+    if (!ctx->otf) ELEM_SWITCH(ctx->elem, T, P.fn = m2_sweep_fn<T>(P.NCH));
     return P;
 }
 
@@ -6366,49 +6369,28 @@ static M2Plan m2_plan(const tspgpu_ctx *ctx)
 static int m2_geom(const tspgpu_ctx *ctx, int what)
 {
     if (!ctx->have_costs || !ctx->symmetric || ctx->n < 5) return 0;
-    const M2Plan P = m2_plan(ctx);
+    const SweepGeom P = m2_plan(ctx);
     return what == 0 ? P.R : what == 1 ? P.BT : P.NCH;
-}
-
-template <typename T> static const void *m2_sweep_fn(int nch)
-{
-    return nch == 1 ? (const void *)k_m2_sweep<T, 1> : nch == 2 ? (const void *)k_m2_sweep<T, 2>
-         : nch == 4 ? (const void *)k_m2_sweep<T, 4> : (const void *)k_m2_sweep<T, 10>;
 }
 
 static int nl_launch_sweep(tspgpu_ctx *ctx, int slot);      // (tspgpu_nl2opt.inc's driver, below)
 
 // the candidate sweep and the selection of one sweep (matrix-free mode: behind the gather of the successors' points);
 // nl: the candidates come from the neighbour lists (k_nl_sweep) instead
-static int m2_launch_select(tspgpu_ctx *ctx, int slot, const M2Plan &P, bool gather = true, bool nl = false)
+static int m2_launch_select(tspgpu_ctx *ctx, int slot, const SweepGeom &P, bool gather = true, bool nl = false)
 {
     const int n = ctx->n;
     const M2Ctl *ctl = ctx->d_m2;
+    int rc;
     if (nl) {
-        const int rc = nl_launch_sweep(ctx, slot);
-        if (rc) return rc;
+        if ((rc = nl_launch_sweep(ctx, slot))) return rc;
     } else if (ctx->otf) {
-        const bool ip = ctx->ceil_int() && ctx->d_ipts;     // int2 points, as launch_sweep
-        if (gather) {
-            if (ip) hipLaunchKernelGGL((k_m2_gather<int2>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->S, n, slot,
-                                       (const int2 *)ctx->d_ipts, reinterpret_cast<int2 *>(ctx->d_spts), ctl);
-            else hipLaunchKernelGGL((k_m2_gather<double2>), dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->S, n, slot,
-                                    (const double2 *)ctx->d_pts, ctx->d_spts, ctl);
-            HIP_TRY(hipGetLastError());
-        }
-#define M2_OTF(K, PTS, SPTS) hipLaunchKernelGGL((k_m2_sweep_otf<K>), dim3(P.W), dim3(P.BT), 0, ctx->stream, ctx->S, PTS, SPTS, n, slot, ctx->m2, ctl)
-        if (ip) M2_OTF(KIND_CEIL_INT, (const int2 *)ctx->d_ipts, reinterpret_cast<const int2 *>(ctx->d_spts));
-        else if (ctx->kind == TSPGPU_EUC_2D) M2_OTF(TSPGPU_EUC_2D, (const double2 *)ctx->d_pts, (const double2 *)ctx->d_spts);
-        else if (ctx->kind == TSPGPU_ATT) M2_OTF(TSPGPU_ATT, (const double2 *)ctx->d_pts, (const double2 *)ctx->d_spts);
-        else M2_OTF(TSPGPU_CEIL_2D, (const double2 *)ctx->d_pts, (const double2 *)ctx->d_spts);
-#undef M2_OTF
+        if (gather && (rc = launch_spts_gather(ctx, slot, &ctl->stop))) return rc;
+        kind_switch(ctx, [&](auto kind, auto *pts, auto *spts) {
+            hipLaunchKernelGGL((k_m2_sweep_otf<kind()>), dim3(P.W), dim3(P.BT), 0, ctx->stream, ctx->S, pts, spts, n, slot, ctx->m2, ctl);
+        });
     } else {
-        if (!ctx->m2_attr[P.fi]) {
-            const void *fn = nullptr;
-            ELEM_SWITCH(ctx->elem, T, fn = m2_sweep_fn<T>(P.NCH));
-            HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->lds_max));
-            ctx->m2_attr[P.fi] = true;
-        }
+        if ((rc = ensure_max_lds(ctx, P.fn))) return rc;
 #define M2_SWEEP(T, N) hipLaunchKernelGGL((k_m2_sweep<T, N>), dim3(P.W), dim3(P.BT), P.lds, ctx->stream, ctx->S, (const T *)ctx->d_mat, \
                                           n, ctx->ld, slot, P.R, ctx->m2, ctl)
         ELEM_SWITCH(ctx->elem, T, { if (P.NCH == 1) M2_SWEEP(T, 1); else if (P.NCH == 2) M2_SWEEP(T, 2);
@@ -6426,17 +6408,13 @@ static int m2_launch_select(tspgpu_ctx *ctx, int slot, const M2Plan &P, bool gat
 static int m2_launch_apply(tspgpu_ctx *ctx, int slot)
 {
     const int n = ctx->n, G = std::min(M2_APPLY_WGS, (n + 1) / 2);
-    if (ctx->otf) {
-#define M2_APPLY_OTF(K, PTS) hipLaunchKernelGGL((k_m2_apply_otf<K>), dim3(G), dim3(256), 0, ctx->stream, ctx->S, PTS, n, slot, ctx->m2, ctx->d_m2)
-        if (ctx->ceil_int() && ctx->d_ipts) M2_APPLY_OTF(KIND_CEIL_INT, (const int2 *)ctx->d_ipts);
-        else if (ctx->kind == TSPGPU_EUC_2D) M2_APPLY_OTF(TSPGPU_EUC_2D, (const double2 *)ctx->d_pts);
-        else if (ctx->kind == TSPGPU_ATT) M2_APPLY_OTF(TSPGPU_ATT, (const double2 *)ctx->d_pts);
-        else M2_APPLY_OTF(TSPGPU_CEIL_2D, (const double2 *)ctx->d_pts);
-#undef M2_APPLY_OTF
-    } else {
+    if (ctx->otf)
+        kind_switch(ctx, [&](auto kind, auto *pts, auto *) {
+            hipLaunchKernelGGL((k_m2_apply_otf<kind()>), dim3(G), dim3(256), 0, ctx->stream, ctx->S, pts, n, slot, ctx->m2, ctx->d_m2);
+        });
+    else
         ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_m2_apply<T>), dim3(G), dim3(256), 0, ctx->stream, ctx->S, (const T *)ctx->d_mat,
                                                      n, ctx->ld, slot, ctx->m2, ctx->d_m2));
-    }
     HIP_TRY(hipGetLastError());
     return E_OK;
 }
@@ -6447,8 +6425,8 @@ static int m2_arm(tspgpu_ctx *ctx, int slot, long budget)
     M2Ctl C;
     memset(&C, 0, sizeof C);
     C.budget = budget;
-    HIP_TRY(hipMemcpyAsync(ctx->d_m2, &C, sizeof C, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));       // (C is on the stack)
+    const int rc = ctl_put(ctx, ctx->d_m2, C);
+    if (rc) return rc;
     hipLaunchKernelGGL(k_rearm, dim3(1), dim3(64), 0, ctx->stream, ctx->S, slot, 1, -1);
     HIP_TRY(hipGetLastError());
     return E_OK;
@@ -6473,7 +6451,7 @@ static int m2_run(tspgpu_ctx *ctx, int slot, long max_sweeps, double t_end, long
     if (max_sweeps == 0) return E_OK;
     int rc = m2_arm(ctx, slot, max_sweeps);
     if (rc) return rc;
-    const M2Plan P = m2_plan(ctx);
+    const SweepGeom P = m2_plan(ctx);
     for (;;) {
         if (t_end >= 0 && now_s() >= t_end) { *late = true; break; }
         const int K = t_end >= 0 ? 1 : 4;
@@ -6481,14 +6459,10 @@ static int m2_run(tspgpu_ctx *ctx, int slot, long max_sweeps, double t_end, long
             if ((rc = m2_launch_select(ctx, slot, P, true, nl))) return rc;
             if ((rc = m2_launch_apply(ctx, slot))) return rc;
         }
-        HIP_TRY(hipMemcpyAsync(&C, ctx->d_m2, sizeof C, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        if ((rc = ctl_get(ctx, &C, ctx->d_m2))) return rc;
         if (C.stop) break;
     }
-    if (*late) {
-        HIP_TRY(hipMemcpyAsync(&C, ctx->d_m2, sizeof C, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-    }
+    if (*late && (rc = ctl_get(ctx, &C, ctx->d_m2))) return rc;
     if (sweeps) *sweeps = (long)C.sweeps;
     if (moves) *moves = (long)C.moves;
     m2_record(ctx, C, nl);
@@ -6505,8 +6479,8 @@ int tspgpu_tour_two_opt_multi(tspgpu_ctx *ctx, int slot, long max_sweeps, double
     if (rc) return rc;
     if ((rc = need_slot(ctx, slot))) return rc;
     bool late = false;
-    if ((rc = m2_run(ctx, slot, max_sweeps, time_left_s >= 0 ? now_s() + time_left_s : -1, sweeps, moves, &late))) return rc;
-    return late ? E_DEADLINE : E_OK;
+    if ((rc = m2_run(ctx, slot, max_sweeps, deadline_of(time_left_s), sweeps, moves, &late))) return rc;
+    return done_code(late);
 }
 
 int tspgpu_two_opt_multi(tspgpu_ctx *ctx, int *path, double *cost, double time_left_s, long *sweeps, long *moves)
@@ -6518,9 +6492,9 @@ int tspgpu_two_opt_multi(tspgpu_ctx *ctx, int *path, double *cost, double time_l
     if (rc) return rc;
     if ((rc = load_path(ctx, 0, path, -1))) return rc;          // recomputes the cost, refinment.c:6-9
     bool late = false;
-    if ((rc = m2_run(ctx, 0, -1, time_left_s >= 0 ? now_s() + time_left_s : -1, sweeps, moves, &late))) return rc;
+    if ((rc = m2_run(ctx, 0, -1, deadline_of(time_left_s), sweeps, moves, &late))) return rc;
     if ((rc = store_path(ctx, 0, path, cost, nullptr))) return rc;
-    return late ? E_DEADLINE : E_OK;
+    return done_code(late);
 }
 
 } // extern "C"
@@ -6541,8 +6515,7 @@ static int m2_once(tspgpu_ctx *ctx, int *path, double *cost, int *nmoves, int *m
     if ((rc = m2_launch_select(ctx, 0, m2_plan(ctx), true, nl))) return rc;
     // the accepted list comes back before anything is applied: a list longer than `cap` leaves the tour as it is
     M2Ctl C;
-    HIP_TRY(hipMemcpyAsync(&C, ctx->d_m2, sizeof C, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if ((rc = ctl_get(ctx, &C, ctx->d_m2))) return rc;
     const size_t m = (size_t)C.m;
     std::vector<int> acc(m), a(m), b(m);
     std::vector<double> d(m);
@@ -6566,8 +6539,7 @@ static int m2_once(tspgpu_ctx *ctx, int *path, double *cost, int *nmoves, int *m
     if (nmoves) *nmoves = (int)idx.size();
     if ((rc = m2_launch_apply(ctx, 0))) return rc;
     if ((rc = store_path(ctx, 0, path, cost, nullptr))) return rc;
-    HIP_TRY(hipMemcpyAsync(&C, ctx->d_m2, sizeof C, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    if ((rc = ctl_get(ctx, &C, ctx->d_m2))) return rc;
     m2_record(ctx, C, nl);
     return E_OK;
 }
@@ -6582,27 +6554,10 @@ static int m2_time(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean, bool nl)
     if (rc) return rc;
     if ((rc = need_slot(ctx, slot))) return rc;
     HIP_TRY(hipMemsetAsync(ctx->d_m2, 0, sizeof(M2Ctl), ctx->stream));
-    const M2Plan P = m2_plan(ctx);
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    float ms = 0;
-    // (the events are destroyed on every way out)
-    auto timed = [&]() -> int {
-        int r;
-        HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-        if ((r = m2_launch_select(ctx, slot, P, true, nl))) return r;   // warm (matrix-free mode: with its gather; the timed launches go without)
-        HIP_TRY(hipEventRecord(e0, ctx->stream));
-        for (int i = 0; i < reps; i++) if ((r = m2_launch_select(ctx, slot, P, false, nl))) return r;
-        HIP_TRY(hipEventRecord(e1, ctx->stream));
-        HIP_TRY(hipEventSynchronize(e1));
-        HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-        return E_OK;
-    };
-    rc = timed();
-    if (e0) hipEventDestroy(e0);
-    if (e1) hipEventDestroy(e1);
-    if (rc) return rc;
-    *ms_mean = ms / reps;
-    return E_OK;
+    const SweepGeom P = m2_plan(ctx);
+    // warm: in matrix-free mode with its gather; the timed launches go without
+    return time_launches(ctx, reps, [&] { return m2_launch_select(ctx, slot, P, true, nl); },
+                         [&] { return m2_launch_select(ctx, slot, P, false, nl); }, ms_mean);
 }
 
 extern "C" {
@@ -6637,17 +6592,13 @@ static int nl_launch_sweep(tspgpu_ctx *ctx, int slot)
     const int n = ctx->n;
     const dim3 grid((n + NL_NODES - 1) / NL_NODES), block(NL_NODES * 32);
     const M2Ctl *ctl = ctx->d_m2;
-    if (ctx->otf) {
-#define NL_OTF(K, PTS) hipLaunchKernelGGL((k_nl_sweep_otf<K>), grid, block, 0, ctx->stream, ctx->S, PTS, n, slot, ctx->nl, ctx->m2, ctl)
-        if (ctx->ceil_int() && ctx->d_ipts) NL_OTF(KIND_CEIL_INT, (const int2 *)ctx->d_ipts);
-        else if (ctx->kind == TSPGPU_EUC_2D) NL_OTF(TSPGPU_EUC_2D, (const double2 *)ctx->d_pts);
-        else if (ctx->kind == TSPGPU_ATT) NL_OTF(TSPGPU_ATT, (const double2 *)ctx->d_pts);
-        else NL_OTF(TSPGPU_CEIL_2D, (const double2 *)ctx->d_pts);
-#undef NL_OTF
-    } else {
+    if (ctx->otf)
+        kind_switch(ctx, [&](auto kind, auto *pts, auto *) {
+            hipLaunchKernelGGL((k_nl_sweep_otf<kind()>), grid, block, 0, ctx->stream, ctx->S, pts, n, slot, ctx->nl, ctx->m2, ctl);
+        });
+    else
         ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_nl_sweep<T>), grid, block, 0, ctx->stream, ctx->S, (const T *)ctx->d_mat, n, ctx->ld, slot,
                                                      ctx->nl, ctx->m2, ctl));
-    }
     HIP_TRY(hipGetLastError());
     return E_OK;
 }
@@ -6674,16 +6625,10 @@ int tspgpu_neighbours_build(tspgpu_ctx *ctx, int K)
     }
     L.K = Kp;
     const dim3 grid((n + NL_BUILD_ROWS - 1) / NL_BUILD_ROWS), block(NL_BUILD_ROWS * 64);
-    if (ctx->otf) {
-#define NL_BUILD_OTF(KD, PTS) hipLaunchKernelGGL((k_nl_build_otf<KD>), grid, block, 0, ctx->stream, PTS, n, L)
-        if (ctx->ceil_int() && ctx->d_ipts) NL_BUILD_OTF(KIND_CEIL_INT, (const int2 *)ctx->d_ipts);
-        else if (ctx->kind == TSPGPU_EUC_2D) NL_BUILD_OTF(TSPGPU_EUC_2D, (const double2 *)ctx->d_pts);
-        else if (ctx->kind == TSPGPU_ATT) NL_BUILD_OTF(TSPGPU_ATT, (const double2 *)ctx->d_pts);
-        else NL_BUILD_OTF(TSPGPU_CEIL_2D, (const double2 *)ctx->d_pts);
-#undef NL_BUILD_OTF
-    } else {
+    if (ctx->otf)
+        kind_switch(ctx, [&](auto kind, auto *pts, auto *) { hipLaunchKernelGGL((k_nl_build_otf<kind()>), grid, block, 0, ctx->stream, pts, n, L); });
+    else
         ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_nl_build<T>), grid, block, 0, ctx->stream, (const T *)ctx->d_mat, n, ctx->ld, L));
-    }
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess) { hipFree(L.node); hipFree(L.w); HIP_TRY(e); }
@@ -6728,8 +6673,8 @@ int tspgpu_tour_two_opt_nl(tspgpu_ctx *ctx, int slot, long max_sweeps, double ti
     if (rc) return rc;
     if ((rc = need_slot(ctx, slot))) return rc;
     bool late = false;
-    if ((rc = m2_run(ctx, slot, max_sweeps, time_left_s >= 0 ? now_s() + time_left_s : -1, sweeps, moves, &late, true))) return rc;
-    return late ? E_DEADLINE : E_OK;
+    if ((rc = m2_run(ctx, slot, max_sweeps, deadline_of(time_left_s), sweeps, moves, &late, true))) return rc;
+    return done_code(late);
 }
 
 int tspgpu_two_opt_nl(tspgpu_ctx *ctx, int *path, double *cost, double time_left_s, int polish,
@@ -6741,7 +6686,7 @@ int tspgpu_two_opt_nl(tspgpu_ctx *ctx, int *path, double *cost, double time_left
     int rc = nl_check(ctx);
     if (rc) return rc;
     if ((rc = load_path(ctx, 0, path, -1))) return rc;          // recomputes the cost, refinment.c:6-9
-    const double t_end = time_left_s >= 0 ? now_s() + time_left_s : -1;
+    const double t_end = deadline_of(time_left_s);
     bool late = false;
     long ps = 0, pm = 0;
     ctx->nl_polish_sweeps = 0;
@@ -6753,7 +6698,7 @@ int tspgpu_two_opt_nl(tspgpu_ctx *ctx, int *path, double *cost, double time_left
     if (polish_sweeps) *polish_sweeps = ps;
     if (polish_moves) *polish_moves = pm;
     if ((rc = store_path(ctx, 0, path, cost, nullptr))) return rc;
-    return late ? E_DEADLINE : E_OK;
+    return done_code(late);
 }
 
 int tspgpu_time_nl_sweep(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean)

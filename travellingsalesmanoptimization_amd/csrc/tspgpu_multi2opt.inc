@@ -137,15 +137,6 @@ __global__ void __launch_bounds__(1024) k_m2_sweep(Tours S, const T *__restrict_
     }
 }
 
-// spts[q] = pts[succ q] for the matrix-free sweep (as k_oropt_gather, under this descent's control block)
-template <typename PT>
-__global__ void __launch_bounds__(256) k_m2_gather(Tours S, int n, int t, const PT *__restrict__ pts, PT *__restrict__ spts, const M2Ctl *ctl)
-{
-    const int q = blockIdx.x * 256 + threadIdx.x;
-    if (q >= n || ctl->stop) return;
-    spts[q] = pts[S.succ[(size_t)t * n + q]];
-}
-
 template <int KIND>
 __global__ void __launch_bounds__(256) k_m2_sweep_otf(Tours S, const typename OrPt<KIND>::type *__restrict__ pts,
                                                       const typename OrPt<KIND>::type *__restrict__ spts, int n, int t, M2Buf B, const M2Ctl *ctl)

@@ -280,7 +280,7 @@ __global__ void __launch_bounds__(1024) k_oropt_apply(Tours S, const T *__restri
 
 // ---------------------------------------------------------------------------
 // Matrix-free mode (TSPGPU_OPT_OR_MATRIX_FREE = 1, single tours): the sibling of k_sweep_otf8.  Per move three launches:
-// k_oropt_gather (P_succ(q) for every q, from the tour the previous apply left), k_oropt_sweep_otf, k_oropt_apply_otf.
+// k_spts_gather (P_succ(q) for every q, from the tour the previous apply left), k_oropt_sweep_otf, k_oropt_apply_otf.
 //
 // k_oropt_sweep_otf: workgroup g owns the tour positions [g R, g R + R), R = OR_OTF_RUN.  The nodes of positions
 // g R - 1 .. g R + R + 2, their points, their dnb and the three c[p][x] per position (computed here with the weight
@@ -309,11 +309,12 @@ static constexpr int OR_OTF_RUN = 16;       // tour positions per workgroup (W =
 static constexpr int OR_OTF_VQ = 4;         // consecutive q per thread and pass
 
 // spts[q] = pts[succ q]; unlike k_gather_spts it does not look at the slot's 2-opt `done` flag (Or-opt runs on finished slots)
+// but at `stop`, the flag of the control block of the descent that runs it (this one's, or the parallel-move 2-opt's)
 template <typename PT>
-__global__ void __launch_bounds__(256) k_oropt_gather(Tours S, int n, int t, const PT *__restrict__ pts, PT *__restrict__ spts, const OrCtl *ctl)
+__global__ void __launch_bounds__(256) k_spts_gather(Tours S, int n, int t, const PT *__restrict__ pts, PT *__restrict__ spts, const int *stop)
 {
     const int q = blockIdx.x * 256 + threadIdx.x;
-    if (q >= n || ctl->stop) return;
+    if (q >= n || *stop) return;
     spts[q] = pts[S.succ[(size_t)t * n + q]];
 }
 
