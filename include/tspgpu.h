@@ -461,6 +461,71 @@ int tspgpu_tour_two_opt_nl(tspgpu_ctx *ctx, int slot, long max_sweeps, double ti
 /* a measurement aid (tools/nl2opt_rate.py): the candidate sweep and the selection `reps` times on slot, nothing applied */
 int tspgpu_time_nl_sweep(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean);
 
+/* ---- Neighbour-list Or-opt (an extension: Or-opt candidates from the neighbour lists, every independent move of a sweep) --
+ * A sweep evaluates at most 10 K' segment moves per node instead of 5 n - 16, and applies every accepted one at once.
+ * Preconditions: `path` a successor array, symmetric costs (a symmetric matrix, or matrix-free mode), n >= 8, lists built by
+ * tspgpu_neighbours_build for the cost source in place (N(v), K' as in "Neighbour-list 2-opt").  No row-in-LDS limit beyond
+ * that section's: every instance tspgpu_two_opt_nl takes with n >= 8 is taken.  These entry points run in matrix-free mode
+ * without TSPGPU_OPT_OR_MATRIX_FREE (that option guards the entry points of "Or-opt", whose code 12 stays).
+ *   1. Move and delta: exactly those of "Or-opt".  A candidate (s, L, q, rev), L in {1, 2, 3}; t is L - 1 steps after s,
+ *      p = pred(s), x = path[t], q' = path[q]; q outside the segment and q != p (q = x is allowed); rev only for L >= 2;
+ *      (h, e) = (s, t), or (t, s) when rev;
+ *          delta = ((c[p][x] + c[q][h]) + c[e][q']) - ((c[p][s] + c[t][x]) + c[q][q'])      in this order: bit-exact for doubles
+ *   2. Candidates of a segment start.  P(0) = 0, P(path[v]) = P(v) + 1.  A segment that contains node 0 is no candidate:
+ *      node 0 is never moved by this rule (as position 0 never moves in "Parallel-move 2-opt").  For s, each L, each
+ *      segment end w ({s} for L = 1, {s, t} otherwise) and each u in N(w), two forms:
+ *          (A) q = u, h = w:                rev = [w == t], 0 for L = 1
+ *          (B) q' = u, q = pred(u), e = w:  rev = [w == s], 0 for L = 1
+ *      kept iff q is outside the segment and q != p; duplicates are harmless: at most 10 K' evaluations per node.
+ *      cand(s) = the lexicographic minimum of (delta, L, q, rev) over these, a candidate only if delta < -1e-7.  Its key is
+ *      (delta, s, L, q, rev), labels as node ids.
+ *   3. Membership.  (s, L, q, rev) is looked at iff one of its two new edges (q, h), (e, q') joins a segment end to a member
+ *      of that end's own list.  The closing edge (p, x) plays no part.
+ *   4. Range.  The edge leaving the node at position k has position k (the edge into node 0: n - 1).  With i = P(s),
+ *      j = P(q) the move removes the edges at positions i - 1, i + L - 1 and j; its range is
+ *      [lo, hi] = [min(i - 1, j), max(i + L - 1, j)], and 0 <= lo < hi <= n - 1: no range wraps.  Only the nodes at
+ *      positions lo + 1 .. hi change position: insertion behind the segment (j > i) shifts the nodes i + L .. j down by L,
+ *      insertion in front (j < i - 1) shifts the nodes j + 1 .. i - 1 up by L.
+ *   5. Conflict and selection.  Two candidates conflict iff their closed ranges intersect.  ONE round: a candidate is accepted
+ *      iff its key is below the key of every candidate it conflicts with.  The smallest key is always accepted.
+ *   6. Apply.  Every accepted move: path[p] = x, path[q] = h, the inner links of the segment reversed when rev,
+ *      path[e] = q'.  *cost grows by the sum of the accepted deltas (exact for integer-valued costs; otherwise the order of
+ *      the sum is not specified).  Disjoint ranges touch disjoint edges; two accepted moves may share one end node (the
+ *      hi + 1 node of one, the lo node of the other).
+ *   7. Or-opt phase.  Sweeps run until one accepts nothing; that sweep is counted.  The result has no improving move with
+ *      the membership property whose segment avoids node 0.
+ *   8. Descent (tspgpu_local_search_nl).  *cost is recomputed as ref_2opt does (src/algorithms/refinment.c:6-9); then the
+ *      neighbour-list 2-opt phase (tspgpu_tour_two_opt_nl to its end, no polish) alternates with the Or-opt phase of rule 7
+ *      until an Or-opt phase applies nothing.  *rounds counts the 2-opt phases.  The result is locally optimal for both
+ *      list neighbourhoods; tspgpu_local_search on it reaches the full ones (there is no polish flag).
+ *   9. Equality with the full rule.  With K' = n - 1 (n <= 17 at K = 16) the candidates of s are every (L, q, rev) rule 1
+ *      allows: the smallest key of a sweep is the move tspgpu_or_opt_once makes, whenever that move's segment does not
+ *      contain node 0.
+ * Codes: no context 14, n < 8 3, no costs 9, an asymmetric matrix 9, lists not built or invalidated 9 (the text of
+ * "Neighbour-list 2-opt"), more accepted moves than `cap` in _once 8 (nothing applied, nothing written), a deadline that
+ * passed 4 (with a valid tour and its cost).  No new device memory: the candidate arrays of "Parallel-move 2-opt" serve.
+ * tspgpu_info: 47 / 48 Or-opt sweeps / moves of the last call of this section (a descent: totals over its rounds), 49 the
+ * most moves one of its sweeps accepted, 50 rounds of the last tspgpu_local_search_nl, 51 segment starts per workgroup of the
+ * candidate sweep. */
+/* one sweep on a host tour.  *cost is the caller's running cost.  The accepted moves come back in ascending key order:
+ * moves[4k .. 4k + 3] = s, L, q, rev, deltas[k]; *nmoves their number (0: nothing improves) */
+int tspgpu_or_opt_nl_once(tspgpu_ctx *ctx, int *path, double *cost, int *nmoves,
+                          int *moves /* [4*cap] */, double *deltas /* [cap] */, int cap);
+/* the Or-opt phase (rule 7) on a host tour; *cost is the caller's running cost, as tspgpu_or_opt takes it */
+int tspgpu_or_opt_nl(tspgpu_ctx *ctx, int *path, double *cost, double time_left_s, long *sweeps, long *moves);
+/* the same on a slot: at most max_sweeps sweeps (< 0: until one accepts nothing); the slot is left as tspgpu_tour_two_opt_nl
+ * leaves one: cost, last delta (the smallest accepted delta of the last sweep, 0: none), and every later slot call sees the tour */
+int tspgpu_tour_or_opt_nl(tspgpu_ctx *ctx, int slot, long max_sweeps, double time_left_s, long *sweeps, long *moves);
+/* the descent (rule 8); the counters (each may be NULL) are totals over the rounds */
+int tspgpu_local_search_nl(tspgpu_ctx *ctx, int *path, double *cost, double time_left_s,
+                           long *two_opt_sweeps, long *two_opt_moves, long *or_sweeps, long *or_moves, int *rounds);
+/* the same on a slot, whose cost is taken as it stands */
+int tspgpu_tour_local_search_nl(tspgpu_ctx *ctx, int slot, double time_left_s,
+                                long *two_opt_sweeps, long *two_opt_moves, long *or_sweeps, long *or_moves, int *rounds);
+/* a measurement aid (tools/ornl_rate.py): the candidate sweep, the compaction and the selection `reps` times on slot,
+ * nothing applied */
+int tspgpu_time_or_nl_sweep(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean);
+
 #ifdef __cplusplus
 }
 #endif

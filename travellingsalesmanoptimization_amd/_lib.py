@@ -28,6 +28,8 @@ INFO_OR_OTF, INFO_OR_OTF_R = 34, 35     # tspgpu_info: form (0 none, 1 full, 2 e
 INFO_MULTI_SWEEPS, INFO_MULTI_MOVES, INFO_MULTI_MAX_MOVES, INFO_MULTI_R, INFO_MULTI_THREADS, INFO_MULTI_NCH = 36, 37, 38, 39, 40, 41
 # ... K' of the neighbour lists in place, sweeps / moves of the last neighbour-list 2-opt phase, sweeps of its polish, nodes per workgroup
 INFO_NL_K, INFO_NL_SWEEPS, INFO_NL_MOVES, INFO_NL_POLISH_SWEEPS, INFO_NL_NODES = 42, 43, 44, 45, 46
+# ... Or-opt sweeps / moves / largest sweep of the last neighbour-list Or-opt call, rounds of the last local_search_nl, starts per workgroup
+INFO_OR_NL_SWEEPS, INFO_OR_NL_MOVES, INFO_OR_NL_MAX_MOVES, INFO_OR_NL_ROUNDS, INFO_OR_NL_STARTS = 47, 48, 49, 50, 51
 EM_FORM_AUTO, EM_FORM_RESIDENT, EM_FORM_PER_STEP = 0, 1, 2
 MOPT_EXCHANGE = 1000
 EXCHANGE_AUTO, EXCHANGE_HOST, EXCHANGE_RCCL = 0, 1, 2
@@ -107,6 +109,12 @@ SIGNATURES = {
     "tspgpu_two_opt_nl": (C.c_int, [_ctx, _ip, _pd, C.c_double, C.c_int, _pl, _pl, _pl, _pl]),
     "tspgpu_tour_two_opt_nl": (C.c_int, [_ctx, C.c_int, C.c_long, C.c_double, _pl, _pl]),
     "tspgpu_time_nl_sweep": (C.c_int, [_ctx, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "tspgpu_or_opt_nl_once": (C.c_int, [_ctx, _ip, _pd, _pi, _ip, _dp, C.c_int]),
+    "tspgpu_or_opt_nl": (C.c_int, [_ctx, _ip, _pd, C.c_double, _pl, _pl]),
+    "tspgpu_tour_or_opt_nl": (C.c_int, [_ctx, C.c_int, C.c_long, C.c_double, _pl, _pl]),
+    "tspgpu_local_search_nl": (C.c_int, [_ctx, _ip, _pd, C.c_double, _pl, _pl, _pl, _pl, _pi]),
+    "tspgpu_tour_local_search_nl": (C.c_int, [_ctx, C.c_int, C.c_double, _pl, _pl, _pl, _pl, _pi]),
+    "tspgpu_time_or_nl_sweep": (C.c_int, [_ctx, C.c_int, C.c_int, C.POINTER(C.c_float)]),
 }
 
 _lib = None

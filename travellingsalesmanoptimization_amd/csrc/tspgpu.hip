@@ -3091,6 +3091,7 @@ __global__ void k_cap_now(Tours S, int slot0, int count)
 #include "tspgpu_oropt.inc"
 #include "tspgpu_multi2opt.inc"
 #include "tspgpu_nl2opt.inc"
+#include "tspgpu_ornl.inc"
 
 // ===========================================================================
 // host side
@@ -3217,6 +3218,9 @@ struct tspgpu_ctx {
     NlBuf nl{};
     bool nl_dropped = false;   // a new cost source took the lists away (the refusal says so)
     long nl_sweeps = 0, nl_moves = 0, nl_polish_sweeps = 0;     // the last neighbour-list phase and its polish
+    // neighbour-list Or-opt (tspgpu_ornl.inc): the last call's sweeps, moves and largest sweep (a descent: over its rounds)
+    long ornl_sweeps = 0, ornl_moves = 0, ornl_max_k = 0;
+    int ornl_rounds = 0;       // rounds of the last tspgpu_local_search_nl
 
     Fused F{};                 // fused path state (allocated on first use, capacity fcap)
     int fcap = 0;
@@ -5042,6 +5046,11 @@ long tspgpu_info(const tspgpu_ctx *ctx, int what)
     case 44: return ctx->nl_moves;
     case 45: return ctx->nl_polish_sweeps;
     case 46: return NL_NODES;
+    case 47: return ctx->ornl_sweeps;
+    case 48: return ctx->ornl_moves;
+    case 49: return ctx->ornl_max_k;
+    case 50: return ctx->ornl_rounds;
+    case 51: return ORNL_STARTS;
     case 12: return (ctx->built && ctx->grid_ok && ctx->opt_nn != 1 && ctx->cost_bound < 134217728.0) ? ctx->grid_G : 0;
     case 13: return ctx->grid_max_occ;
     }
@@ -6374,16 +6383,23 @@ static int m2_geom(const tspgpu_ctx *ctx, int what)
 }
 
 static int nl_launch_sweep(tspgpu_ctx *ctx, int slot);      // (tspgpu_nl2opt.inc's driver, below)
+static int ornl_launch_sweep(tspgpu_ctx *ctx, int slot);    // (tspgpu_ornl.inc's driver, below)
+static int ornl_launch_apply(tspgpu_ctx *ctx, int slot);
 
-// the candidate sweep and the selection of one sweep (matrix-free mode: behind the gather of the successors' points);
-// nl: the candidates come from the neighbour lists (k_nl_sweep) instead
-static int m2_launch_select(tspgpu_ctx *ctx, int slot, const SweepGeom &P, bool gather = true, bool nl = false)
+// where the candidates of a sweep come from and what an accepted one is: every b of the parallel-move 2-opt, the neighbour
+// lists' 2-opt pairs (k_nl_sweep), or the neighbour lists' Or-opt segment moves (k_ornl_sweep, with its own compaction and apply)
+enum M2Kind { M2_FULL, M2_NL, M2_ORNL };
+
+// the candidate sweep and the selection of one sweep (matrix-free mode: behind the gather of the successors' points)
+static int m2_launch_select(tspgpu_ctx *ctx, int slot, const SweepGeom &P, bool gather = true, M2Kind kind = M2_FULL)
 {
     const int n = ctx->n;
     const M2Ctl *ctl = ctx->d_m2;
     int rc;
-    if (nl) {
+    if (kind == M2_NL) {
         if ((rc = nl_launch_sweep(ctx, slot))) return rc;
+    } else if (kind == M2_ORNL) {
+        if ((rc = ornl_launch_sweep(ctx, slot))) return rc;
     } else if (ctx->otf) {
         if (gather && (rc = launch_spts_gather(ctx, slot, &ctl->stop))) return rc;
         kind_switch(ctx, [&](auto kind, auto *pts, auto *spts) {
@@ -6398,15 +6414,17 @@ static int m2_launch_select(tspgpu_ctx *ctx, int slot, const SweepGeom &P, bool 
 #undef M2_SWEEP
     }
     HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_m2_compact, dim3(1), dim3(1024), 0, ctx->stream, ctx->S, n, slot, ctx->m2, ctx->d_m2);
+    if (kind == M2_ORNL) hipLaunchKernelGGL(k_ornl_compact, dim3(1), dim3(1024), 0, ctx->stream, ctx->S, n, slot, ctx->m2, ctx->d_m2);
+    else hipLaunchKernelGGL(k_m2_compact, dim3(1), dim3(1024), 0, ctx->stream, ctx->S, n, slot, ctx->m2, ctx->d_m2);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_m2_select, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->m2, ctl);
     HIP_TRY(hipGetLastError());
     return E_OK;
 }
 
-static int m2_launch_apply(tspgpu_ctx *ctx, int slot)
+static int m2_launch_apply(tspgpu_ctx *ctx, int slot, M2Kind kind = M2_FULL)
 {
+    if (kind == M2_ORNL) return ornl_launch_apply(ctx, slot);
     const int n = ctx->n, G = std::min(M2_APPLY_WGS, (n + 1) / 2);
     if (ctx->otf)
         kind_switch(ctx, [&](auto kind, auto *pts, auto *) {
@@ -6432,22 +6450,23 @@ static int m2_arm(tspgpu_ctx *ctx, int slot, long budget)
     return E_OK;
 }
 
-static void m2_record(tspgpu_ctx *ctx, const M2Ctl &C, bool nl = false)
+static void m2_record(tspgpu_ctx *ctx, const M2Ctl &C, M2Kind kind = M2_FULL)
 {
-    if (nl) { ctx->nl_sweeps = (long)C.sweeps; ctx->nl_moves = (long)C.moves; }
+    if (kind == M2_NL) { ctx->nl_sweeps = (long)C.sweeps; ctx->nl_moves = (long)C.moves; }
+    else if (kind == M2_ORNL) { ctx->ornl_sweeps = (long)C.sweeps; ctx->ornl_moves = (long)C.moves; ctx->ornl_max_k = C.max_k; }
     else { ctx->m2_sweeps = (long)C.sweeps; ctx->m2_moves = (long)C.moves; ctx->m2_max_k = C.max_k; }
 }
 
 // sweeps on `slot` until one accepts nothing, max_sweeps (< 0: no cap) have run or t_end (< 0: none) passes; per sweep the
 // launches of m2_launch_select and m2_launch_apply, four sweeps between looks at the control block (one under a deadline)
-static int m2_run(tspgpu_ctx *ctx, int slot, long max_sweeps, double t_end, long *sweeps, long *moves, bool *late, bool nl = false)
+static int m2_run(tspgpu_ctx *ctx, int slot, long max_sweeps, double t_end, long *sweeps, long *moves, bool *late, M2Kind kind = M2_FULL)
 {
     M2Ctl C;
     memset(&C, 0, sizeof C);
     *late = false;
     if (sweeps) *sweeps = 0;
     if (moves) *moves = 0;
-    m2_record(ctx, C, nl);
+    m2_record(ctx, C, kind);
     if (max_sweeps == 0) return E_OK;
     int rc = m2_arm(ctx, slot, max_sweeps);
     if (rc) return rc;
@@ -6456,8 +6475,8 @@ static int m2_run(tspgpu_ctx *ctx, int slot, long max_sweeps, double t_end, long
         if (t_end >= 0 && now_s() >= t_end) { *late = true; break; }
         const int K = t_end >= 0 ? 1 : 4;
         for (int i = 0; i < K; i++) {
-            if ((rc = m2_launch_select(ctx, slot, P, true, nl))) return rc;
-            if ((rc = m2_launch_apply(ctx, slot))) return rc;
+            if ((rc = m2_launch_select(ctx, slot, P, true, kind))) return rc;
+            if ((rc = m2_launch_apply(ctx, slot, kind))) return rc;
         }
         if ((rc = ctl_get(ctx, &C, ctx->d_m2))) return rc;
         if (C.stop) break;
@@ -6465,7 +6484,7 @@ static int m2_run(tspgpu_ctx *ctx, int slot, long max_sweeps, double t_end, long
     if (*late && (rc = ctl_get(ctx, &C, ctx->d_m2))) return rc;
     if (sweeps) *sweeps = (long)C.sweeps;
     if (moves) *moves = (long)C.moves;
-    m2_record(ctx, C, nl);
+    m2_record(ctx, C, kind);
     return E_OK;
 }
 
@@ -6500,19 +6519,22 @@ int tspgpu_two_opt_multi(tspgpu_ctx *ctx, int *path, double *cost, double time_l
 } // extern "C"
 
 static int nl_check(tspgpu_ctx *ctx);
+static int ornl_check(tspgpu_ctx *ctx);
+static int m2_kind_check(tspgpu_ctx *ctx, M2Kind kind) { return kind == M2_ORNL ? ornl_check(ctx) : kind == M2_NL ? nl_check(ctx) : m2_check(ctx); }
 
-// one sweep on a host tour (tspgpu_two_opt_multi_once; nl: tspgpu_two_opt_nl_once)
-static int m2_once(tspgpu_ctx *ctx, int *path, double *cost, int *nmoves, int *moves_ab, double *deltas, int cap, bool nl)
+// one sweep on a host tour (tspgpu_two_opt_multi_once, tspgpu_two_opt_nl_once: moves_ab holds a, b per move;
+// tspgpu_or_opt_nl_once: s, L, q, rev per move)
+static int m2_once(tspgpu_ctx *ctx, int *path, double *cost, int *nmoves, int *moves_ab, double *deltas, int cap, M2Kind kind)
 {
     if (!ctx) return E_UNAVAILABLE;
     if (!path || !cost || cap < 0 || (cap > 0 && (!moves_ab || !deltas))) return fail(ctx, E_INVALID, "bad argument");
     hipSetDevice(ctx->device);
-    int rc = nl ? nl_check(ctx) : m2_check(ctx);
+    int rc = m2_kind_check(ctx, kind);
     if (rc) return rc;
     if ((rc = load_path(ctx, 0, path, -1))) return rc;
     HIP_TRY(hipMemcpyAsync(ctx->S.cost, cost, 8, hipMemcpyHostToDevice, ctx->stream));     // the caller's running cost, as ref_2opt_once
     if ((rc = m2_arm(ctx, 0, 1))) return rc;
-    if ((rc = m2_launch_select(ctx, 0, m2_plan(ctx), true, nl))) return rc;
+    if ((rc = m2_launch_select(ctx, 0, m2_plan(ctx), true, kind))) return rc;
     // the accepted list comes back before anything is applied: a list longer than `cap` leaves the tour as it is
     M2Ctl C;
     if ((rc = ctl_get(ctx, &C, ctx->d_m2))) return rc;
@@ -6535,41 +6557,51 @@ static int m2_once(tspgpu_ctx *ctx, int *path, double *cost, int *nmoves, int *m
         const int lx = std::min(a[x], b[x]), ly = std::min(a[y], b[y]);
         return lx != ly ? lx < ly : std::max(a[x], b[x]) < std::max(a[y], b[y]);
     });
-    for (size_t k = 0; k < idx.size(); k++) { moves_ab[2 * k] = a[idx[k]]; moves_ab[2 * k + 1] = b[idx[k]]; deltas[k] = d[idx[k]]; }
+    for (size_t k = 0; k < idx.size(); k++) {
+        const int x = idx[k];
+        deltas[k] = d[x];
+        if (kind == M2_ORNL) {              // a = s < b = the packed (L, q, rev): the order above is (delta, s, L, q, rev)
+            moves_ab[4 * k] = a[x]; moves_ab[4 * k + 1] = b[x] >> ORNL_LSHIFT;
+            moves_ab[4 * k + 2] = (b[x] >> 1) & (int)OR_QM; moves_ab[4 * k + 3] = b[x] & 1;
+        } else {
+            moves_ab[2 * k] = a[x]; moves_ab[2 * k + 1] = b[x];
+        }
+    }
     if (nmoves) *nmoves = (int)idx.size();
-    if ((rc = m2_launch_apply(ctx, 0))) return rc;
+    if ((rc = m2_launch_apply(ctx, 0, kind))) return rc;
     if ((rc = store_path(ctx, 0, path, cost, nullptr))) return rc;
     if ((rc = ctl_get(ctx, &C, ctx->d_m2))) return rc;
-    m2_record(ctx, C, nl);
+    m2_record(ctx, C, kind);
     return E_OK;
 }
 
-// the candidate sweep and the selection `reps` times, nothing applied (tspgpu_time_multi_sweep; nl: tspgpu_time_nl_sweep)
-static int m2_time(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean, bool nl)
+// the candidate sweep and the selection `reps` times, nothing applied (tspgpu_time_multi_sweep, tspgpu_time_nl_sweep,
+// tspgpu_time_or_nl_sweep)
+static int m2_time(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean, M2Kind kind)
 {
     if (!ctx) return E_UNAVAILABLE;
     if (!ms_mean || reps <= 0) return fail(ctx, E_INVALID, "bad argument");
     hipSetDevice(ctx->device);
-    int rc = nl ? nl_check(ctx) : m2_check(ctx);
+    int rc = m2_kind_check(ctx, kind);
     if (rc) return rc;
     if ((rc = need_slot(ctx, slot))) return rc;
     HIP_TRY(hipMemsetAsync(ctx->d_m2, 0, sizeof(M2Ctl), ctx->stream));
     const SweepGeom P = m2_plan(ctx);
     // warm: in matrix-free mode with its gather; the timed launches go without
-    return time_launches(ctx, reps, [&] { return m2_launch_select(ctx, slot, P, true, nl); },
-                         [&] { return m2_launch_select(ctx, slot, P, false, nl); }, ms_mean);
+    return time_launches(ctx, reps, [&] { return m2_launch_select(ctx, slot, P, true, kind); },
+                         [&] { return m2_launch_select(ctx, slot, P, false, kind); }, ms_mean);
 }
 
 extern "C" {
 
 int tspgpu_two_opt_multi_once(tspgpu_ctx *ctx, int *path, double *cost, int *nmoves, int *moves_ab, double *deltas, int cap)
 {
-    return m2_once(ctx, path, cost, nmoves, moves_ab, deltas, cap, false);
+    return m2_once(ctx, path, cost, nmoves, moves_ab, deltas, cap, M2_FULL);
 }
 
 int tspgpu_time_multi_sweep(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean)
 {
-    return m2_time(ctx, slot, reps, ms_mean, false);
+    return m2_time(ctx, slot, reps, ms_mean, M2_FULL);
 }
 
 } // extern "C"
@@ -6662,7 +6694,7 @@ int tspgpu_neighbours_get(tspgpu_ctx *ctx, int *nodes, double *weights)
 
 int tspgpu_two_opt_nl_once(tspgpu_ctx *ctx, int *path, double *cost, int *nmoves, int *moves_ab, double *deltas, int cap)
 {
-    return m2_once(ctx, path, cost, nmoves, moves_ab, deltas, cap, true);
+    return m2_once(ctx, path, cost, nmoves, moves_ab, deltas, cap, M2_NL);
 }
 
 int tspgpu_tour_two_opt_nl(tspgpu_ctx *ctx, int slot, long max_sweeps, double time_left_s, long *sweeps, long *moves)
@@ -6673,7 +6705,7 @@ int tspgpu_tour_two_opt_nl(tspgpu_ctx *ctx, int slot, long max_sweeps, double ti
     if (rc) return rc;
     if ((rc = need_slot(ctx, slot))) return rc;
     bool late = false;
-    if ((rc = m2_run(ctx, slot, max_sweeps, deadline_of(time_left_s), sweeps, moves, &late, true))) return rc;
+    if ((rc = m2_run(ctx, slot, max_sweeps, deadline_of(time_left_s), sweeps, moves, &late, M2_NL))) return rc;
     return done_code(late);
 }
 
@@ -6690,7 +6722,7 @@ int tspgpu_two_opt_nl(tspgpu_ctx *ctx, int *path, double *cost, double time_left
     bool late = false;
     long ps = 0, pm = 0;
     ctx->nl_polish_sweeps = 0;
-    if ((rc = m2_run(ctx, 0, -1, t_end, sweeps, moves, &late, true))) return rc;
+    if ((rc = m2_run(ctx, 0, -1, t_end, sweeps, moves, &late, M2_NL))) return rc;
     if (polish && !late) {                  // the parallel-move descent goes on from the slot as it stands
         if ((rc = m2_run(ctx, 0, -1, t_end, &ps, &pm, &late))) return rc;
         ctx->nl_polish_sweeps = ps;
@@ -6703,7 +6735,146 @@ int tspgpu_two_opt_nl(tspgpu_ctx *ctx, int *path, double *cost, double time_left
 
 int tspgpu_time_nl_sweep(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean)
 {
-    return m2_time(ctx, slot, reps, ms_mean, true);
+    return m2_time(ctx, slot, reps, ms_mean, M2_NL);
+}
+
+} // extern "C"
+
+// ---- neighbour-list Or-opt and the descent over the lists (tspgpu_ornl.inc) ---------------------------------------------
+
+// what the neighbour-list 2-opt needs (the descent alternates with it on the same slot), and Or-opt's eight nodes.  No row in
+// LDS beyond the parallel-move limit, and no TSPGPU_OPT_OR_MATRIX_FREE: the costs come from the lists and single gathers
+static int ornl_check(tspgpu_ctx *ctx)
+{
+    const int rc = need_costs(ctx);
+    if (rc) return rc;
+    if (ctx->n < 8) return fail(ctx, E_INVALID, "neighbour-list Or-opt needs at least 8 nodes, got %d", ctx->n);
+    return nl_check(ctx);
+}
+
+static int ornl_launch_sweep(tspgpu_ctx *ctx, int slot)
+{
+    const int n = ctx->n;
+    const dim3 grid((n + ORNL_STARTS - 1) / ORNL_STARTS), block(ORNL_STARTS * 64);
+    const M2Ctl *ctl = ctx->d_m2;
+    if (ctx->otf)
+        kind_switch(ctx, [&](auto kind, auto *pts, auto *) {
+            hipLaunchKernelGGL((k_ornl_sweep_otf<kind()>), grid, block, 0, ctx->stream, ctx->S, pts, n, slot, ctx->nl, ctx->m2, ctl);
+        });
+    else
+        ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_ornl_sweep<T>), grid, block, 0, ctx->stream, ctx->S, (const T *)ctx->d_mat, n, ctx->ld, slot,
+                                                     ctx->nl, ctx->m2, ctl));
+    HIP_TRY(hipGetLastError());
+    return E_OK;
+}
+
+static int ornl_launch_apply(tspgpu_ctx *ctx, int slot)
+{
+    const int n = ctx->n, G = std::min(M2_APPLY_WGS, (n + 1) / 2);
+    if (ctx->otf)
+        kind_switch(ctx, [&](auto kind, auto *pts, auto *) {
+            hipLaunchKernelGGL((k_ornl_apply_otf<kind()>), dim3(G), dim3(ORNL_APPLY_BT), 0, ctx->stream, ctx->S, pts, n, slot, ctx->m2, ctx->d_m2);
+        });
+    else
+        ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_ornl_apply<T>), dim3(G), dim3(ORNL_APPLY_BT), 0, ctx->stream, ctx->S,
+                                                     (const T *)ctx->d_mat, n, ctx->ld, slot, ctx->m2, ctx->d_m2));
+    HIP_TRY(hipGetLastError());
+    return E_OK;
+}
+
+// the descent of tspgpu_local_search_nl on a slot: { neighbour-list 2-opt to its end; neighbour-list Or-opt until a sweep accepts
+// nothing } until an Or-opt phase applies nothing
+static int ornl_descent(tspgpu_ctx *ctx, int slot, double time_left_s, long *two_opt_sweeps, long *two_opt_moves, long *or_sweeps,
+                        long *or_moves, int *rounds, bool *late)
+{
+    const double t_end = deadline_of(time_left_s);
+    long tw = 0, tm = 0, os = 0, om = 0, mk = 0;
+    int nr = 0, rc = E_OK;
+    *late = false;
+    ctx->ornl_sweeps = ctx->ornl_moves = ctx->ornl_max_k = 0;
+    for (;;) {
+        long s = 0, m = 0;
+        if ((rc = m2_run(ctx, slot, -1, t_end, &s, &m, late, M2_NL))) break;
+        tw += s; tm += m; nr++;
+        if (*late) break;
+        if ((rc = m2_run(ctx, slot, -1, t_end, &s, &m, late, M2_ORNL))) break;
+        os += s; om += m; mk = std::max(mk, ctx->ornl_max_k);
+        if (*late || m == 0) break;
+    }
+    ctx->ornl_sweeps = os; ctx->ornl_moves = om; ctx->ornl_max_k = mk; ctx->ornl_rounds = nr;
+    if (two_opt_sweeps) *two_opt_sweeps = tw;
+    if (two_opt_moves) *two_opt_moves = tm;
+    if (or_sweeps) *or_sweeps = os;
+    if (or_moves) *or_moves = om;
+    if (rounds) *rounds = nr;
+    return rc;
+}
+
+extern "C" {
+
+int tspgpu_or_opt_nl_once(tspgpu_ctx *ctx, int *path, double *cost, int *nmoves, int *moves, double *deltas, int cap)
+{
+    return m2_once(ctx, path, cost, nmoves, moves, deltas, cap, M2_ORNL);
+}
+
+int tspgpu_or_opt_nl(tspgpu_ctx *ctx, int *path, double *cost, double time_left_s, long *sweeps, long *moves)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    if (!path || !cost) return fail(ctx, E_INVALID, "null argument");
+    hipSetDevice(ctx->device);
+    int rc = ornl_check(ctx);
+    if (rc) return rc;
+    if ((rc = load_path(ctx, 0, path, -1))) return rc;
+    HIP_TRY(hipMemcpyAsync(ctx->S.cost, cost, 8, hipMemcpyHostToDevice, ctx->stream));     // the caller's running cost, as tspgpu_or_opt
+    bool late = false;
+    if ((rc = m2_run(ctx, 0, -1, deadline_of(time_left_s), sweeps, moves, &late, M2_ORNL))) return rc;
+    if ((rc = store_path(ctx, 0, path, cost, nullptr))) return rc;
+    return done_code(late);
+}
+
+int tspgpu_tour_or_opt_nl(tspgpu_ctx *ctx, int slot, long max_sweeps, double time_left_s, long *sweeps, long *moves)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    hipSetDevice(ctx->device);
+    int rc = ornl_check(ctx);
+    if (rc) return rc;
+    if ((rc = need_slot(ctx, slot))) return rc;
+    bool late = false;
+    if ((rc = m2_run(ctx, slot, max_sweeps, deadline_of(time_left_s), sweeps, moves, &late, M2_ORNL))) return rc;
+    return done_code(late);
+}
+
+int tspgpu_local_search_nl(tspgpu_ctx *ctx, int *path, double *cost, double time_left_s, long *two_opt_sweeps, long *two_opt_moves,
+                           long *or_sweeps, long *or_moves, int *rounds)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    if (!path || !cost) return fail(ctx, E_INVALID, "null argument");
+    hipSetDevice(ctx->device);
+    int rc = ornl_check(ctx);
+    if (rc) return rc;
+    if ((rc = load_path(ctx, 0, path, -1))) return rc;          // recomputes the cost, refinment.c:6-9
+    bool late = false;
+    if ((rc = ornl_descent(ctx, 0, time_left_s, two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds, &late))) return rc;
+    if ((rc = store_path(ctx, 0, path, cost, nullptr))) return rc;
+    return done_code(late);
+}
+
+int tspgpu_tour_local_search_nl(tspgpu_ctx *ctx, int slot, double time_left_s, long *two_opt_sweeps, long *two_opt_moves,
+                                long *or_sweeps, long *or_moves, int *rounds)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    hipSetDevice(ctx->device);
+    int rc = ornl_check(ctx);
+    if (rc) return rc;
+    if ((rc = need_slot(ctx, slot))) return rc;
+    bool late = false;
+    if ((rc = ornl_descent(ctx, slot, time_left_s, two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds, &late))) return rc;
+    return done_code(late);
+}
+
+int tspgpu_time_or_nl_sweep(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean)
+{
+    return m2_time(ctx, slot, reps, ms_mean, M2_ORNL);
 }
 
 } // extern "C"

@@ -53,7 +53,8 @@ class Engine:
                  "otf_kernel", "ceil_int", "em_form", "em_stale", "em_steps", "or_batch_r", "or_single_r",
                  "or_block", "or_nch", "or_otf", "or_otf_R",
                  "multi_sweeps", "multi_moves", "multi_max_moves", "multi_r", "multi_block", "multi_nch",
-                 "nl_k", "nl_sweeps", "nl_moves", "nl_polish_sweeps", "nl_nodes"]
+                 "nl_k", "nl_sweeps", "nl_moves", "nl_polish_sweeps", "nl_nodes",
+                 "or_nl_sweeps", "or_nl_moves", "or_nl_max_moves", "or_nl_rounds", "or_nl_starts"]
         return {k: int(self.L.tspgpu_info(self.ctx, i)) for i, k in enumerate(names)}
 
     # ---- instance
@@ -183,6 +184,33 @@ class Engine:
         rc = self._ck(self.L.tspgpu_two_opt_nl(self.ctx, path, C.byref(c), float(time_left_s), 1 if polish else 0, C.byref(s), C.byref(m),
                                                C.byref(ps), C.byref(pm)), ok=(T_OK, DEADLINE_EXCEEDED))
         return {"cost": c.value, "sweeps": s.value, "moves": m.value, "polish_sweeps": ps.value, "polish_moves": pm.value, "rc": rc}
+
+    def or_opt_nl_once(self, path, cost, cap=None):
+        """one neighbour-list Or-opt sweep (include/tspgpu.h "Neighbour-list Or-opt"); path in place ->
+        (cost, moves, deltas): moves an array [k][4] of s, L, q, rev in ascending key order, deltas [k] (k = 0: nothing
+        improves).  More than `cap` (default n) accepted moves: RESOURCE_EXHAUSTED, nothing applied."""
+        cap = self.n if cap is None else int(cap)
+        c, k = C.c_double(cost), C.c_int()
+        mv = np.empty(4 * max(cap, 1), dtype=np.int32)
+        dl = np.empty(max(cap, 1), dtype=np.float64)
+        self._ck(self.L.tspgpu_or_opt_nl_once(self.ctx, path, C.byref(c), C.byref(k), mv, dl, cap))
+        return c.value, mv[:4 * k.value].reshape(-1, 4).copy(), dl[:k.value].copy()
+
+    def or_opt_nl(self, path, cost, time_left_s=-1.0):
+        """neighbour-list Or-opt sweeps until one accepts nothing; path in place -> (cost, sweeps, moves, rc)."""
+        c, s, m = C.c_double(cost), C.c_long(), C.c_long()
+        rc = self._ck(self.L.tspgpu_or_opt_nl(self.ctx, path, C.byref(c), float(time_left_s), C.byref(s), C.byref(m)),
+                      ok=(T_OK, DEADLINE_EXCEEDED))
+        return c.value, s.value, m.value, rc
+
+    def local_search_nl(self, path, time_left_s=-1.0):
+        """neighbour-list 2-opt and neighbour-list Or-opt in turn until an Or-opt phase applies nothing; path in place ->
+        dict(cost, two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds, rc)."""
+        c, tw, tm, os_, om, nr = C.c_double(), C.c_long(), C.c_long(), C.c_long(), C.c_long(), C.c_int()
+        rc = self._ck(self.L.tspgpu_local_search_nl(self.ctx, path, C.byref(c), float(time_left_s), C.byref(tw), C.byref(tm), C.byref(os_),
+                                                    C.byref(om), C.byref(nr)), ok=(T_OK, DEADLINE_EXCEEDED))
+        return {"cost": c.value, "two_opt_sweeps": tw.value, "two_opt_moves": tm.value, "or_sweeps": os_.value, "or_moves": om.value,
+                "rounds": nr.value, "rc": rc}
 
     def local_search(self, path, time_left_s=-1.0):
         """2-opt and Or-opt in turn until neither improves; path in place ->
@@ -326,6 +354,26 @@ class Engine:
         rc = self._ck(self.L.tspgpu_tour_two_opt_nl(self.ctx, int(slot), int(max_sweeps), float(time_left_s), C.byref(s), C.byref(m)),
                       ok=(T_OK, DEADLINE_EXCEEDED))
         return s.value, m.value, rc
+
+    def tour_or_opt_nl(self, slot, max_sweeps=-1, time_left_s=-1.0):
+        """neighbour-list Or-opt sweeps on a slot -> (sweeps, moves, rc)."""
+        s, m = C.c_long(), C.c_long()
+        rc = self._ck(self.L.tspgpu_tour_or_opt_nl(self.ctx, int(slot), int(max_sweeps), float(time_left_s), C.byref(s), C.byref(m)),
+                      ok=(T_OK, DEADLINE_EXCEEDED))
+        return s.value, m.value, rc
+
+    def tour_local_search_nl(self, slot, time_left_s=-1.0):
+        """the descent of local_search_nl on a slot -> dict(two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds, rc)."""
+        tw, tm, os_, om, nr = C.c_long(), C.c_long(), C.c_long(), C.c_long(), C.c_int()
+        rc = self._ck(self.L.tspgpu_tour_local_search_nl(self.ctx, int(slot), float(time_left_s), C.byref(tw), C.byref(tm), C.byref(os_),
+                                                         C.byref(om), C.byref(nr)), ok=(T_OK, DEADLINE_EXCEEDED))
+        return {"two_opt_sweeps": tw.value, "two_opt_moves": tm.value, "or_sweeps": os_.value, "or_moves": om.value, "rounds": nr.value,
+                "rc": rc}
+
+    def time_or_nl_sweep(self, slot, reps):
+        ms = C.c_float()
+        self._ck(self.L.tspgpu_time_or_nl_sweep(self.ctx, slot, reps, C.byref(ms)))
+        return ms.value
 
     def time_nl_sweep(self, slot, reps):
         ms = C.c_float()

@@ -707,6 +707,10 @@ static int or_opt_refusal(ERROR_CODE e)
     return e == INVALID_ARGUMENT || e == RESOURCE_EXHAUSTED || e == FAILED_PRECONDITION || e == UNIMPLEMENTED;
 }
 
+/* TSP_OR_OPT_NEIGHBOURS=K, K in 1..16 (tsp_run_algorithm): the polish runs the descent over neighbour lists of K nodes
+ * (tspgpu_local_search_nl) instead of tspgpu_local_search; it takes a matrix-free instance as it is */
+static int or_opt_nl_k = 0;
+
 ERROR_CODE tsp_or_opt_polish(tsp_solution *solution)
 {
     if (!solution || !solution->path) return INVALID_ARGUMENT;
@@ -715,6 +719,20 @@ ERROR_CODE tsp_or_opt_polish(tsp_solution *solution)
     if (!g) return UNAVAILABLE;
     long sweeps = 0, moves = 0;
     int rounds = 0;
+    if (or_opt_nl_k) {
+        /* the lists belong to the costs in place: built when the context holds none of that length */
+        const int kp = or_opt_nl_k < tsp_inst.nnodes - 1 ? or_opt_nl_k : tsp_inst.nnodes - 1;
+        long or_sweeps = 0, two_opt_moves = 0;
+        int rc = tspgpu_info(g, 42) == kp ? 0 : tspgpu_neighbours_build(g, or_opt_nl_k);
+        if (rc == 0)
+            rc = tspgpu_local_search_nl(g, solution->path, &solution->cost, time_left(), &sweeps, &two_opt_moves, &or_sweeps, &moves, &rounds);
+        if (or_opt_refusal(from_rc(rc))) log_warn("tspgpu_local_search_nl: %s", tspgpu_last_error(g));
+        else if (rc != 0 && rc != DEADLINE_EXCEEDED) log_error("tspgpu_local_search_nl: %s", tspgpu_last_error(g));
+        else log_debug("Or-opt polish over lists of %d: %d rounds, %ld 2-opt sweeps (%ld moves), %ld Or-opt sweeps (%ld moves), cost %f",
+                       or_opt_nl_k, rounds, sweeps, two_opt_moves, or_sweeps, moves, solution->cost);
+        thread_done(lease);
+        return from_rc(rc);
+    }
     const int rc = tspgpu_local_search(g, solution->path, &solution->cost, time_left(), &sweeps, &moves, &rounds);
     if (or_opt_refusal(from_rc(rc))) log_warn("tspgpu_local_search: %s", tspgpu_last_error(g));
     else if (rc != 0 && rc != DEADLINE_EXCEEDED) log_error("tspgpu_local_search: %s", tspgpu_last_error(g));
@@ -768,7 +786,8 @@ ERROR_CODE h_greedy_local_search(void)
 /* TSP_OR_OPT (1 = polish the incumbent after the heuristic), TSP_OR_OPT_EVERY_START (1 = -alg 2OPT_GREEDY runs
  * h_greedy_local_search) and TSP_OR_OPT_MATRIX_FREE (1 = the TSP_OR_OPT polish also runs on a matrix-free instance,
  * TSPGPU_OPT_OR_MATRIX_FREE), TSP_2OPT_MULTI (1 = ref_2opt, and with it every iteration of mh_VNS's host loop, runs the
- * parallel-move descent tspgpu_two_opt_multi): unset or 0 = off; anything else is an error (-1) */
+ * parallel-move descent tspgpu_two_opt_multi): unset or 0 = off; anything else is an error (-1).  TSP_OR_OPT_NEIGHBOURS=K
+ * (env_neighbours) makes the TSP_OR_OPT polish the descent over neighbour lists of K nodes, on a matrix-free instance too */
 static int env_switch(const char *name)
 {
     const char *v = getenv(name);
@@ -778,15 +797,15 @@ static int env_switch(const char *name)
     return -1;
 }
 
-/* TSP_2OPT_NEIGHBOURS: unset or 0 = off, 1..16 = the list length; anything else is an error (-1) */
-static int env_neighbours(void)
+/* TSP_2OPT_NEIGHBOURS, TSP_OR_OPT_NEIGHBOURS: unset or 0 = off, 1..16 = the list length; anything else is an error (-1) */
+static int env_neighbours(const char *name)
 {
-    const char *v = getenv("TSP_2OPT_NEIGHBOURS");
+    const char *v = getenv(name);
     if (!v) return 0;
     char *end = NULL;
     const long k = strtol(v, &end, 10);
     if (*v && !*end && k >= 0 && k <= 16) return (int)k;
-    fprintf(stderr, "tsp: TSP_2OPT_NEIGHBOURS=\"%s\": expected a list length from 1 to 16 (or 0: off)\n", v);
+    fprintf(stderr, "tsp: %s=\"%s\": expected a list length from 1 to 16 (or 0: off)\n", name, v);
     return -1;
 }
 
@@ -796,10 +815,16 @@ ERROR_CODE tsp_run_algorithm(void)
     const int polish = env_switch("TSP_OR_OPT"), every_start = env_switch("TSP_OR_OPT_EVERY_START");
     const int polish_mf = env_switch("TSP_OR_OPT_MATRIX_FREE");
     const int multi = env_switch("TSP_2OPT_MULTI");
-    const int nl_k = env_neighbours();
+    const int nl_k = env_neighbours("TSP_2OPT_NEIGHBOURS"), or_nl_k = env_neighbours("TSP_OR_OPT_NEIGHBOURS");
     const char *nl_polish_set = getenv("TSP_2OPT_NEIGHBOURS_POLISH");
     const int nl_polish = nl_polish_set ? env_switch("TSP_2OPT_NEIGHBOURS_POLISH") : 1;
-    if (polish < 0 || every_start < 0 || polish_mf < 0 || multi < 0 || nl_k < 0 || nl_polish < 0) return INVALID_ARGUMENT;
+    if (polish < 0 || every_start < 0 || polish_mf < 0 || multi < 0 || nl_k < 0 || nl_polish < 0 || or_nl_k < 0) return INVALID_ARGUMENT;
+    if (or_nl_k && nl_k && or_nl_k != nl_k) {       /* a context holds one set of lists */
+        fprintf(stderr, "tsp: TSP_OR_OPT_NEIGHBOURS=%d and TSP_2OPT_NEIGHBOURS=%d: the two list lengths must be equal\n", or_nl_k, nl_k);
+        return INVALID_ARGUMENT;
+    }
+    or_opt_nl_k = polish > 0 ? or_nl_k : 0;
+    if (or_nl_k && !polish) log_warn("TSP_OR_OPT_NEIGHBOURS=%d has no effect without TSP_OR_OPT=1", or_nl_k);
     two_opt_multi_on = multi;
     two_opt_nl_k = nl_k;
     two_opt_nl_polish = nl_polish;
@@ -821,11 +846,11 @@ ERROR_CODE tsp_run_algorithm(void)
         return UNIMPLEMENTED;
     }
     if (!polish || (e != T_OK && e != DEADLINE_EXCEEDED)) return e;
-    if (tsp_matrix_free && !polish_mf) {
+    if (tsp_matrix_free && !polish_mf && !or_opt_nl_k) {
         log_warn("TSP_OR_OPT=1: Or-opt needs the cost matrix and the instance runs matrix-free; the polish is skipped");
         return e;
     }
-    if (tsp_matrix_free) {      /* TSP_OR_OPT_MATRIX_FREE=1: the single-tour descent from the coordinates */
+    if (tsp_matrix_free && !or_opt_nl_k) {      /* TSP_OR_OPT_MATRIX_FREE=1: the single-tour descent from the coordinates */
         tspgpu_ctx *g = tsp_gpu();
         if (!g) return UNAVAILABLE;
         const int rc = tspgpu_set_option(g, TSPGPU_OPT_OR_MATRIX_FREE, 1);
