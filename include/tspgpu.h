@@ -526,6 +526,47 @@ int tspgpu_tour_local_search_nl(tspgpu_ctx *ctx, int slot, double time_left_s,
  * nothing applied */
 int tspgpu_time_or_nl_sweep(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean);
 
+/* ---- Batched neighbour-list descent (an extension: the descent over the lists on a batch of tours, and the multi-start) ----
+ * The descent of "Neighbour-list Or-opt" (rule 8) on many tours at once: every launch serves every tour of the batch that
+ * is still descending.  For each tour of the batch the descent is exactly rule 8, run on that tour alone:
+ *   1. the neighbour-list 2-opt phase runs until a sweep accepts nothing; that sweep is counted;
+ *   2. the neighbour-list Or-opt phase runs until a sweep accepts nothing; that sweep is counted;
+ *   3. 1 and 2 repeat until an Or-opt phase applies nothing.
+ * Tours do not interact, and a tour's phases advance on the device without a host read in between, so the tours of a batch
+ * need not be in the same phase.  Each slot ends exactly as tspgpu_tour_local_search_nl would leave it: the successor array,
+ * the cost and the last delta as tspgpu_tour_store shows them, the five counters, and a slot that every later slot call can
+ * use.  The cost is bit-equal for double cells as well: the accepted deltas of a sweep are summed by the same tree of fixed
+ * shape.  Matrix mode (uint16, int32, f64 cells) and matrix-free mode; no TSPGPU_OPT_OR_MATRIX_FREE and no row-in-LDS limit
+ * beyond that of "Neighbour-list 2-opt".
+ * Preconditions: those of "Neighbour-list Or-opt" (symmetric costs, n >= 8, lists built for the cost source in place).
+ * Memory: the candidate arrays of "Parallel-move 2-opt" (40 bytes per node) and a control block once per slot of the range,
+ * and the list of live slots, allocated at the first batched call, all or none; a failure is 8 with the byte count in the text.
+ * Codes: no context or handle 14, n < 8 3, no costs 9, an asymmetric matrix 9, lists not built or invalidated 9 (the text
+ * of "Neighbour-list 2-opt"), a bad slot range 3, a slot of the range that holds no tour 9 (nothing is run), a deadline
+ * that passed 4 (every slot a valid tour whose stored cost is that tour's cost).
+ * tspgpu_info: 52 tours of the last batched list descent, 53 its sweep launches (a sweep of every live tour: four kernels),
+ * 54 the most tours live in one launch, 55 workgroups per tour of the batched candidate sweep on this instance (0: none). */
+/* the descent on slots slot0 .. slot0+count-1 at once; per-slot outputs, [count] each (each may be NULL) */
+int tspgpu_tours_local_search_nl(tspgpu_ctx *ctx, int slot0, int count, double time_left_s,
+                                 long *two_opt_sweeps, long *two_opt_moves, long *or_sweeps, long *or_moves, int *rounds);
+/* tspgpu_multistart_local_search with this descent: the NN tour from every listed start (starts NULL: 0 .. nstarts-1), the
+ * batched descent in chunks of TSPGPU_OPT_MAX_TOURS, the lowest final cost wins, ties to the earliest entry of `starts`
+ * (strict <).  costs_out [nstarts] (may be NULL): every start's final cost in list order; the totals (each may be NULL) are
+ * sums over the starts.  A TSPGPU_OPT_SWEEP_CAP other than -1 is refused with 3.  Once the deadline passes: 4, with the best
+ * of the chunks begun so far (the entries of costs_out behind them are left as they were). */
+int tspgpu_multistart_local_search_nl(tspgpu_ctx *ctx, const int *starts, int nstarts, double time_left_s,
+                                      int *best_path, double *best_cost, int *best_start,
+                                      long *total_two_opt_sweeps, long *total_two_opt_moves,
+                                      long *total_or_sweeps, long *total_or_moves, double *costs_out);
+/* tspgpu_neighbours_build on every device's context of a multi-device handle */
+int tspgpu_multi_neighbours_build(tspgpu_multi *m, int K);
+/* tspgpu_multistart_local_search_nl sharded as tspgpu_multi_multistart_local_search is (entry p of the list on device
+ * p mod G, the same exchange) */
+int tspgpu_multi_multistart_local_search_nl(tspgpu_multi *m, const int *starts, int nstarts, double time_left_s,
+                                            int *best_path, double *best_cost, int *best_start,
+                                            long *total_two_opt_sweeps, long *total_two_opt_moves,
+                                            long *total_or_sweeps, long *total_or_moves);
+
 #ifdef __cplusplus
 }
 #endif

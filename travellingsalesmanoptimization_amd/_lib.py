@@ -30,6 +30,8 @@ INFO_MULTI_SWEEPS, INFO_MULTI_MOVES, INFO_MULTI_MAX_MOVES, INFO_MULTI_R, INFO_MU
 INFO_NL_K, INFO_NL_SWEEPS, INFO_NL_MOVES, INFO_NL_POLISH_SWEEPS, INFO_NL_NODES = 42, 43, 44, 45, 46
 # ... Or-opt sweeps / moves / largest sweep of the last neighbour-list Or-opt call, rounds of the last local_search_nl, starts per workgroup
 INFO_OR_NL_SWEEPS, INFO_OR_NL_MOVES, INFO_OR_NL_MAX_MOVES, INFO_OR_NL_ROUNDS, INFO_OR_NL_STARTS = 47, 48, 49, 50, 51
+# ... tours, sweep launches and most live tours of the last batched neighbour-list descent, workgroups per tour of its candidate sweep
+INFO_NL_BATCH_TOURS, INFO_NL_BATCH_LAUNCHES, INFO_NL_BATCH_MAX_LIVE, INFO_NL_BATCH_WGS = 52, 53, 54, 55
 EM_FORM_AUTO, EM_FORM_RESIDENT, EM_FORM_PER_STEP = 0, 1, 2
 MOPT_EXCHANGE = 1000
 EXCHANGE_AUTO, EXCHANGE_HOST, EXCHANGE_RCCL = 0, 1, 2
@@ -115,6 +117,10 @@ SIGNATURES = {
     "tspgpu_local_search_nl": (C.c_int, [_ctx, _ip, _pd, C.c_double, _pl, _pl, _pl, _pl, _pi]),
     "tspgpu_tour_local_search_nl": (C.c_int, [_ctx, C.c_int, C.c_double, _pl, _pl, _pl, _pl, _pi]),
     "tspgpu_time_or_nl_sweep": (C.c_int, [_ctx, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "tspgpu_tours_local_search_nl": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tspgpu_multistart_local_search_nl": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_double, _ip, _pd, _pi, _pl, _pl, _pl, _pl, C.c_void_p]),
+    "tspgpu_multi_neighbours_build": (C.c_int, [_ctx, C.c_int]),
+    "tspgpu_multi_multistart_local_search_nl": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_double, _ip, _pd, _pi, _pl, _pl, _pl, _pl]),
 }
 
 _lib = None

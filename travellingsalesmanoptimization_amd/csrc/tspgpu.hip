@@ -3092,6 +3092,7 @@ __global__ void k_cap_now(Tours S, int slot0, int count)
 #include "tspgpu_multi2opt.inc"
 #include "tspgpu_nl2opt.inc"
 #include "tspgpu_ornl.inc"
+#include "tspgpu_nlbatch.inc"
 
 // ===========================================================================
 // host side
@@ -3221,6 +3222,13 @@ struct tspgpu_ctx {
     // neighbour-list Or-opt (tspgpu_ornl.inc): the last call's sweeps, moves and largest sweep (a descent: over its rounds)
     long ornl_sweeps = 0, ornl_moves = 0, ornl_max_k = 0;
     int ornl_rounds = 0;       // rounds of the last tspgpu_local_search_nl
+    // batched neighbour-list descent (tspgpu_nlbatch.inc): the candidate arrays and a control block per slot of a range of nlb_cap
+    // slots, the list of live slots (device, and its pinned staging); all of them allocated at the first batched call, or none
+    M2Buf nlb{};
+    NlbCtl *d_nlb_ctl = nullptr;
+    int *d_nlb_live = nullptr, *h_nlb_live = nullptr;
+    int nlb_cap = 0;
+    long nlb_tours = 0, nlb_launches = 0, nlb_max_live = 0;     // the last batched descent: tours, sweeps launched, most tours in one
 
     Fused F{};                 // fused path state (allocated on first use, capacity fcap)
     int fcap = 0;
@@ -3323,10 +3331,22 @@ static void free_m2(tspgpu_ctx *ctx)
     memset(&ctx->m2, 0, sizeof ctx->m2);
 }
 
+static void free_nlb(tspgpu_ctx *ctx)
+{
+    void *ptrs[] = {ctx->nlb.raw_d, ctx->nlb.raw_b, ctx->nlb.d, ctx->nlb.a, ctx->nlb.b, ctx->nlb.i, ctx->nlb.j, ctx->nlb.acc, ctx->d_nlb_ctl,
+                    ctx->d_nlb_live};
+    for (void *p : ptrs) if (p) hipFree(p);
+    if (ctx->h_nlb_live) hipHostFree(ctx->h_nlb_live);
+    memset(&ctx->nlb, 0, sizeof ctx->nlb);
+    ctx->d_nlb_ctl = nullptr; ctx->d_nlb_live = ctx->h_nlb_live = nullptr;
+    ctx->nlb_cap = 0;
+}
+
 static void free_tours(tspgpu_ctx *ctx)
 {
     free_tour_arrays(ctx->S);
     free_m2(ctx);              // sized by n
+    free_nlb(ctx);             // sized by n and a slot count
     free_tour_scratch(ctx);
     void *ptrs[] = {ctx->d_tabu_list, ctx->d_best_succ, ctx->d_tabu};
     for (void *p : ptrs) if (p) hipFree(p);
@@ -5051,6 +5071,10 @@ long tspgpu_info(const tspgpu_ctx *ctx, int what)
     case 49: return ctx->ornl_max_k;
     case 50: return ctx->ornl_rounds;
     case 51: return ORNL_STARTS;
+    case 52: return ctx->nlb_tours;
+    case 53: return ctx->nlb_launches;
+    case 54: return ctx->nlb_max_live;
+    case 55: return ctx->have_costs && ctx->symmetric && ctx->n >= 8 ? (ctx->n + ORNL_STARTS - 1) / ORNL_STARTS : 0;
     case 12: return (ctx->built && ctx->grid_ok && ctx->opt_nn != 1 && ctx->cost_bound < 134217728.0) ? ctx->grid_G : 0;
     case 13: return ctx->grid_max_occ;
     }
@@ -6875,6 +6899,190 @@ int tspgpu_tour_local_search_nl(tspgpu_ctx *ctx, int slot, double time_left_s, l
 int tspgpu_time_or_nl_sweep(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean)
 {
     return m2_time(ctx, slot, reps, ms_mean, M2_ORNL);
+}
+
+} // extern "C"
+
+// ---- batched neighbour-list descent (tspgpu_nlbatch.inc) ---------------------------------------------------------------
+
+// the candidate arrays (40 bytes per node and slot), a control block per slot and the live list for a range of `count` slots
+static int nlb_ensure(tspgpu_ctx *ctx, int count)
+{
+    if (count <= ctx->nlb_cap) return E_OK;
+    free_nlb(ctx);
+    M2Buf &B = ctx->nlb;
+    const size_t N = (size_t)ctx->n * count;
+    void **ptrs[] = {(void **)&B.raw_d, (void **)&B.raw_b, (void **)&B.d, (void **)&B.a, (void **)&B.b, (void **)&B.i, (void **)&B.j, (void **)&B.acc,
+                     (void **)&ctx->d_nlb_ctl, (void **)&ctx->d_nlb_live};
+    const size_t bytes[] = {N * 8, N * 4, N * 8, N * 4, N * 4, N * 4, N * 4, N * 4, (size_t)count * sizeof(NlbCtl), (size_t)count * 4};
+    size_t total = 0;
+    for (size_t b : bytes) total += b;
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < 10 && e == hipSuccess; k++) e = hipMalloc(ptrs[k], bytes[k]);
+    if (e == hipSuccess) e = hipHostMalloc(&ctx->h_nlb_live, (size_t)count * 4);
+    if (e != hipSuccess) {                  // all or none: a later call must not find half of them
+        free_nlb(ctx);
+        (void)hipGetLastError();
+        return fail(ctx, E_EXHAUSTED, "the batched neighbour-list descent needs %zu bytes of device memory for %d tours of %d nodes (%s)",
+                    total, count, ctx->n, hipGetErrorString(e));
+    }
+    ctx->nlb_cap = count;
+    return E_OK;
+}
+
+// the slot list of the next launches: staged in pinned memory, so the stream must have drained the previous list first (or_set_live)
+static int nlb_set_live(tspgpu_ctx *ctx, const std::vector<int> &list)
+{
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    memcpy(ctx->h_nlb_live, list.data(), list.size() * 4);
+    HIP_TRY(hipMemcpyAsync(ctx->d_nlb_live, ctx->h_nlb_live, list.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+    return E_OK;
+}
+
+// one sweep of every tour of the first `live` slots of the list: the four launches, grid rows in runs of at most 65 535
+static int nlb_launch_sweep(tspgpu_ctx *ctx, int slot0, int live)
+{
+    const int n = ctx->n, W = (n + ORNL_STARTS - 1) / ORNL_STARTS, G = std::min(NLB_APPLY_WGS, (n + 1) / 2);
+    NlbCtl *ctl = ctx->d_nlb_ctl;
+    const int run = std::max(1, std::min(65535, (1 << 23) / W));    // (a grid holds fewer than 2^32 threads)
+    for (int off = 0; off < live; off += run) {
+        const unsigned rows = (unsigned)std::min(run, live - off);
+        const int *list = ctx->d_nlb_live + off;
+        if (ctx->otf)
+            kind_switch(ctx, [&](auto kind, auto *pts, auto *) {
+                hipLaunchKernelGGL((k_nlb_sweep_otf<kind()>), dim3(W, rows), dim3(256), 0, ctx->stream, ctx->S, pts, n, list, slot0, ctx->nl, ctx->nlb,
+                                   (const NlbCtl *)ctl);
+            });
+        else
+            ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_nlb_sweep<T>), dim3(W, rows), dim3(256), 0, ctx->stream, ctx->S, (const T *)ctx->d_mat, n,
+                                                         ctx->ld, list, slot0, ctx->nl, ctx->nlb, (const NlbCtl *)ctl));
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_nlb_compact, dim3(1, rows), dim3(1024), 0, ctx->stream, ctx->S, n, list, slot0, ctx->nlb, ctl);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(k_nlb_select, dim3((n + 255) / 256, rows), dim3(256), 0, ctx->stream, n, list, slot0, ctx->nlb, (const NlbCtl *)ctl);
+        HIP_TRY(hipGetLastError());
+        if (ctx->otf)
+            kind_switch(ctx, [&](auto kind, auto *pts, auto *) {
+                hipLaunchKernelGGL((k_nlb_apply_otf<kind()>), dim3(G, rows), dim3(256), 0, ctx->stream, ctx->S, pts, n, list, slot0, ctx->nlb, ctl);
+            });
+        else
+            ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_nlb_apply<T>), dim3(G, rows), dim3(256), 0, ctx->stream, ctx->S, (const T *)ctx->d_mat, n,
+                                                         ctx->ld, list, slot0, ctx->nlb, ctl));
+        HIP_TRY(hipGetLastError());
+    }
+    return E_OK;
+}
+
+// ornl_descent on the slots slot0 .. slot0 + count - 1 at once.  The control blocks are armed (2-opt phase, round 1) and the
+// slots re-armed as m2_arm does; then sweeps of all live tours -- four between looks at the control blocks, one under a
+// deadline, as m2_run -- and the tours whose descent has ended leave the list.  out: per-slot counters, [count] each
+static int nlb_descent(tspgpu_ctx *ctx, int slot0, int count, double time_left_s, long *tw, long *tm, long *os, long *om, int *nr, bool *late)
+{
+    const double t_end = deadline_of(time_left_s);
+    *late = false;
+    ctx->nlb_tours = count; ctx->nlb_launches = 0; ctx->nlb_max_live = 0;
+    int rc = nlb_ensure(ctx, count);
+    if (rc) return rc;
+    std::vector<NlbCtl> hc((size_t)count);
+    memset(hc.data(), 0, hc.size() * sizeof(NlbCtl));
+    for (NlbCtl &c : hc) c.rounds = 1;
+    HIP_TRY(hipMemcpyAsync(ctx->d_nlb_ctl, hc.data(), hc.size() * sizeof(NlbCtl), hipMemcpyHostToDevice, ctx->stream));
+    hipLaunchKernelGGL(k_rearm, dim3((count + 255) / 256), dim3(256), 0, ctx->stream, ctx->S, slot0, count, -1);
+    HIP_TRY(hipGetLastError());
+    std::vector<int> live((size_t)count);
+    for (int i = 0; i < count; i++) live[i] = slot0 + i;
+    if ((rc = nlb_set_live(ctx, live))) return rc;
+    while (!live.empty()) {
+        if (t_end >= 0 && now_s() >= t_end) { *late = true; break; }
+        const int K = t_end >= 0 ? 1 : 4;
+        ctx->nlb_max_live = std::max(ctx->nlb_max_live, (long)live.size());
+        for (int i = 0; i < K; i++) {
+            if ((rc = nlb_launch_sweep(ctx, slot0, (int)live.size()))) return rc;
+            ctx->nlb_launches++;
+        }
+        if ((rc = ctl_get(ctx, hc.data(), ctx->d_nlb_ctl, (size_t)count))) return rc;
+        size_t k = 0;
+        for (int t : live) if (!hc[t - slot0].stop) live[k++] = t;
+        if (k == live.size()) continue;
+        live.resize(k);
+        if (k && (rc = nlb_set_live(ctx, live))) return rc;
+    }
+    for (int i = 0; i < count; i++) {
+        tw[i] = (long)hc[i].two_opt_sweeps; tm[i] = (long)hc[i].two_opt_moves;
+        os[i] = (long)hc[i].or_sweeps; om[i] = (long)hc[i].or_moves; nr[i] = hc[i].rounds;
+    }
+    return E_OK;
+}
+
+extern "C" {
+
+int tspgpu_tours_local_search_nl(tspgpu_ctx *ctx, int slot0, int count, double time_left_s, long *two_opt_sweeps, long *two_opt_moves,
+                                 long *or_sweeps, long *or_moves, int *rounds)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    hipSetDevice(ctx->device);
+    int rc = ornl_check(ctx);
+    if (rc) return rc;
+    if (slot0 < 0 || count <= 0 || count > ctx->tcap || slot0 > ctx->tcap - count)      // (the range first: a slot past the end is no slot without a tour)
+        return fail(ctx, E_INVALID, "bad slot range: slot0 %d, count %d of %d slots", slot0, count, ctx->tcap);
+    if ((rc = or_batch_args(ctx, slot0, count))) return rc;
+    std::vector<long> tw(count), tm(count), os(count), om(count);
+    std::vector<int> nr(count);
+    bool late = false;
+    if ((rc = nlb_descent(ctx, slot0, count, time_left_s, tw.data(), tm.data(), os.data(), om.data(), nr.data(), &late))) return rc;
+    if (two_opt_sweeps) std::copy(tw.begin(), tw.end(), two_opt_sweeps);
+    if (two_opt_moves) std::copy(tm.begin(), tm.end(), two_opt_moves);
+    if (or_sweeps) std::copy(os.begin(), os.end(), or_sweeps);
+    if (or_moves) std::copy(om.begin(), om.end(), or_moves);
+    if (rounds) std::copy(nr.begin(), nr.end(), rounds);
+    return done_code(late);
+}
+
+int tspgpu_multistart_local_search_nl(tspgpu_ctx *ctx, const int *starts, int nstarts, double time_left_s, int *best_path, double *best_cost,
+                                      int *best_start, long *total_two_opt_sweeps, long *total_two_opt_moves, long *total_or_sweeps,
+                                      long *total_or_moves, double *costs_out)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    if (!best_path || !best_cost || !best_start || nstarts <= 0) return fail(ctx, E_INVALID, "bad argument");
+    hipSetDevice(ctx->device);
+    int rc = ornl_check(ctx);
+    if (rc) return rc;
+    if (ctx->opt_sweep_cap != -1)
+        return fail(ctx, E_INVALID, "TSPGPU_OPT_SWEEP_CAP = %d: the descent over the neighbour lists runs every phase to its end", ctx->opt_sweep_cap);
+    const double t_end = deadline_of(time_left_s);
+    const int chunk = std::min(nstarts, ctx->opt_max_tours);
+    if ((rc = ensure_tours(ctx, chunk))) return rc;
+    double best = DBL_MAX; int arg = -1; long tot[4] = {0, 0, 0, 0};
+    bool late = false;
+    std::vector<int> hs(chunk), nr(chunk);
+    std::vector<long> tw(chunk), tm(chunk), os(chunk), om(chunk);
+    for (int base = 0; base < nstarts && !late; base += chunk) {
+        const int m = std::min(chunk, nstarts - base);
+        for (int i = 0; i < m; i++) hs[i] = starts ? starts[base + i] : base + i;
+        if ((rc = launch_nn(ctx, 0, hs.data(), m))) return rc;
+        if ((rc = init_slots(ctx, 0, m, -1))) return rc;
+        mark_slots(ctx, 0, m, true);
+        const double left = t_end >= 0 ? std::max(0.0, t_end - now_s()) : -1;
+        if ((rc = nlb_descent(ctx, 0, m, left, tw.data(), tm.data(), os.data(), om.data(), nr.data(), &late))) return rc;
+        HIP_TRY(hipMemcpyAsync(ctx->h_costs, ctx->S.cost, (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        int win = -1;
+        for (int i = 0; i < m; i++) {
+            tot[0] += tw[i]; tot[1] += tm[i]; tot[2] += os[i]; tot[3] += om[i];
+            if (costs_out) costs_out[base + i] = ctx->h_costs[i];
+            if (ctx->h_costs[i] < best) { best = ctx->h_costs[i]; win = i; }    // strict <: ties to the earliest entry
+        }
+        if (win >= 0) {
+            arg = hs[win];
+            if ((rc = store_path(ctx, win, best_path, nullptr, nullptr))) return rc;
+        }
+    }
+    *best_cost = best; *best_start = arg;
+    if (total_two_opt_sweeps) *total_two_opt_sweeps = tot[0];
+    if (total_two_opt_moves) *total_two_opt_moves = tot[1];
+    if (total_or_sweeps) *total_or_sweeps = tot[2];
+    if (total_or_moves) *total_or_moves = tot[3];
+    return done_code(late);
 }
 
 } // extern "C"

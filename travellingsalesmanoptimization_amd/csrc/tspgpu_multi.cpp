@@ -229,6 +229,7 @@ struct Local {           // one device's result
     int start = -1;
     long sweeps = 0;
     long moves = 0;      // Or-opt moves (tspgpu_multi_multistart_local_search)
+    long tw_moves = 0, or_sweeps = 0;   // 2-opt moves and Or-opt sweeps (tspgpu_multi_multistart_local_search_nl)
     int done = 0;
     std::vector<int> path;
     std::string err;
@@ -520,6 +521,59 @@ int tspgpu_multi_multistart_local_search(tspgpu_multi *m, const int *starts, int
     *best_start = owner >= 0 ? L[owner].start : -1;
     if (total_two_opt_sweeps) *total_two_opt_sweeps = sweeps;
     if (total_or_moves) *total_or_moves = moves;
+    return late ? E_DEADLINE : E_OK;
+}
+
+int tspgpu_multi_neighbours_build(tspgpu_multi *m, int K)
+{
+    if (!m) return E_UNAVAILABLE;
+    return per_device(m, [&](int i) { return tspgpu_neighbours_build(m->ctx[i], K); });
+}
+
+// tspgpu_multi_multistart_local_search with the batched descent over the neighbour lists (tspgpu_multistart_local_search_nl per device)
+int tspgpu_multi_multistart_local_search_nl(tspgpu_multi *m, const int *starts, int nstarts, double time_left_s, int *best_path,
+                                            double *best_cost, int *best_start, long *total_two_opt_sweeps, long *total_two_opt_moves,
+                                            long *total_or_sweeps, long *total_or_moves)
+{
+    if (!m) return E_UNAVAILABLE;
+    if (!best_path || !best_cost || !best_start || nstarts <= 0) return mfail(m, E_INVALID, "bad argument");
+    const int G = m->G;
+    const int n = (int)tspgpu_info(m->ctx[0], 0);
+    if (n <= 0) return mfail(m, E_PRECOND, "no instance: call tspgpu_multi_set_points / tspgpu_multi_build_costs first");
+    std::vector<Local> L(G);
+    std::vector<std::vector<int>> mine(G);
+    for (long p = 0; p < nstarts; p++) mine[p % G].push_back(starts ? starts[p] : (int)p);   // list entry p -> device p mod G
+    const double t0 = now_s();
+    int rc = per_device(m, [&](int i) {
+        Local &l = L[i];
+        if (mine[i].empty()) return (int)E_OK;
+        l.path.resize(n);
+        int st = -1;
+        l.rc = tspgpu_multistart_local_search_nl(m->ctx[i], mine[i].data(), (int)mine[i].size(), time_left_s, l.path.data(), &l.cost, &st,
+                                                 &l.sweeps, &l.tw_moves, &l.or_sweeps, &l.moves, nullptr);
+        if (l.rc && l.rc != E_DEADLINE) return l.rc;
+        if (st >= 0) {   // position of the device's winner in the caller's list: its first occurrence on this device
+            for (size_t k = 0; k < mine[i].size(); k++)
+                if (mine[i][k] == st) { l.pos = (long)k * G + i; break; }
+            l.start = st;
+        }
+        return l.rc;
+    });
+    m->last_solve_s = now_s() - t0;
+    if (rc) return rc;
+    int owner = -1;
+    long pos = -1;
+    double cost = DBL_MAX;
+    if ((rc = exchange(m, L, n, best_path, &cost, &pos, &owner))) return rc;
+    bool late = false;
+    long tot[4] = {0, 0, 0, 0};
+    for (const Local &l : L) { late |= l.rc == E_DEADLINE; tot[0] += l.sweeps; tot[1] += l.tw_moves; tot[2] += l.or_sweeps; tot[3] += l.moves; }
+    *best_cost = owner >= 0 ? cost : DBL_MAX;
+    *best_start = owner >= 0 ? L[owner].start : -1;
+    if (total_two_opt_sweeps) *total_two_opt_sweeps = tot[0];
+    if (total_two_opt_moves) *total_two_opt_moves = tot[1];
+    if (total_or_sweeps) *total_or_sweeps = tot[2];
+    if (total_or_moves) *total_or_moves = tot[3];
     return late ? E_DEADLINE : E_OK;
 }
 

@@ -193,9 +193,10 @@ __global__ void __launch_bounds__(256) k_m2_sweep_otf(Tours S, const typename Or
 }
 
 // one workgroup of 1024 threads; thread k owns the nodes [k C, k C + C)
-__global__ void __launch_bounds__(1024) k_m2_compact(Tours S, int n, int t, M2Buf B, M2Ctl *ctl)
+// (the body, for the control block of a single descent or of a tour of a batch: tspgpu_nlbatch.inc; cnts: [1024] in LDS)
+template <typename CTL>
+__device__ __forceinline__ void m2_compact_tour(const Tours &S, int n, int t, const M2Buf &B, CTL *ctl, int *cnts)
 {
-    __shared__ int cnts[1024];
     const int tid = threadIdx.x;
     if (ctl->stop) {
         if (tid == 0) ctl->m = 0;
@@ -237,12 +238,19 @@ __global__ void __launch_bounds__(1024) k_m2_compact(Tours S, int n, int t, M2Bu
     if (tid == 1023) ctl->m = cnts[1023];
 }
 
-__global__ void __launch_bounds__(256) k_m2_select(M2Buf B, const M2Ctl *ctl)
+__global__ void __launch_bounds__(1024) k_m2_compact(Tours S, int n, int t, M2Buf B, M2Ctl *ctl)
+{
+    __shared__ int cnts[1024];
+    m2_compact_tour(S, n, t, B, ctl, cnts);
+}
+
+// candidate x of the m against all of them (the body of k_m2_select; blocks at or past m return at once)
+__device__ __forceinline__ void m2_select_tour(const M2Buf &B, int m)
 {
     __shared__ double sd[256];
     __shared__ u64 sk[256];
     __shared__ int si[256], sj[256];
-    const int m = ctl->m, tid = threadIdx.x;
+    const int tid = threadIdx.x;
     if ((int)blockIdx.x * 256 >= m) return;
     const int x = blockIdx.x * 256 + tid;
     const bool live = x < m;
@@ -262,8 +270,30 @@ __global__ void __launch_bounds__(256) k_m2_select(M2Buf B, const M2Ctl *ctl)
     if (live) B.acc[x] = beaten ? 0 : 1;
 }
 
-template <typename T, typename CS>
-__device__ __forceinline__ void m2_apply_tour(const Tours &S, const CS cs, int n, int t, const M2Buf &B, M2Ctl *ctl)
+__global__ void __launch_bounds__(256) k_m2_select(M2Buf B, const M2Ctl *ctl)
+{
+    m2_select_tour(B, ctl->m);
+}
+
+// the close of a sweep (one thread): the slot's cost, last delta and sweep counter, the control block; a sweep that accepted
+// nothing, or the last one of the budget, ends the run.  tspgpu_nlbatch.inc has the form for a tour of a batch
+__device__ __forceinline__ void m2_close(const Tours &S, int t, M2Ctl *ctl, double sum, double mn, int K)
+{
+    const long long budget = ctl->budget;
+    S.cost[t] += sum;
+    S.last_delta[t] = mn;
+    S.nsweeps[t] += 1;
+    ctl->last_k = K;
+    ctl->max_k = max(ctl->max_k, K);
+    ctl->sweeps += 1;
+    ctl->moves += K;
+    bool stop = K == 0;
+    if (budget >= 0) { ctl->budget = budget - 1; stop |= budget - 1 <= 0; }
+    if (stop) { ctl->stop = 1; S.done[t] = 1; }
+}
+
+template <typename T, typename CS, typename CTL>
+__device__ __forceinline__ void m2_apply_tour(const Tours &S, const CS cs, int n, int t, const M2Buf &B, CTL *ctl)
 {
     typedef typename Elem<T>::acc AT;
     __shared__ double rs[256], rm[256];
@@ -282,20 +312,7 @@ __device__ __forceinline__ void m2_apply_tour(const Tours &S, const CS cs, int n
             if (tid < off) { rs[tid] += rs[tid + off]; rm[tid] = fmin(rm[tid], rm[tid + off]); rk[tid] += rk[tid + off]; }
             __syncthreads();
         }
-        if (tid == 0) {
-            const int K = rk[0];
-            const long long budget = ctl->budget;
-            S.cost[t] += rs[0];
-            S.last_delta[t] = rm[0];
-            S.nsweeps[t] += 1;
-            ctl->last_k = K;
-            ctl->max_k = max(ctl->max_k, K);
-            ctl->sweeps += 1;
-            ctl->moves += K;
-            bool stop = K == 0;
-            if (budget >= 0) { ctl->budget = budget - 1; stop |= budget - 1 <= 0; }
-            if (stop) { ctl->stop = 1; S.done[t] = 1; }
-        }
+        if (tid == 0) m2_close(S, t, ctl, rs[0], rm[0], rk[0]);
     }
     int *ord = S.ord + (size_t)t * n, *pos = S.pos + (size_t)t * n, *succ = S.succ + (size_t)t * n;
     AT *dp = dpos_of<AT>(S, t, n), *dnb = dnb_of<AT>(S, t, n);

@@ -111,10 +111,10 @@ __global__ void __launch_bounds__(256) k_ornl_sweep_otf(Tours S, const typename 
     ornl_sweep_start<int>(S, OrPtsCost<KIND>{pts}, n, t, NL, B);
 }
 
-// one workgroup of 1024 threads; thread k owns the nodes [k C, k C + C)
-__global__ void __launch_bounds__(1024) k_ornl_compact(Tours S, int n, int t, M2Buf B, M2Ctl *ctl)
+// one workgroup of 1024 threads; thread k owns the nodes [k C, k C + C) (the body, as m2_compact_tour; cnts: [1024] in LDS)
+template <typename CTL>
+__device__ __forceinline__ void ornl_compact_tour(const Tours &S, int n, int t, const M2Buf &B, CTL *ctl, int *cnts)
 {
-    __shared__ int cnts[1024];
     const int tid = threadIdx.x;
     if (ctl->stop) {
         if (tid == 0) ctl->m = 0;
@@ -152,8 +152,14 @@ __global__ void __launch_bounds__(1024) k_ornl_compact(Tours S, int n, int t, M2
     if (tid == 1023) ctl->m = cnts[1023];
 }
 
-template <typename T, typename CS>
-__device__ __forceinline__ void ornl_apply_tour(const Tours &S, const CS cs, int n, int t, const M2Buf &B, M2Ctl *ctl)
+__global__ void __launch_bounds__(1024) k_ornl_compact(Tours S, int n, int t, M2Buf B, M2Ctl *ctl)
+{
+    __shared__ int cnts[1024];
+    ornl_compact_tour(S, n, t, B, ctl, cnts);
+}
+
+template <typename T, typename CS, typename CTL>
+__device__ __forceinline__ void ornl_apply_tour(const Tours &S, const CS cs, int n, int t, const M2Buf &B, CTL *ctl)
 {
     typedef typename Elem<T>::acc AT;
     __shared__ double rs[ORNL_APPLY_BT], rm[ORNL_APPLY_BT];
@@ -172,20 +178,7 @@ __device__ __forceinline__ void ornl_apply_tour(const Tours &S, const CS cs, int
             if (tid < off) { rs[tid] += rs[tid + off]; rm[tid] = fmin(rm[tid], rm[tid + off]); rk[tid] += rk[tid + off]; }
             __syncthreads();
         }
-        if (tid == 0) {
-            const int K = rk[0];
-            const long long budget = ctl->budget;
-            S.cost[t] += rs[0];
-            S.last_delta[t] = rm[0];
-            S.nsweeps[t] += 1;
-            ctl->last_k = K;
-            ctl->max_k = max(ctl->max_k, K);
-            ctl->sweeps += 1;
-            ctl->moves += K;
-            bool stop = K == 0;
-            if (budget >= 0) { ctl->budget = budget - 1; stop |= budget - 1 <= 0; }
-            if (stop) { ctl->stop = 1; S.done[t] = 1; }
-        }
+        if (tid == 0) m2_close(S, t, ctl, rs[0], rm[0], rk[0]);
     }
     int *ord = S.ord + (size_t)t * n, *pos = S.pos + (size_t)t * n, *succ = S.succ + (size_t)t * n;
     AT *dp = dpos_of<AT>(S, t, n), *dnb = dnb_of<AT>(S, t, n);

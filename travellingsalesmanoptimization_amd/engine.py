@@ -54,7 +54,8 @@ class Engine:
                  "or_block", "or_nch", "or_otf", "or_otf_R",
                  "multi_sweeps", "multi_moves", "multi_max_moves", "multi_r", "multi_block", "multi_nch",
                  "nl_k", "nl_sweeps", "nl_moves", "nl_polish_sweeps", "nl_nodes",
-                 "or_nl_sweeps", "or_nl_moves", "or_nl_max_moves", "or_nl_rounds", "or_nl_starts"]
+                 "or_nl_sweeps", "or_nl_moves", "or_nl_max_moves", "or_nl_rounds", "or_nl_starts",
+                 "nl_batch_tours", "nl_batch_launches", "nl_batch_max_live", "nl_batch_wgs"]
         return {k: int(self.L.tspgpu_info(self.ctx, i)) for i, k in enumerate(names)}
 
     # ---- instance
@@ -300,6 +301,20 @@ class Engine:
         return {"path": best, "cost": c.value, "start": s.value, "two_opt_sweeps": sw.value, "or_moves": om.value,
                 "costs": costs, "rc": rc}
 
+    def multistart_local_search_nl(self, starts=None, time_left_s=-1.0):
+        """NN + the descent over the neighbour lists from every start, batched (neighbours_build first) ->
+        dict(path, cost, start, two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, costs, rc); costs[i] is the final cost of list entry i."""
+        p, m, keep = self._starts(starts, self.n)
+        best = np.empty(self.n, dtype=np.int32)
+        c, s = C.c_double(), C.c_int()
+        tw, tm, os_, om = C.c_long(), C.c_long(), C.c_long(), C.c_long()
+        costs = np.full(m, np.nan, dtype=np.float64)
+        rc = self._ck(self.L.tspgpu_multistart_local_search_nl(self.ctx, p, m, float(time_left_s), best, C.byref(c), C.byref(s),
+                                                               C.byref(tw), C.byref(tm), C.byref(os_), C.byref(om), costs.ctypes.data),
+                      ok=(T_OK, DEADLINE_EXCEEDED))
+        return {"path": best, "cost": c.value, "start": s.value, "two_opt_sweeps": tw.value, "two_opt_moves": tm.value,
+                "or_sweeps": os_.value, "or_moves": om.value, "costs": costs, "rc": rc}
+
     # ---- device-resident
     def tour_load(self, slot, path):
         self._ck(self.L.tspgpu_tour_load(self.ctx, slot, np.ascontiguousarray(path, np.int32)))
@@ -369,6 +384,17 @@ class Engine:
                                                          C.byref(om), C.byref(nr)), ok=(T_OK, DEADLINE_EXCEEDED))
         return {"two_opt_sweeps": tw.value, "two_opt_moves": tm.value, "or_sweeps": os_.value, "or_moves": om.value, "rounds": nr.value,
                 "rc": rc}
+
+    def tours_local_search_nl(self, slot0, count, time_left_s=-1.0):
+        """the descent of tour_local_search_nl on slots slot0 .. slot0+count-1 at once ->
+        dict(two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds: arrays of count entries, rc)."""
+        count = int(count)
+        tw, tm, os_, om = (np.zeros(max(count, 0), dtype=np.int64) for _ in range(4))
+        nr = np.zeros(max(count, 0), dtype=np.int32)
+        rc = self._ck(self.L.tspgpu_tours_local_search_nl(self.ctx, int(slot0), count, float(time_left_s), tw.ctypes.data, tm.ctypes.data,
+                                                          os_.ctypes.data, om.ctypes.data, nr.ctypes.data),
+                      ok=(T_OK, DEADLINE_EXCEEDED))
+        return {"two_opt_sweeps": tw, "two_opt_moves": tm, "or_sweeps": os_, "or_moves": om, "rounds": nr, "rc": rc}
 
     def time_or_nl_sweep(self, slot, reps):
         ms = C.c_float()
@@ -502,6 +528,23 @@ class MultiEngine:
                                                                   C.byref(sw), C.byref(om)),
                       ok=(T_OK, DEADLINE_EXCEEDED))
         return {"path": best, "cost": c.value, "start": s.value, "two_opt_sweeps": sw.value, "or_moves": om.value, "rc": rc}
+
+    def neighbours_build(self, K):
+        """Engine.neighbours_build on every device's context"""
+        self._ck(self.L.tspgpu_multi_neighbours_build(self.m, int(K)))
+
+    def multistart_local_search_nl(self, starts=None, time_left_s=-1.0):
+        """Engine.multistart_local_search_nl over every device ->
+        dict(path, cost, start, two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rc)."""
+        p, m, keep = Engine._starts(starts, self.n)
+        best = np.empty(self.n, dtype=np.int32)
+        c, s = C.c_double(), C.c_int()
+        tw, tm, os_, om = C.c_long(), C.c_long(), C.c_long(), C.c_long()
+        rc = self._ck(self.L.tspgpu_multi_multistart_local_search_nl(self.m, p, m, float(time_left_s), best, C.byref(c), C.byref(s),
+                                                                     C.byref(tw), C.byref(tm), C.byref(os_), C.byref(om)),
+                      ok=(T_OK, DEADLINE_EXCEEDED))
+        return {"path": best, "cost": c.value, "start": s.value, "two_opt_sweeps": tw.value, "two_opt_moves": tm.value,
+                "or_sweeps": os_.value, "or_moves": om.value, "rc": rc}
 
     def nn_all(self, starts=None, time_left_s=-1.0):
         """h_Greedy_iterative (heuristics.c:34-72) over every device -> (best_path, best_cost, best_start, done, rc)."""

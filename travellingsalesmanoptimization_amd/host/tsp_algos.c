@@ -783,6 +783,56 @@ ERROR_CODE h_greedy_local_search(void)
     return e;
 }
 
+/* TSP_EVERY_START_NEIGHBOURS=K, K in 1..16 (tsp_run_algorithm): h_greedy_2opt with the descent over neighbour lists of K nodes
+ * from EVERY start (tspgpu_multistart_local_search_nl: the starts of a chunk descend together, every launch serves all of them
+ * that still descend).  It takes a matrix-free instance as it is; the incumbent, starting_node and the deadline are handled as
+ * in h_greedy_2opt.  An instance the descent does not take (fewer than 8 nodes, an asymmetric matrix) gets a warning and the
+ * plain h_greedy_2opt. */
+static int every_start_nl_k = 0;
+
+ERROR_CODE h_greedy_local_search_nl(void)
+{
+    log_info("running All Nearest Neighbour + neighbour-list 2OPT + Or-opt");
+    if (past_deadline()) { log_warn("time limit exceeded in greedy neighbour-list local search"); return DEADLINE_EXCEEDED; }
+    tspgpu_ctx *g = tsp_gpu();
+    if (!g) return UNAVAILABLE;
+    struct tspgpu_multi *m = tsp_gpu_multi();
+    tsp_solution s;
+    tsp_init_solution(tsp_inst.nnodes, &s);
+    int start = -1;
+    long sweeps = 0, two_opt_moves = 0, or_sweeps = 0, moves = 0;
+    const double t0 = utils_timeelapsed(&tsp_inst.c);
+    /* the lists belong to the costs in place: built when the context holds none of that length */
+    const int kp = every_start_nl_k < tsp_inst.nnodes - 1 ? every_start_nl_k : tsp_inst.nnodes - 1;
+    int rc = m ? tspgpu_multi_neighbours_build(m, every_start_nl_k)
+               : tspgpu_info(g, 42) == kp ? 0 : tspgpu_neighbours_build(g, every_start_nl_k);
+    if (rc == 0)
+        rc = m ? tspgpu_multi_multistart_local_search_nl(m, NULL, tsp_inst.nnodes, time_left(), s.path, &s.cost, &start, &sweeps,
+                                                         &two_opt_moves, &or_sweeps, &moves)
+               : tspgpu_multistart_local_search_nl(g, NULL, tsp_inst.nnodes, time_left(), s.path, &s.cost, &start, &sweeps, &two_opt_moves,
+                                                   &or_sweeps, &moves, NULL);
+    ERROR_CODE e = from_rc(rc);
+    if (or_opt_refusal(e)) {
+        log_warn("TSP_EVERY_START_NEIGHBOURS=%d: %s; running the plain multi-start", every_start_nl_k,
+                 m ? tspgpu_multi_last_error(m) : tspgpu_last_error(g));
+        free(s.path); free(s.comp);
+        return h_greedy_2opt();
+    }
+    multi_stats("h_greedy_local_search_nl", m, tsp_inst.nnodes, sweeps + or_sweeps, utils_timeelapsed(&tsp_inst.c) - t0, s.cost);
+    if (rc != 0 && rc != DEADLINE_EXCEEDED) {
+        log_error("tspgpu_multistart_local_search_nl: %s", m ? tspgpu_multi_last_error(m) : tspgpu_last_error(g));
+    } else {
+        ERROR_CODE u = tsp_update_best_solution(&s);
+        if (!err_ok(u)) log_error("code %d : Error in neighbour-list local search solution update", u);
+        if (rc == 0) tsp_inst.starting_node = tsp_inst.nnodes - 1;
+        else log_warn("time limit exceeded in greedy neighbour-list local search");
+        log_debug("best start %d, cost %f, %ld 2-opt sweeps (%ld moves), %ld Or-opt sweeps (%ld moves)", start, s.cost, sweeps, two_opt_moves,
+                  or_sweeps, moves);
+    }
+    free(s.path); free(s.comp);
+    return e;
+}
+
 /* TSP_OR_OPT (1 = polish the incumbent after the heuristic), TSP_OR_OPT_EVERY_START (1 = -alg 2OPT_GREEDY runs
  * h_greedy_local_search) and TSP_OR_OPT_MATRIX_FREE (1 = the TSP_OR_OPT polish also runs on a matrix-free instance,
  * TSPGPU_OPT_OR_MATRIX_FREE), TSP_2OPT_MULTI (1 = ref_2opt, and with it every iteration of mh_VNS's host loop, runs the
@@ -823,6 +873,23 @@ ERROR_CODE tsp_run_algorithm(void)
         fprintf(stderr, "tsp: TSP_OR_OPT_NEIGHBOURS=%d and TSP_2OPT_NEIGHBOURS=%d: the two list lengths must be equal\n", or_nl_k, nl_k);
         return INVALID_ARGUMENT;
     }
+    /* TSP_EVERY_START_NEIGHBOURS=K (env_neighbours): -alg 2OPT_GREEDY runs h_greedy_local_search_nl over lists of K nodes */
+    const int es_k = env_neighbours("TSP_EVERY_START_NEIGHBOURS");
+    if (es_k < 0) return INVALID_ARGUMENT;
+    if (es_k && ((nl_k && nl_k != es_k) || (or_nl_k && or_nl_k != es_k))) {
+        fprintf(stderr, "tsp: TSP_EVERY_START_NEIGHBOURS=%d and TSP_%s_NEIGHBOURS=%d: the list lengths must be equal\n", es_k,
+                nl_k && nl_k != es_k ? "2OPT" : "OR_OPT", nl_k && nl_k != es_k ? nl_k : or_nl_k);
+        return INVALID_ARGUMENT;
+    }
+    if (es_k && every_start) {
+        fprintf(stderr, "tsp: TSP_EVERY_START_NEIGHBOURS=%d and TSP_OR_OPT_EVERY_START=1: one descent from every start, not both\n", es_k);
+        return INVALID_ARGUMENT;
+    }
+    every_start_nl_k = es_k;
+    if (es_k && tsp_inst.alg == ALG_2OPT_GREEDY)
+        log_warn("TSP_EVERY_START_NEIGHBOURS=%d: every start runs the descent over the neighbour lists; results differ from the reference's trajectory",
+                 es_k);
+    else if (es_k) log_warn("TSP_EVERY_START_NEIGHBOURS=%d has no effect without -alg 2OPT_GREEDY", es_k);
     or_opt_nl_k = polish > 0 ? or_nl_k : 0;
     if (or_nl_k && !polish) log_warn("TSP_OR_OPT_NEIGHBOURS=%d has no effect without TSP_OR_OPT=1", or_nl_k);
     two_opt_multi_on = multi;
@@ -837,7 +904,7 @@ ERROR_CODE tsp_run_algorithm(void)
     switch (tsp_inst.alg) {
     case ALG_GREEDY: e = h_Greedy(); break;
     case ALG_GREEDY_ITER: e = h_Greedy_iterative(); break;
-    case ALG_2OPT_GREEDY: e = every_start ? h_greedy_local_search() : h_greedy_2opt(); break;
+    case ALG_2OPT_GREEDY: e = es_k ? h_greedy_local_search_nl() : every_start ? h_greedy_local_search() : h_greedy_2opt(); break;
     case ALG_TABU_SEARCH: e = mh_TabuSearch(); break;
     case ALG_VNS: e = mh_VNS(); break;
     case ALG_EXTRAMILEAGE: e = h_ExtraMileage(); break;

@@ -160,6 +160,7 @@ ERROR_CODE tabu_make_move(int *prev, tsp_solution *solution, int bestCase, int i
 
 /* ---- src/main.c ------------------------------------------------------------------ */
 ERROR_CODE h_greedy_local_search(void);                      /* extension: h_greedy_2opt with the 2-opt + Or-opt descent from every start (TSP_OR_OPT_EVERY_START=1) */
+ERROR_CODE h_greedy_local_search_nl(void);                   /* extension: h_greedy_2opt with the descent over the neighbour lists from every start (TSP_EVERY_START_NEIGHBOURS=K) */
 ERROR_CODE tsp_or_opt_polish(tsp_solution *solution);         /* extension: 2-opt + Or-opt descent on the device (TSP_OR_OPT=1) */
 ERROR_CODE tsp_run_algorithm(void);                          /* main.c:4-87 (heuristic algorithms only) */
 
