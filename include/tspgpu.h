@@ -83,7 +83,9 @@ enum {
                                    in ONE launch with the rows streamed and the tour state kept on the chip (k_str2opt, one
                                    workgroup per CU, one grid-wide exchange per sweep): 0 never, 1 (default) where it applies
                                    -- falls back to one launch per sweep when the grid cannot be co-resident --, 2 or fail with
-                                   code 8 (and used from n = 1024 up) */
+                                   code 8 (and used from n = 1024 up).  The LDS-resident descent is tried first: 2 forces this
+                                   kernel only together with TSPGPU_OPT_PERSIST = 0; with TSPGPU_OPT_PERSIST = 1 or 2 an instance
+                                   the LDS-resident kernel takes runs there, and tspgpu_info 24 then reads 0 */
     TSPGPU_OPT_PERSIST_WINDOW = 18 /* rows of that kernel: 0 auto (whole rows where they fit the chip's LDS, else the half
                                    window of n/2 cells ahead of the workgroup's own edges), 1 half-window rows wherever they
                                    apply, 2 whole rows only */,
@@ -325,7 +327,9 @@ int  tspgpu_multi_nn_all(tspgpu_multi *m, const int *starts, int nstarts, double
 
 /* Tour slots: the slot array grows on demand and keeps what the existing slots hold; a slot holds a tour once
  * something was loaded / built / copied into it, and until the next tspgpu_build_costs / tspgpu_set_costs (its edge
- * costs belong to the matrix).  Slot entry points answer FAILED_PRECONDITION (9) for a slot that holds none.
+ * costs belong to the matrix).  Slot entry points answer FAILED_PRECONDITION (9) for a slot that holds none -- a slot the
+ * array has not grown to yet included (tspgpu_set_points and a tspgpu_set_costs of another n start the array empty) --
+ * and INVALID_ARGUMENT (3) for a negative slot.
  * The host-array entry points above and the multi-start entry points use slots from 0 upwards as scratch. */
 /* upload a successor array into tour slot `slot` */
 int tspgpu_tour_load(tspgpu_ctx *ctx, int slot, const int *path);
@@ -356,7 +360,9 @@ int tspgpu_time_or_sweep(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean);
  * pair found there (delta 0, a = b = 0: nothing improving in this part); after the ranks have
  * agreed on the minimum of (delta, a, b) -- one MIN all-reduce -- each applies it with
  * tspgpu_tour_apply_move (refinment.c:74-86,95-114), which also counts the sweep; a delta >= 0
- * marks the slot as locally optimal.  Symmetric matrices only. */
+ * marks the slot as locally optimal.  Both take the slot as it stands, whatever ran on it before: a sweep cap that an
+ * earlier call reached (tspgpu_tour_two_opt with max_sweeps, ...) or a local optimum it found does not hold them back.
+ * Symmetric matrices only. */
 int tspgpu_tour_sweep_part(tspgpu_ctx *ctx, int slot, int part, int nparts, double *delta, int *a, int *b);
 int tspgpu_tour_apply_move(tspgpu_ctx *ctx, int slot, int a, int b, double delta);
 /* fetch slot's successor array / cost / last delta */
@@ -444,7 +450,8 @@ int tspgpu_time_multi_sweep(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean)
  * passed 4 (with a valid tour and its cost), more accepted moves than `cap` in _once 8 (nothing applied).
  * The lists (12 bytes per entry: node and weight) stay on the device and are allocated all or none.
  * tspgpu_info: 42 K' in effect (0: no lists), 43 / 44 sweeps / moves of the last neighbour-list phase (or single sweep),
- * 45 sweeps of the last polish phase, 46 nodes per workgroup of the candidate sweep. */
+ * 45 sweeps of the polish behind that phase (0: it had none -- only tspgpu_two_opt_nl polishes), 46 nodes per workgroup of the
+ * candidate sweep. */
 /* K in 1..16 builds the lists of the cost source in place; 0 drops them; any other K: 3 */
 int tspgpu_neighbours_build(tspgpu_ctx *ctx, int K);
 /* the lists, row v at nodes[v * K'] .. ; weights (may be NULL) the costs c[v][nodes[..]] */

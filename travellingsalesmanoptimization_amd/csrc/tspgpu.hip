@@ -3069,6 +3069,13 @@ __global__ void k_rearm(Tours S, int slot0, int count, int cap)
     if (i < count) { S.done[slot0 + i] = 0; S.nsweeps[slot0 + i] = 0; S.cap_sweeps[slot0 + i] = cap; }
 }
 
+// a slot that an earlier call left finished or at its sweep cap takes part again, its sweep count kept (the sharded sweep's
+// two entry points: the caller decides when the descent ends)
+__global__ void k_reopen(Tours S, int slot)
+{
+    S.done[slot] = 0; S.cap_sweeps[slot] = -1;
+}
+
 // the masked form: only the listed slots (a batch descent re-arms the tours still in it; a finished tour keeps done = 1)
 __global__ void k_rearm_list(Tours S, const int *__restrict__ list, int count, int cap)
 {
@@ -3441,8 +3448,9 @@ static void mark_slots(tspgpu_ctx *ctx, int slot0, int count, bool valid)
 // a slot entry point was handed `slot`: it must exist and hold a tour
 static int need_slot(tspgpu_ctx *ctx, int slot)
 {
-    if (slot < 0 || slot >= ctx->tcap) return fail(ctx, E_INVALID, "slot %d outside [0,%d)", slot, ctx->tcap);
-    if (!ctx->slot_valid[slot]) return fail(ctx, E_PRECOND, "slot %d holds no tour (load, build or copy one into it first)", slot);
+    if (slot < 0) return fail(ctx, E_INVALID, "slot %d is negative", slot);
+    // (the slot array grows on demand and a new instance starts it empty: a slot past its end is a slot nothing was put into)
+    if (slot >= ctx->tcap || !ctx->slot_valid[slot]) return fail(ctx, E_PRECOND, "slot %d holds no tour (load, build or copy one into it first)", slot);
     return E_OK;
 }
 
@@ -3452,6 +3460,8 @@ static int new_instance(tspgpu_ctx *ctx, int n)
     if (n > 131072) return fail(ctx, E_INVALID, "n = %d: at most 131072 nodes", n);
     free_matrix(ctx);
     free_tours(ctx);
+    free_grid(ctx);            // the grid is the old points' (tspgpu_set_points builds the new one)
+    ctx->grid_max_occ = 0;
     ctx->n = n;
     ctx->ld = (n + 31) & ~31; // rows 128-byte aligned for both element kinds
     ctx->have_points = false;
@@ -3697,6 +3707,7 @@ static int make_plan(tspgpu_ctx *ctx, int ntours)
         if (G > ctx->S.pstride) return fail(ctx, E_INTERNAL, "partial stride %d < %d workgroups", ctx->S.pstride, G);
         ctx->plan_kernel = 4; ctx->plan_G = G; ctx->plan_P = P; ctx->plan_BT = 256; ctx->plan_NCH = 0; ctx->plan_D = 0;
         ctx->plan_T = ntours; ctx->plan_lds = 0;
+        ctx->plan_pipe2 = ctx->plan_pipe2_sweep = false; ctx->plan_lds_fused = 0;   // (a matrix plan's, if the context had one before)
         return E_OK;
     }
     // resident sweep: all P+1 (<= 9) rows of a run in LDS at once.  One chunk per thread for
@@ -4534,18 +4545,19 @@ static int run_sweeps(tspgpu_ctx *ctx, int slot0, int ntours, bool tabu, long ma
     // One launch per sweep pays in the latency-bound regime (a few tours in flight: the apply
     // launch is ~30 % of an iteration); in a large batch the separate apply launch serves every
     // tour at once and the leaner sweep wins (measured 7.0e11 vs 5.0e11 evals/s at 64 tours).
+    // "how the last descent ran" (tspgpu_info 15, 20, 21, 24): all of it is this call's, whichever branch below returns
     ctx->lp_used = false;
+    ctx->sp_used = false;
+    ctx->lp_handed = false;
     // (an explicit kernel or launch-structure choice -- TSPGPU_OPT_KERNEL / _FUSED -- keeps to that choice)
     if (!tabu && ntours == 1 && (ctx->opt_persist == 2 || (ctx->opt_persist == 1 && ctx->opt_kernel == 0 && ctx->opt_fused == 1))) {
         bool ran = false;
-        ctx->lp_handed = false;
         const int rc = run_persist(ctx, slot0, &time_left_s, deadline_hit, &ran);     // (half way handed over: time_left_s = what is left)
         if (rc) return rc;
         if (ran) return E_OK;
         if (ctx->lp_handed) return run_rebased(ctx, slot0, max_iters, time_left_s, deadline_hit);
         if (ctx->opt_persist == 2) return fail(ctx, E_EXHAUSTED, "the LDS-resident descent does not apply (uint16 cells, n in [64, ~5400], one idle chip)");
     }
-    ctx->sp_used = false;
     bool stream = !tabu && ntours == 1 && ctx->opt_stream == 2;
     if (!tabu && ntours == 1 && ctx->opt_stream == 1 && ctx->opt_persist == 1 && ctx->opt_kernel == 0 && ctx->opt_fused == 1) {
         // automatic: where the LDS-resident kernels do not take the instance
@@ -5666,6 +5678,7 @@ int tspgpu_tour_sweep_part(tspgpu_ctx *ctx, int slot, int part, int nparts, doub
     const int g_lo = (int)((long)part * G / nparts), g_hi = (int)((long)(part + 1) * G / nparts);
     *delta = 0.0; *a = 0; *b = 0;
     if (g_hi <= g_lo) return E_OK;
+    hipLaunchKernelGGL(k_reopen, dim3(1), dim3(1), 0, ctx->stream, ctx->S, slot);     // (a finished slot's sweep would leave its partials as they were)
     if ((rc = launch_sweep(ctx, slot, 1, false, g_lo, g_hi - g_lo))) return rc;
     std::vector<Partial> h((size_t)(g_hi - g_lo));
     HIP_TRY(hipMemcpyAsync(h.data(), ctx->S.partial + (size_t)slot * ctx->S.pstride + g_lo, h.size() * sizeof(Partial),
@@ -5691,6 +5704,7 @@ int tspgpu_tour_apply_move(tspgpu_ctx *ctx, int slot, int a, int b, double delta
     if ((rc = ensure_plan(ctx, 1, false))) return rc;
     const int G = ctx->plan_G;
     const u64 key = delta < TWO_OPT_EPS ? (a < b ? ((u64)(unsigned)a << 32) | (unsigned)b : ((u64)(unsigned)b << 32) | (unsigned)a) : 0;
+    hipLaunchKernelGGL(k_reopen, dim3(1), dim3(1), 0, ctx->stream, ctx->S, slot);     // (k_apply leaves a finished slot alone)
     hipLaunchKernelGGL(k_set_move, dim3((G + 255) / 256), dim3(256), 0, ctx->stream, ctx->S, slot, G, delta < TWO_OPT_EPS ? delta : 0.0, key);
     HIP_TRY(hipGetLastError());
     if ((rc = launch_apply(ctx, slot, 1, false, false))) return rc;
@@ -6476,7 +6490,8 @@ static int m2_arm(tspgpu_ctx *ctx, int slot, long budget)
 
 static void m2_record(tspgpu_ctx *ctx, const M2Ctl &C, M2Kind kind = M2_FULL)
 {
-    if (kind == M2_NL) { ctx->nl_sweeps = (long)C.sweeps; ctx->nl_moves = (long)C.moves; }
+    // (a phase's polish is counted behind it, tspgpu_two_opt_nl: until then the phase has none)
+    if (kind == M2_NL) { ctx->nl_sweeps = (long)C.sweeps; ctx->nl_moves = (long)C.moves; ctx->nl_polish_sweeps = 0; }
     else if (kind == M2_ORNL) { ctx->ornl_sweeps = (long)C.sweeps; ctx->ornl_moves = (long)C.moves; ctx->ornl_max_k = C.max_k; }
     else { ctx->m2_sweeps = (long)C.sweeps; ctx->m2_moves = (long)C.moves; ctx->m2_max_k = C.max_k; }
 }
