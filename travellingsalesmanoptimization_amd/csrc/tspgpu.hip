@@ -3207,9 +3207,10 @@ struct tspgpu_ctx {
 
     // Or-opt (tspgpu_oropt.inc)
     OrCtl *d_or = nullptr;     // control block, allocated on first use
-    // ... over a batch of tours: one control block per slot, the list of slots a launch works on (device, and its pinned staging)
+    // ... over a batch of tours: one control block per slot
     OrCtl *d_or_ctl = nullptr;
-    int *d_or_live = nullptr, *h_or_live = nullptr;
+    // the list of slots a launch of a batched descent works on (device, and its pinned staging): [tcap], either family's
+    int *d_live = nullptr, *h_live = nullptr;
     int or_batch_R = 0;        // positions per sweep workgroup in the first Or-opt round of the last batched descent
     // ... in matrix-free mode (k_oropt_sweep_otf): single tours only
     int opt_or_otf = 0;        // TSPGPU_OPT_OR_MATRIX_FREE: 0 refuse Or-opt in matrix-free mode (code 12), 1 run it from the points
@@ -3230,10 +3231,9 @@ struct tspgpu_ctx {
     long ornl_sweeps = 0, ornl_moves = 0, ornl_max_k = 0;
     int ornl_rounds = 0;       // rounds of the last tspgpu_local_search_nl
     // batched neighbour-list descent (tspgpu_nlbatch.inc): the candidate arrays and a control block per slot of a range of nlb_cap
-    // slots, the list of live slots (device, and its pinned staging); all of them allocated at the first batched call, or none
+    // slots; all of them allocated at the first batched call, or none
     M2Buf nlb{};
     NlbCtl *d_nlb_ctl = nullptr;
-    int *d_nlb_live = nullptr, *h_nlb_live = nullptr;
     int nlb_cap = 0;
     long nlb_tours = 0, nlb_launches = 0, nlb_max_live = 0;     // the last batched descent: tours, sweeps launched, most tours in one
 
@@ -3317,10 +3317,10 @@ static void free_tour_scratch(tspgpu_ctx *ctx)
     if (ctx->h_status) hipHostFree(ctx->h_status);
     if (ctx->h_costs) hipHostFree(ctx->h_costs);
     if (ctx->d_or_ctl) hipFree(ctx->d_or_ctl);
-    if (ctx->d_or_live) hipFree(ctx->d_or_live);
-    if (ctx->h_or_live) hipHostFree(ctx->h_or_live);
+    if (ctx->d_live) hipFree(ctx->d_live);
+    if (ctx->h_live) hipHostFree(ctx->h_live);
     ctx->d_starts = ctx->d_caps = nullptr; ctx->h_status = nullptr; ctx->h_costs = nullptr;
-    ctx->d_or_ctl = nullptr; ctx->d_or_live = ctx->h_or_live = nullptr;
+    ctx->d_or_ctl = nullptr; ctx->d_live = ctx->h_live = nullptr;
 }
 
 static void free_grid(tspgpu_ctx *ctx)
@@ -3340,12 +3340,10 @@ static void free_m2(tspgpu_ctx *ctx)
 
 static void free_nlb(tspgpu_ctx *ctx)
 {
-    void *ptrs[] = {ctx->nlb.raw_d, ctx->nlb.raw_b, ctx->nlb.d, ctx->nlb.a, ctx->nlb.b, ctx->nlb.i, ctx->nlb.j, ctx->nlb.acc, ctx->d_nlb_ctl,
-                    ctx->d_nlb_live};
+    void *ptrs[] = {ctx->nlb.raw_d, ctx->nlb.raw_b, ctx->nlb.d, ctx->nlb.a, ctx->nlb.b, ctx->nlb.i, ctx->nlb.j, ctx->nlb.acc, ctx->d_nlb_ctl};
     for (void *p : ptrs) if (p) hipFree(p);
-    if (ctx->h_nlb_live) hipHostFree(ctx->h_nlb_live);
     memset(&ctx->nlb, 0, sizeof ctx->nlb);
-    ctx->d_nlb_ctl = nullptr; ctx->d_nlb_live = ctx->h_nlb_live = nullptr;
+    ctx->d_nlb_ctl = nullptr;
     ctx->nlb_cap = 0;
 }
 
@@ -3433,8 +3431,8 @@ static int ensure_tours(tspgpu_ctx *ctx, int want)
     HIP_TRY(hipHostMalloc(&ctx->h_status, T * 4 * 2));
     HIP_TRY(hipHostMalloc(&ctx->h_costs, T * 8));
     HIP_TRY(hipMalloc(&ctx->d_or_ctl, T * sizeof(OrCtl)));     // (armed at the start of every batched Or-opt phase)
-    HIP_TRY(hipMalloc(&ctx->d_or_live, T * 4));
-    HIP_TRY(hipHostMalloc(&ctx->h_or_live, T * 4));
+    HIP_TRY(hipMalloc(&ctx->d_live, T * 4));
+    HIP_TRY(hipHostMalloc(&ctx->h_live, T * 4));
     ctx->tcap = want;
     ctx->slot_valid.resize(T, 0);
     return E_OK;
@@ -3451,6 +3449,16 @@ static int need_slot(tspgpu_ctx *ctx, int slot)
     if (slot < 0) return fail(ctx, E_INVALID, "slot %d is negative", slot);
     // (the slot array grows on demand and a new instance starts it empty: a slot past its end is a slot nothing was put into)
     if (slot >= ctx->tcap || !ctx->slot_valid[slot]) return fail(ctx, E_PRECOND, "slot %d holds no tour (load, build or copy one into it first)", slot);
+    return E_OK;
+}
+
+// the slot list of the next launches of a batched descent: staged in pinned memory, so the stream must have drained the
+// previous list first
+static int set_live(tspgpu_ctx *ctx, const std::vector<int> &list)
+{
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    memcpy(ctx->h_live, list.data(), list.size() * 4);
+    HIP_TRY(hipMemcpyAsync(ctx->d_live, ctx->h_live, list.size() * 4, hipMemcpyHostToDevice, ctx->stream));
     return E_OK;
 }
 
@@ -4891,6 +4899,102 @@ static int launch_nn(tspgpu_ctx *ctx, int slot0, const int *h_starts, int count)
     return E_OK;
 }
 
+// ---- what the entry points of every move family share ------------------------------------------------------------------
+
+// what a descent did on one tour: 2-opt sweeps and moves, Or-opt sweeps and moves, rounds (a family without one leaves it 0)
+struct Descent {
+    long tw = 0, tm = 0, os = 0, om = 0;
+    int nr = 0;
+    void operator+=(const Descent &d) { tw += d.tw; tm += d.tm; os += d.os; om += d.om; nr += d.nr; }
+};
+
+// D[0 .. count) to the caller's arrays, each of them optional
+static void descent_out(const Descent *D, int count, long *tw, long *tm, long *os, long *om, int *nr)
+{
+    for (int i = 0; i < count; i++) {
+        if (tw) tw[i] = D[i].tw;
+        if (tm) tm[i] = D[i].tm;
+        if (os) os[i] = D[i].os;
+        if (om) om[i] = D[i].om;
+        if (nr) nr[i] = D[i].nr;
+    }
+}
+
+// Host tour in, host tour out, for an entry point that has checked its arguments: the family's check, the tour into slot 0
+// (load_path recomputes its cost, refinment.c:6-9; keep_cost: the caller's running cost instead, as ref_2opt_once),
+// body(&late), the tour and its cost back.
+template <typename B> static int with_host_tour(tspgpu_ctx *ctx, int *path, double *cost, bool keep_cost, int (*check)(tspgpu_ctx *), B &&body)
+{
+    hipSetDevice(ctx->device);
+    int rc = check(ctx);
+    if (rc) return rc;
+    if ((rc = load_path(ctx, 0, path, -1))) return rc;
+    if (keep_cost) HIP_TRY(hipMemcpyAsync(ctx->S.cost, cost, 8, hipMemcpyHostToDevice, ctx->stream));
+    bool late = false;
+    if ((rc = body(&late))) return rc;
+    if ((rc = store_path(ctx, 0, path, cost, nullptr))) return rc;
+    return done_code(late);
+}
+
+// the same on a slot that must hold a tour: the family's check, the slot's, body(&late)
+template <typename B> static int with_slot(tspgpu_ctx *ctx, int slot, int (*check)(tspgpu_ctx *), B &&body)
+{
+    hipSetDevice(ctx->device);
+    int rc = check(ctx);
+    if (rc) return rc;
+    if ((rc = need_slot(ctx, slot))) return rc;
+    bool late = false;
+    if ((rc = body(&late))) return rc;
+    return done_code(late);
+}
+
+struct MultiStart {
+    Descent total;          // summed over every start that was processed
+    int m_last = 0;         // tours of the last chunk processed: they are still in slots 0 .. m_last - 1
+};
+
+// The multi-start of every family: the start list (nullptr: nodes 0 .. nstarts - 1) in chunks of TSPGPU_OPT_MAX_TOURS tours.
+// Per chunk of m: the nearest-neighbour tours into slots 0 .. m - 1, their edge costs with sweep cap `cap`,
+// descend(m, time left, &late, Descent[m]) -- the family's descent over those slots, the only thing a family supplies --, the
+// costs back, the incumbent's tour stored.  A chunk in which the deadline strikes is the last one; it still counts.
+template <typename F>
+static int multistart(tspgpu_ctx *ctx, const int *starts, int nstarts, double time_left_s, int cap, int *best_path, double *best_cost,
+                      int *best_start, double *costs_out, MultiStart *out, F &&descend)
+{
+    const double t_end = deadline_of(time_left_s);
+    const int chunk = std::min(nstarts, ctx->opt_max_tours);
+    int rc = ensure_tours(ctx, chunk);
+    if (rc) return rc;
+    double best = DBL_MAX; int arg = -1;
+    bool late = false;
+    std::vector<int> hs(chunk);
+    std::vector<Descent> D(chunk);
+    for (int base = 0; base < nstarts && !late; base += chunk) {
+        const int m = std::min(chunk, nstarts - base);
+        for (int i = 0; i < m; i++) hs[i] = starts ? starts[base + i] : base + i;
+        if ((rc = launch_nn(ctx, 0, hs.data(), m))) return rc;
+        if ((rc = init_slots(ctx, 0, m, cap))) return rc;
+        mark_slots(ctx, 0, m, true);
+        const double left = t_end >= 0 ? std::max(0.0, t_end - now_s()) : -1;
+        if ((rc = descend(m, left, &late, D.data()))) return rc;
+        HIP_TRY(hipMemcpyAsync(ctx->h_costs, ctx->S.cost, (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        int win = -1;
+        for (int i = 0; i < m; i++) {
+            out->total += D[i];
+            if (costs_out) costs_out[base + i] = ctx->h_costs[i];
+            if (ctx->h_costs[i] < best) { best = ctx->h_costs[i]; win = i; }    // strict <, tsp.c:671: ties to the earliest entry
+        }
+        if (win >= 0) {
+            arg = hs[win];
+            if ((rc = store_path(ctx, win, best_path, nullptr, nullptr))) return rc;
+        }
+        out->m_last = m;
+    }
+    *best_cost = best; *best_start = arg;
+    return done_code(late);
+}
+
 // ===========================================================================
 // C ABI
 // ===========================================================================
@@ -5626,42 +5730,31 @@ int tspgpu_multistart_nn_2opt(tspgpu_ctx *ctx, const int *starts, int nstarts, d
     hipSetDevice(ctx->device);
     int rc = need_costs(ctx);
     if (rc) return rc;
-    const int n = ctx->n;
-    const double t_end = time_left_s >= 0 ? now_s() + time_left_s : -1;
-    const int chunk = std::min(nstarts, ctx->opt_max_tours);
-    if ((rc = ensure_tours(ctx, chunk))) return rc;
-    double best = DBL_MAX; int arg = -1; long sweeps = 0;
-    bool late = false;
-    std::vector<int> hs(chunk);
-    for (int base = 0; base < nstarts && !late; base += chunk) {
-        const int m = std::min(chunk, nstarts - base);
-        for (int i = 0; i < m; i++) hs[i] = starts ? starts[base + i] : base + i;
-        if ((rc = launch_nn(ctx, 0, hs.data(), m))) return rc;
-        if ((rc = init_slots(ctx, 0, m, ctx->opt_sweep_cap))) return rc;
-        mark_slots(ctx, 0, m, true);
-        const double left = t_end >= 0 ? std::max(0.0, t_end - now_s()) : -1;
-        if ((rc = run_sweeps(ctx, 0, m, false, -1, left, &late))) return rc;
-        HIP_TRY(hipMemcpyAsync(ctx->h_costs, ctx->S.cost, (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(ctx->h_status, ctx->S.nsweeps, (size_t)m * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        int win = -1;
-        for (int i = 0; i < m; i++) {
-            sweeps += ctx->h_status[i];
-            if (ctx->h_costs[i] < best) { best = ctx->h_costs[i]; win = i; } // strict <, tsp.c:671
-        }
-        if (win >= 0) {
-            arg = hs[win];
-            if ((rc = store_path(ctx, win, best_path, nullptr, nullptr))) return rc;
-        }
-        // what h_Greedy_2opt_mod_costs leaves in *solution: the tour of the last start it processed -- the last
-        // one of the list, or of the chunk in which the deadline struck (always a valid tour, heuristics.c:118-149)
-        if ((late || base + m >= nstarts) && last_path) {
-            if ((rc = store_path(ctx, m - 1, last_path, last_cost, nullptr))) return rc;
-        }
+    // a chunk's sweep counts ride on the loop's cost readback: copied into the sweep-count half of the pinned status words (the
+    // next chunk's NN launch may reuse the first half), added up in front of the next chunk's descent and behind the last one
+    long sweeps = 0;
+    int pending = 0;
+    auto add_pending = [&] { for (int i = 0; i < pending; i++) sweeps += ctx->h_status[ctx->tcap + i]; pending = 0; };
+    MultiStart ms;
+    rc = multistart(ctx, starts, nstarts, time_left_s, ctx->opt_sweep_cap, best_path, best_cost, best_start, nullptr, &ms,
+                    [&](int m, double left, bool *late, Descent *) {
+                        add_pending();
+                        const int e = run_sweeps(ctx, 0, m, false, -1, left, late);
+                        if (e) return e;
+                        HIP_TRY(hipMemcpyAsync(ctx->h_status + ctx->tcap, ctx->S.nsweeps, (size_t)m * 4, hipMemcpyDeviceToHost, ctx->stream));
+                        pending = m;
+                        return (int)E_OK;
+                    });
+    if (rc && rc != E_DEADLINE) return rc;
+    add_pending();
+    // what h_Greedy_2opt_mod_costs leaves in *solution: the tour of the last start it processed -- the last
+    // one of the list, or of the chunk in which the deadline struck (always a valid tour, heuristics.c:118-149)
+    if (last_path) {
+        const int e = store_path(ctx, ms.m_last - 1, last_path, last_cost, nullptr);
+        if (e) return e;
     }
-    *best_cost = best; *best_start = arg;
     if (total_sweeps) *total_sweeps = sweeps;
-    return late ? E_DEADLINE : E_OK;
+    return rc;
 }
 
 int tspgpu_tour_sweep_part(tspgpu_ctx *ctx, int slot, int part, int nparts, double *delta, int *a, int *b)
@@ -5926,7 +6019,7 @@ int tspgpu_extra_mileage(tspgpu_ctx *ctx, int a, int b, double time_left_s, int 
 static int or_max_n(const tspgpu_ctx *ctx, size_t esz) { return (int)((ctx->lds_max - OR_EXTRA) / (4 * esz)) & ~31; }
 
 // batch: the entry points over several slots, which matrix-free mode refuses whatever TSPGPU_OPT_OR_MATRIX_FREE says
-static int or_check(tspgpu_ctx *ctx, bool batch = false)
+static int or_check(tspgpu_ctx *ctx, bool batch)
 {
     int rc = need_costs(ctx);
     if (rc) return rc;
@@ -5945,6 +6038,8 @@ static int or_check(tspgpu_ctx *ctx, bool batch = false)
     if (!ctx->d_or) HIP_TRY(hipMalloc(&ctx->d_or, sizeof(OrCtl)));
     return E_OK;
 }
+
+static int or_check(tspgpu_ctx *ctx) { return or_check(ctx, false); }
 
 template <typename T> static const void *or_sweep_fn(int nch)
 {
@@ -6064,11 +6159,11 @@ static int or_run(tspgpu_ctx *ctx, int slot, long max_moves, double t_end, long 
 }
 
 // the descent of tspgpu_local_search on a slot: { 2-opt to its local optimum; Or-opt until nothing improves } until Or-opt applies nothing
-static int or_descent(tspgpu_ctx *ctx, int slot, double time_left_s, long *two_opt_sweeps, long *or_moves, int *rounds, bool *late)
+static int or_descent(tspgpu_ctx *ctx, int slot, double time_left_s, Descent *out, bool *late)
 {
     const double t_end = deadline_of(time_left_s);
-    long tw = 0, om = 0;
-    int nr = 0, rc = E_OK;
+    Descent D;
+    int rc = E_OK;
     *late = false;
     for (;;) {
         double left = -1;
@@ -6079,16 +6174,14 @@ static int or_descent(tspgpu_ctx *ctx, int slot, double time_left_s, long *two_o
         int ns = 0;
         HIP_TRY(hipMemcpyAsync(&ns, ctx->S.nsweeps + slot, 4, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        tw += ns; nr++;
+        D.tw += ns; D.nr++;
         if (*late) break;
         long m = 0;
         if ((rc = or_run(ctx, slot, -1, t_end, &m, late, nullptr))) break;
-        om += m;
+        D.om += m;
         if (*late || m == 0) break;
     }
-    if (two_opt_sweeps) *two_opt_sweeps = tw;
-    if (or_moves) *or_moves = om;
-    if (rounds) *rounds = nr;
+    *out = D;
     return rc;
 }
 
@@ -6115,15 +6208,6 @@ static SweepGeom or_plan_batch(const tspgpu_ctx *ctx, int live)
     return P;
 }
 
-// the slot list of the next launches: staged in pinned memory, so the stream must have drained the previous list first
-static int or_set_live(tspgpu_ctx *ctx, const std::vector<int> &list)
-{
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    memcpy(ctx->h_or_live, list.data(), list.size() * 4);
-    HIP_TRY(hipMemcpyAsync(ctx->d_or_live, ctx->h_or_live, list.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-    return E_OK;
-}
-
 // one Or-opt round on the first `live` slots of the list: a sweep launch and an apply launch (grid rows in runs of 65 535)
 static int or_launch_round(tspgpu_ctx *ctx, int live, const SweepGeom &P)
 {
@@ -6131,7 +6215,7 @@ static int or_launch_round(tspgpu_ctx *ctx, int live, const SweepGeom &P)
     if (rc) return rc;
     for (int off = 0; off < live; off += 65535) {
         const int rows = std::min(65535, live - off);
-        const int *list = ctx->d_or_live + off;
+        const int *list = ctx->d_live + off;
 #define OR_SWEEP(T, N) hipLaunchKernelGGL((k_oropt_sweep_batch<T, N>), dim3(P.W, rows), dim3(P.BT), P.lds, ctx->stream, ctx->S, \
                                           (const T *)ctx->d_mat, ctx->n, ctx->ld, list, P.R, (const OrCtl *)ctx->d_or_ctl)
         ELEM_SWITCH(ctx->elem, T, { if (P.NCH == 1) OR_SWEEP(T, 1); else if (P.NCH == 2) OR_SWEEP(T, 2); else OR_SWEEP(T, 3); });
@@ -6140,7 +6224,7 @@ static int or_launch_round(tspgpu_ctx *ctx, int live, const SweepGeom &P)
     }
     const int BT = std::min(1024, std::max(64, pow2_ceil(ctx->n / 8)));
     ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_oropt_apply_batch<T>), dim3(live), dim3(BT), 0, ctx->stream, ctx->S, (const T *)ctx->d_mat,
-                                                 ctx->n, ctx->ld, (const int *)ctx->d_or_live, P.W, ctx->d_or_ctl));
+                                                 ctx->n, ctx->ld, (const int *)ctx->d_live, P.W, ctx->d_or_ctl));
     HIP_TRY(hipGetLastError());
     return E_OK;
 }
@@ -6150,13 +6234,13 @@ static int or_launch_round(tspgpu_ctx *ctx, int live, const SweepGeom &P)
 // finished tour keeps done = 1 and is skipped by the sweep kernels, so it runs no extra sweep) and run_sweeps takes the whole
 // range to the 2-opt optimum; then Or-opt rounds -- one sweep and one apply launch for all tours still in the phase -- with the
 // control blocks read back every 8 rounds (every round under a deadline) and the list rebuilt from them.
-// tw / om / nr: per-slot 2-opt sweeps, Or-opt moves and 2-opt descents, [count].
-static int or_descent_batch(tspgpu_ctx *ctx, int slot0, int count, double time_left_s, long *tw, long *om, int *nr, bool *late)
+// D: per-slot 2-opt sweeps, Or-opt moves and 2-opt descents, [count].
+static int or_descent_batch(tspgpu_ctx *ctx, int slot0, int count, double time_left_s, Descent *D, bool *late)
 {
     const double t_end = deadline_of(time_left_s);
     std::vector<int> live(count), act;
     std::vector<OrCtl> hc(count);
-    for (int i = 0; i < count; i++) { live[i] = slot0 + i; tw[i] = om[i] = 0; nr[i] = 0; }
+    for (int i = 0; i < count; i++) { live[i] = slot0 + i; D[i] = Descent{}; }
     *late = false;
     ctx->or_batch_R = 0;
     int rc;
@@ -6165,22 +6249,22 @@ static int or_descent_batch(tspgpu_ctx *ctx, int slot0, int count, double time_l
         double left = -1;
         if (t_end >= 0 && (left = t_end - now_s()) <= 0) { *late = true; break; }
         const int nl = (int)live.size();
-        if ((rc = or_set_live(ctx, live))) return rc;
-        hipLaunchKernelGGL(k_rearm_list, dim3((nl + 255) / 256), dim3(256), 0, ctx->stream, ctx->S, (const int *)ctx->d_or_live, nl, -1);
+        if ((rc = set_live(ctx, live))) return rc;
+        hipLaunchKernelGGL(k_rearm_list, dim3((nl + 255) / 256), dim3(256), 0, ctx->stream, ctx->S, (const int *)ctx->d_live, nl, -1);
         HIP_TRY(hipGetLastError());
         if ((rc = run_sweeps(ctx, slot0, count, false, -1, left, late))) return rc;
         HIP_TRY(hipMemcpyAsync(ctx->h_status, ctx->S.nsweeps + slot0, (size_t)count * 4, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        for (int t : live) { tw[t - slot0] += ctx->h_status[t - slot0]; nr[t - slot0]++; }
+        for (int t : live) { D[t - slot0].tw += ctx->h_status[t - slot0]; D[t - slot0].nr++; }
         if (*late) break;
         // the Or-opt phase of the live tours (the list uploaded above is still theirs)
-        hipLaunchKernelGGL(k_or_arm, dim3((nl + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_or_ctl, (const int *)ctx->d_or_live, nl);
+        hipLaunchKernelGGL(k_or_arm, dim3((nl + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_or_ctl, (const int *)ctx->d_live, nl);
         HIP_TRY(hipGetLastError());
         act = live;
-        bool fresh = true;      // d_or_live holds `act`
+        bool fresh = true;      // d_live holds `act`
         while (!act.empty()) {
             if (t_end >= 0 && now_s() >= t_end) { *late = true; break; }
-            if (!fresh && (rc = or_set_live(ctx, act))) return rc;
+            if (!fresh && (rc = set_live(ctx, act))) return rc;
             fresh = false;
             const SweepGeom P = or_plan_batch(ctx, (int)act.size());
             if (!ctx->or_batch_R) ctx->or_batch_R = P.R;
@@ -6196,7 +6280,7 @@ static int or_descent_batch(tspgpu_ctx *ctx, int slot0, int count, double time_l
         size_t k = 0;
         for (int t : live) {
             const long m = (long)hc[t - slot0].moves;
-            om[t - slot0] += m;
+            D[t - slot0].om += m;
             if (m > 0) live[k++] = t;
         }
         live.resize(k);
@@ -6225,13 +6309,10 @@ int tspgpu_tours_local_search(tspgpu_ctx *ctx, int slot0, int count, double time
     int rc = or_check(ctx, true);
     if (rc) return rc;
     if ((rc = or_batch_args(ctx, slot0, count))) return rc;
-    std::vector<long> tw(count), om(count);
-    std::vector<int> nr(count);
+    std::vector<Descent> D(count);
     bool late = false;
-    if ((rc = or_descent_batch(ctx, slot0, count, time_left_s, tw.data(), om.data(), nr.data(), &late))) return rc;
-    if (two_opt_sweeps) std::copy(tw.begin(), tw.end(), two_opt_sweeps);
-    if (or_moves) std::copy(om.begin(), om.end(), or_moves);
-    if (rounds) std::copy(nr.begin(), nr.end(), rounds);
+    if ((rc = or_descent_batch(ctx, slot0, count, time_left_s, D.data(), &late))) return rc;
+    descent_out(D.data(), count, two_opt_sweeps, nullptr, nullptr, or_moves, rounds);
     return done_code(late);
 }
 
@@ -6245,62 +6326,29 @@ int tspgpu_multistart_local_search(tspgpu_ctx *ctx, const int *starts, int nstar
     if (rc) return rc;
     if (ctx->opt_sweep_cap != -1)
         return fail(ctx, E_INVALID, "TSPGPU_OPT_SWEEP_CAP = %d: the 2-opt + Or-opt descent runs every 2-opt phase to its local optimum", ctx->opt_sweep_cap);
-    const double t_end = deadline_of(time_left_s);
-    const int chunk = std::min(nstarts, ctx->opt_max_tours);
-    if ((rc = ensure_tours(ctx, chunk))) return rc;
-    double best = DBL_MAX; int arg = -1; long sweeps = 0, moves = 0;
-    bool late = false;
-    std::vector<int> hs(chunk), nr(chunk);
-    std::vector<long> tw(chunk), om(chunk);
-    for (int base = 0; base < nstarts && !late; base += chunk) {
-        const int m = std::min(chunk, nstarts - base);
-        for (int i = 0; i < m; i++) hs[i] = starts ? starts[base + i] : base + i;
-        if ((rc = launch_nn(ctx, 0, hs.data(), m))) return rc;
-        if ((rc = init_slots(ctx, 0, m, -1))) return rc;
-        mark_slots(ctx, 0, m, true);
-        const double left = t_end >= 0 ? std::max(0.0, t_end - now_s()) : -1;
-        if ((rc = or_descent_batch(ctx, 0, m, left, tw.data(), om.data(), nr.data(), &late))) return rc;
-        HIP_TRY(hipMemcpyAsync(ctx->h_costs, ctx->S.cost, (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        int win = -1;
-        for (int i = 0; i < m; i++) {
-            sweeps += tw[i]; moves += om[i];
-            if (costs_out) costs_out[base + i] = ctx->h_costs[i];
-            if (ctx->h_costs[i] < best) { best = ctx->h_costs[i]; win = i; }    // strict <: ties to the earliest entry
-        }
-        if (win >= 0) {
-            arg = hs[win];
-            if ((rc = store_path(ctx, win, best_path, nullptr, nullptr))) return rc;
-        }
-    }
-    *best_cost = best; *best_start = arg;
-    if (total_two_opt_sweeps) *total_two_opt_sweeps = sweeps;
-    if (total_or_moves) *total_or_moves = moves;
-    return done_code(late);
+    MultiStart ms;
+    rc = multistart(ctx, starts, nstarts, time_left_s, -1, best_path, best_cost, best_start, costs_out, &ms,
+                    [&](int m, double left, bool *late, Descent *D) { return or_descent_batch(ctx, 0, m, left, D, late); });
+    if (rc && rc != E_DEADLINE) return rc;
+    descent_out(&ms.total, 1, total_two_opt_sweeps, nullptr, nullptr, total_or_moves, nullptr);
+    return rc;
 }
 
 int tspgpu_tour_or_opt(tspgpu_ctx *ctx, int slot, long max_moves, double time_left_s, long *moves)
 {
     if (!ctx) return E_UNAVAILABLE;
-    hipSetDevice(ctx->device);
-    int rc = or_check(ctx);
-    if (rc) return rc;
-    if ((rc = need_slot(ctx, slot))) return rc;
-    bool late = false;
-    if ((rc = or_run(ctx, slot, max_moves, deadline_of(time_left_s), moves, &late, nullptr))) return rc;
-    return done_code(late);
+    return with_slot(ctx, slot, or_check, [&](bool *late) { return or_run(ctx, slot, max_moves, deadline_of(time_left_s), moves, late, nullptr); });
 }
 
 int tspgpu_tour_local_search(tspgpu_ctx *ctx, int slot, double time_left_s, long *two_opt_sweeps, long *or_moves, int *rounds)
 {
     if (!ctx) return E_UNAVAILABLE;
-    hipSetDevice(ctx->device);
-    int rc = or_check(ctx);
-    if (rc) return rc;
-    if ((rc = need_slot(ctx, slot))) return rc;
-    bool late = false;
-    if ((rc = or_descent(ctx, slot, time_left_s, two_opt_sweeps, or_moves, rounds, &late))) return rc;
-    return done_code(late);
+    return with_slot(ctx, slot, or_check, [&](bool *late) {
+        Descent D;
+        const int rc = or_descent(ctx, slot, time_left_s, &D, late);
+        descent_out(&D, 1, two_opt_sweeps, nullptr, nullptr, or_moves, rounds);
+        return rc;
+    });
 }
 
 int tspgpu_time_or_sweep(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean)
@@ -6321,14 +6369,9 @@ int tspgpu_or_opt_once(tspgpu_ctx *ctx, int *path, double *cost, double *delta, 
 {
     if (!ctx) return E_UNAVAILABLE;
     if (!path || !cost) return fail(ctx, E_INVALID, "null argument");
-    hipSetDevice(ctx->device);
-    int rc = or_check(ctx);
-    if (rc) return rc;
-    if ((rc = load_path(ctx, 0, path, -1))) return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->S.cost, cost, 8, hipMemcpyHostToDevice, ctx->stream));     // the caller's running cost, as ref_2opt_once
     OrCtl C;
-    if ((rc = or_run(ctx, 0, 1, -1, nullptr, nullptr, &C))) return rc;
-    if ((rc = store_path(ctx, 0, path, cost, nullptr))) return rc;
+    const int rc = with_host_tour(ctx, path, cost, true, or_check, [&](bool *) { return or_run(ctx, 0, 1, -1, nullptr, nullptr, &C); });
+    if (rc) return rc;
     if (delta) *delta = C.applied ? C.d : 0.0;
     if (move) for (int i = 0; i < 4; i++) move[i] = C.applied ? C.move[i] : -1;
     return E_OK;
@@ -6338,29 +6381,20 @@ int tspgpu_or_opt(tspgpu_ctx *ctx, int *path, double *cost, double time_left_s, 
 {
     if (!ctx) return E_UNAVAILABLE;
     if (!path || !cost) return fail(ctx, E_INVALID, "null argument");
-    hipSetDevice(ctx->device);
-    int rc = or_check(ctx);
-    if (rc) return rc;
-    if ((rc = load_path(ctx, 0, path, -1))) return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->S.cost, cost, 8, hipMemcpyHostToDevice, ctx->stream));
-    bool late = false;
-    if ((rc = or_run(ctx, 0, -1, deadline_of(time_left_s), moves, &late, nullptr))) return rc;
-    if ((rc = store_path(ctx, 0, path, cost, nullptr))) return rc;
-    return done_code(late);
+    return with_host_tour(ctx, path, cost, true, or_check,
+                          [&](bool *late) { return or_run(ctx, 0, -1, deadline_of(time_left_s), moves, late, nullptr); });
 }
 
 int tspgpu_local_search(tspgpu_ctx *ctx, int *path, double *cost, double time_left_s, long *two_opt_sweeps, long *or_moves, int *rounds)
 {
     if (!ctx) return E_UNAVAILABLE;
     if (!path || !cost) return fail(ctx, E_INVALID, "null argument");
-    hipSetDevice(ctx->device);
-    int rc = or_check(ctx);
-    if (rc) return rc;
-    if ((rc = load_path(ctx, 0, path, -1))) return rc;          // recomputes the cost, refinment.c:6-9
-    bool late = false;
-    if ((rc = or_descent(ctx, 0, time_left_s, two_opt_sweeps, or_moves, rounds, &late))) return rc;
-    if ((rc = store_path(ctx, 0, path, cost, nullptr))) return rc;
-    return done_code(late);
+    return with_host_tour(ctx, path, cost, false, or_check, [&](bool *late) {
+        Descent D;
+        const int rc = or_descent(ctx, 0, time_left_s, &D, late);
+        descent_out(&D, 1, two_opt_sweeps, nullptr, nullptr, or_moves, rounds);
+        return rc;
+    });
 }
 
 } // extern "C"
@@ -6532,27 +6566,15 @@ extern "C" {
 int tspgpu_tour_two_opt_multi(tspgpu_ctx *ctx, int slot, long max_sweeps, double time_left_s, long *sweeps, long *moves)
 {
     if (!ctx) return E_UNAVAILABLE;
-    hipSetDevice(ctx->device);
-    int rc = m2_check(ctx);
-    if (rc) return rc;
-    if ((rc = need_slot(ctx, slot))) return rc;
-    bool late = false;
-    if ((rc = m2_run(ctx, slot, max_sweeps, deadline_of(time_left_s), sweeps, moves, &late))) return rc;
-    return done_code(late);
+    return with_slot(ctx, slot, m2_check, [&](bool *late) { return m2_run(ctx, slot, max_sweeps, deadline_of(time_left_s), sweeps, moves, late); });
 }
 
 int tspgpu_two_opt_multi(tspgpu_ctx *ctx, int *path, double *cost, double time_left_s, long *sweeps, long *moves)
 {
     if (!ctx) return E_UNAVAILABLE;
     if (!path || !cost) return fail(ctx, E_INVALID, "null argument");
-    hipSetDevice(ctx->device);
-    int rc = m2_check(ctx);
-    if (rc) return rc;
-    if ((rc = load_path(ctx, 0, path, -1))) return rc;          // recomputes the cost, refinment.c:6-9
-    bool late = false;
-    if ((rc = m2_run(ctx, 0, -1, deadline_of(time_left_s), sweeps, moves, &late))) return rc;
-    if ((rc = store_path(ctx, 0, path, cost, nullptr))) return rc;
-    return done_code(late);
+    return with_host_tour(ctx, path, cost, false, m2_check,
+                          [&](bool *late) { return m2_run(ctx, 0, -1, deadline_of(time_left_s), sweeps, moves, late); });
 }
 
 } // extern "C"
@@ -6739,13 +6761,8 @@ int tspgpu_two_opt_nl_once(tspgpu_ctx *ctx, int *path, double *cost, int *nmoves
 int tspgpu_tour_two_opt_nl(tspgpu_ctx *ctx, int slot, long max_sweeps, double time_left_s, long *sweeps, long *moves)
 {
     if (!ctx) return E_UNAVAILABLE;
-    hipSetDevice(ctx->device);
-    int rc = nl_check(ctx);
-    if (rc) return rc;
-    if ((rc = need_slot(ctx, slot))) return rc;
-    bool late = false;
-    if ((rc = m2_run(ctx, slot, max_sweeps, deadline_of(time_left_s), sweeps, moves, &late, M2_NL))) return rc;
-    return done_code(late);
+    return with_slot(ctx, slot, nl_check,
+                     [&](bool *late) { return m2_run(ctx, slot, max_sweeps, deadline_of(time_left_s), sweeps, moves, late, M2_NL); });
 }
 
 int tspgpu_two_opt_nl(tspgpu_ctx *ctx, int *path, double *cost, double time_left_s, int polish,
@@ -6753,23 +6770,20 @@ int tspgpu_two_opt_nl(tspgpu_ctx *ctx, int *path, double *cost, double time_left
 {
     if (!ctx) return E_UNAVAILABLE;
     if (!path || !cost) return fail(ctx, E_INVALID, "null argument");
-    hipSetDevice(ctx->device);
-    int rc = nl_check(ctx);
-    if (rc) return rc;
-    if ((rc = load_path(ctx, 0, path, -1))) return rc;          // recomputes the cost, refinment.c:6-9
-    const double t_end = deadline_of(time_left_s);
-    bool late = false;
-    long ps = 0, pm = 0;
-    ctx->nl_polish_sweeps = 0;
-    if ((rc = m2_run(ctx, 0, -1, t_end, sweeps, moves, &late, M2_NL))) return rc;
-    if (polish && !late) {                  // the parallel-move descent goes on from the slot as it stands
-        if ((rc = m2_run(ctx, 0, -1, t_end, &ps, &pm, &late))) return rc;
-        ctx->nl_polish_sweeps = ps;
-    }
-    if (polish_sweeps) *polish_sweeps = ps;
-    if (polish_moves) *polish_moves = pm;
-    if ((rc = store_path(ctx, 0, path, cost, nullptr))) return rc;
-    return done_code(late);
+    return with_host_tour(ctx, path, cost, false, nl_check, [&](bool *late) {
+        const double t_end = deadline_of(time_left_s);
+        long ps = 0, pm = 0;
+        ctx->nl_polish_sweeps = 0;
+        int rc = m2_run(ctx, 0, -1, t_end, sweeps, moves, late, M2_NL);
+        if (rc) return rc;
+        if (polish && !*late) {                 // the parallel-move descent goes on from the slot as it stands
+            if ((rc = m2_run(ctx, 0, -1, t_end, &ps, &pm, late))) return rc;
+            ctx->nl_polish_sweeps = ps;
+        }
+        if (polish_sweeps) *polish_sweeps = ps;
+        if (polish_moves) *polish_moves = pm;
+        return (int)E_OK;
+    });
 }
 
 int tspgpu_time_nl_sweep(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean)
@@ -6823,29 +6837,25 @@ static int ornl_launch_apply(tspgpu_ctx *ctx, int slot)
 
 // the descent of tspgpu_local_search_nl on a slot: { neighbour-list 2-opt to its end; neighbour-list Or-opt until a sweep accepts
 // nothing } until an Or-opt phase applies nothing
-static int ornl_descent(tspgpu_ctx *ctx, int slot, double time_left_s, long *two_opt_sweeps, long *two_opt_moves, long *or_sweeps,
-                        long *or_moves, int *rounds, bool *late)
+static int ornl_descent(tspgpu_ctx *ctx, int slot, double time_left_s, Descent *out, bool *late)
 {
     const double t_end = deadline_of(time_left_s);
-    long tw = 0, tm = 0, os = 0, om = 0, mk = 0;
-    int nr = 0, rc = E_OK;
+    Descent D;
+    long mk = 0;
+    int rc = E_OK;
     *late = false;
     ctx->ornl_sweeps = ctx->ornl_moves = ctx->ornl_max_k = 0;
     for (;;) {
         long s = 0, m = 0;
         if ((rc = m2_run(ctx, slot, -1, t_end, &s, &m, late, M2_NL))) break;
-        tw += s; tm += m; nr++;
+        D.tw += s; D.tm += m; D.nr++;
         if (*late) break;
         if ((rc = m2_run(ctx, slot, -1, t_end, &s, &m, late, M2_ORNL))) break;
-        os += s; om += m; mk = std::max(mk, ctx->ornl_max_k);
+        D.os += s; D.om += m; mk = std::max(mk, ctx->ornl_max_k);
         if (*late || m == 0) break;
     }
-    ctx->ornl_sweeps = os; ctx->ornl_moves = om; ctx->ornl_max_k = mk; ctx->ornl_rounds = nr;
-    if (two_opt_sweeps) *two_opt_sweeps = tw;
-    if (two_opt_moves) *two_opt_moves = tm;
-    if (or_sweeps) *or_sweeps = os;
-    if (or_moves) *or_moves = om;
-    if (rounds) *rounds = nr;
+    ctx->ornl_sweeps = D.os; ctx->ornl_moves = D.om; ctx->ornl_max_k = mk; ctx->ornl_rounds = D.nr;
+    *out = D;
     return rc;
 }
 
@@ -6860,27 +6870,15 @@ int tspgpu_or_opt_nl(tspgpu_ctx *ctx, int *path, double *cost, double time_left_
 {
     if (!ctx) return E_UNAVAILABLE;
     if (!path || !cost) return fail(ctx, E_INVALID, "null argument");
-    hipSetDevice(ctx->device);
-    int rc = ornl_check(ctx);
-    if (rc) return rc;
-    if ((rc = load_path(ctx, 0, path, -1))) return rc;
-    HIP_TRY(hipMemcpyAsync(ctx->S.cost, cost, 8, hipMemcpyHostToDevice, ctx->stream));     // the caller's running cost, as tspgpu_or_opt
-    bool late = false;
-    if ((rc = m2_run(ctx, 0, -1, deadline_of(time_left_s), sweeps, moves, &late, M2_ORNL))) return rc;
-    if ((rc = store_path(ctx, 0, path, cost, nullptr))) return rc;
-    return done_code(late);
+    return with_host_tour(ctx, path, cost, true, ornl_check,
+                          [&](bool *late) { return m2_run(ctx, 0, -1, deadline_of(time_left_s), sweeps, moves, late, M2_ORNL); });
 }
 
 int tspgpu_tour_or_opt_nl(tspgpu_ctx *ctx, int slot, long max_sweeps, double time_left_s, long *sweeps, long *moves)
 {
     if (!ctx) return E_UNAVAILABLE;
-    hipSetDevice(ctx->device);
-    int rc = ornl_check(ctx);
-    if (rc) return rc;
-    if ((rc = need_slot(ctx, slot))) return rc;
-    bool late = false;
-    if ((rc = m2_run(ctx, slot, max_sweeps, deadline_of(time_left_s), sweeps, moves, &late, M2_ORNL))) return rc;
-    return done_code(late);
+    return with_slot(ctx, slot, ornl_check,
+                     [&](bool *late) { return m2_run(ctx, slot, max_sweeps, deadline_of(time_left_s), sweeps, moves, late, M2_ORNL); });
 }
 
 int tspgpu_local_search_nl(tspgpu_ctx *ctx, int *path, double *cost, double time_left_s, long *two_opt_sweeps, long *two_opt_moves,
@@ -6888,27 +6886,24 @@ int tspgpu_local_search_nl(tspgpu_ctx *ctx, int *path, double *cost, double time
 {
     if (!ctx) return E_UNAVAILABLE;
     if (!path || !cost) return fail(ctx, E_INVALID, "null argument");
-    hipSetDevice(ctx->device);
-    int rc = ornl_check(ctx);
-    if (rc) return rc;
-    if ((rc = load_path(ctx, 0, path, -1))) return rc;          // recomputes the cost, refinment.c:6-9
-    bool late = false;
-    if ((rc = ornl_descent(ctx, 0, time_left_s, two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds, &late))) return rc;
-    if ((rc = store_path(ctx, 0, path, cost, nullptr))) return rc;
-    return done_code(late);
+    return with_host_tour(ctx, path, cost, false, ornl_check, [&](bool *late) {
+        Descent D;
+        const int rc = ornl_descent(ctx, 0, time_left_s, &D, late);
+        descent_out(&D, 1, two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds);
+        return rc;
+    });
 }
 
 int tspgpu_tour_local_search_nl(tspgpu_ctx *ctx, int slot, double time_left_s, long *two_opt_sweeps, long *two_opt_moves,
                                 long *or_sweeps, long *or_moves, int *rounds)
 {
     if (!ctx) return E_UNAVAILABLE;
-    hipSetDevice(ctx->device);
-    int rc = ornl_check(ctx);
-    if (rc) return rc;
-    if ((rc = need_slot(ctx, slot))) return rc;
-    bool late = false;
-    if ((rc = ornl_descent(ctx, slot, time_left_s, two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds, &late))) return rc;
-    return done_code(late);
+    return with_slot(ctx, slot, ornl_check, [&](bool *late) {
+        Descent D;
+        const int rc = ornl_descent(ctx, slot, time_left_s, &D, late);
+        descent_out(&D, 1, two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds);
+        return rc;
+    });
 }
 
 int tspgpu_time_or_nl_sweep(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean)
@@ -6920,7 +6915,7 @@ int tspgpu_time_or_nl_sweep(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean)
 
 // ---- batched neighbour-list descent (tspgpu_nlbatch.inc) ---------------------------------------------------------------
 
-// the candidate arrays (40 bytes per node and slot), a control block per slot and the live list for a range of `count` slots
+// the candidate arrays (40 bytes per node and slot) and a control block per slot for a range of `count` slots
 static int nlb_ensure(tspgpu_ctx *ctx, int count)
 {
     if (count <= ctx->nlb_cap) return E_OK;
@@ -6928,13 +6923,12 @@ static int nlb_ensure(tspgpu_ctx *ctx, int count)
     M2Buf &B = ctx->nlb;
     const size_t N = (size_t)ctx->n * count;
     void **ptrs[] = {(void **)&B.raw_d, (void **)&B.raw_b, (void **)&B.d, (void **)&B.a, (void **)&B.b, (void **)&B.i, (void **)&B.j, (void **)&B.acc,
-                     (void **)&ctx->d_nlb_ctl, (void **)&ctx->d_nlb_live};
-    const size_t bytes[] = {N * 8, N * 4, N * 8, N * 4, N * 4, N * 4, N * 4, N * 4, (size_t)count * sizeof(NlbCtl), (size_t)count * 4};
+                     (void **)&ctx->d_nlb_ctl};
+    const size_t bytes[] = {N * 8, N * 4, N * 8, N * 4, N * 4, N * 4, N * 4, N * 4, (size_t)count * sizeof(NlbCtl)};
     size_t total = 0;
     for (size_t b : bytes) total += b;
     hipError_t e = hipSuccess;
-    for (int k = 0; k < 10 && e == hipSuccess; k++) e = hipMalloc(ptrs[k], bytes[k]);
-    if (e == hipSuccess) e = hipHostMalloc(&ctx->h_nlb_live, (size_t)count * 4);
+    for (int k = 0; k < 9 && e == hipSuccess; k++) e = hipMalloc(ptrs[k], bytes[k]);
     if (e != hipSuccess) {                  // all or none: a later call must not find half of them
         free_nlb(ctx);
         (void)hipGetLastError();
@@ -6942,15 +6936,6 @@ static int nlb_ensure(tspgpu_ctx *ctx, int count)
                     total, count, ctx->n, hipGetErrorString(e));
     }
     ctx->nlb_cap = count;
-    return E_OK;
-}
-
-// the slot list of the next launches: staged in pinned memory, so the stream must have drained the previous list first (or_set_live)
-static int nlb_set_live(tspgpu_ctx *ctx, const std::vector<int> &list)
-{
-    HIP_TRY(hipStreamSynchronize(ctx->stream));
-    memcpy(ctx->h_nlb_live, list.data(), list.size() * 4);
-    HIP_TRY(hipMemcpyAsync(ctx->d_nlb_live, ctx->h_nlb_live, list.size() * 4, hipMemcpyHostToDevice, ctx->stream));
     return E_OK;
 }
 
@@ -6962,7 +6947,7 @@ static int nlb_launch_sweep(tspgpu_ctx *ctx, int slot0, int live)
     const int run = std::max(1, std::min(65535, (1 << 23) / W));    // (a grid holds fewer than 2^32 threads)
     for (int off = 0; off < live; off += run) {
         const unsigned rows = (unsigned)std::min(run, live - off);
-        const int *list = ctx->d_nlb_live + off;
+        const int *list = ctx->d_live + off;
         if (ctx->otf)
             kind_switch(ctx, [&](auto kind, auto *pts, auto *) {
                 hipLaunchKernelGGL((k_nlb_sweep_otf<kind()>), dim3(W, rows), dim3(256), 0, ctx->stream, ctx->S, pts, n, list, slot0, ctx->nl, ctx->nlb,
@@ -6990,8 +6975,8 @@ static int nlb_launch_sweep(tspgpu_ctx *ctx, int slot0, int live)
 
 // ornl_descent on the slots slot0 .. slot0 + count - 1 at once.  The control blocks are armed (2-opt phase, round 1) and the
 // slots re-armed as m2_arm does; then sweeps of all live tours -- four between looks at the control blocks, one under a
-// deadline, as m2_run -- and the tours whose descent has ended leave the list.  out: per-slot counters, [count] each
-static int nlb_descent(tspgpu_ctx *ctx, int slot0, int count, double time_left_s, long *tw, long *tm, long *os, long *om, int *nr, bool *late)
+// deadline, as m2_run -- and the tours whose descent has ended leave the list.  D: per-slot counters, [count]
+static int nlb_descent(tspgpu_ctx *ctx, int slot0, int count, double time_left_s, Descent *D, bool *late)
 {
     const double t_end = deadline_of(time_left_s);
     *late = false;
@@ -7006,7 +6991,7 @@ static int nlb_descent(tspgpu_ctx *ctx, int slot0, int count, double time_left_s
     HIP_TRY(hipGetLastError());
     std::vector<int> live((size_t)count);
     for (int i = 0; i < count; i++) live[i] = slot0 + i;
-    if ((rc = nlb_set_live(ctx, live))) return rc;
+    if ((rc = set_live(ctx, live))) return rc;
     while (!live.empty()) {
         if (t_end >= 0 && now_s() >= t_end) { *late = true; break; }
         const int K = t_end >= 0 ? 1 : 4;
@@ -7020,11 +7005,11 @@ static int nlb_descent(tspgpu_ctx *ctx, int slot0, int count, double time_left_s
         for (int t : live) if (!hc[t - slot0].stop) live[k++] = t;
         if (k == live.size()) continue;
         live.resize(k);
-        if (k && (rc = nlb_set_live(ctx, live))) return rc;
+        if (k && (rc = set_live(ctx, live))) return rc;
     }
     for (int i = 0; i < count; i++) {
-        tw[i] = (long)hc[i].two_opt_sweeps; tm[i] = (long)hc[i].two_opt_moves;
-        os[i] = (long)hc[i].or_sweeps; om[i] = (long)hc[i].or_moves; nr[i] = hc[i].rounds;
+        D[i].tw = (long)hc[i].two_opt_sweeps; D[i].tm = (long)hc[i].two_opt_moves;
+        D[i].os = (long)hc[i].or_sweeps; D[i].om = (long)hc[i].or_moves; D[i].nr = hc[i].rounds;
     }
     return E_OK;
 }
@@ -7041,15 +7026,10 @@ int tspgpu_tours_local_search_nl(tspgpu_ctx *ctx, int slot0, int count, double t
     if (slot0 < 0 || count <= 0 || count > ctx->tcap || slot0 > ctx->tcap - count)      // (the range first: a slot past the end is no slot without a tour)
         return fail(ctx, E_INVALID, "bad slot range: slot0 %d, count %d of %d slots", slot0, count, ctx->tcap);
     if ((rc = or_batch_args(ctx, slot0, count))) return rc;
-    std::vector<long> tw(count), tm(count), os(count), om(count);
-    std::vector<int> nr(count);
+    std::vector<Descent> D(count);
     bool late = false;
-    if ((rc = nlb_descent(ctx, slot0, count, time_left_s, tw.data(), tm.data(), os.data(), om.data(), nr.data(), &late))) return rc;
-    if (two_opt_sweeps) std::copy(tw.begin(), tw.end(), two_opt_sweeps);
-    if (two_opt_moves) std::copy(tm.begin(), tm.end(), two_opt_moves);
-    if (or_sweeps) std::copy(os.begin(), os.end(), or_sweeps);
-    if (or_moves) std::copy(om.begin(), om.end(), or_moves);
-    if (rounds) std::copy(nr.begin(), nr.end(), rounds);
+    if ((rc = nlb_descent(ctx, slot0, count, time_left_s, D.data(), &late))) return rc;
+    descent_out(D.data(), count, two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds);
     return done_code(late);
 }
 
@@ -7064,40 +7044,12 @@ int tspgpu_multistart_local_search_nl(tspgpu_ctx *ctx, const int *starts, int ns
     if (rc) return rc;
     if (ctx->opt_sweep_cap != -1)
         return fail(ctx, E_INVALID, "TSPGPU_OPT_SWEEP_CAP = %d: the descent over the neighbour lists runs every phase to its end", ctx->opt_sweep_cap);
-    const double t_end = deadline_of(time_left_s);
-    const int chunk = std::min(nstarts, ctx->opt_max_tours);
-    if ((rc = ensure_tours(ctx, chunk))) return rc;
-    double best = DBL_MAX; int arg = -1; long tot[4] = {0, 0, 0, 0};
-    bool late = false;
-    std::vector<int> hs(chunk), nr(chunk);
-    std::vector<long> tw(chunk), tm(chunk), os(chunk), om(chunk);
-    for (int base = 0; base < nstarts && !late; base += chunk) {
-        const int m = std::min(chunk, nstarts - base);
-        for (int i = 0; i < m; i++) hs[i] = starts ? starts[base + i] : base + i;
-        if ((rc = launch_nn(ctx, 0, hs.data(), m))) return rc;
-        if ((rc = init_slots(ctx, 0, m, -1))) return rc;
-        mark_slots(ctx, 0, m, true);
-        const double left = t_end >= 0 ? std::max(0.0, t_end - now_s()) : -1;
-        if ((rc = nlb_descent(ctx, 0, m, left, tw.data(), tm.data(), os.data(), om.data(), nr.data(), &late))) return rc;
-        HIP_TRY(hipMemcpyAsync(ctx->h_costs, ctx->S.cost, (size_t)m * 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        int win = -1;
-        for (int i = 0; i < m; i++) {
-            tot[0] += tw[i]; tot[1] += tm[i]; tot[2] += os[i]; tot[3] += om[i];
-            if (costs_out) costs_out[base + i] = ctx->h_costs[i];
-            if (ctx->h_costs[i] < best) { best = ctx->h_costs[i]; win = i; }    // strict <: ties to the earliest entry
-        }
-        if (win >= 0) {
-            arg = hs[win];
-            if ((rc = store_path(ctx, win, best_path, nullptr, nullptr))) return rc;
-        }
-    }
-    *best_cost = best; *best_start = arg;
-    if (total_two_opt_sweeps) *total_two_opt_sweeps = tot[0];
-    if (total_two_opt_moves) *total_two_opt_moves = tot[1];
-    if (total_or_sweeps) *total_or_sweeps = tot[2];
-    if (total_or_moves) *total_or_moves = tot[3];
-    return done_code(late);
+    MultiStart ms;
+    rc = multistart(ctx, starts, nstarts, time_left_s, -1, best_path, best_cost, best_start, costs_out, &ms,
+                    [&](int m, double left, bool *late, Descent *D) { return nlb_descent(ctx, 0, m, left, D, late); });
+    if (rc && rc != E_DEADLINE) return rc;
+    descent_out(&ms.total, 1, total_two_opt_sweeps, total_two_opt_moves, total_or_sweeps, total_or_moves, nullptr);
+    return rc;
 }
 
 } // extern "C"

@@ -227,10 +227,8 @@ struct Local {           // one device's result
     double cost = DBL_MAX;
     long pos = -1;       // position in the caller's start list of the device's winner (-1: none)
     int start = -1;
-    long sweeps = 0;
-    long moves = 0;      // Or-opt moves (tspgpu_multi_multistart_local_search)
-    long tw_moves = 0, or_sweeps = 0;   // 2-opt moves and Or-opt sweeps (tspgpu_multi_multistart_local_search_nl)
-    int done = 0;
+    long tw = 0, tm = 0, os = 0, om = 0;    // 2-opt sweeps and moves, Or-opt sweeps and moves (a family without one leaves it 0)
+    int done = 0;        // starts processed (tspgpu_multi_nn_all)
     std::vector<int> path;
     std::string err;
 };
@@ -309,6 +307,48 @@ template <typename F> int per_device(tspgpu_multi *m, F fn)
     for (int i = 0; i < m->G; i++)
         if (rc[i] && rc[i] != E_DEADLINE) return mfail(m, rc[i], "device %d: %s", m->dev[i], tspgpu_last_error(m->ctx[i]));
     return E_OK;
+}
+
+// The sharded multi-start of every entry point: list entry p goes to device p mod G, call(ctx, list, count, Local &) runs the
+// single-device entry on a device's share (it fills the Local's path, cost, start and whichever counters the family has), the
+// devices agree on the winner and its tour lands in best_path.  *total receives the counters summed over the devices.
+// E_DEADLINE when a device ran out of time: the results are as valid as after E_OK.
+template <typename F>
+int sharded(tspgpu_multi *m, const int *starts, int nstarts, int *best_path, double *best_cost, int *best_start, Local *total, F call)
+{
+    const int G = m->G;
+    const int n = (int)tspgpu_info(m->ctx[0], 0);
+    if (n <= 0) return mfail(m, E_PRECOND, "no instance: call tspgpu_multi_set_points / tspgpu_multi_build_costs first");
+    std::vector<Local> L(G);
+    std::vector<std::vector<int>> mine(G);
+    for (long p = 0; p < nstarts; p++) mine[p % G].push_back(starts ? starts[p] : (int)p);   // list entry p -> device p mod G
+    const double t0 = now_s();
+    int rc = per_device(m, [&](int i) {
+        Local &l = L[i];
+        if (mine[i].empty()) return (int)E_OK;
+        l.path.resize(n);
+        l.rc = call(m->ctx[i], mine[i].data(), (int)mine[i].size(), l);
+        if (l.rc && l.rc != E_DEADLINE) return l.rc;
+        if (l.start >= 0) {   // position of the device's winner in the caller's list: its first occurrence on this device
+            for (size_t k = 0; k < mine[i].size(); k++)
+                if (mine[i][k] == l.start) { l.pos = (long)k * G + i; break; }
+        }
+        return l.rc;
+    });
+    m->last_solve_s = now_s() - t0;
+    if (rc) return rc;
+    int owner = -1;
+    long pos = -1;
+    double cost = DBL_MAX;
+    if ((rc = exchange(m, L, n, best_path, &cost, &pos, &owner))) return rc;
+    bool late = false;
+    for (const Local &l : L) {
+        late |= l.rc == E_DEADLINE;
+        total->tw += l.tw; total->tm += l.tm; total->os += l.os; total->om += l.om; total->done += l.done;
+    }
+    *best_cost = owner >= 0 ? cost : DBL_MAX;
+    *best_start = owner >= 0 ? L[owner].start : -1;
+    return late ? E_DEADLINE : E_OK;
 }
 
 } // namespace
@@ -443,41 +483,13 @@ int tspgpu_multi_multistart_nn_2opt(tspgpu_multi *m, const int *starts, int nsta
                                     double *best_cost, int *best_start, long *total_sweeps)
 {
     if (!m || !best_path || !best_cost || !best_start || nstarts <= 0) return mfail(m, E_INVALID, "bad argument");
-    const int G = m->G;
-    const int n = (int)tspgpu_info(m->ctx[0], 0);
-    if (n <= 0) return mfail(m, E_PRECOND, "no instance: call tspgpu_multi_set_points / tspgpu_multi_build_costs first");
-    std::vector<Local> L(G);
-    std::vector<std::vector<int>> mine(G);
-    for (long p = 0; p < nstarts; p++) mine[p % G].push_back(starts ? starts[p] : (int)p);   // list entry p -> device p mod G
-    const double t0 = now_s();
-    int rc = per_device(m, [&](int i) {
-        Local &l = L[i];
-        if (mine[i].empty()) return (int)E_OK;
-        l.path.resize(n);
-        int st = -1;
-        l.rc = tspgpu_multistart_nn_2opt(m->ctx[i], mine[i].data(), (int)mine[i].size(), time_left_s, l.path.data(), &l.cost, &st,
-                                         &l.sweeps, nullptr, nullptr);
-        if (l.rc && l.rc != E_DEADLINE) return l.rc;
-        if (st >= 0) {   // position of the device's winner in the caller's list: its first occurrence on this device
-            for (size_t k = 0; k < mine[i].size(); k++)
-                if (mine[i][k] == st) { l.pos = (long)k * G + i; break; }
-            l.start = st;
-        }
-        return l.rc;
+    Local T;
+    const int rc = sharded(m, starts, nstarts, best_path, best_cost, best_start, &T, [&](tspgpu_ctx *ctx, const int *list, int count, Local &l) {
+        return tspgpu_multistart_nn_2opt(ctx, list, count, time_left_s, l.path.data(), &l.cost, &l.start, &l.tw, nullptr, nullptr);
     });
-    m->last_solve_s = now_s() - t0;
-    if (rc) return rc;
-    int owner = -1;
-    long pos = -1;
-    double cost = DBL_MAX;
-    if ((rc = exchange(m, L, n, best_path, &cost, &pos, &owner))) return rc;
-    bool late = false;
-    long sweeps = 0;
-    for (const Local &l : L) { late |= l.rc == E_DEADLINE; sweeps += l.sweeps; }
-    *best_cost = owner >= 0 ? cost : DBL_MAX;
-    *best_start = owner >= 0 ? L[owner].start : -1;
-    if (total_sweeps) *total_sweeps = sweeps;
-    return late ? E_DEADLINE : E_OK;
+    if (rc && rc != E_DEADLINE) return rc;
+    if (total_sweeps) *total_sweeps = T.tw;
+    return rc;
 }
 
 // tspgpu_multi_multistart_nn_2opt with the 2-opt + Or-opt descent from every start (tspgpu_multistart_local_search per device)
@@ -486,42 +498,14 @@ int tspgpu_multi_multistart_local_search(tspgpu_multi *m, const int *starts, int
 {
     if (!m) return E_UNAVAILABLE;
     if (!best_path || !best_cost || !best_start || nstarts <= 0) return mfail(m, E_INVALID, "bad argument");
-    const int G = m->G;
-    const int n = (int)tspgpu_info(m->ctx[0], 0);
-    if (n <= 0) return mfail(m, E_PRECOND, "no instance: call tspgpu_multi_set_points / tspgpu_multi_build_costs first");
-    std::vector<Local> L(G);
-    std::vector<std::vector<int>> mine(G);
-    for (long p = 0; p < nstarts; p++) mine[p % G].push_back(starts ? starts[p] : (int)p);   // list entry p -> device p mod G
-    const double t0 = now_s();
-    int rc = per_device(m, [&](int i) {
-        Local &l = L[i];
-        if (mine[i].empty()) return (int)E_OK;
-        l.path.resize(n);
-        int st = -1;
-        l.rc = tspgpu_multistart_local_search(m->ctx[i], mine[i].data(), (int)mine[i].size(), time_left_s, l.path.data(), &l.cost, &st,
-                                              &l.sweeps, &l.moves, nullptr);
-        if (l.rc && l.rc != E_DEADLINE) return l.rc;
-        if (st >= 0) {   // position of the device's winner in the caller's list: its first occurrence on this device
-            for (size_t k = 0; k < mine[i].size(); k++)
-                if (mine[i][k] == st) { l.pos = (long)k * G + i; break; }
-            l.start = st;
-        }
-        return l.rc;
+    Local T;
+    const int rc = sharded(m, starts, nstarts, best_path, best_cost, best_start, &T, [&](tspgpu_ctx *ctx, const int *list, int count, Local &l) {
+        return tspgpu_multistart_local_search(ctx, list, count, time_left_s, l.path.data(), &l.cost, &l.start, &l.tw, &l.om, nullptr);
     });
-    m->last_solve_s = now_s() - t0;
-    if (rc) return rc;
-    int owner = -1;
-    long pos = -1;
-    double cost = DBL_MAX;
-    if ((rc = exchange(m, L, n, best_path, &cost, &pos, &owner))) return rc;
-    bool late = false;
-    long sweeps = 0, moves = 0;
-    for (const Local &l : L) { late |= l.rc == E_DEADLINE; sweeps += l.sweeps; moves += l.moves; }
-    *best_cost = owner >= 0 ? cost : DBL_MAX;
-    *best_start = owner >= 0 ? L[owner].start : -1;
-    if (total_two_opt_sweeps) *total_two_opt_sweeps = sweeps;
-    if (total_or_moves) *total_or_moves = moves;
-    return late ? E_DEADLINE : E_OK;
+    if (rc && rc != E_DEADLINE) return rc;
+    if (total_two_opt_sweeps) *total_two_opt_sweeps = T.tw;
+    if (total_or_moves) *total_or_moves = T.om;
+    return rc;
 }
 
 int tspgpu_multi_neighbours_build(tspgpu_multi *m, int K)
@@ -537,84 +521,30 @@ int tspgpu_multi_multistart_local_search_nl(tspgpu_multi *m, const int *starts, 
 {
     if (!m) return E_UNAVAILABLE;
     if (!best_path || !best_cost || !best_start || nstarts <= 0) return mfail(m, E_INVALID, "bad argument");
-    const int G = m->G;
-    const int n = (int)tspgpu_info(m->ctx[0], 0);
-    if (n <= 0) return mfail(m, E_PRECOND, "no instance: call tspgpu_multi_set_points / tspgpu_multi_build_costs first");
-    std::vector<Local> L(G);
-    std::vector<std::vector<int>> mine(G);
-    for (long p = 0; p < nstarts; p++) mine[p % G].push_back(starts ? starts[p] : (int)p);   // list entry p -> device p mod G
-    const double t0 = now_s();
-    int rc = per_device(m, [&](int i) {
-        Local &l = L[i];
-        if (mine[i].empty()) return (int)E_OK;
-        l.path.resize(n);
-        int st = -1;
-        l.rc = tspgpu_multistart_local_search_nl(m->ctx[i], mine[i].data(), (int)mine[i].size(), time_left_s, l.path.data(), &l.cost, &st,
-                                                 &l.sweeps, &l.tw_moves, &l.or_sweeps, &l.moves, nullptr);
-        if (l.rc && l.rc != E_DEADLINE) return l.rc;
-        if (st >= 0) {   // position of the device's winner in the caller's list: its first occurrence on this device
-            for (size_t k = 0; k < mine[i].size(); k++)
-                if (mine[i][k] == st) { l.pos = (long)k * G + i; break; }
-            l.start = st;
-        }
-        return l.rc;
+    Local T;
+    const int rc = sharded(m, starts, nstarts, best_path, best_cost, best_start, &T, [&](tspgpu_ctx *ctx, const int *list, int count, Local &l) {
+        return tspgpu_multistart_local_search_nl(ctx, list, count, time_left_s, l.path.data(), &l.cost, &l.start, &l.tw, &l.tm, &l.os, &l.om,
+                                                 nullptr);
     });
-    m->last_solve_s = now_s() - t0;
-    if (rc) return rc;
-    int owner = -1;
-    long pos = -1;
-    double cost = DBL_MAX;
-    if ((rc = exchange(m, L, n, best_path, &cost, &pos, &owner))) return rc;
-    bool late = false;
-    long tot[4] = {0, 0, 0, 0};
-    for (const Local &l : L) { late |= l.rc == E_DEADLINE; tot[0] += l.sweeps; tot[1] += l.tw_moves; tot[2] += l.or_sweeps; tot[3] += l.moves; }
-    *best_cost = owner >= 0 ? cost : DBL_MAX;
-    *best_start = owner >= 0 ? L[owner].start : -1;
-    if (total_two_opt_sweeps) *total_two_opt_sweeps = tot[0];
-    if (total_two_opt_moves) *total_two_opt_moves = tot[1];
-    if (total_or_sweeps) *total_or_sweeps = tot[2];
-    if (total_or_moves) *total_or_moves = tot[3];
-    return late ? E_DEADLINE : E_OK;
+    if (rc && rc != E_DEADLINE) return rc;
+    if (total_two_opt_sweeps) *total_two_opt_sweeps = T.tw;
+    if (total_two_opt_moves) *total_two_opt_moves = T.tm;
+    if (total_or_sweeps) *total_or_sweeps = T.os;
+    if (total_or_moves) *total_or_moves = T.om;
+    return rc;
 }
 
 int tspgpu_multi_nn_all(tspgpu_multi *m, const int *starts, int nstarts, double time_left_s, int *best_path, double *best_cost,
                         int *best_start, int *done_starts)
 {
     if (!m || !best_path || !best_cost || !best_start || nstarts <= 0) return mfail(m, E_INVALID, "bad argument");
-    const int G = m->G;
-    const int n = (int)tspgpu_info(m->ctx[0], 0);
-    if (n <= 0) return mfail(m, E_PRECOND, "no instance: call tspgpu_multi_set_points / tspgpu_multi_build_costs first");
-    std::vector<Local> L(G);
-    std::vector<std::vector<int>> mine(G);
-    for (long p = 0; p < nstarts; p++) mine[p % G].push_back(starts ? starts[p] : (int)p);
-    const double t0 = now_s();
-    int rc = per_device(m, [&](int i) {
-        Local &l = L[i];
-        if (mine[i].empty()) return (int)E_OK;
-        l.path.resize(n);
-        int st = -1;
-        l.rc = tspgpu_nn_all_timed(m->ctx[i], mine[i].data(), (int)mine[i].size(), time_left_s, l.path.data(), &l.cost, &st, &l.done);
-        if (l.rc && l.rc != E_DEADLINE) return l.rc;
-        if (st >= 0) {
-            for (size_t k = 0; k < mine[i].size(); k++)
-                if (mine[i][k] == st) { l.pos = (long)k * G + i; break; }
-            l.start = st;
-        }
-        return l.rc;
+    Local T;
+    const int rc = sharded(m, starts, nstarts, best_path, best_cost, best_start, &T, [&](tspgpu_ctx *ctx, const int *list, int count, Local &l) {
+        return tspgpu_nn_all_timed(ctx, list, count, time_left_s, l.path.data(), &l.cost, &l.start, &l.done);
     });
-    m->last_solve_s = now_s() - t0;
-    if (rc) return rc;
-    int owner = -1;
-    long pos = -1;
-    double cost = DBL_MAX;
-    if ((rc = exchange(m, L, n, best_path, &cost, &pos, &owner))) return rc;
-    bool late = false;
-    int done = 0;
-    for (const Local &l : L) { late |= l.rc == E_DEADLINE; done += l.done; }
-    *best_cost = owner >= 0 ? cost : DBL_MAX;
-    *best_start = owner >= 0 ? L[owner].start : -1;
-    if (done_starts) *done_starts = done;
-    return late ? E_DEADLINE : E_OK;
+    if (rc && rc != E_DEADLINE) return rc;
+    if (done_starts) *done_starts = T.done;
+    return rc;
 }
 
 } // extern "C"
