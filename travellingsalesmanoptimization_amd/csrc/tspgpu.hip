@@ -3106,7 +3106,114 @@ __global__ void k_cap_now(Tours S, int slot0, int count)
 // ===========================================================================
 struct GraphEntry { int slot0, ntours, tabu, K; hipGraphExec_t exec; };
 
-struct tspgpu_ctx {
+// ---- the memory of a context, by its four lifetimes ---------------------------------------------------------
+// A group frees what it holds when it is reset and when the context is deleted.  Tours, Fused, M2Buf, NlBuf and HistBuf stay
+// what the kernels take by value, structs of raw pointers; each has ONE table of rows (tspgpu_mem.h) or a tuple of owners
+// next to it, and allocation, fill, copy and free all go through that.
+#include "tspgpu_hipmem.h"
+using tspmem::Row; using tspmem::Rows;
+#define MEM_GROUP __attribute__((visibility("hidden")))     // (see tspgpu_mem.h)
+
+struct MEM_GROUP ContextMem {             // until tspgpu_destroy: allocated on first use, grown or replaced in place
+    DevBuf<int> d_flags;
+    DevBuf<double2> d_pts;      // replaced by tspgpu_set_points
+    DevBuf<int2> d_ipts;        // ceil_int(): the coordinates as integers relative to the bounding box's corner (k_sweep_otf8<KIND_CEIL_INT>)
+    DevBuf<double2> d_spts;     // gathered successor points (ensure_spts)
+    PinBuf<int> h_ord;          // pinned staging of load_path
+    DevBuf<double> d_trace;     // tabu / VNS cost trace
+    HistBuf hist{nullptr, nullptr, nullptr, 0};     // (a view the resident descent advances; the owners hold the arrays)
+    DevBuf<int> hist_a, hist_b; DevBuf<double> hist_d;
+    DevBuf<unsigned long long> d_stamps;
+    DevBuf<u64> d_lp_slots; PinBuf<int> h_lp;       // LDS-resident descent: exchange slots, the control words behind them
+    DevBuf<int> d_lp_best;      // tabu walk / VNS: the best tour by array cell [ld], its direction and flag [2]
+    DevBuf<int> d_vns_rand;     // VNS: the caller's rand() values of a launch
+    DevBuf<OrCtl> d_or;         // control block of the single-tour Or-opt
+    DevBuf<M2Ctl> d_m2;         // ... of the parallel-move 2-opt
+};
+
+struct MEM_GROUP InstanceMem {            // of one n: new_instance drops it
+    // parallel-move 2-opt (tspgpu_multi2opt.inc): the candidate arrays of the slot a descent runs on, on first use
+    M2Buf m2{};
+    // batched neighbour-list descent (tspgpu_nlbatch.inc): the candidate arrays and a control block per slot of a range of nlb_cap
+    // slots; all of them allocated at the first batched call, or none
+    M2Buf nlb{};
+    NlbCtl *d_nlb_ctl = nullptr;
+    int nlb_cap = 0;
+    // uniform grid over the points for the grid NN (k_nn_grid): built on the host in tspgpu_set_points
+    DevBuf<double2> d_gxy; DevBuf<int> d_gidx, d_gpos, d_cstart, d_gcell;
+    DevBuf<unsigned> d_knn;     // [n][NN_K] neighbour lists of k_nn_grid's KNN form (built at the first single-tour NN)
+    int grid_G = 0; bool grid_ok = false;
+
+    static Rows m2_rows(M2Buf &B, size_t n)
+    {
+        return {{&B.raw_d, n * 8}, {&B.raw_b, n * 4}, {&B.d, n * 8}, {&B.a, n * 4}, {&B.b, n * 4}, {&B.i, n * 4}, {&B.j, n * 4}, {&B.acc, n * 4}};
+    }
+    Rows nlb_rows(size_t n) { Rows r = m2_rows(nlb, n); r.push_back({&d_nlb_ctl, sizeof(NlbCtl)}); return r; }     // per slot
+    void drop_nlb() { tspmem::free_rows<HipMem>(nlb_rows(0)); nlb_cap = 0; }
+    void drop_grid() { tspmem::reset_all(d_gxy, d_gidx, d_gpos, d_cstart, d_gcell, d_knn); grid_G = 0; grid_ok = false; }
+    void reset() { tspmem::free_rows<HipMem>(m2_rows(m2, 0)); drop_nlb(); drop_grid(); }
+    ~InstanceMem() { reset(); }
+};
+
+struct MEM_GROUP CostMem {                // of one cost source: free_matrix drops it
+    DevBuf<void> d_mat;         // [n][ld] cells of the kind in `elem`; empty in matrix-free mode
+    // neighbour-list 2-opt (tspgpu_nl2opt.inc): the lists of the cost source in place (tspgpu_neighbours_build)
+    NlBuf nl{};
+    DevBuf<int> nl_node; DevBuf<double> nl_w;
+    void drop_nl() { tspmem::reset_all(nl_node, nl_w); nl = NlBuf{}; }
+    void reset() { drop_nl(); d_mat.reset(); }
+};
+
+struct MEM_GROUP SlotMem {                // of one slot capacity: ensure_tours replaces it as a whole, a new instance drops it
+    int tcap = 0;
+    Tours S{};
+    int *d_starts = nullptr, *d_caps = nullptr;
+    int *h_status = nullptr;    // pinned: done[tcap] then nsweeps[tcap]
+    double *h_costs = nullptr;  // pinned [tcap]
+    OrCtl *d_or_ctl = nullptr;  // Or-opt over a batch of tours: one control block per slot
+    // the list of slots a launch of a batched descent works on (device, and its pinned staging): [tcap], either family's
+    int *d_live = nullptr, *h_live = nullptr;
+    // tabu, sized by n: allocated with the first slots and kept when they grow
+    int *d_tabu_list = nullptr, *d_best_succ = nullptr;
+    TabuState *d_tabu = nullptr;
+    Fused F{};                  // fused path state (allocated on first use, capacity fcap)
+    int fcap = 0;
+
+    // per slot; new slots are zero-filled (no sweep cap: 0xff) and the old ones copied
+    Rows tour_rows(size_t n, size_t pstride)
+    {
+        const size_t slack = 64;    // vector reads of the last tour's tail (load_run)
+        const int none = Row::NO_FILL; const bool keep = true, pinned = true;
+        return {{&S.ord, n * 4, slack * 4, 0, keep}, {&S.pos, n * 4, slack * 4, 0, keep}, {&S.succ, n * 4, slack * 4, 0, keep},
+                {&S.dpos, n * 8, slack * 8, 0, keep}, {&S.dnb, n * 8, slack * 8, 0, keep},
+                {&S.dir, 4, 0, 0, keep}, {&S.cost, 8, 0, 0, keep}, {&S.last_delta, 8, 0, 0, keep}, {&S.done, 4, 0, 0, keep},
+                {&S.nsweeps, 4, 0, 0, keep}, {&S.cap_sweeps, 4, 0, 0xff, keep}, {&S.status, 4, 0, 0, keep},
+                {&S.partial, pstride * sizeof(Partial)},
+                {&d_starts, 4}, {&d_caps, 4},
+                {&d_tabu_list, 0, (n + 64) * 4},    // + slack: the sweeps read it with 16-byte vectors up to ld
+                {&d_best_succ, 0, n * 4}, {&d_tabu, 0, sizeof(TabuState)},
+                {&h_status, 4 * 2, 0, none, !keep, pinned}, {&h_costs, 8, 0, none, !keep, pinned},
+                {&d_or_ctl, sizeof(OrCtl)},         // (armed at the start of every batched Or-opt phase)
+                {&d_live, 4}, {&h_live, 4, 0, none, !keep, pinned}};
+    }
+    Rows fused_rows(size_t n, size_t pstride)
+    {
+        const size_t slack = 64;
+        Rows r;
+        for (int p = 0; p < 2; p++)
+            r.insert(r.end(), {{&F.ord[p], n * 4, slack * 4}, {&F.pos[p], n * 4, slack * 4, 0}, {&F.nl[p], n * 4, slack * 4, 0},
+                               {&F.nr[p], n * 4, slack * 4, 0}, {&F.dl[p], n * 8, slack * 8, 0}, {&F.dr[p], n * 8, slack * 8, 0},
+                               {&F.dir[p], 4}, {&F.k[p], 4}, {&F.stop[p], 4}, {&F.cost[p], 8}, {&F.partial[p], pstride * sizeof(Partial)}});
+        r.insert(r.end(), {{&F.cur, 4}, {&F.bestkey, 4 * 8},
+                           {&F.payload[0], pstride * 16 * 4}, {&F.payload[1], pstride * 16 * 4}});      // 16 ints per workgroup record
+        return r;
+    }
+    void drop_fused() { tspmem::free_rows<HipMem>(fused_rows(0, 0)); fcap = 0; }
+    void reset() { tspmem::free_rows<HipMem>(tour_rows(0, 0)); drop_fused(); S.pstride = 0; tcap = 0; }
+    ~SlotMem() { reset(); }
+};
+
+struct tspgpu_ctx : ContextMem, InstanceMem, CostMem, SlotMem {
     int device = 0;
     hipStream_t stream = nullptr;
     int cus = 256;
@@ -3122,45 +3229,23 @@ struct tspgpu_ctx {
     bool have_points = false, have_costs = false, symmetric = true;
     bool built = false;      // the matrix (or the matrix-free mode) comes from tspgpu_build_costs, not from a caller
     int elem = 0; // TSPGPU_ELEM_F64 / _I32 / _U16 in use
-    double2 *d_pts = nullptr;
-    void *d_mat = nullptr;   // [n][ld] cells of the kind in `elem`; nullptr in matrix-free mode
     bool otf = false;        // matrix-free: weights recomputed from d_pts
     int opt_otf = 0;         // 0 auto, 1 force matrix-free, 2 never
-    double2 *d_spts = nullptr; size_t spts_cap = 0;
-    int2 *d_ipts = nullptr;  // ceil_int(): the coordinates as integers relative to the bounding box's corner (k_sweep_otf8<KIND_CEIL_INT>)
-    // uniform grid over the points for the grid NN (k_nn_grid): built on the host in tspgpu_set_points
-    double2 *d_gxy = nullptr; int *d_gidx = nullptr, *d_gpos = nullptr, *d_cstart = nullptr, *d_gcell = nullptr;
-    unsigned *d_knn = nullptr;   // [n][NN_K] neighbour lists of k_nn_grid's KNN form (built at the first single-tour NN)
-    int grid_G = 0, grid_max_occ = 0; bool grid_ok = false;
+    int grid_max_occ = 0;
     double grid_x0 = 0, grid_y0 = 0, grid_cell = 1, grid_inv = 0, grid_eps = 0;
     int opt_nn = 0;          // 0 auto, 1 matrix / strided kernels, 2 grid kernel
     double cost_bound = 0;   // upper bound of any entry the uploaded points can produce
     bool int_coords = false; // every coordinate an integer below 2^25 in magnitude
     bool ceil_int() const { return kind == TSPGPU_CEIL_2D && int_coords && cost_bound < 4194304.0; }   // edge_w<KIND_CEIL_INT> applies
-    int *d_flags = nullptr;
 
     // tours
-    int tcap = 0;
-    Tours S{};
     std::vector<unsigned char> slot_valid;   // [tcap] host side: the slot holds a complete tour state
-    int *d_starts = nullptr, *d_caps = nullptr;
-    int *h_status = nullptr; // pinned: done[tcap] then nsweeps[tcap]
-    double *h_costs = nullptr; // pinned [tcap]
-    int *h_ord = nullptr; size_t h_ord_n = 0; hipEvent_t ev_ord = nullptr; bool ord_pending = false;   // pinned staging of load_path
-
-    // tabu
-    int *d_tabu_list = nullptr, *d_best_succ = nullptr;
-    TabuState *d_tabu = nullptr;
-    double *d_trace = nullptr; int trace_cap = 0;
-
-    // history
-    HistBuf hist{nullptr, nullptr, nullptr, 0};
+    hipEvent_t ev_ord = nullptr; bool ord_pending = false;   // guards the reuse of h_ord
 
     // launch plan
     int plan_kernel = 0, plan_G = 0, plan_P = 0, plan_BT = 0, plan_NCH = 0, plan_D = 0, plan_T = 0;
     int opt_depth = 0, opt_ablate = 0, opt_stamps = 0;
     bool plan_tabu_fits = true;   // the tabu variants' extra n + 32 LDS bytes fit beside the rows
-    unsigned long long *d_stamps = nullptr;
     size_t plan_lds = 0;
     size_t plan_lds_fused = 0;  // dynamic LDS of the one-launch-per-sweep kernel (four row buffers in its two-edge streaming form)
     bool plan_pipe2 = false;    // the fused pipelined kernel streams two tour edges per barrier interval (pipe_stream2)
@@ -3183,9 +3268,7 @@ struct tspgpu_ctx {
     int opt_lp_poll_sleep = 0;  // probe hook 95
     int opt_vns_launch_k = 65536;   // VNS iterations a launch may complete (test hook 94 lowers it to force relaunches)
     int opt_lp_fail_at = 0;     // test hook 96: the next N RE-launches of a descent (deadline runs relaunch per sweep budget) fail their rendezvous
-    u64 *d_lp_slots = nullptr; int *h_lp = nullptr;   // (the control words sit behind the slots)
-    int *d_lp_best = nullptr; int lp_best_n = 0;      // tabu walk / VNS: the best tour by array cell [ld], its direction and flag [2]
-    int *d_vns_rand = nullptr; long vns_rand_cap = 0; int vns_launch_nrand = 0;   // VNS: the caller's rand() values of a launch
+    int vns_launch_nrand = 0;   // VNS: the caller's rand() values of a launch
     int lp_skip = 0, lp_backoff = 16;   // the grid did not come up co-resident: the next lp_skip descents keep to the one-launch-per-sweep
                                         // path, then it is tried again (16, 32, ... 1024 descents apart while it keeps failing)
     bool lp_used = false;      // the last descent ran in k_lds2opt
@@ -3206,11 +3289,6 @@ struct tspgpu_ctx {
     long em_stale = 0, em_steps = 0;   // stale rescans and insertions of the last construction
 
     // Or-opt (tspgpu_oropt.inc)
-    OrCtl *d_or = nullptr;     // control block, allocated on first use
-    // ... over a batch of tours: one control block per slot
-    OrCtl *d_or_ctl = nullptr;
-    // the list of slots a launch of a batched descent works on (device, and its pinned staging): [tcap], either family's
-    int *d_live = nullptr, *h_live = nullptr;
     int or_batch_R = 0;        // positions per sweep workgroup in the first Or-opt round of the last batched descent
     // ... in matrix-free mode (k_oropt_sweep_otf): single tours only
     int opt_or_otf = 0;        // TSPGPU_OPT_OR_MATRIX_FREE: 0 refuse Or-opt in matrix-free mode (code 12), 1 run it from the points
@@ -3218,27 +3296,18 @@ struct tspgpu_ctx {
     int or_otf_form = 0;       // how the last matrix-free Or-opt sweep ran: 0 none, 1 every candidate, 2 with the early-out
     int or_otf_R = 0;          // its tour positions per workgroup
 
-    // parallel-move 2-opt (tspgpu_multi2opt.inc): control block and the candidate arrays of the slot a descent runs on, on first use
-    M2Ctl *d_m2 = nullptr;
-    M2Buf m2{};
+    // parallel-move 2-opt (tspgpu_multi2opt.inc)
     long m2_sweeps = 0, m2_moves = 0, m2_max_k = 0;    // the last parallel-move descent
 
-    // neighbour-list 2-opt (tspgpu_nl2opt.inc): the lists of the cost source in place (tspgpu_neighbours_build)
-    NlBuf nl{};
+    // neighbour-list 2-opt (tspgpu_nl2opt.inc)
     bool nl_dropped = false;   // a new cost source took the lists away (the refusal says so)
     long nl_sweeps = 0, nl_moves = 0, nl_polish_sweeps = 0;     // the last neighbour-list phase and its polish
     // neighbour-list Or-opt (tspgpu_ornl.inc): the last call's sweeps, moves and largest sweep (a descent: over its rounds)
     long ornl_sweeps = 0, ornl_moves = 0, ornl_max_k = 0;
     int ornl_rounds = 0;       // rounds of the last tspgpu_local_search_nl
-    // batched neighbour-list descent (tspgpu_nlbatch.inc): the candidate arrays and a control block per slot of a range of nlb_cap
-    // slots; all of them allocated at the first batched call, or none
-    M2Buf nlb{};
-    NlbCtl *d_nlb_ctl = nullptr;
-    int nlb_cap = 0;
+    // batched neighbour-list descent (tspgpu_nlbatch.inc)
     long nlb_tours = 0, nlb_launches = 0, nlb_max_live = 0;     // the last batched descent: tours, sweeps launched, most tours in one
 
-    Fused F{};                 // fused path state (allocated on first use, capacity fcap)
-    int fcap = 0;
     int opt_fused = 1;         // 1 = one launch per sweep where applicable
 
     std::vector<GraphEntry> graphs;
@@ -3270,171 +3339,42 @@ static void drop_graphs(tspgpu_ctx *ctx)
     ctx->graphs.clear();
 }
 
-static void free_nl(tspgpu_ctx *ctx)
-{
-    if (ctx->nl.node) hipFree(ctx->nl.node);
-    if (ctx->nl.w) hipFree(ctx->nl.w);
-    memset(&ctx->nl, 0, sizeof ctx->nl);
-}
-
 static void free_matrix(tspgpu_ctx *ctx)
 {
     if (ctx->nl.K) ctx->nl_dropped = true;  // the neighbour lists belong to the old costs
-    free_nl(ctx);
-    if (ctx->d_mat) hipFree(ctx->d_mat);
-    ctx->d_mat = nullptr; ctx->have_costs = false;
+    ctx->CostMem::reset();
+    ctx->have_costs = false;
     ctx->or_otf_form = ctx->or_otf_R = 0;
     std::fill(ctx->slot_valid.begin(), ctx->slot_valid.end(), 0);   // the slots' edge costs belong to the old matrix
     drop_graphs(ctx);
 }
 
-static void free_fused(tspgpu_ctx *ctx)
+// room for `count` elements in a buffer whose address captured launches hold
+template <class BUF> static int reserve_captured(tspgpu_ctx *ctx, BUF &buf, size_t count)
 {
-    Fused &F = ctx->F;
-    for (int p = 0; p < 2; p++) {
-        void *fp[] = {F.ord[p], F.pos[p], F.nl[p], F.nr[p], F.dl[p], F.dr[p], F.dir[p], F.k[p], F.stop[p], F.cost[p], F.partial[p]};
-        for (void *q : fp) if (q) hipFree(q);
-    }
-    if (F.cur) hipFree(F.cur);
-    if (F.bestkey) hipFree(F.bestkey);
-    for (int p = 0; p < 2; p++) if (F.payload[p]) hipFree(F.payload[p]);
-    memset(&F, 0, sizeof F);
-    ctx->fcap = 0;
-}
-
-static void free_tour_arrays(Tours &S)
-{
-    void *ptrs[] = {S.ord, S.pos, S.succ, S.dpos, S.dnb, S.cost, S.last_delta, S.dir, S.done, S.nsweeps, S.cap_sweeps, S.status, S.partial};
-    for (void *p : ptrs) if (p) hipFree(p);
-    memset(&S, 0, sizeof S);
-}
-
-// per-capacity scratch next to the slots (start lists, pinned status words)
-static void free_tour_scratch(tspgpu_ctx *ctx)
-{
-    if (ctx->d_starts) hipFree(ctx->d_starts);
-    if (ctx->d_caps) hipFree(ctx->d_caps);
-    if (ctx->h_status) hipHostFree(ctx->h_status);
-    if (ctx->h_costs) hipHostFree(ctx->h_costs);
-    if (ctx->d_or_ctl) hipFree(ctx->d_or_ctl);
-    if (ctx->d_live) hipFree(ctx->d_live);
-    if (ctx->h_live) hipHostFree(ctx->h_live);
-    ctx->d_starts = ctx->d_caps = nullptr; ctx->h_status = nullptr; ctx->h_costs = nullptr;
-    ctx->d_or_ctl = nullptr; ctx->d_live = ctx->h_live = nullptr;
-}
-
-static void free_grid(tspgpu_ctx *ctx)
-{
-    void *ptrs[] = {ctx->d_gxy, ctx->d_gidx, ctx->d_gpos, ctx->d_cstart, ctx->d_gcell, ctx->d_knn};
-    for (void *p : ptrs) if (p) hipFree(p);
-    ctx->d_gxy = nullptr; ctx->d_gidx = ctx->d_gpos = ctx->d_cstart = ctx->d_gcell = nullptr; ctx->d_knn = nullptr;
-    ctx->grid_G = 0; ctx->grid_ok = false;
-}
-
-static void free_m2(tspgpu_ctx *ctx)
-{
-    void *ptrs[] = {ctx->m2.raw_d, ctx->m2.raw_b, ctx->m2.d, ctx->m2.a, ctx->m2.b, ctx->m2.i, ctx->m2.j, ctx->m2.acc};
-    for (void *p : ptrs) if (p) hipFree(p);
-    memset(&ctx->m2, 0, sizeof ctx->m2);
-}
-
-static void free_nlb(tspgpu_ctx *ctx)
-{
-    void *ptrs[] = {ctx->nlb.raw_d, ctx->nlb.raw_b, ctx->nlb.d, ctx->nlb.a, ctx->nlb.b, ctx->nlb.i, ctx->nlb.j, ctx->nlb.acc, ctx->d_nlb_ctl};
-    for (void *p : ptrs) if (p) hipFree(p);
-    memset(&ctx->nlb, 0, sizeof ctx->nlb);
-    ctx->d_nlb_ctl = nullptr;
-    ctx->nlb_cap = 0;
-}
-
-static void free_tours(tspgpu_ctx *ctx)
-{
-    free_tour_arrays(ctx->S);
-    free_m2(ctx);              // sized by n
-    free_nlb(ctx);             // sized by n and a slot count
-    free_tour_scratch(ctx);
-    void *ptrs[] = {ctx->d_tabu_list, ctx->d_best_succ, ctx->d_tabu};
-    for (void *p : ptrs) if (p) hipFree(p);
-    ctx->d_tabu_list = ctx->d_best_succ = nullptr; ctx->d_tabu = nullptr;
-    free_fused(ctx);
-    ctx->tcap = 0;
-    ctx->slot_valid.clear();
+    if (count <= buf.n) return E_OK;
     drop_graphs(ctx);
+    HIP_TRY(buf.reserve(count));
+    return E_OK;
 }
 
 // Tour slots [0, want).  Growing keeps the contents of the slots that exist (a tour loaded into slot 0 survives a
 // later tspgpu_tour_nn(20) or a multi-start); new slots are zero-filled and marked invalid until something is
 // loaded / built / copied into them (slot_valid: the slot entry points answer FAILED_PRECONDITION otherwise).
+// All or none: a failed allocation leaves the capacity, every array, the fused state and the captured graphs as they were.
 static int ensure_tours(tspgpu_ctx *ctx, int want)
 {
     if (want <= ctx->tcap) return E_OK;
     want = std::max(want, 16);
-    const int n = ctx->n;
-    const size_t T = (size_t)want, N = (size_t)n, O = (size_t)ctx->tcap;
-    Tours S{};
-    const size_t slack = 64; // vector reads of the last tour's tail (load_run)
-    HIP_TRY(hipMalloc(&S.ord, (T * N + slack) * 4));
-    HIP_TRY(hipMalloc(&S.pos, (T * N + slack) * 4));
-    HIP_TRY(hipMalloc(&S.succ, (T * N + slack) * 4));
-    HIP_TRY(hipMalloc(&S.dpos, (T * N + slack) * 8));
-    HIP_TRY(hipMalloc(&S.dnb, (T * N + slack) * 8));
-    HIP_TRY(hipMemsetAsync(S.ord, 0, (T * N + slack) * 4, ctx->stream));
-    HIP_TRY(hipMemsetAsync(S.pos, 0, (T * N + slack) * 4, ctx->stream));
-    HIP_TRY(hipMemsetAsync(S.succ, 0, (T * N + slack) * 4, ctx->stream));
-    HIP_TRY(hipMemsetAsync(S.dpos, 0, (T * N + slack) * 8, ctx->stream));
-    HIP_TRY(hipMemsetAsync(S.dnb, 0, (T * N + slack) * 8, ctx->stream));
-    HIP_TRY(hipMalloc(&S.dir, T * 4));
-    HIP_TRY(hipMalloc(&S.cost, T * 8));
-    HIP_TRY(hipMalloc(&S.last_delta, T * 8));
-    HIP_TRY(hipMalloc(&S.done, T * 4));
-    HIP_TRY(hipMalloc(&S.nsweeps, T * 4));
-    HIP_TRY(hipMalloc(&S.cap_sweeps, T * 4));
-    HIP_TRY(hipMalloc(&S.status, T * 4));
-    HIP_TRY(hipMemsetAsync(S.dir, 0, T * 4, ctx->stream));
-    HIP_TRY(hipMemsetAsync(S.cost, 0, T * 8, ctx->stream));
-    HIP_TRY(hipMemsetAsync(S.last_delta, 0, T * 8, ctx->stream));
-    HIP_TRY(hipMemsetAsync(S.done, 0, T * 4, ctx->stream));
-    HIP_TRY(hipMemsetAsync(S.nsweeps, 0, T * 4, ctx->stream));
-    HIP_TRY(hipMemsetAsync(S.cap_sweeps, 0xff, T * 4, ctx->stream));
-    HIP_TRY(hipMemsetAsync(S.status, 0, T * 4, ctx->stream));
-    S.pstride = std::max(MAX_WGS_PER_TOUR, (n + 7) / 8 + 8); // the matrix-free sweep runs n/8 workgroups per tour
-    HIP_TRY(hipMalloc(&S.partial, T * (size_t)S.pstride * sizeof(Partial)));
-    if (O) {
-        const Tours &P = ctx->S;
-        const hipMemcpyKind dd = hipMemcpyDeviceToDevice;
-        HIP_TRY(hipMemcpyAsync(S.ord, P.ord, O * N * 4, dd, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(S.pos, P.pos, O * N * 4, dd, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(S.succ, P.succ, O * N * 4, dd, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(S.dpos, P.dpos, O * N * 8, dd, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(S.dnb, P.dnb, O * N * 8, dd, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(S.dir, P.dir, O * 4, dd, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(S.cost, P.cost, O * 8, dd, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(S.last_delta, P.last_delta, O * 8, dd, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(S.done, P.done, O * 4, dd, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(S.nsweeps, P.nsweeps, O * 4, dd, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(S.cap_sweeps, P.cap_sweeps, O * 4, dd, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(S.status, P.status, O * 4, dd, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        free_tour_arrays(ctx->S);
-        free_tour_scratch(ctx);
-        free_fused(ctx);          // sized by the slot count; only live inside a run
+    const int pstride = std::max(MAX_WGS_PER_TOUR, (ctx->n + 7) / 8 + 8); // the matrix-free sweep runs n/8 workgroups per tour
+    HIP_TRY(tspmem::grow(HipMem{ctx->stream}, ctx->tour_rows((size_t)ctx->n, (size_t)pstride), (size_t)ctx->tcap, (size_t)want));
+    ctx->S.pstride = pstride;
+    if (ctx->tcap) {
+        ctx->drop_fused();        // sized by the slot count; only live inside a run
         drop_graphs(ctx);         // captured launches hold the old pointers
     }
-    ctx->S = S;
-    HIP_TRY(hipMalloc(&ctx->d_starts, T * 4));
-    HIP_TRY(hipMalloc(&ctx->d_caps, T * 4));
-    if (!ctx->d_tabu_list) {
-        HIP_TRY(hipMalloc(&ctx->d_tabu_list, (N + 64) * 4));   // + slack: the sweeps read it with 16-byte vectors up to ld
-        HIP_TRY(hipMalloc(&ctx->d_best_succ, N * 4));
-        HIP_TRY(hipMalloc(&ctx->d_tabu, sizeof(TabuState)));
-    }
-    HIP_TRY(hipHostMalloc(&ctx->h_status, T * 4 * 2));
-    HIP_TRY(hipHostMalloc(&ctx->h_costs, T * 8));
-    HIP_TRY(hipMalloc(&ctx->d_or_ctl, T * sizeof(OrCtl)));     // (armed at the start of every batched Or-opt phase)
-    HIP_TRY(hipMalloc(&ctx->d_live, T * 4));
-    HIP_TRY(hipHostMalloc(&ctx->h_live, T * 4));
     ctx->tcap = want;
-    ctx->slot_valid.resize(T, 0);
+    ctx->slot_valid.resize((size_t)want, 0);
     return E_OK;
 }
 
@@ -3467,8 +3407,10 @@ static int new_instance(tspgpu_ctx *ctx, int n)
     if (n < 4) return fail(ctx, E_INVALID, "need at least 4 nodes, got %d", n);
     if (n > 131072) return fail(ctx, E_INVALID, "n = %d: at most 131072 nodes", n);
     free_matrix(ctx);
-    free_tours(ctx);
-    free_grid(ctx);            // the grid is the old points' (tspgpu_set_points builds the new one)
+    ctx->SlotMem::reset();
+    ctx->InstanceMem::reset(); // (the grid is the old points': tspgpu_set_points builds the new one)
+    ctx->slot_valid.clear();
+    drop_graphs(ctx);
     ctx->grid_max_occ = 0;
     ctx->n = n;
     ctx->ld = (n + 31) & ~31; // rows 128-byte aligned for both element kinds
@@ -3495,7 +3437,7 @@ static size_t elem_size(int elem) { return elem == TSPGPU_ELEM_F64 ? 8 : elem ==
 template <typename F> static void kind_switch(const tspgpu_ctx *ctx, F &&f)
 {
     double2 *const pts = ctx->d_pts, *const spts = ctx->d_spts;
-    if (ctx->ceil_int() && ctx->d_ipts) f(std::integral_constant<int, KIND_CEIL_INT>{}, ctx->d_ipts, reinterpret_cast<int2 *>(spts));
+    if (ctx->ceil_int() && ctx->d_ipts) f(std::integral_constant<int, KIND_CEIL_INT>{}, ctx->d_ipts.p, reinterpret_cast<int2 *>(spts));
     else if (ctx->kind == TSPGPU_EUC_2D) f(std::integral_constant<int, TSPGPU_EUC_2D>{}, pts, spts);
     else if (ctx->kind == TSPGPU_ATT) f(std::integral_constant<int, TSPGPU_ATT>{}, pts, spts);
     else f(std::integral_constant<int, TSPGPU_CEIL_2D>{}, pts, spts);
@@ -3504,11 +3446,7 @@ template <typename F> static void kind_switch(const tspgpu_ctx *ctx, F &&f)
 // room for `points` gathered successor points
 static int ensure_spts(tspgpu_ctx *ctx, size_t points)
 {
-    if (ctx->spts_cap >= points) return E_OK;
-    if (ctx->d_spts) hipFree(ctx->d_spts);
-    ctx->d_spts = nullptr; ctx->spts_cap = 0;
-    HIP_TRY(hipMalloc(&ctx->d_spts, points * sizeof(double2)));
-    ctx->spts_cap = points;
+    HIP_TRY(ctx->d_spts.reserve(points));
     return E_OK;
 }
 
@@ -3852,8 +3790,8 @@ static int launch_sweep(tspgpu_ctx *ctx, int slot0, int ntours, bool tabu, int g
         const int n = ctx->n;
         const bool otf8 = ctx->cost_bound < 33554432.0 && n < 131072;
         if (otf8 && ctx->ceil_int() && ctx->d_ipts) {      // (the int2 successors' points take the front half of the double2 buffer)
-            A.ipts = ctx->d_ipts; A.ispts = reinterpret_cast<const int2 *>(ctx->d_spts);
-            hipLaunchKernelGGL(k_gather_ispts, dim3((n + 255) / 256, ntours), dim3(256), 0, ctx->stream, ctx->S, n, slot0, ctx->d_ipts, reinterpret_cast<int2 *>(ctx->d_spts));
+            A.ipts = ctx->d_ipts; A.ispts = reinterpret_cast<const int2 *>(ctx->d_spts.p);
+            hipLaunchKernelGGL(k_gather_ispts, dim3((n + 255) / 256, ntours), dim3(256), 0, ctx->stream, ctx->S, n, slot0, ctx->d_ipts, reinterpret_cast<int2 *>(ctx->d_spts.p));
         } else
             hipLaunchKernelGGL(k_gather_spts, dim3((n + 255) / 256, ntours), dim3(256), 0, ctx->stream, ctx->S, n, slot0, ctx->d_pts, ctx->d_spts);
         HIP_TRY(hipGetLastError());
@@ -3930,29 +3868,7 @@ static int done_code(bool late) { return late ? E_DEADLINE : E_OK; }
 static int ensure_fused(tspgpu_ctx *ctx)
 {
     if (ctx->fcap >= ctx->tcap) return E_OK;
-    Fused &F = ctx->F;
-    const size_t T = (size_t)ctx->tcap, N = (size_t)ctx->n, slack = 64;
-    for (int p = 0; p < 2; p++) {
-        HIP_TRY(hipMalloc(&F.ord[p], (T * N + slack) * 4));
-        HIP_TRY(hipMalloc(&F.pos[p], (T * N + slack) * 4));
-        HIP_TRY(hipMalloc(&F.nl[p], (T * N + slack) * 4));
-        HIP_TRY(hipMalloc(&F.nr[p], (T * N + slack) * 4));
-        HIP_TRY(hipMalloc(&F.dl[p], (T * N + slack) * 8));
-        HIP_TRY(hipMalloc(&F.dr[p], (T * N + slack) * 8));
-        HIP_TRY(hipMalloc(&F.dir[p], T * 4));
-        HIP_TRY(hipMalloc(&F.k[p], T * 4));
-        HIP_TRY(hipMalloc(&F.stop[p], T * 4));
-        HIP_TRY(hipMalloc(&F.cost[p], T * 8));
-        HIP_TRY(hipMalloc(&F.partial[p], T * (size_t)ctx->S.pstride * sizeof(Partial)));
-        HIP_TRY(hipMemsetAsync(F.pos[p], 0, (T * N + slack) * 4, ctx->stream));
-        HIP_TRY(hipMemsetAsync(F.nl[p], 0, (T * N + slack) * 4, ctx->stream));
-        HIP_TRY(hipMemsetAsync(F.nr[p], 0, (T * N + slack) * 4, ctx->stream));
-        HIP_TRY(hipMemsetAsync(F.dl[p], 0, (T * N + slack) * 8, ctx->stream));
-        HIP_TRY(hipMemsetAsync(F.dr[p], 0, (T * N + slack) * 8, ctx->stream));
-    }
-    HIP_TRY(hipMalloc(&F.cur, T * 4));
-    HIP_TRY(hipMalloc(&F.bestkey, T * 4 * 8));
-    for (int p = 0; p < 2; p++) HIP_TRY(hipMalloc(&F.payload[p], T * (size_t)ctx->S.pstride * 16 * 4));   // 16 ints per workgroup record
+    HIP_TRY(tspmem::grow(HipMem{ctx->stream}, ctx->fused_rows((size_t)ctx->n, (size_t)ctx->S.pstride), 0, (size_t)ctx->tcap));
     ctx->fcap = ctx->tcap;
     return E_OK;
 }
@@ -4197,16 +4113,9 @@ static int run_persist(tspgpu_ctx *ctx, int slot, double *time_left_io, bool *de
         win = true;
     }
     if (ctx->lp_skip > 0) { ctx->lp_skip--; return E_OK; }
-    if (!ctx->d_lp_slots) {
-        HIP_TRY(hipMalloc(&ctx->d_lp_slots, (size_t)2 * LP_BT * 64 + 64));      // exchange slots, then the control words
-        HIP_TRY(hipHostMalloc(&ctx->h_lp, 64));
-    }
-    if ((tabu || vns) && ctx->lp_best_n < ctx->ld) {
-        if (ctx->d_lp_best) hipFree(ctx->d_lp_best);
-        ctx->d_lp_best = nullptr; ctx->lp_best_n = 0;
-        HIP_TRY(hipMalloc(&ctx->d_lp_best, ((size_t)ctx->ld + 16) * 4));
-        ctx->lp_best_n = ctx->ld;
-    }
+    HIP_TRY(ctx->d_lp_slots.reserve(((size_t)2 * LP_BT * 64 + 64) / 8));   // exchange slots, then the control words
+    HIP_TRY(ctx->h_lp.reserve(16));
+    if (tabu || vns) HIP_TRY(ctx->d_lp_best.reserve((size_t)ctx->ld + 16));
     const int pk = (tabu ? ctx->max8k : ctx->max16k) ? 1 : 0;
     const void *fn = win ? (tabu ? (pk ? (const void *)k_lds2opt_w<true, true> : (const void *)k_lds2opt_w<false, true>)
                                  : vns ? (pk ? (const void *)k_lds2opt_w<true, false, true> : (const void *)k_lds2opt_w<false, false, true>)
@@ -4250,25 +4159,14 @@ static int run_persist(tspgpu_ctx *ctx, int slot, double *time_left_io, bool *de
             // kick + the rejected ones, 8 on average; the kernel stops in front of a kick phase it cannot finish)
             vns_launch_k = std::min(vns->k - vns->it, ctx->opt_vns_launch_k);
             const long want = std::min<long>(vns->nrand - vns->used, 32L * vns_launch_k + 1024);
-            if (want > ctx->vns_rand_cap) {
-                if (ctx->d_vns_rand) hipFree(ctx->d_vns_rand);
-                ctx->d_vns_rand = nullptr; ctx->vns_rand_cap = 0;
-                HIP_TRY(hipMalloc(&ctx->d_vns_rand, (size_t)(want + 64) * 4));
-                ctx->vns_rand_cap = want;
-            }
+            if (want > 0) HIP_TRY(ctx->d_vns_rand.reserve((size_t)want + 64));
             if (want > 0) HIP_TRY(hipMemcpyAsync(ctx->d_vns_rand, vns->h_rand + vns->used, (size_t)want * 4, hipMemcpyHostToDevice, ctx->stream));
-            if (vns->h_trace && vns_launch_k > ctx->trace_cap) {
-                if (ctx->d_trace) hipFree(ctx->d_trace);
-                ctx->d_trace = nullptr; ctx->trace_cap = 0;
-                HIP_TRY(hipMalloc(&ctx->d_trace, (size_t)vns_launch_k * 8));
-                ctx->trace_cap = vns_launch_k;
-                drop_graphs(ctx);
-            }
+            if (vns->h_trace) { const int rc = reserve_captured(ctx, ctx->d_trace, (size_t)vns_launch_k); if (rc) return rc; }
             ctx->vns_launch_nrand = (int)want;
         }
         PersistArgs A;
         memset(&A, 0, sizeof A);
-        A.S = ctx->S; A.mat = (const u16 *)ctx->d_mat; A.n = ctx->n; A.ld = ctx->ld; A.slot = slot;
+        A.S = ctx->S; A.mat = (const u16 *)ctx->d_mat.p; A.n = ctx->n; A.ld = ctx->ld; A.slot = slot;
         A.E = E; A.nl = (ctx->n + 7) & ~7; A.budget = budget; A.Ws = Ws; A.nstage = nstage;
         A.slots = ctx->d_lp_slots; A.ctl = d_ctl; A.hist = ctx->hist;
         A.hello_ticks = ctx->opt_lp_hello;   // 2 ms (test hook 97: negative = workgroup 0 withholds its record for that long)
@@ -4397,10 +4295,8 @@ static int run_pstream(tspgpu_ctx *ctx, int slot, double *time_left_io, bool *de
     size_t lds = 0;
     if (!stream_fits(ctx, P, W, BT, NCH, lds)) return E_OK;
     if (ctx->lp_skip > 0) { ctx->lp_skip--; return E_OK; }
-    if (!ctx->d_lp_slots) {
-        HIP_TRY(hipMalloc(&ctx->d_lp_slots, (size_t)2 * LP_BT * 64 + 64));
-        HIP_TRY(hipHostMalloc(&ctx->h_lp, 64));
-    }
+    HIP_TRY(ctx->d_lp_slots.reserve(((size_t)2 * LP_BT * 64 + 64) / 8));
+    HIP_TRY(ctx->h_lp.reserve(16));
     // (the register budget follows the block: 768 threads leave 170 registers a thread, 512 leave 256)
     const int vi = NCH == 1 ? (BT <= 768 ? 0 : 1) : (BT <= 512 ? 2 : 3);
     const void *fn = vi == 0 ? (const void *)k_str2opt<1, 768> : vi == 1 ? (const void *)k_str2opt<1, 1024>
@@ -4432,7 +4328,7 @@ static int run_pstream(tspgpu_ctx *ctx, int slot, double *time_left_io, bool *de
         HIP_TRY(hipMemsetAsync(ctx->d_lp_slots, 0, (size_t)2 * W * 64 + 64, ctx->stream));
         StreamArgs A;
         memset(&A, 0, sizeof A);
-        A.S = ctx->S; A.mat = (const u16 *)ctx->d_mat; A.n = ctx->n; A.ld = ctx->ld; A.slot = slot;
+        A.S = ctx->S; A.mat = (const u16 *)ctx->d_mat.p; A.n = ctx->n; A.ld = ctx->ld; A.slot = slot;
         A.P = P; A.budget = budget; A.poll_sleep = ctx->opt_lp_poll_sleep; A.ablate = ctx->opt_ablate;
         A.slots = ctx->d_lp_slots; A.ctl = d_ctl; A.hist = ctx->hist;
         A.hello_ticks = ctx->opt_lp_hello;
@@ -4690,7 +4586,7 @@ static int init_slots(tspgpu_ctx *ctx, int slot0, int ntours, int cap)
     }
     const int BT = std::min(1024, std::max(64, pow2_ceil(n / 4)));
     ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_tour_init<T>), dim3(ntours), dim3(BT), 0, ctx->stream, ctx->S,
-                                                 (const T *)ctx->d_mat, n, ctx->ld, slot0, caps, ctx->d_pts, ctx->kind));
+                                                 (const T *)ctx->d_mat.p, n, ctx->ld, slot0, caps, ctx->d_pts, ctx->kind));
     HIP_TRY(hipGetLastError());
     return E_OK;
 }
@@ -4711,10 +4607,9 @@ static int load_path(tspgpu_ctx *ctx, int slot, const int *path, int cap)
     // through a pinned buffer of the context: the copy is asynchronous and the call does not wait for it (an event guards
     // the buffer's reuse) -- one host synchronisation less per descent (~15 us; a VNS iteration is ~5 sweeps)
     const size_t n = (size_t)ctx->n;
-    if (ctx->h_ord_n < n) {
-        if (ctx->h_ord) { HIP_TRY(hipStreamSynchronize(ctx->stream)); hipHostFree(ctx->h_ord); ctx->h_ord = nullptr; ctx->h_ord_n = 0; }
-        HIP_TRY(hipHostMalloc(&ctx->h_ord, n * 4));
-        ctx->h_ord_n = n;
+    if (ctx->h_ord.n < n) {
+        if (ctx->h_ord) HIP_TRY(hipStreamSynchronize(ctx->stream));
+        HIP_TRY(ctx->h_ord.reserve(n));
         if (!ctx->ev_ord) HIP_TRY(hipEventCreateWithFlags(&ctx->ev_ord, hipEventDisableTiming));
         ctx->ord_pending = false;
     }
@@ -4744,7 +4639,7 @@ static int store_path(tspgpu_ctx *ctx, int slot, int *path, double *cost, double
 // keep the matrix / strided kernels.
 static int build_grid(tspgpu_ctx *ctx, const double *xy, int n, double x0, double x1, double y0, double y1)
 {
-    free_grid(ctx);
+    ctx->drop_grid();
     const double w = x1 - x0, h = y1 - y0, extent = std::max(w, h);
     if (!(extent >= 0) || !std::isfinite(extent)) return E_OK;        // NaN / inf coordinates: no grid
     int G = 1;
@@ -4788,11 +4683,8 @@ static int build_grid(tspgpu_ctx *ctx, const double *xy, int n, double x0, doubl
         const int c = cid[gidx[p]];
         gcell[p] = (c % G) | ((c / G) << 16);
     }
-    HIP_TRY(hipMalloc(&ctx->d_gxy, (size_t)n * sizeof(double2)));
-    HIP_TRY(hipMalloc(&ctx->d_gidx, (size_t)n * 4));
-    HIP_TRY(hipMalloc(&ctx->d_gpos, (size_t)n * 4));
-    HIP_TRY(hipMalloc(&ctx->d_cstart, (C + 1) * 4));
-    HIP_TRY(hipMalloc(&ctx->d_gcell, (size_t)n * 4));
+    HIP_TRY(tspmem::alloc_all<HipMem>({{&ctx->d_gxy, (size_t)n}, {&ctx->d_gidx, (size_t)n}, {&ctx->d_gpos, (size_t)n},
+                                       {&ctx->d_cstart, C + 1}, {&ctx->d_gcell, (size_t)n}}));
     HIP_TRY(hipMemcpy(ctx->d_gcell, gcell.data(), (size_t)n * 4, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(ctx->d_gxy, gxy.data(), (size_t)n * sizeof(double2), hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(ctx->d_gidx, gidx.data(), (size_t)n * 4, hipMemcpyHostToDevice));
@@ -4851,7 +4743,7 @@ static int launch_nn(tspgpu_ctx *ctx, int slot0, const int *h_starts, int count)
         A.knn = nullptr;
         if (knn) {
             if (!ctx->d_knn) {
-                HIP_TRY(hipMalloc(&ctx->d_knn, (size_t)n * NN_K * 4));
+                HIP_TRY(ctx->d_knn.alloc((size_t)n * NN_K));
                 const dim3 g((n + 255) / 256), b(256);
                 if (kind == TSPGPU_EUC_2D) hipLaunchKernelGGL((k_knn_build<TSPGPU_EUC_2D>), g, b, 0, ctx->stream, A, ctx->d_knn);
                 else if (kind == TSPGPU_ATT) hipLaunchKernelGGL((k_knn_build<TSPGPU_ATT>), g, b, 0, ctx->stream, A, ctx->d_knn);
@@ -4875,7 +4767,7 @@ static int launch_nn(tspgpu_ctx *ctx, int slot0, const int *h_starts, int count)
         int BT = std::min(1024, std::max(64, (nvec + 63) & ~63));
         if ((nvec + BT - 1) / BT <= 16) {
             ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_nn_vec<T>), dim3(count), dim3(BT), 0, ctx->stream, ctx->S,
-                                                         (const T *)ctx->d_mat, n, ctx->ld, slot0, ctx->d_starts));
+                                                         (const T *)ctx->d_mat.p, n, ctx->ld, slot0, ctx->d_starts));
             HIP_TRY(hipGetLastError());
             launched = true;
         }
@@ -4885,7 +4777,7 @@ static int launch_nn(tspgpu_ctx *ctx, int slot0, const int *h_starts, int count)
         while ((long)BT * 128 < n && BT < 1024) BT *= 2; // register visited mask: n <= 128*BT
         if ((long)BT * 128 < n) return fail(ctx, E_EXHAUSTED, "nn kernel supports n <= 131072");
         ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_nn<T>), dim3(count), dim3(BT), 0, ctx->stream, ctx->S,
-                                                     (const T *)ctx->d_mat, n, ctx->ld, slot0, ctx->d_starts, ctx->d_pts, ctx->kind));
+                                                     (const T *)ctx->d_mat.p, n, ctx->ld, slot0, ctx->d_starts, ctx->d_pts, ctx->kind));
         HIP_TRY(hipGetLastError());
     }
     // Only a caller matrix can hold NOT_CONNECTED off the diagonal; built matrices never leave a tour open.
@@ -5029,7 +4921,7 @@ int tspgpu_create(int device, tspgpu_ctx **out)
     // (MI355X_MICROARCH.md, register files / LDS); the generic attribute still says 64 KiB.
     ctx->lds_max = 160 * 1024;
     if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) { delete ctx; return E_INTERNAL; }
-    if (hipMalloc(&ctx->d_flags, 64) != hipSuccess) { delete ctx; return E_INTERNAL; }
+    if (ctx->d_flags.alloc(16) != hipSuccess) { delete ctx; return E_INTERNAL; }
     *out = ctx;
     return E_OK;
 }
@@ -5039,28 +4931,12 @@ void tspgpu_destroy(tspgpu_ctx *ctx)
     if (!ctx) return;
     hipSetDevice(ctx->device);
     hipStreamSynchronize(ctx->stream);
-    free_matrix(ctx);
-    free_tours(ctx);
-    if (ctx->d_pts) hipFree(ctx->d_pts);
-    if (ctx->d_flags) hipFree(ctx->d_flags);
-    if (ctx->d_lp_slots) hipFree(ctx->d_lp_slots);
-    if (ctx->h_ord) hipHostFree(ctx->h_ord);
-    if (ctx->d_lp_best) hipFree(ctx->d_lp_best);
-    if (ctx->d_vns_rand) hipFree(ctx->d_vns_rand);
     if (ctx->ev_ord) hipEventDestroy(ctx->ev_ord);
-    if (ctx->h_lp) hipHostFree(ctx->h_lp);
-    if (ctx->d_trace) hipFree(ctx->d_trace);
-    if (ctx->d_stamps) hipFree(ctx->d_stamps);
-    if (ctx->d_spts) hipFree(ctx->d_spts);
-    if (ctx->d_ipts) hipFree(ctx->d_ipts);
-    if (ctx->d_or) hipFree(ctx->d_or);
-    if (ctx->d_m2) hipFree(ctx->d_m2);
-    free_nl(ctx);
-    free_grid(ctx);
-    if (ctx->hist.a) { hipFree(ctx->hist.a); hipFree(ctx->hist.b); hipFree(ctx->hist.d); }
     for (auto e : ctx->ev) hipEventDestroy(e);
-    hipStreamDestroy(ctx->stream);
-    delete ctx;
+    drop_graphs(ctx);
+    const hipStream_t stream = ctx->stream;
+    delete ctx;                 // every group frees what it holds, before the stream it was filled on goes
+    hipStreamDestroy(stream);
 }
 
 const char *tspgpu_last_error(const tspgpu_ctx *ctx) { return ctx ? ctx->err.c_str() : "null context"; }
@@ -5076,14 +4952,14 @@ int tspgpu_set_option(tspgpu_ctx *ctx, int option, long value)
     case TSPGPU_OPT_WGS_PER_TOUR: if (value < 0 || value > MAX_WGS_PER_TOUR) return fail(ctx, E_INVALID, "bad wgs"); ctx->opt_wgs = (int)value; ctx->plan_kernel = 0; break;
     case TSPGPU_OPT_HISTORY: {
         if (value < 0 || value > (1 << 22)) return fail(ctx, E_INVALID, "bad history size");
-        if (ctx->hist.a) { hipFree(ctx->hist.a); hipFree(ctx->hist.b); hipFree(ctx->hist.d); ctx->hist = HistBuf{nullptr, nullptr, nullptr, 0}; }
+        drop_graphs(ctx);       // (captured launches hold the old arrays: they go first, so a failure below leaves "no history")
+        tspmem::reset_all(ctx->hist_a, ctx->hist_b, ctx->hist_d);
+        ctx->hist = HistBuf{nullptr, nullptr, nullptr, 0}; ctx->opt_hist = 0;
         if (value > 0) {
-            HIP_TRY(hipMalloc(&ctx->hist.a, value * 4));
-            HIP_TRY(hipMalloc(&ctx->hist.b, value * 4));
-            HIP_TRY(hipMalloc(&ctx->hist.d, value * 8));
-            ctx->hist.cap = (int)value;
+            HIP_TRY(tspmem::alloc_all<HipMem>({{&ctx->hist_a, (size_t)value}, {&ctx->hist_b, (size_t)value}, {&ctx->hist_d, (size_t)value}}));
+            ctx->hist = HistBuf{ctx->hist_a, ctx->hist_b, ctx->hist_d, (int)value};
         }
-        ctx->opt_hist = (int)value; drop_graphs(ctx);
+        ctx->opt_hist = (int)value;
         break;
     }
     case TSPGPU_OPT_GRAPH: ctx->opt_graph = value ? 1 : 0; break;
@@ -5101,7 +4977,7 @@ int tspgpu_set_option(tspgpu_ctx *ctx, int option, long value)
     case 97: ctx->opt_lp_hello = value ? value : 200000; ctx->lp_skip = 0; ctx->lp_backoff = 16; break; // undocumented: rendezvous limit of k_lds2opt (tests)
     case 98: // undocumented: per-workgroup phase stamps of the pipelined sweep (single tour)
         ctx->opt_stamps = value ? 1 : 0; drop_graphs(ctx);
-        if (value && !ctx->d_stamps) HIP_TRY(hipMalloc(&ctx->d_stamps, (size_t)MAX_WGS_PER_TOUR * 64 * 8));
+        if (value) HIP_TRY(ctx->d_stamps.reserve((size_t)MAX_WGS_PER_TOUR * 64));
         if (value) HIP_TRY(hipMemset(ctx->d_stamps, 0, (size_t)MAX_WGS_PER_TOUR * 64 * 8));
         break;
     case TSPGPU_OPT_MATRIX_FREE: if (value < 0 || value > 2) return fail(ctx, E_INVALID, "bad matrix-free mode"); ctx->opt_otf = (int)value; break;
@@ -5204,8 +5080,7 @@ int tspgpu_set_points(tspgpu_ctx *ctx, const double *xy, int n, int edge_weight_
     hipSetDevice(ctx->device);
     int rc = new_instance(ctx, n);
     if (rc) return rc;
-    if (ctx->d_pts) { hipFree(ctx->d_pts); ctx->d_pts = nullptr; }
-    HIP_TRY(hipMalloc(&ctx->d_pts, (size_t)n * sizeof(double2)));
+    HIP_TRY(ctx->d_pts.alloc((size_t)n));
     HIP_TRY(hipMemcpy(ctx->d_pts, xy, (size_t)n * sizeof(double2), hipMemcpyHostToDevice));
     ctx->kind = edge_weight_type;
     ctx->have_points = true;
@@ -5219,11 +5094,11 @@ int tspgpu_set_points(tspgpu_ctx *ctx, const double *xy, int n, int edge_weight_
     }
     const double diag = std::sqrt((x1 - x0) * (x1 - x0) + (y1 - y0) * (y1 - y0));
     ctx->cost_bound = (edge_weight_type == TSPGPU_ATT ? diag / std::sqrt(10.0) : diag) + 2.0;
-    if (ctx->d_ipts) { hipFree(ctx->d_ipts); ctx->d_ipts = nullptr; }
+    ctx->d_ipts.reset();
     if (ctx->ceil_int()) {
         std::vector<int> ip((size_t)2 * n);
         for (int i = 0; i < n; i++) { ip[2 * i] = (int)(xy[2 * i] - x0); ip[2 * i + 1] = (int)(xy[2 * i + 1] - y0); }
-        HIP_TRY(hipMalloc(&ctx->d_ipts, (size_t)n * sizeof(int2)));
+        HIP_TRY(ctx->d_ipts.alloc((size_t)n));
         HIP_TRY(hipMemcpy(ctx->d_ipts, ip.data(), (size_t)n * sizeof(int2), hipMemcpyHostToDevice));
     }
     return build_grid(ctx, xy, n, x0, x1, y0, y1);
@@ -5234,7 +5109,7 @@ static int launch_build(tspgpu_ctx *ctx)
     const int n = ctx->n, ld = ctx->ld;
     if (ctx->elem == TSPGPU_ELEM_F64) {
         dim3 grid((ld / 2 + 255) / 256, n);
-        hipLaunchKernelGGL((k_build_costs<double>), grid, dim3(256), 0, ctx->stream, ctx->d_pts, n, ld, ctx->kind, (double *)ctx->d_mat);
+        hipLaunchKernelGGL((k_build_costs<double>), grid, dim3(256), 0, ctx->stream, ctx->d_pts, n, ld, ctx->kind, (double *)ctx->d_mat.p);
     } else {
         const int kind = ctx->ceil_int() ? KIND_CEIL_INT : ctx->kind;
         // one triangle + transposed store (k_build_costs_tri); TSPGPU_OPT_BUILD_KERNEL = 1 keeps the full-matrix form
@@ -5247,12 +5122,12 @@ static int launch_build(tspgpu_ctx *ctx)
         // 131 us, but n = 4096 15.4 vs 11.8 us -- 528 workgroups of four times the arithmetic fill the chip worse than 2080
         const bool big = tri && ctx->opt_build_tile != 64 && (n >= 8192 || (ctx->opt_build_tile == 128 && n >= 1024));
         const int NTB = (n + TRIB - 1) / TRIB;
-#define BUILD_INT(T, K) do { if (big && f32r && K == TSPGPU_EUC_2D) hipLaunchKernelGGL((k_build_costs_tri128<T, TSPGPU_EUC_2D, true>), dim3(NTB * (NTB + 1) / 2), dim3(256), 0, ctx->stream, ctx->d_pts, n, ld, NTB, (T *)ctx->d_mat); \
-                             else if (big) hipLaunchKernelGGL((k_build_costs_tri128<T, K, false>), dim3(NTB * (NTB + 1) / 2), dim3(256), 0, ctx->stream, ctx->d_pts, n, ld, NTB, (T *)ctx->d_mat); \
-                             else if (tri && f32r && K == TSPGPU_EUC_2D) hipLaunchKernelGGL((k_build_costs_tri<T, TSPGPU_EUC_2D, true>), dim3(NT * (NT + 1) / 2), dim3(256), 0, ctx->stream, ctx->d_pts, n, ld, NT, (T *)ctx->d_mat); \
-                             else if (tri) hipLaunchKernelGGL((k_build_costs_tri<T, K, false>), dim3(NT * (NT + 1) / 2), dim3(256), 0, ctx->stream, ctx->d_pts, n, ld, NT, (T *)ctx->d_mat); \
+#define BUILD_INT(T, K) do { if (big && f32r && K == TSPGPU_EUC_2D) hipLaunchKernelGGL((k_build_costs_tri128<T, TSPGPU_EUC_2D, true>), dim3(NTB * (NTB + 1) / 2), dim3(256), 0, ctx->stream, ctx->d_pts, n, ld, NTB, (T *)ctx->d_mat.p); \
+                             else if (big) hipLaunchKernelGGL((k_build_costs_tri128<T, K, false>), dim3(NTB * (NTB + 1) / 2), dim3(256), 0, ctx->stream, ctx->d_pts, n, ld, NTB, (T *)ctx->d_mat.p); \
+                             else if (tri && f32r && K == TSPGPU_EUC_2D) hipLaunchKernelGGL((k_build_costs_tri<T, TSPGPU_EUC_2D, true>), dim3(NT * (NT + 1) / 2), dim3(256), 0, ctx->stream, ctx->d_pts, n, ld, NT, (T *)ctx->d_mat.p); \
+                             else if (tri) hipLaunchKernelGGL((k_build_costs_tri<T, K, false>), dim3(NT * (NT + 1) / 2), dim3(256), 0, ctx->stream, ctx->d_pts, n, ld, NT, (T *)ctx->d_mat.p); \
                              else hipLaunchKernelGGL((k_build_costs_int<T, K>), dim3((ld / (16 / (int)sizeof(T)) + 255) / 256, (n + BUILD_ROWS - 1) / BUILD_ROWS), dim3(256), 0, ctx->stream, \
-                                                     ctx->d_pts, n, ld, (T *)ctx->d_mat); } while (0)
+                                                     ctx->d_pts, n, ld, (T *)ctx->d_mat.p); } while (0)
 #define BUILD_KIND(T) do { if (kind == TSPGPU_EUC_2D) BUILD_INT(T, TSPGPU_EUC_2D); else if (kind == TSPGPU_ATT) BUILD_INT(T, TSPGPU_ATT); \
                            else if (kind == KIND_CEIL_INT) BUILD_INT(T, KIND_CEIL_INT); else BUILD_INT(T, TSPGPU_CEIL_2D); } while (0)
         if (ctx->elem == TSPGPU_ELEM_I32) BUILD_KIND(int); else BUILD_KIND(u16);
@@ -5295,7 +5170,7 @@ int tspgpu_build_costs(tspgpu_ctx *ctx, double *host_out)
     }
     if (!row_fits) return fail(ctx, E_EXHAUSTED, "n = %d: a matrix row does not fit LDS and matrix-free mode is disabled", ctx->n);
     if (!labels_fit) return fail(ctx, E_EXHAUSTED, "n = %d exceeds the matrix-mode limit of %d nodes and matrix-free mode is disabled", ctx->n, MATRIX_MAX_N);
-    HIP_TRY(hipMalloc(&ctx->d_mat, cells * elem_size(ctx->elem)));
+    HIP_TRY(ctx->d_mat.alloc(cells * elem_size(ctx->elem)));
     int rc = launch_build(ctx);
     if (rc) return rc;
     ctx->symmetric = true; // Euclidean
@@ -5323,8 +5198,9 @@ int tspgpu_set_costs(tspgpu_ctx *ctx, const double *host_costs, int n)
     ctx->built = false;
     const int ld = ctx->ld;
     const size_t cells = (size_t)n * ld;
-    double *stage = nullptr;
-    HIP_TRY(hipMalloc(&stage, cells * 8));
+    DevBuf<void> owner;          // the matrix as doubles: it becomes the matrix where that is the cell type
+    HIP_TRY(owner.alloc(cells * 8));
+    double *const stage = static_cast<double *>(owner.p);
     HIP_TRY(hipMemsetAsync(stage, 0, cells * 8, ctx->stream));
     HIP_TRY(hipMemcpy2DAsync(stage, (size_t)ld * 8, host_costs, (size_t)n * 8, (size_t)n * 8, n, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemsetAsync(ctx->d_flags, 0, 32, ctx->stream));
@@ -5338,22 +5214,20 @@ int tspgpu_set_costs(tspgpu_ctx *ctx, const double *host_costs, int n)
     ctx->max8k = fits16 && flags[4] == 0;
     ctx->symmetric = flags[1] == 0;
     if ((ctx->opt_elem == TSPGPU_ELEM_I32 && !integral) || (ctx->opt_elem == TSPGPU_ELEM_U16 && !fits16)) {
-        hipFree(stage);
         return fail(ctx, E_INVALID, "integer storage requested but the matrix is not representable (int32: integers in [-1, 2^27); uint16: integers in [0, 65534] with a -1 diagonal)");
     }
     if (ctx->opt_elem != TSPGPU_ELEM_AUTO) ctx->elem = ctx->opt_elem;
     else ctx->elem = fits16 ? TSPGPU_ELEM_U16 : integral ? TSPGPU_ELEM_I32 : TSPGPU_ELEM_F64;
     if (ctx->elem == TSPGPU_ELEM_F64) {
-        ctx->d_mat = stage;
+        ctx->d_mat = std::move(owner);
     } else {
-        HIP_TRY(hipMalloc(&ctx->d_mat, cells * elem_size(ctx->elem)));
+        HIP_TRY(ctx->d_mat.alloc(cells * elem_size(ctx->elem)));
         if (ctx->elem == TSPGPU_ELEM_I32)
-            hipLaunchKernelGGL((k_from_f64<int>), dim3((ld + 255) / 256, n), dim3(256), 0, ctx->stream, stage, n, ld, (int *)ctx->d_mat);
+            hipLaunchKernelGGL((k_from_f64<int>), dim3((ld + 255) / 256, n), dim3(256), 0, ctx->stream, stage, n, ld, (int *)ctx->d_mat.p);
         else
-            hipLaunchKernelGGL((k_from_f64<u16>), dim3((ld + 255) / 256, n), dim3(256), 0, ctx->stream, stage, n, ld, (u16 *)ctx->d_mat);
+            hipLaunchKernelGGL((k_from_f64<u16>), dim3((ld + 255) / 256, n), dim3(256), 0, ctx->stream, stage, n, ld, (u16 *)ctx->d_mat.p);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(ctx->stream));
-        hipFree(stage);
     }
     ctx->have_costs = true;
     ctx->plan_kernel = 0;
@@ -5368,20 +5242,18 @@ int tspgpu_get_costs(tspgpu_ctx *ctx, double *host_out)
     if (rc) return rc;
     if (ctx->otf) return fail(ctx, E_PRECOND, "matrix-free mode: no matrix is held");
     const int n = ctx->n, ld = ctx->ld;
-    const double *src = (const double *)ctx->d_mat;
-    double *tmp = nullptr;
+    const double *src = (const double *)ctx->d_mat.p;
+    DevBuf<double> tmp;
     if (ctx->elem != TSPGPU_ELEM_F64) {
-        HIP_TRY(hipMalloc(&tmp, (size_t)n * ld * 8));
+        HIP_TRY(tmp.alloc((size_t)n * ld));
         if (ctx->elem == TSPGPU_ELEM_I32)
-            hipLaunchKernelGGL((k_to_f64<int>), dim3((ld + 255) / 256, n), dim3(256), 0, ctx->stream, (const int *)ctx->d_mat, n, ld, tmp);
+            hipLaunchKernelGGL((k_to_f64<int>), dim3((ld + 255) / 256, n), dim3(256), 0, ctx->stream, (const int *)ctx->d_mat.p, n, ld, tmp);
         else
-            hipLaunchKernelGGL((k_to_f64<u16>), dim3((ld + 255) / 256, n), dim3(256), 0, ctx->stream, (const u16 *)ctx->d_mat, n, ld, tmp);
+            hipLaunchKernelGGL((k_to_f64<u16>), dim3((ld + 255) / 256, n), dim3(256), 0, ctx->stream, (const u16 *)ctx->d_mat.p, n, ld, tmp);
         src = tmp;
     }
-    hipError_t e = hipMemcpy2DAsync(host_out, (size_t)n * 8, src, (size_t)ld * 8, (size_t)n * 8, n, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (tmp) hipFree(tmp);
-    if (e != hipSuccess) return fail(ctx, E_INTERNAL, "matrix download: %s", hipGetErrorString(e));
+    HIP_TRY(hipMemcpy2DAsync(host_out, (size_t)n * 8, src, (size_t)ld * 8, (size_t)n * 8, n, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
     return E_OK;
 }
 
@@ -5544,13 +5416,7 @@ int tspgpu_tabu_search(tspgpu_ctx *ctx, int *path, double *cost, int k, int *bes
     if ((rc = load_path(ctx, 0, path, k))) return rc;
     HIP_TRY(hipMemcpyAsync(ctx->S.cost, cost, 8, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(ctx->d_best_succ, path, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
-    if (k > ctx->trace_cap) {
-        if (ctx->d_trace) hipFree(ctx->d_trace);
-        ctx->d_trace = nullptr; ctx->trace_cap = 0;
-        HIP_TRY(hipMalloc(&ctx->d_trace, (size_t)k * 8));
-        ctx->trace_cap = k;
-        drop_graphs(ctx);
-    }
+    if ((rc = reserve_captured(ctx, ctx->d_trace, (size_t)k))) return rc;
     // tabu_init (metaheuristic.c:65-84) then the first policy step (:126-143 -> :40-59)
     int tenure = (int)(0.125 * n + 1), t_max = (int)(0.25 * n), t_min = (int)(0.125 * n), up = 1;
     if (tenure == t_max || tenure == t_min) up = !up;
@@ -5897,9 +5763,9 @@ static int em_check(tspgpu_ctx *ctx)
     const int n = ctx->n, ld = ctx->ld;
     HIP_TRY(hipMemsetAsync(ctx->d_flags, 0, 4, ctx->stream));
     const dim3 grid((n + 255) / 256, n);
-    if (ctx->elem == TSPGPU_ELEM_F64) hipLaunchKernelGGL((k_em_check<double>), grid, dim3(256), 0, ctx->stream, (const double *)ctx->d_mat, n, ld, ctx->d_flags);
-    else if (ctx->elem == TSPGPU_ELEM_I32) hipLaunchKernelGGL((k_em_check<int>), grid, dim3(256), 0, ctx->stream, (const int *)ctx->d_mat, n, ld, ctx->d_flags);
-    else hipLaunchKernelGGL((k_em_check<u16>), grid, dim3(256), 0, ctx->stream, (const u16 *)ctx->d_mat, n, ld, ctx->d_flags);
+    if (ctx->elem == TSPGPU_ELEM_F64) hipLaunchKernelGGL((k_em_check<double>), grid, dim3(256), 0, ctx->stream, (const double *)ctx->d_mat.p, n, ld, ctx->d_flags);
+    else if (ctx->elem == TSPGPU_ELEM_I32) hipLaunchKernelGGL((k_em_check<int>), grid, dim3(256), 0, ctx->stream, (const int *)ctx->d_mat.p, n, ld, ctx->d_flags);
+    else hipLaunchKernelGGL((k_em_check<u16>), grid, dim3(256), 0, ctx->stream, (const u16 *)ctx->d_mat.p, n, ld, ctx->d_flags);
     HIP_TRY(hipGetLastError());
     int flag = 0;
     HIP_TRY(hipMemcpyAsync(&flag, ctx->d_flags, 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -5924,18 +5790,15 @@ int tspgpu_farthest_pair(tspgpu_ctx *ctx, int *a, int *b, double *cost)
     hipSetDevice(ctx->device);
     int rc = em_check(ctx);
     if (rc) return rc;
-    u64 *d_key = nullptr, key = 0;
-    HIP_TRY(hipMalloc(&d_key, 8));
+    DevBuf<u64> d_key;
+    u64 key = 0;
+    HIP_TRY(d_key.alloc(1));
     EmArgs A = em_args(ctx);
-    hipError_t e = hipMemsetAsync(d_key, 0, 8, ctx->stream);
-    if (e == hipSuccess) {
-        EM_WF_SWITCH(ctx, WF, hipLaunchKernelGGL((k_em_farthest<WF>), dim3(ctx->n), dim3(EM_BT), 0, ctx->stream, A, d_key));
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipMemcpyAsync(&key, d_key, 8, hipMemcpyDeviceToHost, ctx->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    hipFree(d_key);
-    if (e != hipSuccess) return fail(ctx, E_INTERNAL, "farthest pair: %s", hipGetErrorString(e));
+    HIP_TRY(hipMemsetAsync(d_key, 0, 8, ctx->stream));
+    EM_WF_SWITCH(ctx, WF, hipLaunchKernelGGL((k_em_farthest<WF>), dim3(ctx->n), dim3(EM_BT), 0, ctx->stream, A, d_key.p));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&key, d_key, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
     const u64 lin = ~key & EM_FMASK, n = (u64)ctx->n;
     *a = (int)(lin / n); *b = (int)(lin % n);
     *cost = (double)(key >> 35);
@@ -5953,10 +5816,10 @@ int tspgpu_extra_mileage(tspgpu_ctx *ctx, int a, int b, double time_left_s, int 
     if (time_left_s >= 0 && time_left_s <= 0) return fail(ctx, E_DEADLINE, "time limit exceeded before the first insertion");
     // one allocation: control block | skey[n] | eu, ev, ec, succ [n] | stale [3][n]
     const size_t N = (size_t)n, bytes = sizeof(EmCtl) + N * 8 + N * 4 * 4 + N * 4 * 3;
-    unsigned char *mem = nullptr;
-    HIP_TRY(hipMalloc(&mem, bytes));
+    DevBuf<unsigned char> mem;
+    HIP_TRY(mem.alloc(bytes));
     EmArgs A = em_args(ctx);
-    A.ctl = reinterpret_cast<EmCtl *>(mem);
+    A.ctl = reinterpret_cast<EmCtl *>(mem.p);
     A.skey = reinterpret_cast<u64 *>(mem + sizeof(EmCtl));
     A.eu = reinterpret_cast<int *>(mem + sizeof(EmCtl) + N * 8);
     A.ev = A.eu + N; A.ec = A.ev + N; A.succ = A.ec + N; A.stale = A.succ + N;
@@ -6001,13 +5864,11 @@ int tspgpu_extra_mileage(tspgpu_ctx *ctx, int a, int b, double time_left_s, int 
         if (C.stop) rc = fail(ctx, E_DEADLINE, "time limit exceeded after %d of %d insertions", C.steps, n - 2);
         else if (C.steps != n - 2) rc = fail(ctx, E_INTERNAL, "Extra Mileage ended after %d of %d insertions", C.steps, n - 2);
         else {
-            hipError_t e = hipMemcpyAsync(path, A.succ, N * 4, hipMemcpyDeviceToHost, ctx->stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-            if (e != hipSuccess) rc = fail(ctx, E_INTERNAL, "tour download: %s", hipGetErrorString(e));
-            else *cost = 2.0 * (double)C.cab + (double)C.dsum;     // heuristics.c:184 then :362, exact in integers
+            HIP_TRY(hipMemcpyAsync(path, A.succ, N * 4, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+            *cost = 2.0 * (double)C.cab + (double)C.dsum;     // heuristics.c:184 then :362, exact in integers
         }
     }
-    hipFree(mem);
     return rc;
 }
 
@@ -6035,7 +5896,7 @@ static int or_check(tspgpu_ctx *ctx, bool batch)
             return fail(ctx, E_EXHAUSTED, "Or-opt keeps four matrix rows in LDS: n = %d is past the limit of %d nodes for %d-byte cells",
                         ctx->n, lim, (int)elem_size(ctx->elem));
     }
-    if (!ctx->d_or) HIP_TRY(hipMalloc(&ctx->d_or, sizeof(OrCtl)));
+    HIP_TRY(ctx->d_or.reserve(1));
     return E_OK;
 }
 
@@ -6105,7 +5966,7 @@ static int or_launch_sweep(tspgpu_ctx *ctx, int slot, const SweepGeom &P, bool g
     if (ctx->otf) return or_launch_sweep_otf(ctx, slot, P, gather);
     const int rc = ensure_max_lds(ctx, P.fn);
     if (rc) return rc;
-#define OR_SWEEP(T, N) hipLaunchKernelGGL((k_oropt_sweep<T, N>), dim3(P.W), dim3(P.BT), P.lds, ctx->stream, ctx->S, (const T *)ctx->d_mat, \
+#define OR_SWEEP(T, N) hipLaunchKernelGGL((k_oropt_sweep<T, N>), dim3(P.W), dim3(P.BT), P.lds, ctx->stream, ctx->S, (const T *)ctx->d_mat.p, \
                                           ctx->n, ctx->ld, slot, P.R, (const OrCtl *)ctx->d_or)
     ELEM_SWITCH(ctx->elem, T, { if (P.NCH == 1) OR_SWEEP(T, 1); else if (P.NCH == 2) OR_SWEEP(T, 2); else OR_SWEEP(T, 3); });
 #undef OR_SWEEP
@@ -6121,7 +5982,7 @@ static int or_launch_apply(tspgpu_ctx *ctx, int slot, const SweepGeom &P)
             hipLaunchKernelGGL((k_oropt_apply_otf<kind()>), dim3(1), dim3(BT), 0, ctx->stream, ctx->S, pts, ctx->n, slot, P.W, ctx->d_or);
         });
     else
-        ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_oropt_apply<T>), dim3(1), dim3(BT), 0, ctx->stream, ctx->S, (const T *)ctx->d_mat,
+        ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_oropt_apply<T>), dim3(1), dim3(BT), 0, ctx->stream, ctx->S, (const T *)ctx->d_mat.p,
                                                      ctx->n, ctx->ld, slot, P.W, ctx->d_or));
     HIP_TRY(hipGetLastError());
     return E_OK;
@@ -6140,7 +6001,7 @@ static int or_run(tspgpu_ctx *ctx, int slot, long max_moves, double t_end, long 
     if (moves) *moves = 0;
     if (last) *last = C;
     if (max_moves == 0) return E_OK;
-    int rc = ctl_put(ctx, ctx->d_or, C);
+    int rc = ctl_put(ctx, ctx->d_or.p, C);
     if (rc) return rc;
     const SweepGeom P = or_plan(ctx);
     for (;;) {
@@ -6150,7 +6011,7 @@ static int or_run(tspgpu_ctx *ctx, int slot, long max_moves, double t_end, long 
             if ((rc = or_launch_sweep(ctx, slot, P))) return rc;
             if ((rc = or_launch_apply(ctx, slot, P))) return rc;
         }
-        if ((rc = ctl_get(ctx, &C, ctx->d_or))) return rc;
+        if ((rc = ctl_get(ctx, &C, ctx->d_or.p))) return rc;
         if (C.stop) break;
     }
     if (moves) *moves = (long)C.moves;
@@ -6217,13 +6078,13 @@ static int or_launch_round(tspgpu_ctx *ctx, int live, const SweepGeom &P)
         const int rows = std::min(65535, live - off);
         const int *list = ctx->d_live + off;
 #define OR_SWEEP(T, N) hipLaunchKernelGGL((k_oropt_sweep_batch<T, N>), dim3(P.W, rows), dim3(P.BT), P.lds, ctx->stream, ctx->S, \
-                                          (const T *)ctx->d_mat, ctx->n, ctx->ld, list, P.R, (const OrCtl *)ctx->d_or_ctl)
+                                          (const T *)ctx->d_mat.p, ctx->n, ctx->ld, list, P.R, (const OrCtl *)ctx->d_or_ctl)
         ELEM_SWITCH(ctx->elem, T, { if (P.NCH == 1) OR_SWEEP(T, 1); else if (P.NCH == 2) OR_SWEEP(T, 2); else OR_SWEEP(T, 3); });
 #undef OR_SWEEP
         HIP_TRY(hipGetLastError());
     }
     const int BT = std::min(1024, std::max(64, pow2_ceil(ctx->n / 8)));
-    ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_oropt_apply_batch<T>), dim3(live), dim3(BT), 0, ctx->stream, ctx->S, (const T *)ctx->d_mat,
+    ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_oropt_apply_batch<T>), dim3(live), dim3(BT), 0, ctx->stream, ctx->S, (const T *)ctx->d_mat.p,
                                                  ctx->n, ctx->ld, (const int *)ctx->d_live, P.W, ctx->d_or_ctl));
     HIP_TRY(hipGetLastError());
     return E_OK;
@@ -6412,21 +6273,9 @@ static int m2_check(tspgpu_ctx *ctx)
         return fail(ctx, E_EXHAUSTED, "n = %d: a matrix row of %d-byte cells does not fit LDS (at most %d nodes)", n,
                     (int)elem_size(ctx->elem), (int)((ctx->lds_max - M2_EXTRA) / elem_size(ctx->elem)) & ~31);
     if (ctx->otf && (rc = ensure_spts(ctx, (size_t)n))) return rc;     // sized as make_plan sizes them for one tour
-    if (!ctx->d_m2) HIP_TRY(hipMalloc(&ctx->d_m2, sizeof(M2Ctl)));
-    if (!ctx->m2.raw_d) {
-        M2Buf &B = ctx->m2;
-        const size_t N = (size_t)n;
-        void **ptrs[] = {(void **)&B.raw_d, (void **)&B.raw_b, (void **)&B.d, (void **)&B.a, (void **)&B.b, (void **)&B.i, (void **)&B.j,
-                         (void **)&B.acc};
-        const size_t bytes[] = {8, 4, 8, 4, 4, 4, 4, 4};
-        for (int k = 0; k < 8; k++) {
-            const hipError_t e = hipMalloc(ptrs[k], N * bytes[k]);
-            if (e != hipSuccess) {          // all eight or none: a later call must not find half of them
-                free_m2(ctx);
-                HIP_TRY(e);
-            }
-        }
-    }
+    HIP_TRY(ctx->d_m2.reserve(1));
+    // all eight or none: a later call must not find half of them
+    if (!ctx->m2.raw_d) HIP_TRY(tspmem::grow(HipMem{ctx->stream}, ctx->m2_rows(ctx->m2, (size_t)n), 0, 1));
     return E_OK;
 }
 
@@ -6479,7 +6328,7 @@ static int m2_launch_select(tspgpu_ctx *ctx, int slot, const SweepGeom &P, bool 
         });
     } else {
         if ((rc = ensure_max_lds(ctx, P.fn))) return rc;
-#define M2_SWEEP(T, N) hipLaunchKernelGGL((k_m2_sweep<T, N>), dim3(P.W), dim3(P.BT), P.lds, ctx->stream, ctx->S, (const T *)ctx->d_mat, \
+#define M2_SWEEP(T, N) hipLaunchKernelGGL((k_m2_sweep<T, N>), dim3(P.W), dim3(P.BT), P.lds, ctx->stream, ctx->S, (const T *)ctx->d_mat.p, \
                                           n, ctx->ld, slot, P.R, ctx->m2, ctl)
         ELEM_SWITCH(ctx->elem, T, { if (P.NCH == 1) M2_SWEEP(T, 1); else if (P.NCH == 2) M2_SWEEP(T, 2);
                                     else if (P.NCH == 4) M2_SWEEP(T, 4); else M2_SWEEP(T, 10); });
@@ -6503,7 +6352,7 @@ static int m2_launch_apply(tspgpu_ctx *ctx, int slot, M2Kind kind = M2_FULL)
             hipLaunchKernelGGL((k_m2_apply_otf<kind()>), dim3(G), dim3(256), 0, ctx->stream, ctx->S, pts, n, slot, ctx->m2, ctx->d_m2);
         });
     else
-        ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_m2_apply<T>), dim3(G), dim3(256), 0, ctx->stream, ctx->S, (const T *)ctx->d_mat,
+        ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_m2_apply<T>), dim3(G), dim3(256), 0, ctx->stream, ctx->S, (const T *)ctx->d_mat.p,
                                                      n, ctx->ld, slot, ctx->m2, ctx->d_m2));
     HIP_TRY(hipGetLastError());
     return E_OK;
@@ -6515,7 +6364,7 @@ static int m2_arm(tspgpu_ctx *ctx, int slot, long budget)
     M2Ctl C;
     memset(&C, 0, sizeof C);
     C.budget = budget;
-    const int rc = ctl_put(ctx, ctx->d_m2, C);
+    const int rc = ctl_put(ctx, ctx->d_m2.p, C);
     if (rc) return rc;
     hipLaunchKernelGGL(k_rearm, dim3(1), dim3(64), 0, ctx->stream, ctx->S, slot, 1, -1);
     HIP_TRY(hipGetLastError());
@@ -6551,10 +6400,10 @@ static int m2_run(tspgpu_ctx *ctx, int slot, long max_sweeps, double t_end, long
             if ((rc = m2_launch_select(ctx, slot, P, true, kind))) return rc;
             if ((rc = m2_launch_apply(ctx, slot, kind))) return rc;
         }
-        if ((rc = ctl_get(ctx, &C, ctx->d_m2))) return rc;
+        if ((rc = ctl_get(ctx, &C, ctx->d_m2.p))) return rc;
         if (C.stop) break;
     }
-    if (*late && (rc = ctl_get(ctx, &C, ctx->d_m2))) return rc;
+    if (*late && (rc = ctl_get(ctx, &C, ctx->d_m2.p))) return rc;
     if (sweeps) *sweeps = (long)C.sweeps;
     if (moves) *moves = (long)C.moves;
     m2_record(ctx, C, kind);
@@ -6598,7 +6447,7 @@ static int m2_once(tspgpu_ctx *ctx, int *path, double *cost, int *nmoves, int *m
     if ((rc = m2_launch_select(ctx, 0, m2_plan(ctx), true, kind))) return rc;
     // the accepted list comes back before anything is applied: a list longer than `cap` leaves the tour as it is
     M2Ctl C;
-    if ((rc = ctl_get(ctx, &C, ctx->d_m2))) return rc;
+    if ((rc = ctl_get(ctx, &C, ctx->d_m2.p))) return rc;
     const size_t m = (size_t)C.m;
     std::vector<int> acc(m), a(m), b(m);
     std::vector<double> d(m);
@@ -6631,7 +6480,7 @@ static int m2_once(tspgpu_ctx *ctx, int *path, double *cost, int *nmoves, int *m
     if (nmoves) *nmoves = (int)idx.size();
     if ((rc = m2_launch_apply(ctx, 0, kind))) return rc;
     if ((rc = store_path(ctx, 0, path, cost, nullptr))) return rc;
-    if ((rc = ctl_get(ctx, &C, ctx->d_m2))) return rc;
+    if ((rc = ctl_get(ctx, &C, ctx->d_m2.p))) return rc;
     m2_record(ctx, C, kind);
     return E_OK;
 }
@@ -6690,7 +6539,7 @@ static int nl_launch_sweep(tspgpu_ctx *ctx, int slot)
             hipLaunchKernelGGL((k_nl_sweep_otf<kind()>), grid, block, 0, ctx->stream, ctx->S, pts, n, slot, ctx->nl, ctx->m2, ctl);
         });
     else
-        ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_nl_sweep<T>), grid, block, 0, ctx->stream, ctx->S, (const T *)ctx->d_mat, n, ctx->ld, slot,
+        ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_nl_sweep<T>), grid, block, 0, ctx->stream, ctx->S, (const T *)ctx->d_mat.p, n, ctx->ld, slot,
                                                      ctx->nl, ctx->m2, ctl));
     HIP_TRY(hipGetLastError());
     return E_OK;
@@ -6702,29 +6551,26 @@ int tspgpu_neighbours_build(tspgpu_ctx *ctx, int K)
 {
     if (!ctx) return E_UNAVAILABLE;
     hipSetDevice(ctx->device);
-    if (K == 0) { free_nl(ctx); ctx->nl_dropped = false; return E_OK; }
+    if (K == 0) { ctx->drop_nl(); ctx->nl_dropped = false; return E_OK; }
     if (K < 0 || K > NL_KMAX) return fail(ctx, E_INVALID, "neighbour lists hold 1 to %d nodes, got K = %d", NL_KMAX, K);
     int rc = need_costs(ctx);
     if (rc) return rc;
     if (!ctx->symmetric) return fail(ctx, E_PRECOND, "neighbour lists need a symmetric cost matrix");
     const int n = ctx->n, Kp = std::min(K, n - 1);
-    free_nl(ctx);
+    ctx->drop_nl();             // a build that fails leaves no lists
     ctx->nl_dropped = false;
-    NlBuf L{};
-    const hipError_t e0 = hipMalloc(&L.node, (size_t)n * Kp * 4), e1 = e0 == hipSuccess ? hipMalloc(&L.w, (size_t)n * Kp * 8) : e0;
-    if (e1 != hipSuccess) {                 // both or none
-        if (L.node) hipFree(L.node);
-        HIP_TRY(e1);
-    }
-    L.K = Kp;
+    DevBuf<int> node;
+    DevBuf<double> w;
+    HIP_TRY(tspmem::alloc_all<HipMem>({{&node, (size_t)n * Kp}, {&w, (size_t)n * Kp}}));
+    const NlBuf L{Kp, node, w};
     const dim3 grid((n + NL_BUILD_ROWS - 1) / NL_BUILD_ROWS), block(NL_BUILD_ROWS * 64);
     if (ctx->otf)
         kind_switch(ctx, [&](auto kind, auto *pts, auto *) { hipLaunchKernelGGL((k_nl_build_otf<kind()>), grid, block, 0, ctx->stream, pts, n, L); });
     else
-        ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_nl_build<T>), grid, block, 0, ctx->stream, (const T *)ctx->d_mat, n, ctx->ld, L));
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
-    if (e != hipSuccess) { hipFree(L.node); hipFree(L.w); HIP_TRY(e); }
+        ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_nl_build<T>), grid, block, 0, ctx->stream, (const T *)ctx->d_mat.p, n, ctx->ld, L));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    ctx->nl_node = std::move(node); ctx->nl_w = std::move(w);
     ctx->nl = L;
     return E_OK;
 }
@@ -6815,7 +6661,7 @@ static int ornl_launch_sweep(tspgpu_ctx *ctx, int slot)
             hipLaunchKernelGGL((k_ornl_sweep_otf<kind()>), grid, block, 0, ctx->stream, ctx->S, pts, n, slot, ctx->nl, ctx->m2, ctl);
         });
     else
-        ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_ornl_sweep<T>), grid, block, 0, ctx->stream, ctx->S, (const T *)ctx->d_mat, n, ctx->ld, slot,
+        ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_ornl_sweep<T>), grid, block, 0, ctx->stream, ctx->S, (const T *)ctx->d_mat.p, n, ctx->ld, slot,
                                                      ctx->nl, ctx->m2, ctl));
     HIP_TRY(hipGetLastError());
     return E_OK;
@@ -6830,7 +6676,7 @@ static int ornl_launch_apply(tspgpu_ctx *ctx, int slot)
         });
     else
         ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_ornl_apply<T>), dim3(G), dim3(ORNL_APPLY_BT), 0, ctx->stream, ctx->S,
-                                                     (const T *)ctx->d_mat, n, ctx->ld, slot, ctx->m2, ctx->d_m2));
+                                                     (const T *)ctx->d_mat.p, n, ctx->ld, slot, ctx->m2, ctx->d_m2));
     HIP_TRY(hipGetLastError());
     return E_OK;
 }
@@ -6919,18 +6765,11 @@ int tspgpu_time_or_nl_sweep(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean)
 static int nlb_ensure(tspgpu_ctx *ctx, int count)
 {
     if (count <= ctx->nlb_cap) return E_OK;
-    free_nlb(ctx);
-    M2Buf &B = ctx->nlb;
-    const size_t N = (size_t)ctx->n * count;
-    void **ptrs[] = {(void **)&B.raw_d, (void **)&B.raw_b, (void **)&B.d, (void **)&B.a, (void **)&B.b, (void **)&B.i, (void **)&B.j, (void **)&B.acc,
-                     (void **)&ctx->d_nlb_ctl};
-    const size_t bytes[] = {N * 8, N * 4, N * 8, N * 4, N * 4, N * 4, N * 4, N * 4, (size_t)count * sizeof(NlbCtl)};
-    size_t total = 0;
-    for (size_t b : bytes) total += b;
-    hipError_t e = hipSuccess;
-    for (int k = 0; k < 9 && e == hipSuccess; k++) e = hipMalloc(ptrs[k], bytes[k]);
+    ctx->drop_nlb();
+    const Rows rows = ctx->nlb_rows((size_t)ctx->n);
+    const size_t total = tspmem::rows_bytes(rows, (size_t)count);
+    const hipError_t e = tspmem::grow(HipMem{ctx->stream}, rows, 0, (size_t)count);
     if (e != hipSuccess) {                  // all or none: a later call must not find half of them
-        free_nlb(ctx);
         (void)hipGetLastError();
         return fail(ctx, E_EXHAUSTED, "the batched neighbour-list descent needs %zu bytes of device memory for %d tours of %d nodes (%s)",
                     total, count, ctx->n, hipGetErrorString(e));
@@ -6954,7 +6793,7 @@ static int nlb_launch_sweep(tspgpu_ctx *ctx, int slot0, int live)
                                    (const NlbCtl *)ctl);
             });
         else
-            ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_nlb_sweep<T>), dim3(W, rows), dim3(256), 0, ctx->stream, ctx->S, (const T *)ctx->d_mat, n,
+            ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_nlb_sweep<T>), dim3(W, rows), dim3(256), 0, ctx->stream, ctx->S, (const T *)ctx->d_mat.p, n,
                                                          ctx->ld, list, slot0, ctx->nl, ctx->nlb, (const NlbCtl *)ctl));
         HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_nlb_compact, dim3(1, rows), dim3(1024), 0, ctx->stream, ctx->S, n, list, slot0, ctx->nlb, ctl);
@@ -6966,7 +6805,7 @@ static int nlb_launch_sweep(tspgpu_ctx *ctx, int slot0, int live)
                 hipLaunchKernelGGL((k_nlb_apply_otf<kind()>), dim3(G, rows), dim3(256), 0, ctx->stream, ctx->S, pts, n, list, slot0, ctx->nlb, ctl);
             });
         else
-            ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_nlb_apply<T>), dim3(G, rows), dim3(256), 0, ctx->stream, ctx->S, (const T *)ctx->d_mat, n,
+            ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_nlb_apply<T>), dim3(G, rows), dim3(256), 0, ctx->stream, ctx->S, (const T *)ctx->d_mat.p, n,
                                                          ctx->ld, list, slot0, ctx->nlb, ctl));
         HIP_TRY(hipGetLastError());
     }

@@ -38,6 +38,7 @@
 #include <vector>
 
 #include "tspgpu.h"
+#include "tspgpu_hipmem.h"
 
 namespace {
 
@@ -101,8 +102,8 @@ struct tspgpu_multi {
     std::vector<int> dev;
     std::vector<tspgpu_ctx *> ctx;
     std::vector<hipStream_t> stream;
-    std::vector<long long *> d_key;     // [G] 2 int64 per device: send, receive
-    std::vector<int *> d_path;          // [G][n]
+    std::vector<DevBuf<long long>> d_key;   // [G] 2 int64 per device: send, receive
+    std::vector<DevBuf<int>> d_path;        // [G][n]
     int n = 0;
     bool distinct = true;
     int opt_exchange = 0;               // 0 auto, 1 host, 2 rccl
@@ -190,8 +191,7 @@ int ensure_buffers(tspgpu_multi *m, int n)
     if (m->n == n && !m->d_path.empty() && m->d_path[0]) return E_OK;
     for (int i = 0; i < m->G; i++) {
         M_HIP(hipSetDevice(m->dev[i]));
-        if (m->d_path[i]) { hipFree(m->d_path[i]); m->d_path[i] = nullptr; }
-        M_HIP(hipMalloc(&m->d_path[i], (size_t)n * 4));
+        M_HIP(m->d_path[i].alloc((size_t)n));
     }
     m->n = n;
     return E_OK;
@@ -393,12 +393,12 @@ int tspgpu_multi_create(const int *device_ids, int ndev, tspgpu_multi **out)
             if (m->dev[i] == m->dev[j]) m->distinct = false;
     m->ctx.assign(ndev, nullptr);
     m->stream.assign(ndev, nullptr);
-    m->d_key.assign(ndev, nullptr);
-    m->d_path.assign(ndev, nullptr);
+    m->d_key.resize(ndev);
+    m->d_path.resize(ndev);
     for (int i = 0; i < ndev; i++) {
         int rc = tspgpu_create(m->dev[i], &m->ctx[i]);
         if (rc == E_OK && (hipSetDevice(m->dev[i]) != hipSuccess || hipStreamCreateWithFlags(&m->stream[i], hipStreamNonBlocking) != hipSuccess ||
-                           hipMalloc(&m->d_key[i], 16) != hipSuccess)) rc = E_INTERNAL;
+                           m->d_key[i].alloc(2) != hipSuccess)) rc = E_INTERNAL;
         if (rc) { tspgpu_multi_destroy(m); return rc; }
     }
     *out = m;
@@ -416,8 +416,7 @@ void tspgpu_multi_destroy(tspgpu_multi *m)
         // launch check of an unrelated context (HIP_TRY(hipGetLastError())) would report it
         if (!m->ctx[i]) continue;
         hipSetDevice(m->dev[i]);
-        if (m->d_key[i]) hipFree(m->d_key[i]);
-        if (m->d_path[i]) hipFree(m->d_path[i]);
+        tspmem::reset_all(m->d_key[i], m->d_path[i]);
         if (m->stream[i]) hipStreamDestroy(m->stream[i]);
         if (m->ctx[i]) tspgpu_destroy(m->ctx[i]);
     }
