@@ -574,6 +574,53 @@ int tspgpu_multi_multistart_local_search_nl(tspgpu_multi *m, const int *starts, 
                                             long *total_two_opt_sweeps, long *total_two_opt_moves,
                                             long *total_or_sweeps, long *total_or_moves);
 
+/* ---- Neighbour-list VNS (an extension: W independent walks of "descent over the lists, incumbent, kicks" on the device) ----
+ * mh_VNS's loop (metaheuristic.c:279-318) with the descent of "Neighbour-list Or-opt" (rule 8) in the place of ref_2opt, on
+ * `walks` tours at once: every launch serves every walk that is still walking, and the incumbents, the kicks, the cost
+ * recompute and the re-arming stay on the device -- no host read stands between two iterations of a walk.
+ * For each walk w, alone and independent of the others, k iterations of the steps 1 to 3:
+ *   1. Descent: rule 8 of "Neighbour-list Or-opt", exactly as tspgpu_local_search_nl runs it on that tour: the cost is
+ *      recomputed first (refinment.c:6-9), then the list 2-opt phase and the list Or-opt phase alternate until an Or-opt
+ *      phase applies nothing; the empty sweeps are counted.
+ *   2. Incumbent: a local optimum whose cost is strictly below best_costs[w] becomes the incumbent, cost and successor
+ *      array (src/tsp.c:669-676); trace[w][it] receives the local optimum's cost.
+ *   3. Kicks: r = rand % 9 - 2 kicks (r <= 0: none), behind the last iteration too, as in mh_VNS and tspgpu_vns_search.
+ *      A kick is the kick of tspgpu_vns_search (vns_kick, metaheuristic.c:344-409, :490-500).
+ *   4. The numbers are the caller's, one stream per walk: walk w reads rand_values[w * nrand .. (w + 1) * nrand) in order and
+ *      consumed[w] says how many it used.  A walk whose numbers run out inside a kick phase is left in front of that kick
+ *      phase, exactly as tspgpu_vns_search leaves its single walk: its tour is the local optimum, kick_pending[w] = 1,
+ *      iterations[w] is not advanced and consumed[w] counts up to the end of the previous kick phase.  The other walks run
+ *      to their own end; the call returns 8 once every walk is finished or dry.  Calling again with fresh numbers for the
+ *      dry walks continues each walk so that the result equals an uninterrupted run on the concatenated streams.
+ *   5. The state between calls is per walk and in host arrays, like tspgpu_vns_search's: paths, iterations, kick_pending,
+ *      best_paths and best_costs, all in and out.  A walk with iterations[w] == k at entry is left alone.
+ *   6. The deadline is polled between groups of launches.  Once it has passed the call returns 4; every walk then holds a
+ *      valid tour and that tour's cost, a consistent iterations[w], and kick_pending[w] = 1 only if the walk's descent has
+ *      ended and its kicks have not run (0 otherwise).  A walk caught inside a descent is NOT promised to continue on the
+ *      same trajectory when called again: the next call begins a new descent on the tour the deadline left.
+ *   7. The state after a kick phase is that of a freshly loaded tour: exactly what tspgpu_tour_load of the kicked successor
+ *      array would leave in the slot (the order array from node 0, direction +1, positions, successors, edge weights, cost
+ *      and sweep counters of the load, its summation order for double cells included).  So every iteration equals
+ *      tspgpu_tour_load + tspgpu_tour_local_search_nl on the kicked tour, bit for bit, for f64 cells too.
+ * Matrix mode (uint16, int32, f64 cells) and matrix-free mode; no TSPGPU_OPT_OR_MATRIX_FREE.  The slots 0 .. walks-1 are
+ * scratch, like slot 0 of the other host-array entry points; they hold the walks' tours afterwards.
+ * Preconditions and codes: those of "Batched neighbour-list descent" -- no context 14, n < 8 3, no costs 9, an asymmetric
+ * matrix 9, lists not built or invalidated 9 --, and walks <= 0, k < 0, nrand < 0, a NULL where an array is required or an
+ * iterations[w] outside [0, k] 3, a paths[w] that is no n-cycle 3 (nothing is run).
+ * Memory: beyond that of "Batched neighbour-list descent", per walk two int arrays of n (the second order array, the
+ * incumbent), nrand ints, k doubles and a control block; all or none, a failure is 8 with the byte count in the text.
+ * trace is indexed by the iteration, [walks][k]: a cell is written by the call in which that iteration's descent ends.
+ * tspgpu_info: 56 walks of the last call, 57 iterations it completed (summed over the walks), 58 its sweep rounds launched
+ * (a round: the four kernels of the batched descent and the step kernel), 59 the most walks live in one round, 60 walks
+ * that ended dry. */
+int tspgpu_vns_walks_nl(tspgpu_ctx *ctx, int walks, int k, double time_left_s,
+                        int *paths /* [walks][n] in/out */, double *costs /* [walks] out: cost of paths[w] */,
+                        const int *rand_values /* [walks][nrand] */, long nrand, long *consumed /* [walks] out */,
+                        int *iterations /* [walks] in/out */, int *kick_pending /* [walks] in/out */,
+                        int *best_paths /* [walks][n] in/out */, double *best_costs /* [walks] in/out */,
+                        double *trace /* [walks][k] or NULL; only the iterations this call completes are written */,
+                        long *totals /* [walks][6] or NULL: two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds, kicks of this call */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -32,6 +32,8 @@ INFO_NL_K, INFO_NL_SWEEPS, INFO_NL_MOVES, INFO_NL_POLISH_SWEEPS, INFO_NL_NODES =
 INFO_OR_NL_SWEEPS, INFO_OR_NL_MOVES, INFO_OR_NL_MAX_MOVES, INFO_OR_NL_ROUNDS, INFO_OR_NL_STARTS = 47, 48, 49, 50, 51
 # ... tours, sweep launches and most live tours of the last batched neighbour-list descent, workgroups per tour of its candidate sweep
 INFO_NL_BATCH_TOURS, INFO_NL_BATCH_LAUNCHES, INFO_NL_BATCH_MAX_LIVE, INFO_NL_BATCH_WGS = 52, 53, 54, 55
+# ... walks, iterations completed, sweep rounds, most live walks and dry walks of the last neighbour-list VNS call
+INFO_VNS_NL_WALKS, INFO_VNS_NL_ITERATIONS, INFO_VNS_NL_ROUNDS, INFO_VNS_NL_MAX_LIVE, INFO_VNS_NL_DRY = 56, 57, 58, 59, 60
 EM_FORM_AUTO, EM_FORM_RESIDENT, EM_FORM_PER_STEP = 0, 1, 2
 MOPT_EXCHANGE = 1000
 EXCHANGE_AUTO, EXCHANGE_HOST, EXCHANGE_RCCL = 0, 1, 2
@@ -119,6 +121,8 @@ SIGNATURES = {
     "tspgpu_time_or_nl_sweep": (C.c_int, [_ctx, C.c_int, C.c_int, C.POINTER(C.c_float)]),
     "tspgpu_tours_local_search_nl": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tspgpu_multistart_local_search_nl": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_double, _ip, _pd, _pi, _pl, _pl, _pl, _pl, C.c_void_p]),
+    "tspgpu_vns_walks_nl": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_double, _ip, _dp, C.c_void_p, C.c_long, C.c_void_p, _ip, _ip, _ip, _dp,
+                                      C.c_void_p, C.c_void_p]),
     "tspgpu_multi_neighbours_build": (C.c_int, [_ctx, C.c_int]),
     "tspgpu_multi_multistart_local_search_nl": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_double, _ip, _pd, _pi, _pl, _pl, _pl, _pl]),
 }

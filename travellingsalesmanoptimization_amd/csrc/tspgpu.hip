@@ -590,13 +590,13 @@ __device__ __forceinline__ int wrap(int p, int n) { return p < 0 ? p + n : (p >=
 // i = 0..n-1 of c[i][succ i], accumulated in that order (doubles), so that
 // non-integer matrices give the same bits.  One workgroup per tour.
 // ---------------------------------------------------------------------------
+// (the body: k_tour_init on slot t, and the step kernel of tspgpu_nlvns.inc on the tour its kicks leave.  chunk: [1024]
+// doubles of LDS; the whole workgroup calls it)
 template <typename T>
-__global__ void __launch_bounds__(1024) k_tour_init(Tours S, const T *__restrict__ mat, int n, int ld, int slot0,
-                                                    const int *__restrict__ caps, const double2 *__restrict__ pts, int kind)
+__device__ __forceinline__ void tour_init_body(const Tours &S, const T *__restrict__ mat, int n, int ld, int t, int cap,
+                                               const double2 *__restrict__ pts, int kind, double *chunk)
 {
-    __shared__ double chunk[1024];
     typedef typename Elem<T>::acc AT;
-    const int t = slot0 + blockIdx.x;
     const int *ord = S.ord + (size_t)t * n;
     int *pos = S.pos + (size_t)t * n;
     AT *dp = dpos_of<AT>(S, t, n);
@@ -641,9 +641,17 @@ __global__ void __launch_bounds__(1024) k_tour_init(Tours S, const T *__restrict
         S.dir[t] = 1;
         S.done[t] = 0;
         S.nsweeps[t] = 0;
-        S.cap_sweeps[t] = caps ? caps[blockIdx.x] : -1;
+        S.cap_sweeps[t] = cap;
         S.status[t] = 0;
     }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(1024) k_tour_init(Tours S, const T *__restrict__ mat, int n, int ld, int slot0,
+                                                    const int *__restrict__ caps, const double2 *__restrict__ pts, int kind)
+{
+    __shared__ double chunk[1024];
+    tour_init_body<T>(S, mat, n, ld, slot0 + blockIdx.x, caps ? caps[blockIdx.x] : -1, pts, kind, chunk);
 }
 
 // ---------------------------------------------------------------------------
@@ -3100,6 +3108,7 @@ __global__ void k_cap_now(Tours S, int slot0, int count)
 #include "tspgpu_nl2opt.inc"
 #include "tspgpu_ornl.inc"
 #include "tspgpu_nlbatch.inc"
+#include "tspgpu_nlvns.inc"
 
 // ===========================================================================
 // host side
@@ -3139,6 +3148,12 @@ struct MEM_GROUP InstanceMem {            // of one n: new_instance drops it
     M2Buf nlb{};
     NlbCtl *d_nlb_ctl = nullptr;
     int nlb_cap = 0;
+    // neighbour-list VNS (tspgpu_nlvns.inc): per walk a second order array, the incumbent and a control block, for nlv_cap walks;
+    // the walks' number blocks and trace rows of the call in hand.  All of them, or none
+    int *d_nlv_ord = nullptr, *d_nlv_best = nullptr;
+    NlvCtl *d_nlv_ctl = nullptr;
+    int nlv_cap = 0;
+    DevBuf<int> d_nlv_rand; DevBuf<double> d_nlv_trace;
     // uniform grid over the points for the grid NN (k_nn_grid): built on the host in tspgpu_set_points
     DevBuf<double2> d_gxy; DevBuf<int> d_gidx, d_gpos, d_cstart, d_gcell;
     DevBuf<unsigned> d_knn;     // [n][NN_K] neighbour lists of k_nn_grid's KNN form (built at the first single-tour NN)
@@ -3149,7 +3164,9 @@ struct MEM_GROUP InstanceMem {            // of one n: new_instance drops it
         return {{&B.raw_d, n * 8}, {&B.raw_b, n * 4}, {&B.d, n * 8}, {&B.a, n * 4}, {&B.b, n * 4}, {&B.i, n * 4}, {&B.j, n * 4}, {&B.acc, n * 4}};
     }
     Rows nlb_rows(size_t n) { Rows r = m2_rows(nlb, n); r.push_back({&d_nlb_ctl, sizeof(NlbCtl)}); return r; }     // per slot
-    void drop_nlb() { tspmem::free_rows<HipMem>(nlb_rows(0)); nlb_cap = 0; }
+    Rows nlv_rows(size_t n) { return {{&d_nlv_ord, n * 4}, {&d_nlv_best, n * 4}, {&d_nlv_ctl, sizeof(NlvCtl)}}; }           // per walk
+    void drop_nlv() { tspmem::free_rows<HipMem>(nlv_rows(0)); nlv_cap = 0; tspmem::reset_all(d_nlv_rand, d_nlv_trace); }
+    void drop_nlb() { tspmem::free_rows<HipMem>(nlb_rows(0)); nlb_cap = 0; drop_nlv(); }
     void drop_grid() { tspmem::reset_all(d_gxy, d_gidx, d_gpos, d_cstart, d_gcell, d_knn); grid_G = 0; grid_ok = false; }
     void reset() { tspmem::free_rows<HipMem>(m2_rows(m2, 0)); drop_nlb(); drop_grid(); }
     ~InstanceMem() { reset(); }
@@ -3307,6 +3324,8 @@ struct tspgpu_ctx : ContextMem, InstanceMem, CostMem, SlotMem {
     int ornl_rounds = 0;       // rounds of the last tspgpu_local_search_nl
     // batched neighbour-list descent (tspgpu_nlbatch.inc)
     long nlb_tours = 0, nlb_launches = 0, nlb_max_live = 0;     // the last batched descent: tours, sweeps launched, most tours in one
+    // neighbour-list VNS (tspgpu_nlvns.inc): the last call's walks, iterations completed, sweep rounds, most walks live in one, dry walks
+    long nlv_walks = 0, nlv_iterations = 0, nlv_rounds = 0, nlv_max_live = 0, nlv_dry = 0;
 
     int opt_fused = 1;         // 1 = one launch per sweep where applicable
 
@@ -5066,6 +5085,11 @@ long tspgpu_info(const tspgpu_ctx *ctx, int what)
     case 52: return ctx->nlb_tours;
     case 53: return ctx->nlb_launches;
     case 54: return ctx->nlb_max_live;
+    case 56: return ctx->nlv_walks;
+    case 57: return ctx->nlv_iterations;
+    case 58: return ctx->nlv_rounds;
+    case 59: return ctx->nlv_max_live;
+    case 60: return ctx->nlv_dry;
     case 55: return ctx->have_costs && ctx->symmetric && ctx->n >= 8 ? (ctx->n + ORNL_STARTS - 1) / ORNL_STARTS : 0;
     case 12: return (ctx->built && ctx->grid_ok && ctx->opt_nn != 1 && ctx->cost_bound < 134217728.0) ? ctx->grid_G : 0;
     case 13: return ctx->grid_max_occ;
@@ -6889,6 +6913,153 @@ int tspgpu_multistart_local_search_nl(tspgpu_ctx *ctx, const int *starts, int ns
     if (rc && rc != E_DEADLINE) return rc;
     descent_out(&ms.total, 1, total_two_opt_sweeps, total_two_opt_moves, total_or_sweeps, total_or_moves, nullptr);
     return rc;
+}
+
+} // extern "C"
+
+// ---- neighbour-list VNS (tspgpu_nlvns.inc) -----------------------------------------------------------------------------
+
+// per walk beyond the batched descent's: two int arrays of n and a control block; nrand numbers; k trace cells.  All or none
+static int nlv_ensure(tspgpu_ctx *ctx, int walks, long nrand, int k)
+{
+    const size_t n = (size_t)ctx->n, nr = (size_t)walks * (size_t)nrand, nt = (size_t)walks * (size_t)k;
+    const Rows rows = ctx->nlv_rows(n);
+    hipError_t e = hipSuccess;
+    if (walks > ctx->nlv_cap) {
+        ctx->drop_nlv();
+        if ((e = tspmem::grow(HipMem{ctx->stream}, rows, 0, (size_t)walks)) == hipSuccess) ctx->nlv_cap = walks;
+    }
+    if (e == hipSuccess) e = ctx->d_nlv_rand.reserve(std::max<size_t>(nr, 1));
+    if (e == hipSuccess) e = ctx->d_nlv_trace.reserve(std::max<size_t>(nt, 1));
+    if (e != hipSuccess) {
+        (void)hipGetLastError();
+        ctx->drop_nlv();
+        return fail(ctx, E_EXHAUSTED, "the neighbour-list VNS needs %zu bytes of device memory for %d walks of %d nodes, %ld numbers and %d iterations each (%s)",
+                    tspmem::rows_bytes(rows, (size_t)walks) + nr * 4 + nt * 8, walks, ctx->n, nrand, k, hipGetErrorString(e));
+    }
+    return E_OK;
+}
+
+static int nlv_launch_step(tspgpu_ctx *ctx, int live, bool trace)
+{
+    const int n = ctx->n;
+    for (int off = 0; off < live; off += 65535 * 16) {      // (a grid of 1024-thread workgroups holds fewer than 2^32 threads)
+        const unsigned wgs = (unsigned)std::min(65535 * 16, live - off);
+        ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_nlv_step<T>), dim3(wgs), dim3(1024), 0, ctx->stream, ctx->S, (const T *)ctx->d_mat.p, n, ctx->ld,
+                                                     (const int *)(ctx->d_live + off), 0, ctx->nlb, ctx->d_nlb_ctl, ctx->d_nlv_ctl, ctx->d_nlv_ord,
+                                                     ctx->d_nlv_best, (const int *)ctx->d_nlv_rand.p, trace ? ctx->d_nlv_trace.p : nullptr,
+                                                     (const double2 *)ctx->d_pts.p, ctx->kind));
+        HIP_TRY(hipGetLastError());
+    }
+    return E_OK;
+}
+
+// the walks on slots 0 .. walks-1: upload, arm, sweep rounds of five launches (the four of the batched descent and the step)
+// -- four rounds between looks at the control blocks, one under a deadline, as nlb_descent --, download
+static int nlv_walks(tspgpu_ctx *ctx, int walks, int k, double time_left_s, int *paths, double *costs, const int *rand_values, long nrand,
+                     long *consumed, int *iterations, int *kick_pending, int *best_paths, double *best_costs, double *trace, long *totals)
+{
+    const double t_end = deadline_of(time_left_s);
+    const size_t n = (size_t)ctx->n, W = (size_t)walks;
+    int rc;
+    // every path is an n-cycle, or nothing is run
+    std::vector<int> ords(W * n), ord;
+    for (size_t w = 0; w < W; w++) {
+        if ((rc = succ_to_order(ctx, paths + w * n, ord))) return fail(ctx, E_INVALID, "paths[%zu] is not a single n-cycle", w);
+        memcpy(ords.data() + w * n, ord.data(), n * 4);
+    }
+    if ((rc = ensure_tours(ctx, walks))) return rc;
+    if ((rc = nlb_ensure(ctx, walks))) return rc;
+    if ((rc = nlv_ensure(ctx, walks, nrand, k))) return rc;
+    ctx->nlv_walks = walks; ctx->nlv_iterations = ctx->nlv_rounds = ctx->nlv_max_live = ctx->nlv_dry = 0;
+
+    std::vector<NlbCtl> hc(W);
+    std::vector<NlvCtl> hv(W);
+    memset(hc.data(), 0, W * sizeof(NlbCtl));
+    memset(hv.data(), 0, W * sizeof(NlvCtl));
+    std::vector<int> live;
+    for (size_t w = 0; w < W; w++) {
+        const bool finished = iterations[w] >= k, resume = !finished && kick_pending[w] != 0;
+        hv[w].it = iterations[w]; hv[w].k = k; hv[w].halt = finished ? 1 : 0;
+        hv[w].kick_pending = resume ? 1 : 0; hv[w].resume = resume ? 1 : 0;
+        hv[w].nrand = nrand; hv[w].best = best_costs[w];
+        hc[w].stop = finished || resume ? 1 : 0;            // a walk in front of a kick phase skips its descent
+        hc[w].rounds = finished || resume ? 0 : 1;
+        if (!finished) live.push_back((int)w);
+    }
+    HIP_TRY(hipMemcpyAsync(ctx->S.ord, ords.data(), W * n * 4, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = init_slots(ctx, 0, walks, -1))) return rc;    // (recomputes the cost: refinment.c:6-9)
+    mark_slots(ctx, 0, walks, true);
+    HIP_TRY(hipMemcpyAsync(ctx->d_nlv_best, best_paths, W * n * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (nrand > 0) HIP_TRY(hipMemcpyAsync(ctx->d_nlv_rand.p, rand_values, W * (size_t)nrand * 4, hipMemcpyHostToDevice, ctx->stream));
+    if (trace && k > 0) HIP_TRY(hipMemsetAsync(ctx->d_nlv_trace.p, 0xff, W * (size_t)k * 8, ctx->stream));     // (NaN: a cell not written)
+    HIP_TRY(hipMemcpyAsync(ctx->d_nlb_ctl, hc.data(), W * sizeof(NlbCtl), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->d_nlv_ctl, hv.data(), W * sizeof(NlvCtl), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));             // (the copies read pageable memory of this call)
+
+    bool late = false;
+    if (!live.empty() && (rc = set_live(ctx, live))) return rc;
+    while (!live.empty()) {
+        if (t_end >= 0 && now_s() >= t_end) { late = true; break; }
+        const int K = t_end >= 0 ? 1 : 4;
+        ctx->nlv_max_live = std::max(ctx->nlv_max_live, (long)live.size());
+        for (int i = 0; i < K; i++) {
+            if ((rc = nlb_launch_sweep(ctx, 0, (int)live.size()))) return rc;
+            if ((rc = nlv_launch_step(ctx, (int)live.size(), trace != nullptr))) return rc;
+            ctx->nlv_rounds++;
+        }
+        HIP_TRY(hipMemcpyAsync(hv.data(), ctx->d_nlv_ctl, W * sizeof(NlvCtl), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipStreamSynchronize(ctx->stream));
+        size_t m = 0;
+        for (int t : live) if (!hv[t].halt) live[m++] = t;
+        if (m == live.size()) continue;
+        live.resize(m);
+        if (m && (rc = set_live(ctx, live))) return rc;
+    }
+
+    std::vector<double> tr(trace ? W * (size_t)k : 0);
+    HIP_TRY(hipMemcpyAsync(hc.data(), ctx->d_nlb_ctl, W * sizeof(NlbCtl), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(hv.data(), ctx->d_nlv_ctl, W * sizeof(NlvCtl), hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(paths, ctx->S.succ, W * n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(costs, ctx->S.cost, W * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(best_paths, ctx->d_nlv_best, W * n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    if (!tr.empty()) HIP_TRY(hipMemcpyAsync(tr.data(), ctx->d_nlv_trace.p, tr.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    for (size_t w = 0; w < W; w++) {
+        ctx->nlv_iterations += hv[w].it - iterations[w];
+        if (hv[w].halt == 2) ctx->nlv_dry++;
+        iterations[w] = hv[w].it; kick_pending[w] = hv[w].kick_pending; best_costs[w] = hv[w].best; consumed[w] = (long)hv[w].cursor;
+        for (size_t i = 0; i < tr.size() / W; i++)
+            if (tr[w * k + i] == tr[w * k + i]) trace[w * k + i] = tr[w * k + i];
+        if (totals) {
+            long *o = totals + 6 * w;
+            o[0] = (long)hc[w].two_opt_sweeps; o[1] = (long)hc[w].two_opt_moves; o[2] = (long)hc[w].or_sweeps; o[3] = (long)hc[w].or_moves;
+            o[4] = hc[w].rounds; o[5] = (long)hv[w].kicks;
+        }
+    }
+    if (late) return E_DEADLINE;
+    if (ctx->nlv_dry)
+        return fail(ctx, E_EXHAUSTED, "the random numbers of %ld of %d walks ran out in front of a kick phase: call again with more for them",
+                    ctx->nlv_dry, walks);
+    return E_OK;
+}
+
+extern "C" {
+
+int tspgpu_vns_walks_nl(tspgpu_ctx *ctx, int walks, int k, double time_left_s, int *paths, double *costs, const int *rand_values, long nrand,
+                        long *consumed, int *iterations, int *kick_pending, int *best_paths, double *best_costs, double *trace, long *totals)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    if (walks <= 0 || k < 0 || nrand < 0 || !paths || !costs || !consumed || !iterations || !kick_pending || !best_paths || !best_costs ||
+        (nrand > 0 && !rand_values))
+        return fail(ctx, E_INVALID, "bad argument");
+    hipSetDevice(ctx->device);
+    const int rc = ornl_check(ctx);
+    if (rc) return rc;
+    for (int w = 0; w < walks; w++)
+        if (iterations[w] < 0 || iterations[w] > k) return fail(ctx, E_INVALID, "iterations[%d] = %d is outside [0, %d]", w, iterations[w], k);
+    return nlv_walks(ctx, walks, k, time_left_s, paths, costs, rand_values, nrand, consumed, iterations, kick_pending, best_paths, best_costs,
+                     trace, totals);
 }
 
 } // extern "C"

@@ -55,7 +55,8 @@ class Engine:
                  "multi_sweeps", "multi_moves", "multi_max_moves", "multi_r", "multi_block", "multi_nch",
                  "nl_k", "nl_sweeps", "nl_moves", "nl_polish_sweeps", "nl_nodes",
                  "or_nl_sweeps", "or_nl_moves", "or_nl_max_moves", "or_nl_rounds", "or_nl_starts",
-                 "nl_batch_tours", "nl_batch_launches", "nl_batch_max_live", "nl_batch_wgs"]
+                 "nl_batch_tours", "nl_batch_launches", "nl_batch_max_live", "nl_batch_wgs",
+                 "vns_nl_walks", "vns_nl_iterations", "vns_nl_rounds", "vns_nl_max_live", "vns_nl_dry"]
         return {k: int(self.L.tspgpu_info(self.ctx, i)) for i, k in enumerate(names)}
 
     # ---- instance
@@ -248,6 +249,31 @@ class Engine:
                       ok=(T_OK, DEADLINE_EXCEEDED, 8))
         return {"rc": rc, "cost": c.value, "best_cost": bc.value, "iterations": it.value, "kick_pending": kp.value,
                 "consumed": used.value, "trace": trace}
+
+    def vns_walks_nl(self, paths, k, rand_values, best_paths, best_costs, iterations=None, kick_pending=None, time_left_s=-1.0,
+                     want_trace=False):
+        """W walks of the neighbour-list VNS (include/tspgpu.h "Neighbour-list VNS").  paths, best_paths [W][n] int32 and
+        best_costs [W] float64 in place; rand_values [W][nrand]; iterations, kick_pending [W] (default: zeros) are copied ->
+        dict(rc, costs, best_costs, iterations, kick_pending, consumed, trace [W][k] (NaN: not written by this call) or None,
+        totals: dict of [W] arrays two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds, kicks)."""
+        W = paths.shape[0]
+        assert paths.dtype == np.int32 and best_paths.dtype == np.int32 and best_costs.dtype == np.float64
+        assert paths.flags.c_contiguous and best_paths.flags.c_contiguous and best_costs.flags.c_contiguous
+        assert paths.shape == best_paths.shape == (W, self.n) and best_costs.shape == (W,)
+        rv = np.ascontiguousarray(rand_values, dtype=np.int32).reshape(W, -1)
+        it = np.zeros(W, dtype=np.int32) if iterations is None else np.array(iterations, dtype=np.int32)
+        kp = np.zeros(W, dtype=np.int32) if kick_pending is None else np.array(kick_pending, dtype=np.int32)
+        costs = np.zeros(W, dtype=np.float64)
+        used = np.zeros(W, dtype=np.int64)
+        totals = np.zeros((W, 6), dtype=np.int64)
+        trace = np.full((W, max(int(k), 1)), np.nan, dtype=np.float64) if want_trace else None
+        rc = self._ck(self.L.tspgpu_vns_walks_nl(self.ctx, W, int(k), float(time_left_s), paths.reshape(-1), costs, rv.ctypes.data, rv.shape[1],
+                                                 used.ctypes.data, it, kp, best_paths.reshape(-1), best_costs,
+                                                 trace.ctypes.data if want_trace else None, totals.ctypes.data),
+                      ok=(T_OK, DEADLINE_EXCEEDED, 8))
+        names = ("two_opt_sweeps", "two_opt_moves", "or_sweeps", "or_moves", "rounds", "kicks")
+        return {"rc": rc, "costs": costs, "best_costs": best_costs, "iterations": it, "kick_pending": kp, "consumed": used,
+                "trace": trace[:, :int(k)] if want_trace else None, "totals": {nm: totals[:, i].copy() for i, nm in enumerate(names)}}
 
     # ---- multi-start
     @staticmethod

@@ -621,6 +621,76 @@ ERROR_CODE tabu_make_move(int *prev, tsp_solution *solution, int bestCase, int i
     return T_OK;
 }
 
+/* TSP_VNS_NEIGHBOURS=K, K in 1..16 (tsp_run_algorithm): mh_VNS runs TSP_VNS_WALKS walks of the neighbour-list VNS
+ * (tspgpu_vns_walks_nl) over lists of K nodes instead of its own loop */
+static int vns_nl_k = 0, vns_nl_walks = 1;
+enum { VNS_NL_NUMBERS = 1 << 22 };              /* random numbers drawn ahead per call, over all walks */
+
+/* mh_VNS over the neighbour lists.  Every walk starts from the tour in *best (the All-NN tour).  Per call at most C
+ * iterations (W (32 C + 1024) <= 2^22) and 32 c + 1024 numbers per walk for the c <= C iterations it covers: block w of the numbers peeked from the program's glibc stream goes to walk w.
+ * One walk consumes the stream as used, exactly like the loop below; more walks consume the whole peeked block, so a run is
+ * deterministic for a seed, a walk count and k.  The calls are rebased (iterations counted from the slowest walk), so the
+ * trace rows stay C cells long.  The winner is the lowest incumbent, ties to the lowest walk; f gets walk 0's trace. */
+static ERROR_CODE vns_nl_loop(tsp_solution *best, FILE *f)
+{
+    tspgpu_ctx *g = tsp_gpu();
+    if (!g) return UNAVAILABLE;
+    const int n = tsp_inst.nnodes, W = vns_nl_walks, k = tsp_env.k;
+    const int kp = vns_nl_k < n - 1 ? vns_nl_k : n - 1;
+    int rc = tspgpu_info(g, 42) == kp ? 0 : tspgpu_neighbours_build(g, vns_nl_k);
+    if (rc) { log_fatal("code %d : TSP_VNS_NEIGHBOURS=%d: %s", rc, vns_nl_k, tspgpu_last_error(g)); tsp_handlefatal(); }
+    long C = W == 1 ? 16384 : (VNS_NL_NUMBERS / W - 1024) / 32;
+    if (C < 1) C = 1;
+    if (C > 16384) C = 16384;
+    int *paths = (int *)malloc((size_t)W * n * sizeof(int)), *bests = (int *)malloc((size_t)W * n * sizeof(int));
+    int *it = (int *)calloc((size_t)W, sizeof(int)), *itl = (int *)calloc((size_t)W, sizeof(int)), *pending = (int *)calloc((size_t)W, sizeof(int));
+    double *costs = (double *)calloc((size_t)W, sizeof(double)), *bcosts = (double *)malloc((size_t)W * sizeof(double));
+    long *used = (long *)calloc((size_t)W, sizeof(long));
+    double *trace = f ? (double *)malloc((size_t)W * C * sizeof(double)) : NULL;
+    if (!paths || !bests || !it || !itl || !pending || !costs || !bcosts || !used || (f && !trace)) {
+        log_fatal("out of memory for %d walks", W); tsp_handlefatal();
+    }
+    for (int w = 0; w < W; w++) {
+        memcpy(paths + (size_t)w * n, best->path, (size_t)n * sizeof(int));
+        memcpy(bests + (size_t)w * n, best->path, (size_t)n * sizeof(int));
+        bcosts[w] = best->cost;
+    }
+    ERROR_CODE e = T_OK;
+    double shown = best->cost;
+    for (;;) {
+        int lo = it[0];
+        for (int w = 1; w < W; w++) if (it[w] < lo) lo = it[w];
+        if (lo >= k) break;
+        if (past_deadline()) { e = DEADLINE_EXCEEDED; break; }
+        const int kk = k - lo > C ? (int)C : k - lo;
+        const long per = 32L * kk + 1024;
+        for (int w = 0; w < W; w++) itl[w] = it[w] - lo;
+        const int *rv = tsp_rand_peek(per * W);
+        if (!rv) { log_fatal("out of memory for %ld random numbers", per * W); tsp_handlefatal(); }
+        if (trace) for (long i = 0; i < (long)W * kk; i++) trace[i] = NAN;
+        rc = tspgpu_vns_walks_nl(g, W, kk, time_left(), paths, costs, rv, per, used, itl, pending, bests, bcosts, trace, NULL);
+        tsp_rand_consume(W == 1 ? used[0] : per * W);
+        /* RESOURCE_EXHAUSTED with progress: walks ran dry in front of a kick phase, come back with more (see mh_VNS) */
+        int progress = 0;
+        for (int w = 0; w < W; w++) { if (lo + itl[w] > it[w] || used[w] > 0) progress = 1; it[w] = lo + itl[w]; }
+        const int refill = rc == RESOURCE_EXHAUSTED && progress;
+        if (rc != 0 && rc != DEADLINE_EXCEEDED && !refill) {
+            log_fatal("code %d : Error in the neighbour-list VNS: %s", rc, tspgpu_last_error(g));
+            tsp_handlefatal();
+        }
+        for (int w = 0; w < W; w++) if (bcosts[w] < shown) shown = bcosts[w];
+        if (shown < best->cost) { log_info("found new best: %f ", shown); best->cost = shown; }
+        if (trace) for (int i = 0; i < kk; i++) if (!isnan(trace[i])) fprintf(f, "%d,%f\n", lo + i, trace[i]);
+        if (rc == DEADLINE_EXCEEDED) { e = DEADLINE_EXCEEDED; break; }
+    }
+    int win = 0;
+    for (int w = 1; w < W; w++) if (bcosts[w] < bcosts[win]) win = w;
+    best->cost = bcosts[win];
+    memcpy(best->path, bests + (size_t)win * n, (size_t)n * sizeof(int));
+    free(paths); free(bests); free(it); free(itl); free(pending); free(costs); free(bcosts); free(used); free(trace);
+    return e;
+}
+
 /* metaheuristic.c:251-341.  The loop -- local search, incumbent, r = rand() % 9 - 2 kicks -- runs on the device
  * (tspgpu_vns_search: inside the LDS-resident kernel where the instance allows it).  The random numbers stay the
  * program's: they are drawn here from the glibc stream (tsp_rand_peek), handed over in order, and what the device did
@@ -643,7 +713,8 @@ ERROR_CODE mh_VNS(void)
     FILE *f = fopen("results/VNSResults.dat", "w+");
     e = T_OK;
     const char *on_host = getenv("TSP_VNS_HOST");
-    if ((on_host && atoi(on_host)) || two_opt_multi_on || two_opt_nl_k) {      /* (the resident loop's local search is the reference's descent) */
+    if (vns_nl_k) e = vns_nl_loop(&best, f);
+    else if ((on_host && atoi(on_host)) || two_opt_multi_on || two_opt_nl_k) {      /* (the resident loop's local search is the reference's descent) */
         for (int it = 0; it < tsp_env.k; it++) {
             if (past_deadline()) { e = DEADLINE_EXCEEDED; break; }
             e = ref_2opt(&s, tsp_inst.costs, true);
@@ -885,6 +956,32 @@ ERROR_CODE tsp_run_algorithm(void)
         fprintf(stderr, "tsp: TSP_EVERY_START_NEIGHBOURS=%d and TSP_OR_OPT_EVERY_START=1: one descent from every start, not both\n", es_k);
         return INVALID_ARGUMENT;
     }
+    /* TSP_VNS_NEIGHBOURS=K (env_neighbours): -alg VNS runs TSP_VNS_WALKS walks of the neighbour-list VNS over lists of K nodes */
+    const int vns_k = env_neighbours("TSP_VNS_NEIGHBOURS");
+    if (vns_k < 0) return INVALID_ARGUMENT;
+    if (vns_k && ((nl_k && nl_k != vns_k) || (or_nl_k && or_nl_k != vns_k))) {
+        fprintf(stderr, "tsp: TSP_VNS_NEIGHBOURS=%d and TSP_%s_NEIGHBOURS=%d: the list lengths must be equal\n", vns_k,
+                nl_k && nl_k != vns_k ? "2OPT" : "OR_OPT", nl_k && nl_k != vns_k ? nl_k : or_nl_k);
+        return INVALID_ARGUMENT;
+    }
+    int vns_w = 1;
+    {
+        const char *v = getenv("TSP_VNS_WALKS");
+        char *end = NULL;
+        const long w = v ? strtol(v, &end, 10) : 1;
+        if (v && (!*v || *end || w < 1 || w > VNS_NL_NUMBERS / (32 + 1024))) {
+            fprintf(stderr, "tsp: TSP_VNS_WALKS=\"%s\": expected a walk count from 1 to %d\n", v, VNS_NL_NUMBERS / (32 + 1024));
+            return INVALID_ARGUMENT;
+        }
+        vns_w = (int)w;
+    }
+    vns_nl_k = tsp_inst.alg == ALG_VNS ? vns_k : 0;
+    vns_nl_walks = vns_w;
+    if (vns_k && tsp_inst.alg == ALG_VNS)
+        log_warn("TSP_VNS_NEIGHBOURS=%d: mh_VNS runs %d walk%s of the neighbour-list VNS; results differ from the reference's trajectory",
+                 vns_k, vns_w, vns_w == 1 ? "" : "s");
+    else if (vns_k) log_warn("TSP_VNS_NEIGHBOURS=%d has no effect without -alg VNS", vns_k);
+    else if (getenv("TSP_VNS_WALKS")) log_warn("TSP_VNS_WALKS has no effect without TSP_VNS_NEIGHBOURS");
     every_start_nl_k = es_k;
     if (es_k && tsp_inst.alg == ALG_2OPT_GREEDY)
         log_warn("TSP_EVERY_START_NEIGHBOURS=%d: every start runs the descent over the neighbour lists; results differ from the reference's trajectory",
