@@ -121,7 +121,9 @@ int  tspgpu_set_option(tspgpu_ctx *ctx, int option, long value);
  * the first Or-opt round of the last batched descent (tspgpu_tours_local_search and the calls built on it; 0: none ran), 31 the R of a single-tour Or-opt sweep on this instance (0: no matrix),
  * 32 / 33 threads per workgroup (256, 512 or 1024) and 16-byte vectors per thread and matrix row (1, 2 or 3) of an Or-opt sweep,
  * single-tour or batched, on this instance (0 where 31 is 0), 34 how the last matrix-free Or-opt sweep ran (0 none, 1 every candidate
- * evaluated, 2 with the exact early-out), 35 tour positions per workgroup of that sweep (0 where 34 is 0) */
+ * evaluated, 2 with the exact early-out), 35 tour positions per workgroup of that sweep (0 where 34 is 0); 36 .. 60 in the
+ * sections below; 61 the last LDS-resident descent ran in an instantiation of k_lds2opt compiled for its shape (plain 2-opt,
+ * packed 16-bit costs, (n, edges per workgroup) = (4096, 16) or (1024, 4); 0: the generic kernel) */
 long tspgpu_info(const tspgpu_ctx *ctx, int what);
 
 /* ---- instance / cost matrix ------------------------------------------- */

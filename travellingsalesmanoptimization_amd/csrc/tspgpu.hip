@@ -3297,6 +3297,9 @@ struct tspgpu_ctx : ContextMem, InstanceMem, CostMem, SlotMem {
     int opt_otf_early = 0;         // hook 91: 0 automatic, 1 the early-out kernel for every matrix-free sweep, 2 never
     bool plan_otf_early = false;   // the matrix-free plan is the early-out kernel's (runs of 64 edges: plain 2-opt over integer points)
     bool lp_attr[6] = {false, false, false, false, false, false};
+    bool lp_shaped_attr[2] = {false, false};   // ... of the shaped instantiations (lp_shaped_fn)
+    bool lp_shaped = false;    // the last LDS-resident descent ran in a shaped instantiation of k_lds2opt
+    int opt_lp_generic = 0;    // undocumented (option 89): 1 = never a shaped instantiation
     bool max16k = false;       // every off-diagonal cell <= 16383 (packed 16-bit deltas cannot overflow)
     bool max8k = false;        // ... <= 8190 (the tabu form of the packed loop: a poisoned pair must exceed every valid delta)
 
@@ -4098,6 +4101,14 @@ static bool persist_fits_w(const tspgpu_ctx *ctx, int &E, int &W, size_t &lds, i
     return W <= ctx->cus && W <= 256;
 }
 
+// The shaped instantiations of k_lds2opt (plain packed descent, n == nl): the one place that lists them.
+static const void *lp_shaped_fn(int n, int E, int &idx)
+{
+    if (n == 4096 && E == 16) { idx = 0; return (const void *)k_lds2opt<true, false, false, 4096, 16>; }
+    if (n == 1024 && E == 4) { idx = 1; return (const void *)k_lds2opt<true, false, false, 1024, 4>; }
+    return nullptr;
+}
+
 // *ran = false: nothing was touched (does not apply, or the grid did not come up co-resident): the caller takes the
 // one-launch-per-sweep path.  Deadline: launches with a sweep budget of a third of the time left, measured per sweep;
 // every launch leaves a consistent tour (the sweep that ran is applied, refinment.c:17-26).
@@ -4142,14 +4153,22 @@ static int run_persist(tspgpu_ctx *ctx, int slot, double *time_left_io, bool *de
                    : vns ? (pk ? (const void *)k_lds2opt<true, false, true> : (const void *)k_lds2opt<false, false, true>)
                    : tabu ? (pk ? (const void *)k_lds2opt<true, true> : (const void *)k_lds2opt<false, true>)
                           : (pk ? (const void *)k_lds2opt<true, false> : (const void *)k_lds2opt<false, false>);
-    bool &attr = win ? ctx->lpw_attr[pk + (tabu ? 2 : vns ? 4 : 0)] : ctx->lp_attr[pk + (tabu ? 2 : vns ? 4 : 0)];
+    bool *attr_p = win ? &ctx->lpw_attr[pk + (tabu ? 2 : vns ? 4 : 0)] : &ctx->lp_attr[pk + (tabu ? 2 : vns ? 4 : 0)];
+    bool shaped = false;
+    // (E comes from the device's compute units: 16 / 4 on a whole MI355X; with fewer CUs E is larger, no shape is listed and
+    // the generic kernel runs -- tspgpu_info 61 tells)
+    if (!win && !tabu && !vns && pk && !ctx->opt_lp_generic) {
+        int idx = 0;
+        if (const void *sfn = lp_shaped_fn(ctx->n, E, idx)) { fn = sfn; attr_p = &ctx->lp_shaped_attr[idx]; shaped = true; }
+    }
+    bool &attr = *attr_p;
     if (!attr) {
         HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->lds_max));
         attr = true;
     }
     const int block = win ? LW_BT : LP_BT;
     const double t_end = time_left_s >= 0 ? now_s() + time_left_s : -1;
-    if (t_end >= 0 && time_left_s <= 0) { if (deadline_hit) *deadline_hit = true; *ran = true; ctx->lp_used = true; ctx->lp_window = win; return E_OK; }
+    if (t_end >= 0 && time_left_s <= 0) { if (deadline_hit) *deadline_hit = true; *ran = true; ctx->lp_used = true; ctx->lp_window = win; ctx->lp_shaped = false; return E_OK; }
     double sweep_s = 8e-6;
     bool first = true, late = false;
     int retries = 0;
@@ -4283,6 +4302,7 @@ static int run_persist(tspgpu_ctx *ctx, int slot, double *time_left_io, bool *de
     *ran = true;
     ctx->lp_used = true;
     ctx->lp_window = win;
+    ctx->lp_shaped = shaped;
     return E_OK;
 }
 
@@ -4986,6 +5006,7 @@ int tspgpu_set_option(tspgpu_ctx *ctx, int option, long value)
     case TSPGPU_OPT_BLOCK: if (value < 0 || value > 1024) return fail(ctx, E_INVALID, "bad block"); ctx->opt_block = (int)value; ctx->plan_kernel = 0; break;
     case TSPGPU_OPT_DEPTH: if (value < 0 || value > 8) return fail(ctx, E_INVALID, "bad depth"); ctx->opt_depth = (int)value; ctx->plan_kernel = 0; break;
     case 99: ctx->opt_ablate = (int)value; drop_graphs(ctx); break; // undocumented: kernel ablation for profiling
+    case 89: ctx->opt_lp_generic = value ? 1 : 0; break; // undocumented: the generic k_lds2opt where a shaped instantiation exists (tests)
     case 90: ctx->opt_or_otf_early = value == 1 || value == 2 ? (int)value : 0; break; // undocumented: see or_otf_early()
     case 91: ctx->opt_otf_early = value == 1 || value == 2 ? (int)value : 0; ctx->plan_kernel = 0; drop_graphs(ctx); break; // undocumented: see otf_early()
     case 92: ctx->opt_build_tile = (int)value; break; // undocumented: tile of the triangle build (tools/build_probe.py)
@@ -5090,6 +5111,7 @@ long tspgpu_info(const tspgpu_ctx *ctx, int what)
     case 58: return ctx->nlv_rounds;
     case 59: return ctx->nlv_max_live;
     case 60: return ctx->nlv_dry;
+    case 61: return ctx->lp_used && ctx->lp_shaped ? 1 : 0;
     case 55: return ctx->have_costs && ctx->symmetric && ctx->n >= 8 ? (ctx->n + ORNL_STARTS - 1) / ORNL_STARTS : 0;
     case 12: return (ctx->built && ctx->grid_ok && ctx->opt_nn != 1 && ctx->cost_bound < 134217728.0) ? ctx->grid_G : 0;
     case 13: return ctx->grid_max_occ;

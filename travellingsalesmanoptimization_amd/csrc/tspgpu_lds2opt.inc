@@ -125,13 +125,34 @@ __device__ __forceinline__ unsigned lp_pk_min(unsigned a, unsigned b)
 // <= 8190 (2 * 16383 - 2 * cost must exceed every valid delta); the 32-bit form recognises the poison by its value.
 // VNS: mh_VNS's loop around the descent (tspgpu_lds_vns.inc) -- its own instantiation, so that the plain descent carries
 // none of its code or registers.
-template <bool PK16, bool TABU, bool VNS = false>
+// NLC, EC: the SHAPED form of the plain packed descent (NLC > 0): the host promises n == nl == NLC (a power of two, so that
+// every wrap of an array cell is a mask), E == EC (even) and W == NLC / EC workgroups, hence the "once" evaluation geometry,
+// k0 = wg * EC and no overlapping last workgroup.  The sweep loop then knows its strides and trip counts: the evaluation is
+// unrolled over the EC/2 rows of the thread's half with immediate LDS offsets, the half's w[k] arrive in wide reads, the
+// minima stay packed until a column is known to hold the workgroup's minimum, and the exchange reads its wave candidates
+// with independent wide reads.  Same algorithm, keys, records, slots and barriers; NLC == 0 is the generic kernel, unchanged.
+// (The shaped form reads A again from the kernel-argument segment at offset 0: PersistArgs must stay the ONLY argument.)
+template <bool PK16, bool TABU, bool VNS = false, int NLC = 0, int EC = 0>
 __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int EMAX = LP_EMAX, BT = LP_BT;
+    constexpr bool SH = NLC > 0;
+    constexpr int WC = NLC / (EC > 0 ? EC : 1);             // workgroups of the shaped form
+    typedef __attribute__((address_space(4))) const PersistArgs c_PersistArgs;      // (the kernel arguments where they lie)
+    static_assert(!SH || (PK16 && !TABU && !VNS), "the shaped form is the plain packed descent");
+    static_assert(!SH || ((NLC & (NLC - 1)) == 0 && NLC % 16 == 0 && NLC / 8 <= LP_BT), "shaped n: a power of two, at most 8 cells a thread");
+    static_assert(!SH || (EC >= 2 && EC % 2 == 0 && EC <= LP_EMAX && NLC % EC == 0 && NLC / EC <= 256), "shaped E: even, W = n / E <= 256");
     constexpr unsigned POISON = PK16 ? 16383u : 65535u;     // on the diagonal: delta(k, k) = 2 POISON - 2 w[k] >= 0
-    const int n = A.n, nl = A.nl, ld = A.ld, E = A.E, W = (int)gridDim.x, wg = (int)blockIdx.x, tid = (int)threadIdx.x, t = A.slot;
+    const int n = SH ? NLC : A.n, nl = SH ? NLC : A.nl, ld = A.ld, E = SH ? EC : A.E, W = SH ? WC : (int)gridDim.x,
+              wg = (int)blockIdx.x, tid = (int)threadIdx.x, t = A.slot;
+    // array cells wrap at n: from above (p < 2n), from below (p >= -n), at n exactly -- one mask in the shaped form
+#define LP_WRAP_HI(p) if constexpr (SH) p &= NLC - 1; else if (p >= n) p -= n
+#define LP_WRAP_LO(p) if constexpr (SH) p &= NLC - 1; else if (p < 0) p += n
+#define LP_WRAP_EQS(p) if constexpr (SH) p &= NLC - 1; else if (p == n) p = 0
+#define LP_TID (SH ? tid_sweep : tid)
+#define LP_LM0 (SH ? lm0_sweep : lm0)
+#define LP_WRAP_EQ(p) (SH ? ((p) & (NLC - 1)) : ((p) == n ? 0 : (p)))
     const size_t tn = (size_t)t * n;
     // LDS: E+1 rows of nl cells | wt: nl words (w | label << 16) | one staging row (scratch between the staging uses)
     u16 *rows = reinterpret_cast<u16 *>(smem);
@@ -142,7 +163,7 @@ __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
     int *scr32 = reinterpret_cast<int *>(stage);      // [40..47] wave minima
     u16 *age16 = stage + max(nl, 128);                // TABU: iterations since the node at the cell was moved (0xFFFF: never)
     constexpr int DINF = 0x7fffffff;
-    const int k0 = min(wg * E, n - E);                // own edges: array cells k0 .. k0+E-1 (the last workgroup overlaps its neighbour:
+    const int k0 = SH ? wg * E : min(wg * E, n - E);  // own edges: array cells k0 .. k0+E-1 (the last workgroup overlaps its neighbour:
                                                       // a pair found twice is found with the same key); own rows: cells k0 .. k0+E
     const int m0 = tid * 8;                           // the 8 array cells this thread evaluates against every own edge
     const bool act = m0 < nl;
@@ -176,8 +197,24 @@ __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
         u64 *cand = scr + 2 + (s & 1) * 8;            // (two sets in turn: the next exchange does not wait for this one's readers)
         if (wv < nwp && (long long)a == wm) { cand[2 * wv] = a; cand[2 * wv + 1] = b; }
         __syncthreads();
-        u64 x0 = cand[0], x1 = cand[1];
-        for (int i = 1; i < nwp; i++) { const u64 y = cand[2 * i]; if (y < x0) { x0 = y; x1 = cand[2 * i + 1]; } }
+        u64 x0, x1;
+        if constexpr (SH) {
+            // every wave's candidate in one 16-byte read of its own, all in flight together; the minimum is taken in registers
+            constexpr int NWP = (WC + 63) >> 6;
+            v4u32 c[NWP];
+#pragma unroll
+            for (int i = 0; i < NWP; i++) c[i] = *reinterpret_cast<const v4u32 *>(cand + 2 * i);
+            x0 = c[0].x | (u64)c[0].y << 32; x1 = c[0].z | (u64)c[0].w << 32;
+#pragma unroll
+            for (int i = 1; i < NWP; i++) {
+                const u64 y0 = c[i].x | (u64)c[i].y << 32, y1 = c[i].z | (u64)c[i].w << 32;
+                const bool lt = y0 < x0;
+                x0 = lt ? y0 : x0; x1 = lt ? y1 : x1;
+            }
+        } else {
+            x0 = cand[0]; x1 = cand[1];
+            for (int i = 1; i < nwp; i++) { const u64 y = cand[2 * i]; if (y < x0) { x0 = y; x1 = cand[2 * i + 1]; } }
+        }
         r0 = ((u64)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(x0 >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)x0);
         r1 = ((u64)(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(x1 >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)x1);
     };
@@ -213,7 +250,7 @@ __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
     // staging row) -- so that one barrier per row is enough.
     auto reload = [&](unsigned need) __attribute__((always_inline)) {
         const int lane = tid & 63;
-        int oc = k0 + min(lane, E); if (oc >= n) oc -= n;
+        int oc = k0 + min(lane, E); LP_WRAP_HI(oc);
         const unsigned ownlab = wt16[2 * oc + 1];                  // lane r: the node at the own cell r
         unsigned offs[8];                                          // byte offsets of the own chunk's labels in a node-order row
         if (act) {
@@ -229,6 +266,9 @@ __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
                 if (act) R[r] = *reinterpret_cast<const v4u32 *>(A.mat + (size_t)x * ld + m0);
             }
         }
+        // (shaped form: the row mask is opaque from here on, so that its bits are tested again where the rows are written and
+        // not kept as 17 lane masks across the loads)
+        if constexpr (SH) asm volatile("" : "+s"(need));
         const int last = 31 - __builtin_clz(need);
         int left = __builtin_popcount(need);                       // rows still to be written to a buffer
         unsigned char *bufT = reinterpret_cast<unsigned char *>(rows + (size_t)last * nl);
@@ -340,6 +380,11 @@ __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
     const u16 *rchunk = rows + (size_t)rlo * nl + me0;     // this thread's 8 cells of its first row
     const u16 *rex = rows + (size_t)rlo * nl + mexe;       // ... and the cell behind them
     while (status == LP_ST_RUNNING) {
+        // shaped form: the thread index is opaque inside a sweep (LP_TID), so that the lane masks and small indices derived
+        // from it are computed where they are used (one compare each) and not held in scalar registers across the whole loop
+        int tid_sweep = 0;
+        int lm0_sweep = 0;                            // (likewise the first cell of the lane's (edge, chunk) item: LP_LM0)
+        if constexpr (SH) { tid_sweep = tid; lm0_sweep = lm0; asm volatile("" : "+v"(tid_sweep), "+v"(lm0_sweep)); }
         // ---- evaluation: for each of the 8 own columns the minimum over the thread's own edges of
         // G_k[m] + G_{k+1}[m+1] - w[k] (one row ahead in registers: the next row's loads are in flight under this row's arithmetic)
         int col[8], lcol[8];
@@ -349,6 +394,62 @@ __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
             const int r = tid & 63;
             etmask = (unsigned)__ballot(r < E && tabu_edge(k0 + min(r, E - 1)));
         }
+        unsigned pacc[4] = {0, 0, 0, 0};              // shaped form: the 8 columns' minima, packed, w[m] subtracted
+        if constexpr (SH) {
+            // EC/2 rows, unrolled: row r of the half lies r * NLC cells behind rchunk (an immediate offset), the half's w[k] are
+            // EC/2 consecutive words of wt.  Every thread is active or idle for good (n == nl: no padding cell, no mirror).
+            constexpr int RC = EC / 2;
+            if (NLC / 8 >= BT || eact) {
+                unsigned wkw[RC];
+                {
+                    const unsigned *wp = wt + k0 + rlo;           // (k0 and rlo are multiples of EC/2 words)
+                    if constexpr (RC % 4 == 0) {
+#pragma unroll
+                        for (int q = 0; q < RC / 4; q++) {
+                            const v4u32 w4 = *reinterpret_cast<const v4u32 *>(wp + 4 * q);
+                            wkw[4 * q] = w4.x; wkw[4 * q + 1] = w4.y; wkw[4 * q + 2] = w4.z; wkw[4 * q + 3] = w4.w;
+                        }
+                    } else if constexpr (RC % 2 == 0) {
+#pragma unroll
+                        for (int q = 0; q < RC / 2; q++) {
+                            const u64 w2 = *reinterpret_cast<const u64 *>(wp + 2 * q);
+                            wkw[2 * q] = (unsigned)w2; wkw[2 * q + 1] = (unsigned)(w2 >> 32);
+                        }
+                    } else {
+#pragma unroll
+                        for (int q = 0; q < RC; q++) wkw[q] = wp[q];
+                    }
+                }
+                unsigned acc[4] = {0x7fff7fffu, 0x7fff7fffu, 0x7fff7fffu, 0x7fff7fffu};
+                v4u32 X = *reinterpret_cast<const v4u32 *>(rchunk);
+                v4u32 Xn = *reinterpret_cast<const v4u32 *>(rchunk + NLC);
+                unsigned exn = rex[NLC];
+#pragma unroll
+                for (int r = 0; r < RC; r++) {
+                    const v4u32 Xc = Xn;
+                    const unsigned exc = exn;
+                    if (r + 1 < RC) {                             // (one row ahead: the loads fly under this row's arithmetic)
+                        Xn = *reinterpret_cast<const v4u32 *>(rchunk + (size_t)(r + 2) * NLC);
+                        exn = rex[(size_t)(r + 2) * NLC];
+                    }
+                    const unsigned Y[4] = {__builtin_amdgcn_alignbit(Xc.y, Xc.x, 16), __builtin_amdgcn_alignbit(Xc.z, Xc.y, 16),
+                                           __builtin_amdgcn_alignbit(Xc.w, Xc.z, 16), __builtin_amdgcn_alignbit(exc, Xc.w, 16)};
+                    const unsigned Xa[4] = {X.x, X.y, X.z, X.w};
+                    const unsigned wk2 = __builtin_amdgcn_perm(wkw[r], wkw[r], 0x01000100u);     // w[k] in both halves
+#pragma unroll
+                    for (int j = 0; j < 4; j++) acc[j] = lp_pk_min(acc[j], lp_pk_sub(lp_pk_add(Xa[j], Y[j]), wk2));
+                    X = Xc;
+                }
+                // - w[m], still packed (|delta| <= 2 * 16383: no 16-bit overflow); unpacked only where the minimum turns out to be
+                const v4u32 wa = *reinterpret_cast<const v4u32 *>(wt + me0), wb = *reinterpret_cast<const v4u32 *>(wt + me0 + 4);
+                pacc[0] = lp_pk_sub(acc[0], __builtin_amdgcn_perm(wa.y, wa.x, 0x05040100u));
+                pacc[1] = lp_pk_sub(acc[1], __builtin_amdgcn_perm(wa.w, wa.z, 0x05040100u));
+                pacc[2] = lp_pk_sub(acc[2], __builtin_amdgcn_perm(wb.y, wb.x, 0x05040100u));
+                pacc[3] = lp_pk_sub(acc[3], __builtin_amdgcn_perm(wb.w, wb.z, 0x05040100u));
+                const unsigned pm = lp_pk_min(lp_pk_min(pacc[0], pacc[1]), lp_pk_min(pacc[2], pacc[3]));
+                tmin = min((int)(short)(pm & 0xffffu), (int)pm >> 16);
+            }
+        } else
         if (eact) {
             unsigned acc[4] = {0x7fff7fffu, 0x7fff7fffu, 0x7fff7fffu, 0x7fff7fffu};
 #pragma unroll
@@ -414,10 +515,10 @@ __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
         }
         if (lact) {                                   // the (edge, chunk) items the halves do not reach: one per lane
             const u16 *ra = rows + (size_t)lr * nl;
-            const v4u32 Xa4 = *reinterpret_cast<const v4u32 *>(ra + lm0), Xb4 = *reinterpret_cast<const v4u32 *>(ra + nl + lm0);
+            const v4u32 Xa4 = *reinterpret_cast<const v4u32 *>(ra + LP_LM0), Xb4 = *reinterpret_cast<const v4u32 *>(ra + nl + LP_LM0);
             const unsigned exb = ra[nl + lmex];
             const int wkl = (int)wt16[2 * (k0 + lr)];
-            const v4u32 wa = *reinterpret_cast<const v4u32 *>(wt + lm0), wb = *reinterpret_cast<const v4u32 *>(wt + lm0 + 4);
+            const v4u32 wa = *reinterpret_cast<const v4u32 *>(wt + LP_LM0), wb = *reinterpret_cast<const v4u32 *>(wt + LP_LM0 + 4);
             const unsigned xs[9] = {Xb4.x & 0xffffu, Xb4.x >> 16, Xb4.y & 0xffffu, Xb4.y >> 16, Xb4.z & 0xffffu, Xb4.z >> 16,
                                     Xb4.w & 0xffffu, Xb4.w >> 16, exb};
             const unsigned as[8] = {Xa4.x & 0xffffu, Xa4.x >> 16, Xa4.y & 0xffffu, Xa4.y >> 16, Xa4.z & 0xffffu, Xa4.z >> 16,
@@ -443,8 +544,8 @@ __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
         }
         LP_PHASE(0);                                  // evaluation
         const int wmin = wave_min_i32(tmin);
-        if ((tid & 63) == 0) scr32[40 + (tid >> 6)] = wmin;
-        if (tid == 0) scr[0] = ~0ull;
+        if ((LP_TID & 63) == 0) scr32[40 + (LP_TID >> 6)] = wmin;
+        if (LP_TID == 0) scr[0] = ~0ull;
         __syncthreads();
         int dmin = scr32[40];
 #pragma unroll
@@ -457,7 +558,7 @@ __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
         const bool found = TABU ? dmin < DINF : dmin < 0;      // (tabu_best_move takes the best admissible pair whatever its sign)
         if (found) {
             auto offer = [&](int k, int m, unsigned xa, unsigned yb) __attribute__((always_inline)) {
-                const int kp = k + 1 == n ? 0 : k + 1, mp = m + 1 == n ? 0 : m + 1;
+                const int kp = LP_WRAP_EQ(k + 1), mp = LP_WRAP_EQ(m + 1);
                 const unsigned lk = dir > 0 ? wt16[2 * k + 1] : wt16[2 * kp + 1];
                 const unsigned lm = dir > 0 ? wt16[2 * m + 1] : wt16[2 * mp + 1];
                 const unsigned la = min(lk, lm), lb = max(lk, lm);
@@ -473,7 +574,7 @@ __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
 #pragma unroll
                 for (int v = 0; v < 8; v++) {
                     if (lcol[v] == dmin) {
-                        const int m = lm0 + v, mp = m + 1 == n ? 0 : m + 1;
+                        const int m = LP_LM0 + v, mp = LP_WRAP_EQ(m + 1);
                         offer(k0 + lr, m, rows[(size_t)lr * nl + m], rows[(size_t)(lr + 1) * nl + mp]);
                     }
                 }
@@ -481,10 +582,13 @@ __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
             unsigned cm = 0;
             if (eact && tmin == dmin) {
 #pragma unroll
-                for (int v = 0; v < 8; v++) cm |= (col[v] == dmin ? 1u : 0u) << v;
+                for (int v = 0; v < 8; v++) {
+                    if constexpr (SH) col[v] = (v & 1) ? ((int)pacc[v >> 1] >> 16) : (int)(short)(pacc[v >> 1] & 0xffffu);
+                    cm |= (col[v] == dmin ? 1u : 0u) << v;
+                }
             }
             unsigned long long ball = __ballot(cm != 0);
-            const int lane = tid & 63;
+            const int lane = LP_TID & 63;
             while (ball) {
                 const int src = __builtin_ctzll(ball);
                 ball &= ball - 1;
@@ -494,7 +598,7 @@ __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
                 while (cms) {
                     const int v = __builtin_ctz(cms);
                     cms &= cms - 1;
-                    const int m = m0s + v, mp = m + 1 == n ? 0 : m + 1;
+                    const int m = m0s + v, mp = LP_WRAP_EQ(m + 1);
                     if (lane < rcnts) {
                         const int r = rlos + lane, k = k0 + r;
                         const unsigned xa = rows[(size_t)r * nl + m], yb = rows[(size_t)(r + 1) * nl + mp];
@@ -509,7 +613,7 @@ __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
         }
         __syncthreads();
         const u64 kmin = scr[0];
-        const bool have = found ? mykey == kmin : tid == 0;
+        const bool have = found ? mykey == kmin : LP_TID == 0;
         LP_PHASE(1);                                  // workgroup reduction + tie order
         // ---- exchange
         sdone++;
@@ -520,7 +624,7 @@ __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
         const bool nomove = (r0 >> 24) == 0xFFFFFFFFFull;
         if (nomove && !TABU) {                        // the final, non-improving sweep
             lastd = 0;
-            if (wg == 0 && tid == 0 && t == 0 && kd <= A.hist.cap) { A.hist.a[kd - 1] = -1; A.hist.b[kd - 1] = -1; A.hist.d[kd - 1] = 0.0; }
+            if (wg == 0 && LP_TID == 0 && t == 0 && kd <= A.hist.cap) { A.hist.a[kd - 1] = -1; A.hist.b[kd - 1] = -1; A.hist.d[kd - 1] = 0.0; }
             if constexpr (!VNS) { status = LP_ST_OPTIMUM; break; }
             else {
                 // mh_VNS: incumbent, trace, kicks; then the next iteration's local search
@@ -537,19 +641,19 @@ __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
         const unsigned wTT = (unsigned)((r1 >> 16) & 0xffffu), wHH = (unsigned)(r1 & 0xffffu);
         const bool e1_is_a = (r1 >> 56) & 1;
         sumd += d; lastd = d;
-        if (wg == 0 && tid == 0 && t == 0 && kd <= A.hist.cap) { A.hist.a[kd - 1] = la; A.hist.b[kd - 1] = lb; A.hist.d[kd - 1] = (double)d; }
+        if (wg == 0 && LP_TID == 0 && t == 0 && kd <= A.hist.cap) { A.hist.a[kd - 1] = la; A.hist.b[kd - 1] = lb; A.hist.d[kd - 1] = (double)d; }
 
         // ---- the move as an array operation (see Tours): ref_reverse_path flips the arc succ a .. b; flipping the other
         // arc and toggling dir gives the same successor function, so the shorter arc [lo, lo+M) is reversed
         const int ea = e1_is_a ? e1 : e2, eb = e1_is_a ? e2 : e1;
         const int s1 = dir > 0 ? ea : eb, s2 = dir > 0 ? eb : ea;
-        int L = s2 - s1; if (L < 0) L += n;
+        int L = s2 - s1; LP_WRAP_LO(L);
         const bool other = n - L < L;
         const int M = other ? n - L : L;
-        int lo = (other ? s2 : s1) + 1; if (lo == n) lo = 0;
+        int lo = (other ? s2 : s1) + 1; LP_WRAP_EQS(lo);
         if (other) dir = -dir;
-        int eTT = lo - 1; if (eTT < 0) eTT += n;          // the edge in front of the range joins the two tails,
-        int eHH = lo + M - 1; if (eHH >= n) eHH -= n;     // the edge at its last cell the two heads
+        int eTT = lo - 1; LP_WRAP_LO(eTT);          // the edge in front of the range joins the two tails,
+        int eHH = lo + M - 1; LP_WRAP_HI(eHH);     // the edge at its last cell the two heads
         const int hs = M >> 1, hw = (M - 1) >> 1, nrow = E + 1;
         unsigned wOldTT = 0, wOldHH = 0;              // TABU: the costs of the two edges the move removes (for the poison patches)
         if constexpr (TABU) {
@@ -563,15 +667,15 @@ __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
         unsigned need = 0, swp = 0;                   // swp bit r: row r changes places with the row mirv (lane r) above it
         int mirv = 0;
         {
-            int off = k0 - lo; if (off < 0) off += n;
+            int off = k0 - lo; LP_WRAP_LO(off);
             if (off < M || off + E >= n) {
-                const int r = tid & 63;
+                const int r = LP_TID & 63;
                 bool nd = false, sw = false;
                 if (r <= E) {
-                    int rel = off + r; if (rel >= n) rel -= n;
+                    int rel = off + r; LP_WRAP_HI(rel);
                     if (rel < M) {
-                        int pm = lo + (M - 1 - rel); if (pm >= n) pm -= n;
-                        int rm = pm - k0; if (rm < 0) rm += n;
+                        int pm = lo + (M - 1 - rel); LP_WRAP_HI(pm);
+                        int rm = pm - k0; LP_WRAP_LO(rm);
                         nd = rm > E; sw = !nd && rm > r; mirv = rm;
                     }
                 }
@@ -581,15 +685,15 @@ __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
         LP_PHASE2(1);
         if (M <= 16) {
             // a short range (7 of 10 moves): every swap there is -- rows, labels, edge costs -- in one step, 8 lanes an item
-            const int item = tid >> 3, u = tid & 7;
+            const int item = LP_TID >> 3, u = LP_TID & 7;
             u16 *base = rows + (size_t)item * nl;
             int st = 1, last = M - 1, cnt = item <= E && !((need >> item) & 1) ? hs : 0;
             if (item == E + 1) { base = wt16 + 1; st = 2; cnt = hs; }
             if (item == E + 2) { base = wt16; st = 2; last = M - 2; cnt = hw; }
             if (TABU && item == E + 3) { base = age16; st = 1; cnt = hs; }
             if (u < cnt) {
-                int p1 = lo + u; if (p1 >= n) p1 -= n;
-                int p2 = lo + last - u; if (p2 >= n) p2 -= n;
+                int p1 = lo + u; LP_WRAP_HI(p1);
+                int p2 = lo + last - u; LP_WRAP_HI(p2);
                 const u16 x = base[p1 * st], y = base[p2 * st];
                 base[p1 * st] = y; base[p2 * st] = x;
             }
@@ -602,9 +706,9 @@ __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
                 if (I > 0) {
                     int lgi = 0;
                     while ((1 << lgi) < I && lgi < 9) lgi++;
-                    const int rpi = BT >> lgi, j0 = tid & ((1 << lgi) - 1), rs0 = tid >> lgi;
-                    int a = lo + 8 * j0; if (a >= n) a -= n;
-                    int b = lo + M - 8 * j0 - 8; if (b >= n) b -= n;
+                    const int rpi = BT >> lgi, j0 = LP_TID & ((1 << lgi) - 1), rs0 = LP_TID >> lgi;
+                    int a = lo + 8 * j0; LP_WRAP_HI(a);
+                    int b = lo + M - 8 * j0 - 8; LP_WRAP_HI(b);
                     const bool wrapped = a + 8 > n || b + 8 > n;      // the item crosses the array end: cell by cell
                     for (int row0 = 0; row0 <= E; row0 += 2 * rpi) {
                         v4u32 va[2], vb[2];
@@ -631,8 +735,8 @@ __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
                             } else if (ok[q]) {
                                 u16 *base = rows + (size_t)row * nl;
                                 for (int c = 0; c < 8; c++) {
-                                    int p1 = a + c; if (p1 >= n) p1 -= n;
-                                    int p2 = b + 7 - c; if (p2 >= n) p2 -= n;
+                                    int p1 = a + c; LP_WRAP_HI(p1);
+                                    int p2 = b + 7 - c; LP_WRAP_HI(p2);
                                     const u16 x = base[p1], y = base[p2];
                                     base[p1] = y; base[p2] = x;
                                 }
@@ -641,26 +745,26 @@ __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
                     }
                 }
                 {   // the middle of every matrix row
-                    const int row = tid >> 3, u = 8 * I + (tid & 7);
+                    const int row = LP_TID >> 3, u = 8 * I + (LP_TID & 7);
                     if (row <= E && u < hs && !((need >> row) & 1)) {
-                        int p1 = lo + u; if (p1 >= n) p1 -= n;
-                        int p2 = lo + M - 1 - u; if (p2 >= n) p2 -= n;
+                        int p1 = lo + u; LP_WRAP_HI(p1);
+                        int p2 = lo + M - 1 - u; LP_WRAP_HI(p2);
                         u16 *base = rows + (size_t)row * nl;
                         const u16 x = base[p1], y = base[p2];
                         base[p1] = y; base[p2] = x;
                     }
                 }
-                for (int u = tid; u < hs; u += BT) {      // the labels
-                    int p1 = lo + u; if (p1 >= n) p1 -= n;
-                    int p2 = lo + M - 1 - u; if (p2 >= n) p2 -= n;
+                for (int u = LP_TID; u < hs; u += BT) {      // the labels
+                    int p1 = lo + u; LP_WRAP_HI(p1);
+                    int p2 = lo + M - 1 - u; LP_WRAP_HI(p2);
                     const u16 x = wt16[2 * p1 + 1], y = wt16[2 * p2 + 1];
                     wt16[2 * p1 + 1] = y; wt16[2 * p2 + 1] = x;
                 }
             }
             LP_PHASE2(2);
-            for (int u = tid; u < hw; u += BT) {          // the M-1 edge costs inside the range
-                int p1 = lo + u; if (p1 >= n) p1 -= n;
-                int p2 = lo + M - 2 - u; if (p2 >= n) p2 -= n;
+            for (int u = LP_TID; u < hw; u += BT) {          // the M-1 edge costs inside the range
+                int p1 = lo + u; LP_WRAP_HI(p1);
+                int p2 = lo + M - 2 - u; LP_WRAP_HI(p2);
                 const u16 x = wt16[2 * p1], y = wt16[2 * p2];
                 wt16[2 * p1] = y; wt16[2 * p2] = x;
             }
@@ -673,7 +777,7 @@ __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
                 }
             }
         }
-        if (tid == BT - 1) { wt16[2 * eTT] = (u16)wTT; wt16[2 * eHH] = (u16)wHH; }
+        if (LP_TID == BT - 1) { wt16[2 * eTT] = (u16)wTT; wt16[2 * eHH] = (u16)wHH; }
         LP_PHASE(5);                                  // (decode + own swaps, before the barrier)
         __syncthreads();
         if (swp) {
@@ -742,6 +846,12 @@ __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
     }
 #undef LP_PHASE
 #undef LP_PHASE2
+#undef LP_WRAP_HI
+#undef LP_WRAP_LO
+#undef LP_WRAP_EQS
+#undef LP_WRAP_EQ
+#undef LP_TID
+#undef LP_LM0
     if (clk) {
         unsigned long long *o = A.stamps + (size_t)wg * 16;
         for (int i = 0; i < 6; i++) o[i] = ph[i];
@@ -749,28 +859,43 @@ __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
         for (int i = 0; i < 4; i++) o[9 + i] = ph2[i];
         if constexpr (VNS) { o[13] = vns_ph[0]; o[14] = vns_ph[1]; o[15] = vns_ph[2]; }
     }
-    // ---- the tour state back to the slot (every workgroup its own cells)
-    if (tid < E) {
-        const int p = k0 + tid;
-        int pn = p + 1; if (pn == n) pn = 0;
-        int pp = p - 1; if (pp < 0) pp += n;
-        const int lab = wt16[2 * p + 1];
-        A.S.ord[tn + p] = lab;
-        reinterpret_cast<int *>(A.S.dpos + tn)[p] = (int)wt16[2 * p];
-        A.S.pos[tn + lab] = p;
-        A.S.succ[tn + lab] = dir > 0 ? (int)wt16[2 * pn + 1] : (int)wt16[2 * pp + 1];
-        reinterpret_cast<int *>(A.S.dnb + tn)[lab] = dir > 0 ? (int)wt16[2 * p] : (int)wt16[2 * pp];
+    // ---- the tour state back to the slot (every workgroup its own cells).  Shaped form: the slot's arrays are read from the
+    // kernel arguments AGAIN, through a pointer the compiler cannot see through -- a dozen 64-bit pointers that are used
+    // before and behind the sweep loop only would otherwise live (spilled to lanes) across all of it.
+#define LP_WRITE_BACK(S_, t_, tn_, ctl_)                                                                                  \
+    if (tid < E) {                                                                                                        \
+        const int p = k0 + tid;                                                                                           \
+        int pn = p + 1; if (pn == n) pn = 0;                                                                              \
+        int pp = p - 1; if (pp < 0) pp += n;                                                                              \
+        const int lab = wt16[2 * p + 1];                                                                                  \
+        S_.ord[tn_ + p] = lab;                                                                                            \
+        reinterpret_cast<int *>(S_.dpos + tn_)[p] = (int)wt16[2 * p];                                                     \
+        S_.pos[tn_ + lab] = p;                                                                                            \
+        S_.succ[tn_ + lab] = dir > 0 ? (int)wt16[2 * pn + 1] : (int)wt16[2 * pp + 1];                                     \
+        reinterpret_cast<int *>(S_.dnb + tn_)[lab] = dir > 0 ? (int)wt16[2 * p] : (int)wt16[2 * pp];                      \
+    }                                                                                                                     \
+    if (wg == 0 && tid == 0) {                                                                                            \
+        S_.dir[t_] = dir;                                                                                                 \
+        S_.cost[t_] = cost0 + (double)sumd;                                                                               \
+        S_.nsweeps[t_] = kd;                                                                                              \
+        if (sdone > 0) S_.last_delta[t_] = (double)lastd;                                                                 \
+        if (status == LP_ST_OPTIMUM || status == LP_ST_CAPPED) S_.done[t_] = 1;                                           \
+        if constexpr (TABU || VNS) *A.best_out = best;                                                                    \
+        if constexpr (VNS) { A.vns_state[0] = vit; A.vns_state[1] = vcur; A.vns_state[2] = status == LP_ST_NEED_RAND ? 1 : 0; } \
+        ctl_[1] = status; ctl_[2] = sdone;                                                                                \
     }
-    if (wg == 0 && tid == 0) {
-        A.S.dir[t] = dir;
-        A.S.cost[t] = cost0 + (double)sumd;
-        A.S.nsweeps[t] = kd;
-        if (sdone > 0) A.S.last_delta[t] = (double)lastd;
-        if (status == LP_ST_OPTIMUM || status == LP_ST_CAPPED) A.S.done[t] = 1;
-        if constexpr (TABU || VNS) *A.best_out = best;
-        if constexpr (VNS) { A.vns_state[0] = vit; A.vns_state[1] = vcur; A.vns_state[2] = status == LP_ST_NEED_RAND ? 1 : 0; }
-        A.ctl[1] = status; A.ctl[2] = sdone;
+    if constexpr (SH) {
+        // (the kernel-argument segment begins with the explicit arguments: PersistArgs, the only one, lies at offset 0)
+        static_assert(std::is_same_v<decltype(&k_lds2opt<PK16, TABU, VNS, NLC, EC>), void (*)(PersistArgs)>, "PersistArgs must stay the kernel's only argument");
+        c_PersistArgs *Ak = (c_PersistArgs *)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(Ak));
+        const int tk = Ak->slot;
+        const size_t tnk = (size_t)tk * n;
+        LP_WRITE_BACK(Ak->S, tk, tnk, Ak->ctl)
+    } else {
+        LP_WRITE_BACK(A.S, t, tn, A.ctl)
     }
+#undef LP_WRITE_BACK
 }
 
 // the best tour of the tabu walk as a successor array (behind the kernel boundary: every cell of best_ord is visible)

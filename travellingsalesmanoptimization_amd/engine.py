@@ -56,7 +56,8 @@ class Engine:
                  "nl_k", "nl_sweeps", "nl_moves", "nl_polish_sweeps", "nl_nodes",
                  "or_nl_sweeps", "or_nl_moves", "or_nl_max_moves", "or_nl_rounds", "or_nl_starts",
                  "nl_batch_tours", "nl_batch_launches", "nl_batch_max_live", "nl_batch_wgs",
-                 "vns_nl_walks", "vns_nl_iterations", "vns_nl_rounds", "vns_nl_max_live", "vns_nl_dry"]
+                 "vns_nl_walks", "vns_nl_iterations", "vns_nl_rounds", "vns_nl_max_live", "vns_nl_dry",
+                 "persist_shaped"]
         return {k: int(self.L.tspgpu_info(self.ctx, i)) for i, k in enumerate(names)}
 
     # ---- instance
