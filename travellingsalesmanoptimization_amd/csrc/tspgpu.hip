@@ -50,6 +50,7 @@
 #include <vector>
 
 #include "tspgpu.h"
+#include "tspgpu_relaunch.h"    // LP_ST_*, and the host's protocol over them (run_persist, run_pstream)
 
 #ifndef TSPGPU_RPC
 #define TSPGPU_RPC 3   // rows landed per chunk in the resident bodies (tools: -DTSPGPU_RPC=2 to compare)
@@ -3280,24 +3281,19 @@ struct tspgpu_ctx : ContextMem, InstanceMem, CostMem, SlotMem {
     long lp_sweeps = 0;        // sweeps run by the launches of the last LDS-resident descent / walk
     int vns_mode = 0;          // the last tspgpu_vns_search: 1 resident throughout, 2 host kicks throughout, 3 resident launches first,
                                // then (the grid lost its co-residency) host kicks
-    bool lpw_attr[6] = {false, false, false, false, false, false};
     long opt_lp_hello = 200000; // rendezvous limit in 10 ns ticks
     int opt_lp_poll_sleep = 0;  // probe hook 95
     int opt_vns_launch_k = 65536;   // VNS iterations a launch may complete (test hook 94 lowers it to force relaunches)
     int opt_lp_fail_at = 0;     // test hook 96: the next N RE-launches of a descent (deadline runs relaunch per sweep budget) fail their rendezvous
     int vns_launch_nrand = 0;   // VNS: the caller's rand() values of a launch
-    int lp_skip = 0, lp_backoff = 16;   // the grid did not come up co-resident: the next lp_skip descents keep to the one-launch-per-sweep
-                                        // path, then it is tried again (16, 32, ... 1024 descents apart while it keeps failing)
+    relaunch::Gate lp_gate;     // the grid did not come up co-resident: the next descents keep to the one-launch-per-sweep path
     bool lp_used = false;      // the last descent ran in k_lds2opt
     // streamed persistent descent (k_str2opt): single tours past the LDS-resident sizes, uint16 cells
     int opt_stream = 1;        // 0 never, 1 where it applies (uint16 cells, one tour, n past k_lds2opt_w, a whole idle chip), 2 or fail
     bool sp_used = false;      // the last descent ran in k_str2opt
-    bool sp_attr[4] = {false, false, false, false};
     int opt_sp_nch = 0;        // probe hook 93
     int opt_otf_early = 0;         // hook 91: 0 automatic, 1 the early-out kernel for every matrix-free sweep, 2 never
     bool plan_otf_early = false;   // the matrix-free plan is the early-out kernel's (runs of 64 edges: plain 2-opt over integer points)
-    bool lp_attr[6] = {false, false, false, false, false, false};
-    bool lp_shaped_attr[2] = {false, false};   // ... of the shaped instantiations (lp_shaped_fn)
     bool lp_shaped = false;    // the last LDS-resident descent ran in a shaped instantiation of k_lds2opt
     int opt_lp_generic = 0;    // undocumented (option 89): 1 = never a shaped instantiation
     bool max16k = false;       // every off-diagonal cell <= 16383 (packed 16-bit deltas cannot overflow)
@@ -3479,6 +3475,35 @@ static int ensure_max_lds(tspgpu_ctx *ctx, const void *fn)
     if (std::find(seen.begin(), seen.end(), fn) != seen.end()) return E_OK;
     HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->lds_max));
     seen.push_back(fn);
+    return E_OK;
+}
+
+// at least `count` timing events in ctx->ev
+static int ensure_events(tspgpu_ctx *ctx, int count)
+{
+    while ((int)ctx->ev.size() < count) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); ctx->ev.push_back(e); }
+    return E_OK;
+}
+
+// K iterations of body(i) as one graph launch: captured the first time the key (slot0, ntours, tabu, K) is seen, then replayed
+template <typename B> static int replay_graph(tspgpu_ctx *ctx, int slot0, int ntours, int tabu, int K, B &&body)
+{
+    hipGraphExec_t exec = nullptr;
+    for (auto &g : ctx->graphs)
+        if (g.slot0 == slot0 && g.ntours == ntours && g.tabu == tabu && g.K == K) exec = g.exec;
+    if (!exec) {
+        hipGraph_t graph;
+        HIP_TRY(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
+        int rc = E_OK;
+        for (int i = 0; i < K && !rc; i++) rc = body(i);
+        hipError_t ce = hipStreamEndCapture(ctx->stream, &graph);
+        if (rc) return rc;
+        if (ce != hipSuccess) return fail(ctx, E_INTERNAL, "graph capture failed: %s", hipGetErrorString(ce));
+        HIP_TRY(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
+        hipGraphDestroy(graph);
+        ctx->graphs.push_back({slot0, ntours, tabu, K, exec});
+    }
+    HIP_TRY(hipGraphLaunch(exec, ctx->stream));
     return E_OK;
 }
 
@@ -3938,7 +3963,7 @@ static int run_fused(tspgpu_ctx *ctx, int slot0, int ntours, double time_left_s,
     const bool f64 = ctx->elem == TSPGPU_ELEM_F64;
     const dim3 grid1((n + 255) / 256, ntours);
     const bool pk = ctx->elem == TSPGPU_ELEM_U16;
-    const double t_end = time_left_s >= 0 ? now_s() + time_left_s : -1;
+    const double t_end = deadline_of(time_left_s);
     if (t_end >= 0 && time_left_s <= 0) { if (deadline_hit) *deadline_hit = true; return E_OK; }   // not one sweep
     if (f64) hipLaunchKernelGGL((k_fused_begin<double, false>), grid1, dim3(256), 0, ctx->stream, ctx->S, ctx->F, n, slot0);
     else if (pk) hipLaunchKernelGGL((k_fused_begin<int, true>), grid1, dim3(256), 0, ctx->stream, ctx->S, ctx->F, n, slot0);
@@ -3959,21 +3984,8 @@ static int run_fused(tspgpu_ctx *ctx, int slot0, int ntours, double time_left_s,
     auto issue_batch = [&](int *h_done) -> int {
         int rc = E_OK;
         if (ctx->opt_graph) {
-            hipGraphExec_t exec = nullptr;
-            for (auto &g : ctx->graphs)
-                if (g.slot0 == slot0 && g.ntours == ntours && g.tabu == 2 && g.K == K) exec = g.exec;
-            if (!exec) {
-                hipGraph_t graph;
-                HIP_TRY(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-                for (int i = 0; i < K && !rc; i++) rc = launch_fused(ctx, slot0, ntours, i & 1);
-                hipError_t ce = hipStreamEndCapture(ctx->stream, &graph);
-                if (rc) return rc;
-                if (ce != hipSuccess) return fail(ctx, E_INTERNAL, "graph capture failed: %s", hipGetErrorString(ce));
-                HIP_TRY(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-                hipGraphDestroy(graph);
-                ctx->graphs.push_back({slot0, ntours, 2, K, exec});
-            }
-            HIP_TRY(hipGraphLaunch(exec, ctx->stream));
+            // (key 2: neither the plain nor the tabu pairs of run_sweeps_plain)
+            if ((rc = replay_graph(ctx, slot0, ntours, 2, K, [&](int i) { return launch_fused(ctx, slot0, ntours, i & 1); }))) return rc;
             issued += K;
         } else if ((rc = launch_eager(K))) return rc;
         if (ctx->opt_timing) HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
@@ -3991,7 +4003,7 @@ static int run_fused(tspgpu_ctx *ctx, int slot0, int ntours, double time_left_s,
             // timing mode: one event pair around the whole batch (the launches of a batch run back to
             // back, so batch time / K is the mean launch duration); only batches in which every launch
             // swept are counted
-            while ((int)ctx->ev.size() < 2) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); ctx->ev.push_back(e); }
+            if ((rc = ensure_events(ctx, 2))) return rc;
             const long before = issued;
             HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
             if ((rc = issue_batch(ctx->h_status))) return rc;
@@ -4014,7 +4026,7 @@ static int run_fused(tspgpu_ctx *ctx, int slot0, int ntours, double time_left_s,
         // `done` words, so the device never waits for the host (a graph launch + a sync cost
         // ~20 us per batch otherwise); the price is one batch of immediately-returning launches
         // after the tour has finished.
-        while ((int)ctx->ev.size() < 4) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); ctx->ev.push_back(e); }
+        if ((rc = ensure_events(ctx, 4))) return rc;
         int *buf[2] = {ctx->h_status, ctx->h_status + ctx->tcap};
         if ((rc = issue_batch(buf[0]))) return rc;
         HIP_TRY(hipEventRecord(ctx->ev[2], ctx->stream));
@@ -4102,16 +4114,80 @@ static bool persist_fits_w(const tspgpu_ctx *ctx, int &E, int &W, size_t &lds, i
 }
 
 // The shaped instantiations of k_lds2opt (plain packed descent, n == nl): the one place that lists them.
-static const void *lp_shaped_fn(int n, int E, int &idx)
+static const void *lp_shaped_fn(int n, int E)
 {
-    if (n == 4096 && E == 16) { idx = 0; return (const void *)k_lds2opt<true, false, false, 4096, 16>; }
-    if (n == 1024 && E == 4) { idx = 1; return (const void *)k_lds2opt<true, false, false, 1024, 4>; }
+    if (n == 4096 && E == 16) return (const void *)k_lds2opt<true, false, false, 4096, 16>;
+    if (n == 1024 && E == 4) return (const void *)k_lds2opt<true, false, false, 1024, 4>;
     return nullptr;
 }
 
-// *ran = false: nothing was touched (does not apply, or the grid did not come up co-resident): the caller takes the
-// one-launch-per-sweep path.  Deadline: launches with a sweep budget of a third of the time left, measured per sweep;
-// every launch leaves a consistent tour (the sweep that ran is applied, refinment.c:17-26).
+// ---- the one-launch descents: run_persist and run_pstream around relaunch::drive (tspgpu_relaunch.h) ----------------------
+static_assert((int)relaunch::INTERNAL == (int)E_INTERNAL && (int)relaunch::GO_ON == (int)E_OK, "the driver's codes are the engine's");
+// wanted: always, or where nothing else was chosen (TSPGPU_OPT_KERNEL / _FUSED keep to that choice)
+static bool resident_wanted(const tspgpu_ctx *ctx) { return ctx->opt_persist == 2 || (ctx->opt_persist == 1 && ctx->opt_kernel == 0 && ctx->opt_fused == 1); }
+
+// For a launch of W workgroups: their exchange slots and the control words behind them zeroed (one memset for both), and
+// the fields that PersistArgs and StreamArgs have in common.
+template <typename ARGS> static int resident_args(tspgpu_ctx *ctx, ARGS &A, int slot, int W, int budget, bool first)
+{
+    HIP_TRY(hipMemsetAsync(ctx->d_lp_slots, 0, (size_t)2 * W * 64 + 64, ctx->stream));
+    memset(&A, 0, sizeof A);
+    A.S = ctx->S; A.mat = (const u16 *)ctx->d_mat.p; A.n = ctx->n; A.ld = ctx->ld; A.slot = slot; A.budget = budget;
+    A.slots = ctx->d_lp_slots; A.ctl = reinterpret_cast<int *>(ctx->d_lp_slots + (size_t)2 * W * 8); A.hist = ctx->hist;
+    A.hello_ticks = ctx->opt_lp_hello;   // 2 ms (test hook 97: negative = workgroup 0 withholds its record for that long)
+    if (ctx->opt_lp_fail_at > 0 && !first) { ctx->opt_lp_fail_at--; A.hello_ticks = -5000; }   // test hook 96: the next N relaunches fail their rendezvous
+    A.spin_ticks = 100000000;            // 1 s
+    A.poll_sleep = ctx->opt_lp_poll_sleep; A.stamps = ctx->opt_stamps ? ctx->d_stamps : nullptr;
+    return E_OK;
+}
+
+// One launch between its timing events; back in ctx->h_lp the control words ([1] status, [2] sweeps run) and at [8] the double
+// `also`; the stream drained.  relaunch::drive's launch callable: the two errors that the driver makes of it are worded here.
+template <typename ARGS>
+static int launch_resident(tspgpu_ctx *ctx, const char *what, const void *fn, int W, int block, size_t lds, ARGS &A, bool first, int &status, int &sweeps, const double *also = nullptr)
+{
+    void *args[] = {&A};
+    if (ctx->opt_timing) { const int rc = ensure_events(ctx, 2); if (rc) return rc; }
+    if (ctx->opt_timing) HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
+    const hipError_t le = hipLaunchKernel(fn, dim3(W), dim3(block), args, lds, ctx->stream);
+    if (le != hipSuccess) {                     // (e.g. a device that does not grant 160 KiB of LDS to one workgroup)
+        (void)hipGetLastError();
+        if (!first) fail(ctx, E_INTERNAL, "%s: launch failed: %s", what, hipGetErrorString(le));
+        return status = relaunch::REFUSED, E_OK;
+    }
+    if (ctx->opt_timing) HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->h_lp, A.ctl, 32, hipMemcpyDeviceToHost, ctx->stream));
+    if (also) HIP_TRY(hipMemcpyAsync(ctx->h_lp + 8, also, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    status = ctx->h_lp[1]; sweeps = ctx->h_lp[2];
+    if (status == LP_ST_RUNNING) fail(ctx, E_INTERNAL, "%s: no status written (after %d sweeps)", what, sweeps);
+    return E_OK;
+}
+
+// A launch completed: the time between its events goes to the sweep statistics; a descent is over at a local optimum or at
+// its sweep cap, a launch that used up its budget is followed by another.
+static int descent_completed(tspgpu_ctx *ctx, int status, int sd)
+{
+    if (ctx->opt_timing && sd > 0) {
+        float ms = 0;
+        HIP_TRY(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
+        ctx->sweep_ms_total += ms; ctx->sweep_launches += sd;
+    }
+    return status == LP_ST_OPTIMUM || status == LP_ST_CAPPED ? relaunch::STOP : relaunch::GO_ON;
+}
+static int hand_over(bool) { return relaunch::HAND_OVER; }
+
+// What relaunch::drive answered, for the context and the caller.  *ran stays false where the one-launch-per-sweep path has to
+// take over; lp_handed then tells whether from the start or from the tour the last completed launch wrote back.
+static int resident_result(tspgpu_ctx *ctx, const relaunch::Result &r, bool *deadline_hit, bool *ran)
+{
+    ctx->lp_sweeps = r.sweeps;
+    if (!r.code && !r.ran) ctx->lp_handed = r.handed;
+    if (r.late && deadline_hit) *deadline_hit = true;
+    *ran = r.ran;
+    return r.code;
+}
+
 struct PersistTabu { int k, tenure, t_min, t_max, up; double best; };
 // mh_VNS's loop in the LDS-resident kernels (tspgpu_lds_vns.inc): in/out state of tspgpu_vns_search across launches
 struct PersistVns {
@@ -4126,9 +4202,10 @@ struct PersistVns {
     int it_entry;           // `it` when the call was entered
 };
 
-// *time_left_io: the deadline budget; when the descent has to be handed to the one-launch-per-sweep path half way (the grid
-// lost its co-residency after the first launch: another context took CUs) it holds the time that is left and *ran stays
-// false -- the slot holds the consistent tour the last completed launch wrote back, the caller continues from there.
+// *ran = false: nothing was touched (does not apply, or the grid did not come up co-resident), or -- lp_handed -- the grid
+// lost its co-residency after the first launch (another context took CUs): the slot holds the consistent tour the last
+// completed launch wrote back and *time_left_io the time that is left.  Either way the caller takes the one-launch-per-sweep
+// path.  Every launch leaves a consistent tour (the sweep that ran is applied, refinment.c:17-26).
 static int run_persist(tspgpu_ctx *ctx, int slot, double *time_left_io, bool *deadline_hit, bool *ran, const PersistTabu *tabu = nullptr,
                        PersistVns *vns = nullptr)
 {
@@ -4142,142 +4219,74 @@ static int run_persist(tspgpu_ctx *ctx, int slot, double *time_left_io, bool *de
         if (ctx->opt_persist_window == 2 || !persist_fits_w(ctx, E, W, lds, Ws, nstage, tabu != nullptr)) return E_OK;
         win = true;
     }
-    if (ctx->lp_skip > 0) { ctx->lp_skip--; return E_OK; }
+    if (ctx->lp_gate.skip_this()) return E_OK;
     HIP_TRY(ctx->d_lp_slots.reserve(((size_t)2 * LP_BT * 64 + 64) / 8));   // exchange slots, then the control words
     HIP_TRY(ctx->h_lp.reserve(16));
     if (tabu || vns) HIP_TRY(ctx->d_lp_best.reserve((size_t)ctx->ld + 16));
     const int pk = (tabu ? ctx->max8k : ctx->max16k) ? 1 : 0;
-    const void *fn = win ? (tabu ? (pk ? (const void *)k_lds2opt_w<true, true> : (const void *)k_lds2opt_w<false, true>)
-                                 : vns ? (pk ? (const void *)k_lds2opt_w<true, false, true> : (const void *)k_lds2opt_w<false, false, true>)
-                                 : (pk ? (const void *)k_lds2opt_w<true, false> : (const void *)k_lds2opt_w<false, false>))
-                   : vns ? (pk ? (const void *)k_lds2opt<true, false, true> : (const void *)k_lds2opt<false, false, true>)
-                   : tabu ? (pk ? (const void *)k_lds2opt<true, true> : (const void *)k_lds2opt<false, true>)
-                          : (pk ? (const void *)k_lds2opt<true, false> : (const void *)k_lds2opt<false, false>);
-    bool *attr_p = win ? &ctx->lpw_attr[pk + (tabu ? 2 : vns ? 4 : 0)] : &ctx->lp_attr[pk + (tabu ? 2 : vns ? 4 : 0)];
-    bool shaped = false;
+    void (*const fns[2][3][2])(PersistArgs) = {     // [half-window rows][plain descent, tabu walk, VNS loop][packed deltas]
+        {{k_lds2opt<false, false>, k_lds2opt<true, false>}, {k_lds2opt<false, true>, k_lds2opt<true, true>}, {k_lds2opt<false, false, true>, k_lds2opt<true, false, true>}},
+        {{k_lds2opt_w<false, false>, k_lds2opt_w<true, false>}, {k_lds2opt_w<false, true>, k_lds2opt_w<true, true>}, {k_lds2opt_w<false, false, true>, k_lds2opt_w<true, false, true>}}};
     // (E comes from the device's compute units: 16 / 4 on a whole MI355X; with fewer CUs E is larger, no shape is listed and
     // the generic kernel runs -- tspgpu_info 61 tells)
-    if (!win && !tabu && !vns && pk && !ctx->opt_lp_generic) {
-        int idx = 0;
-        if (const void *sfn = lp_shaped_fn(ctx->n, E, idx)) { fn = sfn; attr_p = &ctx->lp_shaped_attr[idx]; shaped = true; }
-    }
-    bool &attr = *attr_p;
-    if (!attr) {
-        HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->lds_max));
-        attr = true;
-    }
-    const int block = win ? LW_BT : LP_BT;
-    const double t_end = time_left_s >= 0 ? now_s() + time_left_s : -1;
+    const void *const sfn = !win && !tabu && !vns && pk && !ctx->opt_lp_generic ? lp_shaped_fn(ctx->n, E) : nullptr;
+    const void *const fn = sfn ? sfn : (const void *)fns[win][tabu ? 1 : vns ? 2 : 0][pk];
+    if (const int rc = ensure_max_lds(ctx, fn)) return rc;
+    const double t_end = deadline_of(time_left_s);
     if (t_end >= 0 && time_left_s <= 0) { if (deadline_hit) *deadline_hit = true; *ran = true; ctx->lp_used = true; ctx->lp_window = win; ctx->lp_shaped = false; return E_OK; }
-    double sweep_s = 8e-6;
-    bool first = true, late = false;
-    int retries = 0;
     if (vns) vns->need_rand = false;
-    ctx->lp_sweeps = 0;
-    // hand the rest of the descent to the per-sweep path (nothing of this launch was written: the slot is consistent)
-    auto hand_over = [&]() {
-        ctx->lp_handed = !first;
-        ctx->lp_skip = ctx->lp_backoff; ctx->lp_backoff = std::min(1024, ctx->lp_backoff * 2);
-        if (time_left_io && t_end >= 0) *time_left_io = std::max(0.0, t_end - now_s());
+    // one launch: fill(A) queues what the walk needs in front of it and completes the arguments
+    auto launch = [&](int budget, bool first, int &status, int &sd, auto &&fill, const double *also = nullptr) -> int {
+        PersistArgs A;
+        int rc = resident_args(ctx, A, slot, W, budget, first);
+        A.E = E; A.nl = (ctx->n + 7) & ~7; A.Ws = Ws; A.nstage = nstage;
+        if (!rc) rc = fill(A);
+        return rc ? rc : launch_resident(ctx, "LDS-resident descent", fn, W, win ? LW_BT : LP_BT, lds, A, first, status, sd, also);
+    };
+    // the walks keep their best tour by array cell, every workgroup its own cells (d_lp_best), and its cost in the tabu state
+    auto best_cost = [&]() { return reinterpret_cast<double *>(reinterpret_cast<char *>(ctx->d_tabu) + offsetof(TabuState, best_cost)); };
+    auto walk_fill = [&](PersistArgs &A, double best0) -> int {
+        HIP_TRY(hipMemsetAsync(ctx->d_lp_best + ctx->ld, 0, 8, ctx->stream));
+        A.best0 = best0; A.best_ord = ctx->d_lp_best; A.best_dir = ctx->d_lp_best + ctx->ld; A.best_out = best_cost();
         return E_OK;
     };
-    for (;;) {
-        int budget = -1;
-        if (t_end >= 0) {
-            const double left = t_end - now_s();
-            if (left <= 0) { late = true; break; }
-            budget = (int)std::min(1048576.0, std::max(1.0, left / 3.0 / sweep_s));
-        }
-        int *d_ctl = reinterpret_cast<int *>(ctx->d_lp_slots + (size_t)2 * W * 8);   // (one memset for both)
-        HIP_TRY(hipMemsetAsync(ctx->d_lp_slots, 0, (size_t)2 * W * 64 + 64, ctx->stream));
-        if (tabu || vns) HIP_TRY(hipMemsetAsync(ctx->d_lp_best + ctx->ld, 0, 8, ctx->stream));
-        int vns_launch_k = 0;
-        if (vns) {
+    // A walk's launch completed: its best tour becomes the successor array.  Only now -- a launch that lost its grid half
+    // way leaves a MIXTURE of old and new cells in best_ord (the workgroups that passed the last exchange wrote theirs, the
+    // one that timed out did not), and d_best_succ must keep the last good launch's tour for the hand-over
+    auto walk_completed = [&](int status, int sd) -> int {
+        hipLaunchKernelGGL(k_lds_best_succ, dim3((ctx->n + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_lp_best, ctx->d_lp_best + ctx->ld, ctx->d_best_succ, ctx->n);
+        HIP_TRY(hipGetLastError());
+        return descent_completed(ctx, status, sd);
+    };
+    relaunch::Result r;
+    if (tabu) {
+        auto fill = [&](PersistArgs &A) -> int {
+            A.tabu_k = tabu->k; A.tenure0 = tabu->tenure; A.t_min = tabu->t_min; A.t_max = tabu->t_max; A.up0 = tabu->up;
+            A.budget = -1; A.trace = ctx->d_trace;
+            return walk_fill(A, tabu->best);
+        };
+        r = relaunch::drive(ctx->lp_gate, now_s, t_end, 8e-6, time_left_io, [&](int budget, bool first, int &st, int &sd) { return launch(budget, first, st, sd, fill); },
+                            walk_completed, [&](bool first) -> int {
+                                return first ? (int)relaunch::HAND_OVER : fail(ctx, E_INTERNAL, "LDS-resident tabu walk: exchange lost after %d iterations", ctx->h_lp[2]); });
+    } else if (vns) {
+        auto fill = [&](PersistArgs &A) -> int {
+            int rc = walk_fill(A, vns->best);
+            if (rc) return rc;
             // this launch: at most 65536 iterations, the numbers they can be expected to need (a kick phase draws 1 + 3 per
             // kick + the rejected ones, 8 on average; the kernel stops in front of a kick phase it cannot finish)
-            vns_launch_k = std::min(vns->k - vns->it, ctx->opt_vns_launch_k);
-            const long want = std::min<long>(vns->nrand - vns->used, 32L * vns_launch_k + 1024);
+            A.vns_k = std::min(vns->k - vns->it, ctx->opt_vns_launch_k);
+            const long want = std::min<long>(vns->nrand - vns->used, 32L * A.vns_k + 1024);
             if (want > 0) HIP_TRY(ctx->d_vns_rand.reserve((size_t)want + 64));
             if (want > 0) HIP_TRY(hipMemcpyAsync(ctx->d_vns_rand, vns->h_rand + vns->used, (size_t)want * 4, hipMemcpyHostToDevice, ctx->stream));
-            if (vns->h_trace) { const int rc = reserve_captured(ctx, ctx->d_trace, (size_t)vns_launch_k); if (rc) return rc; }
+            if (vns->h_trace && (rc = reserve_captured(ctx, ctx->d_trace, (size_t)A.vns_k))) return rc;
             ctx->vns_launch_nrand = (int)want;
-        }
-        PersistArgs A;
-        memset(&A, 0, sizeof A);
-        A.S = ctx->S; A.mat = (const u16 *)ctx->d_mat.p; A.n = ctx->n; A.ld = ctx->ld; A.slot = slot;
-        A.E = E; A.nl = (ctx->n + 7) & ~7; A.budget = budget; A.Ws = Ws; A.nstage = nstage;
-        A.slots = ctx->d_lp_slots; A.ctl = d_ctl; A.hist = ctx->hist;
-        A.hello_ticks = ctx->opt_lp_hello;   // 2 ms (test hook 97: negative = workgroup 0 withholds its record for that long)
-        if (ctx->opt_lp_fail_at > 0 && !first) { ctx->opt_lp_fail_at--; A.hello_ticks = -5000; }   // test hook 96: the next N relaunches fail their rendezvous
-        A.spin_ticks = 100000000;      // 1 s
-        A.poll_sleep = ctx->opt_lp_poll_sleep;
-        A.stamps = ctx->opt_stamps ? ctx->d_stamps : nullptr;
-        if (tabu) {
-            A.budget = -1;
-            A.tabu_k = tabu->k; A.tenure0 = tabu->tenure; A.t_min = tabu->t_min; A.t_max = tabu->t_max; A.up0 = tabu->up;
-            A.best0 = tabu->best; A.best_ord = ctx->d_lp_best; A.best_dir = ctx->d_lp_best + ctx->ld; A.trace = ctx->d_trace;
-            A.best_out = reinterpret_cast<double *>(reinterpret_cast<char *>(ctx->d_tabu) + offsetof(TabuState, best_cost));
-        }
-        if (vns) {
-            A.vns_k = vns_launch_k; A.vns_it0 = vns->it; A.vns_phase = vns->phase;
-            A.vns_rand = ctx->d_vns_rand; A.vns_nrand = ctx->vns_launch_nrand; A.vns_state = d_ctl + 4;
-            A.best0 = vns->best; A.best_ord = ctx->d_lp_best; A.best_dir = ctx->d_lp_best + ctx->ld;
+            A.vns_it0 = vns->it; A.vns_phase = vns->phase; A.vns_rand = ctx->d_vns_rand; A.vns_nrand = (int)want; A.vns_state = A.ctl + 4;
             A.trace = vns->h_trace ? ctx->d_trace : nullptr;
-            A.best_out = reinterpret_cast<double *>(reinterpret_cast<char *>(ctx->d_tabu) + offsetof(TabuState, best_cost));
-        }
-        void *args[] = {&A};
-        const double t0 = now_s();
-        if (ctx->opt_timing) {
-            while ((int)ctx->ev.size() < 2) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); ctx->ev.push_back(e); }
-            HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
-        }
-        {
-            const hipError_t le = hipLaunchKernel(fn, dim3(W), dim3(block), args, lds, ctx->stream);
-            if (le != hipSuccess) {                    // (e.g. a device that does not grant 160 KiB of LDS to one workgroup)
-                (void)hipGetLastError();
-                if (first) { ctx->lp_skip = 1 << 30; return E_OK; }      // (this device never grants the launch)
-                return fail(ctx, E_INTERNAL, "LDS-resident descent: launch failed: %s", hipGetErrorString(le));
-            }
-        }
-        if (ctx->opt_timing) HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
-        HIP_TRY(hipMemcpyAsync(ctx->h_lp, d_ctl, 32, hipMemcpyDeviceToHost, ctx->stream));
-        if (vns) HIP_TRY(hipMemcpyAsync(ctx->h_lp + 8, reinterpret_cast<char *>(ctx->d_tabu) + offsetof(TabuState, best_cost), 8, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        const int status = ctx->h_lp[1], sd = ctx->h_lp[2];
-        if (status == LP_ST_NO_RENDEZVOUS) {
-            if (first) {                                               // nothing written: the other path takes over
-                ctx->lp_skip = ctx->lp_backoff; ctx->lp_backoff = std::min(1024, ctx->lp_backoff * 2);
-                return E_OK;
-            }
-            if (++retries > 3) return hand_over();     // another context holds CUs: the per-sweep path finishes the descent
-            continue;
-        }
-        if (status == LP_ST_LOST) {
-            // an exchange timed out mid-launch (the grid is no longer co-resident): nothing of this launch was written
-            if (tabu && !first) return fail(ctx, E_INTERNAL, "LDS-resident tabu walk: exchange lost after %d iterations", sd);
-            return hand_over();
-        }
-        if (status == LP_ST_RUNNING)
-            return fail(ctx, E_INTERNAL, "LDS-resident descent: no status written (after %d sweeps)", sd);
-        first = false;
-        ctx->lp_backoff = 16;
-        ctx->lp_sweeps += sd;
-        if (tabu || vns) {
-            // the launch completed: its best tour (written by array cell, every workgroup its own cells) becomes the successor
-            // array.  Only now -- a launch that lost its grid half way leaves a MIXTURE of old and new cells in best_ord
-            // (the workgroups that passed the last exchange wrote theirs, the one that timed out did not), and d_best_succ
-            // must keep the last good launch's tour for the hand-over
-            hipLaunchKernelGGL(k_lds_best_succ, dim3((ctx->n + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_lp_best, ctx->d_lp_best + ctx->ld,
-                               ctx->d_best_succ, ctx->n);
-            HIP_TRY(hipGetLastError());
-        }
-        if (ctx->opt_timing && sd > 0) {
-            float ms = 0;
-            HIP_TRY(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-            ctx->sweep_ms_total += ms; ctx->sweep_launches += sd;
-        }
-        if (sd > 0) sweep_s = (now_s() - t0) / sd;
-        if (vns) {
+            return E_OK;
+        };
+        auto completed = [&](int status, int sd) -> int {
+            const int next = walk_completed(status, sd);
+            if (next > 0) return next;
             // what the launch completed: iterations, numbers, the incumbent's cost, the local optima's costs
             const int it1 = ctx->h_lp[4];
             if (vns->h_trace && it1 > vns->it) {
@@ -4286,23 +4295,21 @@ static int run_persist(tspgpu_ctx *ctx, int slot, double *time_left_io, bool *de
             }
             vns->it = it1; vns->used += ctx->h_lp[5]; vns->phase = ctx->h_lp[6];
             memcpy(&vns->best, ctx->h_lp + 8, 8);
-            if (status == LP_ST_NEED_RAND) {
-                // out of numbers -- of this launch's window, or of all the caller gave
-                if (vns->used + ctx->vns_launch_nrand - ctx->h_lp[5] >= vns->nrand) { vns->need_rand = true; break; }
-                continue;
+            if (status == LP_ST_NEED_RAND) {    // out of numbers: of all the caller gave, or only of this launch's window
+                vns->need_rand = vns->used + ctx->vns_launch_nrand - ctx->h_lp[5] >= vns->nrand;
+                return vns->need_rand ? relaunch::STOP : relaunch::GO_ON;
             }
-            if (status == LP_ST_VNS_DONE) {
-                if (vns->it >= vns->k) break;
-                continue;                              // (a launch completes at most 65536 iterations)
-            }
-        }
-        if (status == LP_ST_OPTIMUM || status == LP_ST_CAPPED) break;
-    }
-    if (late && deadline_hit) *deadline_hit = true;
-    *ran = true;
-    ctx->lp_used = true;
-    ctx->lp_window = win;
-    ctx->lp_shaped = shaped;
+            if (status == LP_ST_VNS_DONE) return vns->it >= vns->k ? relaunch::STOP : relaunch::GO_ON;   // (a launch completes at most 65536 iterations)
+            return next;
+        };
+        r = relaunch::drive(ctx->lp_gate, now_s, t_end, 8e-6, time_left_io,
+                            [&](int budget, bool first, int &st, int &sd) { return launch(budget, first, st, sd, fill, best_cost()); }, completed, hand_over);
+    } else
+        r = relaunch::drive(ctx->lp_gate, now_s, t_end, 8e-6, time_left_io,
+                            [&](int budget, bool first, int &st, int &sd) { return launch(budget, first, st, sd, [](PersistArgs &) -> int { return E_OK; }); },
+                            [&](int status, int sd) { return descent_completed(ctx, status, sd); }, hand_over);
+    if (const int rc = resident_result(ctx, r, deadline_hit, ran); rc || !*ran) return rc;
+    ctx->lp_used = true; ctx->lp_window = win; ctx->lp_shaped = sfn != nullptr;
     return E_OK;
 }
 
@@ -4324,8 +4331,7 @@ static bool stream_fits(const tspgpu_ctx *ctx, int &P, int &W, int &BT, int &NCH
     return lds <= ctx->lds_max && W <= 256;
 }
 
-// *ran = false: nothing was touched (does not apply, or the grid did not come up co-resident).  Deadline: launches with a
-// sweep budget, as run_persist; every launch leaves a consistent tour in the slot.
+// *ran, *time_left_io and the deadline as run_persist.
 static int run_pstream(tspgpu_ctx *ctx, int slot, double *time_left_io, bool *deadline_hit, bool *ran)
 {
     *ran = false;
@@ -4333,89 +4339,23 @@ static int run_pstream(tspgpu_ctx *ctx, int slot, double *time_left_io, bool *de
     int P = 0, W = 0, BT = 0, NCH = 0;
     size_t lds = 0;
     if (!stream_fits(ctx, P, W, BT, NCH, lds)) return E_OK;
-    if (ctx->lp_skip > 0) { ctx->lp_skip--; return E_OK; }
+    if (ctx->lp_gate.skip_this()) return E_OK;
     HIP_TRY(ctx->d_lp_slots.reserve(((size_t)2 * LP_BT * 64 + 64) / 8));
     HIP_TRY(ctx->h_lp.reserve(16));
     // (the register budget follows the block: 768 threads leave 170 registers a thread, 512 leave 256)
-    const int vi = NCH == 1 ? (BT <= 768 ? 0 : 1) : (BT <= 512 ? 2 : 3);
-    const void *fn = vi == 0 ? (const void *)k_str2opt<1, 768> : vi == 1 ? (const void *)k_str2opt<1, 1024>
-                   : vi == 2 ? (const void *)k_str2opt<2, 512> : (const void *)k_str2opt<2, 1024>;
-    if (!ctx->sp_attr[vi]) {
-        HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->lds_max));
-        ctx->sp_attr[vi] = true;
-    }
-    const double t_end = time_left_s >= 0 ? now_s() + time_left_s : -1;
+    const void *fn = NCH == 1 ? (BT <= 768 ? (const void *)k_str2opt<1, 768> : (const void *)k_str2opt<1, 1024>)
+                              : (BT <= 512 ? (const void *)k_str2opt<2, 512> : (const void *)k_str2opt<2, 1024>);
+    if (const int rc = ensure_max_lds(ctx, fn)) return rc;
+    const double t_end = deadline_of(time_left_s);
     if (t_end >= 0 && time_left_s <= 0) { if (deadline_hit) *deadline_hit = true; *ran = true; ctx->sp_used = true; return E_OK; }
-    double sweep_s = 2e-9 * (double)ctx->n * ctx->n / 5.0e3 + 5e-6;     // first guess: the rows at 5 TB/s + the exchange
-    bool first = true, late = false;
-    int retries = 0;
-    ctx->lp_sweeps = 0;
-    auto hand_over = [&]() {
-        ctx->lp_handed = !first;
-        ctx->lp_skip = ctx->lp_backoff; ctx->lp_backoff = std::min(1024, ctx->lp_backoff * 2);
-        if (time_left_io && t_end >= 0) *time_left_io = std::max(0.0, t_end - now_s());
-        return E_OK;
-    };
-    for (;;) {
-        int budget = -1;
-        if (t_end >= 0) {
-            const double left = t_end - now_s();
-            if (left <= 0) { late = true; break; }
-            budget = (int)std::min(1048576.0, std::max(1.0, left / 3.0 / sweep_s));
-        }
-        int *d_ctl = reinterpret_cast<int *>(ctx->d_lp_slots + (size_t)2 * W * 8);
-        HIP_TRY(hipMemsetAsync(ctx->d_lp_slots, 0, (size_t)2 * W * 64 + 64, ctx->stream));
+    const double sweep_s = 2e-9 * (double)ctx->n * ctx->n / 5.0e3 + 5e-6;     // first guess: the rows at 5 TB/s + the exchange
+    const relaunch::Result r = relaunch::drive(ctx->lp_gate, now_s, t_end, sweep_s, time_left_io, [&](int budget, bool first, int &status, int &sd) -> int {
         StreamArgs A;
-        memset(&A, 0, sizeof A);
-        A.S = ctx->S; A.mat = (const u16 *)ctx->d_mat.p; A.n = ctx->n; A.ld = ctx->ld; A.slot = slot;
-        A.P = P; A.budget = budget; A.poll_sleep = ctx->opt_lp_poll_sleep; A.ablate = ctx->opt_ablate;
-        A.slots = ctx->d_lp_slots; A.ctl = d_ctl; A.hist = ctx->hist;
-        A.hello_ticks = ctx->opt_lp_hello;
-        if (ctx->opt_lp_fail_at > 0 && !first) { ctx->opt_lp_fail_at--; A.hello_ticks = -5000; }
-        A.spin_ticks = 100000000;      // 1 s
-        A.stamps = ctx->opt_stamps ? ctx->d_stamps : nullptr;
-        void *args[] = {&A};
-        const double t0 = now_s();
-        if (ctx->opt_timing) {
-            while ((int)ctx->ev.size() < 2) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); ctx->ev.push_back(e); }
-            HIP_TRY(hipEventRecord(ctx->ev[0], ctx->stream));
-        }
-        {
-            const hipError_t le = hipLaunchKernel(fn, dim3(W), dim3(BT), args, lds, ctx->stream);
-            if (le != hipSuccess) {
-                (void)hipGetLastError();
-                if (first) { ctx->lp_skip = 1 << 30; return E_OK; }
-                return fail(ctx, E_INTERNAL, "streamed persistent descent: launch failed: %s", hipGetErrorString(le));
-            }
-        }
-        if (ctx->opt_timing) HIP_TRY(hipEventRecord(ctx->ev[1], ctx->stream));
-        HIP_TRY(hipMemcpyAsync(ctx->h_lp, d_ctl, 32, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        const int status = ctx->h_lp[1], sd = ctx->h_lp[2];
-        if (status == LP_ST_NO_RENDEZVOUS) {
-            if (first) {
-                ctx->lp_skip = ctx->lp_backoff; ctx->lp_backoff = std::min(1024, ctx->lp_backoff * 2);
-                return E_OK;
-            }
-            if (++retries > 3) return hand_over();
-            continue;
-        }
-        if (status == LP_ST_LOST) return hand_over();  // an exchange timed out mid-launch: nothing of this launch was written
-        if (status == LP_ST_RUNNING)
-            return fail(ctx, E_INTERNAL, "streamed persistent descent: no status written (after %d sweeps)", sd);
-        first = false;
-        ctx->lp_backoff = 16;
-        ctx->lp_sweeps += sd;
-        if (ctx->opt_timing && sd > 0) {
-            float ms = 0;
-            HIP_TRY(hipEventElapsedTime(&ms, ctx->ev[0], ctx->ev[1]));
-            ctx->sweep_ms_total += ms; ctx->sweep_launches += sd;
-        }
-        if (sd > 0) sweep_s = (now_s() - t0) / sd;
-        if (status == LP_ST_OPTIMUM || status == LP_ST_CAPPED) break;
-    }
-    if (late && deadline_hit) *deadline_hit = true;
-    *ran = true;
+        const int rc = resident_args(ctx, A, slot, W, budget, first);
+        A.P = P; A.ablate = ctx->opt_ablate;
+        return rc ? rc : launch_resident(ctx, "streamed persistent descent", fn, W, BT, lds, A, first, status, sd);
+    }, [&](int status, int sd) { return descent_completed(ctx, status, sd); }, hand_over);
+    if (const int rc = resident_result(ctx, r, deadline_hit, ran); rc || !*ran) return rc;
     ctx->sp_used = true;
     return E_OK;
 }
@@ -4492,8 +4432,7 @@ static int run_sweeps(tspgpu_ctx *ctx, int slot0, int ntours, bool tabu, long ma
     ctx->lp_used = false;
     ctx->sp_used = false;
     ctx->lp_handed = false;
-    // (an explicit kernel or launch-structure choice -- TSPGPU_OPT_KERNEL / _FUSED -- keeps to that choice)
-    if (!tabu && ntours == 1 && (ctx->opt_persist == 2 || (ctx->opt_persist == 1 && ctx->opt_kernel == 0 && ctx->opt_fused == 1))) {
+    if (!tabu && ntours == 1 && resident_wanted(ctx)) {
         bool ran = false;
         const int rc = run_persist(ctx, slot0, &time_left_s, deadline_hit, &ran);     // (half way handed over: time_left_s = what is left)
         if (rc) return rc;
@@ -4502,7 +4441,7 @@ static int run_sweeps(tspgpu_ctx *ctx, int slot0, int ntours, bool tabu, long ma
         if (ctx->opt_persist == 2) return fail(ctx, E_EXHAUSTED, "the LDS-resident descent does not apply (uint16 cells, n in [64, ~5400], one idle chip)");
     }
     bool stream = !tabu && ntours == 1 && ctx->opt_stream == 2;
-    if (!tabu && ntours == 1 && ctx->opt_stream == 1 && ctx->opt_persist == 1 && ctx->opt_kernel == 0 && ctx->opt_fused == 1) {
+    if (!tabu && ntours == 1 && ctx->opt_stream == 1 && resident_wanted(ctx)) {      // (PERSIST = 2 does not get here)
         // automatic: where the LDS-resident kernels do not take the instance
         int e_, w_, ws_, ns_;
         size_t l_;
@@ -4527,7 +4466,7 @@ static int run_sweeps_plain(tspgpu_ctx *ctx, int slot0, int ntours, bool tabu, l
     if (!tabu && ctx->symmetric && fused_kernel(ctx->elem, ctx->plan_NCH, ctx->plan_kernel, ctx->plan_pipe2) &&
         (ctx->opt_fused == 2 || (ctx->opt_fused == 1 && ntours <= 4)))
         return run_fused(ctx, slot0, ntours, time_left_s, deadline_hit);
-    const double t_end = time_left_s >= 0 ? now_s() + time_left_s : -1;
+    const double t_end = deadline_of(time_left_s);
     const int K = std::max(1, ctx->opt_batch);
     long issued = 0;
     double iter_dt = est_iter_s(ctx, ntours);   // seconds per (sweep, apply) pair: estimate, then measured
@@ -4543,29 +4482,13 @@ static int run_sweeps_plain(tspgpu_ctx *ctx, int slot0, int ntours, bool tabu, l
         }
         const bool use_graph = ctx->opt_graph && !ctx->opt_timing && todo == K;
         if (use_graph) {
-            hipGraphExec_t exec = nullptr;
-            for (auto &g : ctx->graphs)
-                if (g.slot0 == slot0 && g.ntours == ntours && g.tabu == (int)tabu && g.K == K) exec = g.exec;
-            if (!exec) {
-                hipGraph_t graph;
-                HIP_TRY(hipStreamBeginCapture(ctx->stream, hipStreamCaptureModeThreadLocal));
-                int rc = E_OK;
-                for (int i = 0; i < K && !rc; i++) {
-                    rc = launch_sweep(ctx, slot0, ntours, tabu);
-                    if (!rc) rc = launch_apply(ctx, slot0, ntours, tabu, tabu);
-                }
-                hipError_t ce = hipStreamEndCapture(ctx->stream, &graph);
-                if (rc) return rc;
-                if (ce != hipSuccess) return fail(ctx, E_INTERNAL, "graph capture failed: %s", hipGetErrorString(ce));
-                HIP_TRY(hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0));
-                hipGraphDestroy(graph);
-                ctx->graphs.push_back({slot0, ntours, (int)tabu, K, exec});
-            }
-            HIP_TRY(hipGraphLaunch(exec, ctx->stream));
+            const int rc = replay_graph(ctx, slot0, ntours, (int)tabu, K, [&](int) {
+                const int r = launch_sweep(ctx, slot0, ntours, tabu);
+                return r ? r : launch_apply(ctx, slot0, ntours, tabu, tabu);
+            });
+            if (rc) return rc;
         } else {
-            if (ctx->opt_timing && (int)ctx->ev.size() < 2 * K) {
-                while ((int)ctx->ev.size() < 2 * K) { hipEvent_t e; HIP_TRY(hipEventCreate(&e)); ctx->ev.push_back(e); }
-            }
+            if (ctx->opt_timing) { const int rc = ensure_events(ctx, 2 * K); if (rc) return rc; }
             for (int i = 0; i < todo; i++) {
                 if (ctx->opt_timing) HIP_TRY(hipEventRecord(ctx->ev[2 * i], ctx->stream));
                 int rc = launch_sweep(ctx, slot0, ntours, tabu);
@@ -5014,7 +4937,7 @@ int tspgpu_set_option(tspgpu_ctx *ctx, int option, long value)
     case 94: ctx->opt_vns_launch_k = value > 0 ? (int)std::min<long>(value, 65536) : 65536; break; // undocumented: VNS iterations per launch (tests)
     case 95: ctx->opt_lp_poll_sleep = (int)value; break; // undocumented: s_sleep(1) repetitions between polls of the exchange slots (tools/persist_probe.py)
     case 96: ctx->opt_lp_fail_at = (int)value; break; // undocumented: see opt_lp_fail_at (tests)
-    case 97: ctx->opt_lp_hello = value ? value : 200000; ctx->lp_skip = 0; ctx->lp_backoff = 16; break; // undocumented: rendezvous limit of k_lds2opt (tests)
+    case 97: ctx->opt_lp_hello = value ? value : 200000; ctx->lp_gate.rearm(); break; // undocumented: rendezvous limit of k_lds2opt (tests)
     case 98: // undocumented: per-workgroup phase stamps of the pipelined sweep (single tour)
         ctx->opt_stamps = value ? 1 : 0; drop_graphs(ctx);
         if (value) HIP_TRY(ctx->d_stamps.reserve((size_t)MAX_WGS_PER_TOUR * 64));
@@ -5023,8 +4946,8 @@ int tspgpu_set_option(tspgpu_ctx *ctx, int option, long value)
     case TSPGPU_OPT_MATRIX_FREE: if (value < 0 || value > 2) return fail(ctx, E_INVALID, "bad matrix-free mode"); ctx->opt_otf = (int)value; break;
     case TSPGPU_OPT_FUSED: if (value < 0 || value > 2) return fail(ctx, E_INVALID, "bad fused mode"); ctx->opt_fused = (int)value; break;
     case TSPGPU_OPT_MAX_TOURS: if (value < 1 || value > (1 << 20)) return fail(ctx, E_INVALID, "bad max tours"); ctx->opt_max_tours = (int)value; break;
-    case TSPGPU_OPT_PERSIST: if (value < 0 || value > 2) return fail(ctx, E_INVALID, "bad persist mode"); ctx->opt_persist = (int)value; ctx->lp_skip = 0; ctx->lp_backoff = 16; break;
-    case TSPGPU_OPT_STREAM_PERSIST: if (value < 0 || value > 2) return fail(ctx, E_INVALID, "bad stream-persist mode"); ctx->opt_stream = (int)value; ctx->lp_skip = 0; ctx->lp_backoff = 16; break;
+    case TSPGPU_OPT_PERSIST: if (value < 0 || value > 2) return fail(ctx, E_INVALID, "bad persist mode"); ctx->opt_persist = (int)value; ctx->lp_gate.rearm(); break;
+    case TSPGPU_OPT_STREAM_PERSIST: if (value < 0 || value > 2) return fail(ctx, E_INVALID, "bad stream-persist mode"); ctx->opt_stream = (int)value; ctx->lp_gate.rearm(); break;
     case TSPGPU_OPT_PERSIST_EDGES: if (value < 0 || value > LW_EMAX) return fail(ctx, E_INVALID, "edges per workgroup: 0 (auto) .. %d", LW_EMAX); ctx->opt_persist_edges = (int)value; break;
     case TSPGPU_OPT_BUILD_KERNEL: if (value < 0 || value > 1) return fail(ctx, E_INVALID, "bad build kernel"); ctx->opt_build = (int)value; break;
     case TSPGPU_OPT_PERSIST_WINDOW: if (value < 0 || value > 2) return fail(ctx, E_INVALID, "bad window mode"); ctx->opt_persist_window = (int)value; break;
@@ -5470,7 +5393,7 @@ int tspgpu_tabu_search(tspgpu_ctx *ctx, int *path, double *cost, int k, int *bes
     if ((rc = tabu_prepare(ctx, nullptr, tenure, 0, t_min, t_max, up, 1, *cost))) return rc;
     bool ran = false;
     ctx->lp_used = false;
-    if (k > 0 && ctx->symmetric && (ctx->opt_persist == 2 || (ctx->opt_persist == 1 && ctx->opt_kernel == 0 && ctx->opt_fused == 1))) {
+    if (k > 0 && ctx->symmetric && resident_wanted(ctx)) {
         // the whole walk in one launch, matrix and ages in LDS (k_lds2opt<., true>) where it applies
         const PersistTabu pt = {k, tenure, t_min, t_max, up, *cost};
         if ((rc = run_persist(ctx, 0, nullptr, nullptr, &ran, &pt))) return rc;
@@ -5523,13 +5446,13 @@ int tspgpu_vns_search(tspgpu_ctx *ctx, int *path, double *cost, int k, double ti
     const int n = ctx->n;
     *consumed = 0;
     if (*iterations >= k) return E_OK;
-    const double t_end = time_left_s >= 0 ? now_s() + time_left_s : -1;
+    const double t_end = deadline_of(time_left_s);
     if ((rc = load_path(ctx, 0, path, -1))) return rc;              // (recomputes the cost: refinment.c:6-9)
     bool resident_done = false;
     ctx->lp_used = false;
     PersistVns pv = {k, *iterations, *kick_pending ? 1 : 0, rand_values, nrand, 0, *best_cost, trace, false, *iterations};
     bool late = false;
-    if (ctx->symmetric && (ctx->opt_persist == 2 || (ctx->opt_persist == 1 && ctx->opt_kernel == 0 && ctx->opt_fused == 1))) {
+    if (ctx->symmetric && resident_wanted(ctx)) {
         HIP_TRY(hipMemcpyAsync(ctx->d_best_succ, best_path, (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
         double left = t_end >= 0 ? std::max(0.0, t_end - now_s()) : -1.0;
         bool ran = false;

@@ -77,8 +77,6 @@ static constexpr int LP_EMAX = 16, LP_BT = 512;
 static constexpr u64 LP_KEYMASK = (1ull << 60) - 1;
 static constexpr u64 LP_NONE = 0xFFFFFFFFFull << 24;     // "no improving pair": delta field all ones, labels 0
 static constexpr int LP_DBIAS = 131072;
-enum { LP_ST_RUNNING = 0, LP_ST_OPTIMUM = 1, LP_ST_CAPPED = 2, LP_ST_NO_RENDEZVOUS = 3, LP_ST_LOST = 4, LP_ST_BUDGET = 5,
-       LP_ST_VNS_DONE = 6, LP_ST_NEED_RAND = 7 };
 
 __device__ __forceinline__ void lp_ld128(const u64 *p, u64 &a, u64 &b)
 {
