@@ -123,7 +123,8 @@ int  tspgpu_set_option(tspgpu_ctx *ctx, int option, long value);
  * single-tour or batched, on this instance (0 where 31 is 0), 34 how the last matrix-free Or-opt sweep ran (0 none, 1 every candidate
  * evaluated, 2 with the exact early-out), 35 tour positions per workgroup of that sweep (0 where 34 is 0); 36 .. 60 in the
  * sections below; 61 the last LDS-resident descent ran in an instantiation of k_lds2opt compiled for its shape (plain 2-opt,
- * packed 16-bit costs, (n, edges per workgroup) = (4096, 16) or (1024, 4); 0: the generic kernel) */
+ * packed 16-bit costs, (n, edges per workgroup) = (4096, 16) or (1024, 4); 0: the generic kernel); 62 .. 67 in
+ * "Neighbour-list 3-opt" below */
 long tspgpu_info(const tspgpu_ctx *ctx, int what);
 
 /* ---- instance / cost matrix ------------------------------------------- */
@@ -534,6 +535,80 @@ int tspgpu_tour_local_search_nl(tspgpu_ctx *ctx, int slot, double time_left_s,
 /* a measurement aid (tools/ornl_rate.py): the candidate sweep, the compaction and the selection `reps` times on slot,
  * nothing applied */
 int tspgpu_time_or_nl_sweep(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean);
+
+/* ---- Neighbour-list 3-opt (an extension: pure 3-opt moves from the neighbour lists, every independent move of a sweep) ----
+ * The moves "Or-opt" cannot reach: segment insertion of any length, the double reversal and the two mixed forms.  A sweep
+ * evaluates 8 W^2 chains per node instead of all triples of edges, and applies every accepted move at once.
+ * Preconditions: those of "Neighbour-list Or-opt" -- `path` a successor array, symmetric costs (a symmetric matrix, or
+ * matrix-free mode), n >= 8, lists built by tspgpu_neighbours_build for the cost source in place.  Every entry point takes a
+ * `width` in 1 .. 16 (any other value: 3); W = min(width, K'), and only the first W entries of a list are used.
+ *   1. Positions.  P(0) = 0, P(path[v]) = P(v) + 1; o[p] is the node at position p.  The tour edge at position p joins o[p]
+ *      and o[(p + 1) mod n].
+ *   2. Move.  Three edge positions i < j < k; a = o[i], a' = o[i+1], b = o[j], b' = o[j+1], c = o[k], c' = o[(k+1) mod n];
+ *      A = the nodes at i+1 .. j, B = the nodes at j+1 .. k.  The three edges are removed and the positions i+1 .. k refilled:
+ *          kind 0:  A reversed, B reversed    adds (a,b)  (a',c)  (b',c')
+ *          kind 1:  B, A                      adds (a,b') (c,a')  (b,c')
+ *          kind 2:  B reversed, A             adds (a,c)  (b',a') (b,c')
+ *          kind 3:  B, A reversed             adds (a,b') (c,b)   (a',c')
+ *      The three reconnections that are single 2-opt moves are not moves of this rule.
+ *   3. Chain and delta.  A candidate is written as a chain t1 .. t6: removed {t1,t2}, {t3,t4}, {t5,t6}, added {t2,t3},
+ *      {t4,t5}, {t6,t1};
+ *          delta = ((c[t2][t3] + c[t4][t5]) + c[t6][t1]) - ((c[t1][t2] + c[t3][t4]) + c[t5][t6])      in this order: bit-exact for doubles
+ *   4. Candidates of t1.  For s2 in {0: t2 = succ(t1), 1: t2 = pred(t1)}, j3 < W with t3 = N(t2)[j3], s4 in {0, 1} with t4 =
+ *      succ or pred of t3, j5 < W with t5 = N(t4)[j5], s6 in {0, 1} with t6 = succ or pred of t5 -- no gain pruning: 8 W^2
+ *      evaluations per node.  A chain is kept iff (i) its three removed edges sit at three different positions, (ii) its
+ *      added set is that of one of the four kinds for those positions taken in ascending order, compared by role (edge rank,
+ *      tail or head) and not by label, and (iii) no added edge has two equal ends or is one of the removed edges as a node pair.
+ *          code = 1 << 30 | s2 << 10 | j3 << 6 | s4 << 5 | j5 << 1 | s6
+ *      cand(t1) = the lexicographic minimum of (delta, code), a candidate only if delta < -1e-7.  Its key is (delta, t1, code).
+ *   5. Membership.  The move (i, j, k, kind) is looked at iff one of the writings of its alternating cycle as a chain (a start
+ *      node and a direction whose first edge is a removed one) has t3 among the first W of N(t2) and t5 among the first W
+ *      of N(t4).  Several writings may survive as candidates of different t1; they have the same range, conflict with each
+ *      other, and exactly one of them is accepted.
+ *   6. Range.  [i, k] with 0 <= i < k <= n - 1.  Only the nodes at the positions i+1 .. k change position; position 0 never
+ *      moves and no range wraps.  Node 0 may be a (i = 0) and may be c' (k = n - 1).
+ *   7. Conflict and selection.  Exactly rules 3-4 of "Parallel-move 2-opt": closed ranges that intersect conflict, ONE round,
+ *      a candidate is accepted iff its key is below the key of every candidate it conflicts with.  The smallest key is
+ *      always accepted.
+ *   8. Apply.  Every accepted move at once: the order of i+1 .. k is that of the move's kind.  *cost grows by the sum of the
+ *      accepted deltas (exact for integer-valued costs; summed by the fixed-shape tree of "Parallel-move 2-opt").  Two
+ *      accepted moves may share one end node (the k + 1 node of one, the i node of the other).
+ *   9. Phase.  Sweeps run until one accepts nothing; that sweep is counted.
+ *  10. Descent (tspgpu_local_search_nl3).  *cost is recomputed as ref_2opt does (src/algorithms/refinment.c:6-9); the
+ *      alternation of rule 8 of "Neighbour-list Or-opt" runs to its end (without a further recompute); the 3-opt phase runs;
+ *      both repeat until a 3-opt phase applies nothing.  The tour, the cost and the five counters at the end of the first
+ *      rule-8 part are exactly those of tspgpu_local_search_nl on the same input: the final cost is never above that one, and
+ *      strictly below iff a 3-opt move was applied.
+ *  11. Full lists.  With W = K' = n - 1 every move of rule 2 that passes rule 4's test (iii) is looked at.
+ * Codes: no context 14, a width outside 1 .. 16 3, n < 8 3, no costs 9, an asymmetric matrix 9, lists not built or
+ * invalidated 9 (the text of "Neighbour-list 2-opt"), more accepted moves than `cap` in _once 8 (nothing applied, nothing
+ * written), a deadline that passed 4 (with a valid tour and its cost).  No new device memory: the candidate arrays of
+ * "Parallel-move 2-opt" serve.
+ * tspgpu_info: 62 the W in effect, 63 / 64 3-opt sweeps / moves of the last call of this section (a descent: totals over its
+ * phases), 65 the most moves one of its sweeps accepted, 66 3-opt phases of the last tspgpu_local_search_nl3, 67 nodes per
+ * workgroup of the candidate sweep.  (A descent also leaves 43-45 and 47-50 as "Neighbour-list Or-opt" describes them,
+ * with totals over all its rule-8 parts.) */
+/* one sweep on a host tour.  *cost is the caller's running cost.  The accepted moves come back in ascending key order:
+ * moves[4m .. 4m + 3] = i, j, k, kind, deltas[m]; *nmoves their number (0: nothing improves) */
+int tspgpu_three_opt_nl_once(tspgpu_ctx *ctx, int width, int *path, double *cost, int *nmoves,
+                             int *moves /* [4*cap] */, double *deltas /* [cap] */, int cap);
+/* the 3-opt phase (rule 9) on a host tour; *cost is the caller's running cost */
+int tspgpu_three_opt_nl(tspgpu_ctx *ctx, int width, int *path, double *cost, double time_left_s, long *sweeps, long *moves);
+/* the same on a slot: at most max_sweeps sweeps (< 0: until one accepts nothing); the slot is left as tspgpu_tour_or_opt_nl
+ * leaves one */
+int tspgpu_tour_three_opt_nl(tspgpu_ctx *ctx, int slot, int width, long max_sweeps, double time_left_s, long *sweeps, long *moves);
+/* the descent (rule 10); the counters (each may be NULL) are totals over the whole descent, *rounds the list 2-opt phases,
+ * *three_phases the 3-opt phases */
+int tspgpu_local_search_nl3(tspgpu_ctx *ctx, int width, int *path, double *cost, double time_left_s,
+                            long *two_opt_sweeps, long *two_opt_moves, long *or_sweeps, long *or_moves, int *rounds,
+                            long *three_sweeps, long *three_moves, int *three_phases);
+/* the same on a slot, whose cost is taken as it stands */
+int tspgpu_tour_local_search_nl3(tspgpu_ctx *ctx, int slot, int width, double time_left_s,
+                                 long *two_opt_sweeps, long *two_opt_moves, long *or_sweeps, long *or_moves, int *rounds,
+                                 long *three_sweeps, long *three_moves, int *three_phases);
+/* a measurement aid (tools/three_opt_nl_rate.py): the candidate sweep, the compaction and the selection `reps` times on slot,
+ * nothing applied */
+int tspgpu_time_three_nl_sweep(tspgpu_ctx *ctx, int slot, int width, int reps, float *ms_mean);
 
 /* ---- Batched neighbour-list descent (an extension: the descent over the lists on a batch of tours, and the multi-start) ----
  * The descent of "Neighbour-list Or-opt" (rule 8) on many tours at once: every launch serves every tour of the batch that

@@ -34,6 +34,9 @@ INFO_OR_NL_SWEEPS, INFO_OR_NL_MOVES, INFO_OR_NL_MAX_MOVES, INFO_OR_NL_ROUNDS, IN
 INFO_NL_BATCH_TOURS, INFO_NL_BATCH_LAUNCHES, INFO_NL_BATCH_MAX_LIVE, INFO_NL_BATCH_WGS = 52, 53, 54, 55
 # ... walks, iterations completed, sweep rounds, most live walks and dry walks of the last neighbour-list VNS call
 INFO_VNS_NL_WALKS, INFO_VNS_NL_ITERATIONS, INFO_VNS_NL_ROUNDS, INFO_VNS_NL_MAX_LIVE, INFO_VNS_NL_DRY = 56, 57, 58, 59, 60
+# ... W in effect, sweeps / moves / largest sweep of the last neighbour-list 3-opt call, 3-opt phases of the last local_search_nl3,
+# nodes per workgroup of its candidate sweep (61 is the shape-specialised LDS-resident descent's flag)
+INFO_THREE_NL_W, INFO_THREE_NL_SWEEPS, INFO_THREE_NL_MOVES, INFO_THREE_NL_MAX_MOVES, INFO_THREE_NL_PHASES, INFO_THREE_NL_NODES = 62, 63, 64, 65, 66, 67
 EM_FORM_AUTO, EM_FORM_RESIDENT, EM_FORM_PER_STEP = 0, 1, 2
 MOPT_EXCHANGE = 1000
 EXCHANGE_AUTO, EXCHANGE_HOST, EXCHANGE_RCCL = 0, 1, 2
@@ -119,6 +122,12 @@ SIGNATURES = {
     "tspgpu_local_search_nl": (C.c_int, [_ctx, _ip, _pd, C.c_double, _pl, _pl, _pl, _pl, _pi]),
     "tspgpu_tour_local_search_nl": (C.c_int, [_ctx, C.c_int, C.c_double, _pl, _pl, _pl, _pl, _pi]),
     "tspgpu_time_or_nl_sweep": (C.c_int, [_ctx, C.c_int, C.c_int, C.POINTER(C.c_float)]),
+    "tspgpu_three_opt_nl_once": (C.c_int, [_ctx, C.c_int, _ip, _pd, _pi, _ip, _dp, C.c_int]),
+    "tspgpu_three_opt_nl": (C.c_int, [_ctx, C.c_int, _ip, _pd, C.c_double, _pl, _pl]),
+    "tspgpu_tour_three_opt_nl": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_long, C.c_double, _pl, _pl]),
+    "tspgpu_local_search_nl3": (C.c_int, [_ctx, C.c_int, _ip, _pd, C.c_double, _pl, _pl, _pl, _pl, _pi, _pl, _pl, _pi]),
+    "tspgpu_tour_local_search_nl3": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_double, _pl, _pl, _pl, _pl, _pi, _pl, _pl, _pi]),
+    "tspgpu_time_three_nl_sweep": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float)]),
     "tspgpu_tours_local_search_nl": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "tspgpu_multistart_local_search_nl": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_double, _ip, _pd, _pi, _pl, _pl, _pl, _pl, C.c_void_p]),
     "tspgpu_vns_walks_nl": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_double, _ip, _dp, C.c_void_p, C.c_long, C.c_void_p, _ip, _ip, _ip, _dp,

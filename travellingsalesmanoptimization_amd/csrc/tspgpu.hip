@@ -3108,6 +3108,7 @@ __global__ void k_cap_now(Tours S, int slot0, int count)
 #include "tspgpu_multi2opt.inc"
 #include "tspgpu_nl2opt.inc"
 #include "tspgpu_ornl.inc"
+#include "tspgpu_nl3opt.inc"
 #include "tspgpu_nlbatch.inc"
 #include "tspgpu_nlvns.inc"
 
@@ -3321,6 +3322,11 @@ struct tspgpu_ctx : ContextMem, InstanceMem, CostMem, SlotMem {
     // neighbour-list Or-opt (tspgpu_ornl.inc): the last call's sweeps, moves and largest sweep (a descent: over its rounds)
     long ornl_sweeps = 0, ornl_moves = 0, ornl_max_k = 0;
     int ornl_rounds = 0;       // rounds of the last tspgpu_local_search_nl
+    // neighbour-list 3-opt (tspgpu_nl3opt.inc): the width asked for and W = min(width, K') in effect; the last call's sweeps,
+    // moves and largest sweep (a descent: over its phases), and the 3-opt phases of the last tspgpu_local_search_nl3
+    int nl3_width = 0, nl3_w = 0;
+    long nl3_sweeps = 0, nl3_moves = 0, nl3_max_k = 0;
+    int nl3_phases = 0;
     // batched neighbour-list descent (tspgpu_nlbatch.inc)
     long nlb_tours = 0, nlb_launches = 0, nlb_max_live = 0;     // the last batched descent: tours, sweeps launched, most tours in one
     // neighbour-list VNS (tspgpu_nlvns.inc): the last call's walks, iterations completed, sweep rounds, most walks live in one, dry walks
@@ -5035,6 +5041,12 @@ long tspgpu_info(const tspgpu_ctx *ctx, int what)
     case 59: return ctx->nlv_max_live;
     case 60: return ctx->nlv_dry;
     case 61: return ctx->lp_used && ctx->lp_shaped ? 1 : 0;
+    case 62: return ctx->nl3_w;
+    case 63: return ctx->nl3_sweeps;
+    case 64: return ctx->nl3_moves;
+    case 65: return ctx->nl3_max_k;
+    case 66: return ctx->nl3_phases;
+    case 67: return NL3_NODES;
     case 55: return ctx->have_costs && ctx->symmetric && ctx->n >= 8 ? (ctx->n + ORNL_STARTS - 1) / ORNL_STARTS : 0;
     case 12: return (ctx->built && ctx->grid_ok && ctx->opt_nn != 1 && ctx->cost_bound < 134217728.0) ? ctx->grid_G : 0;
     case 13: return ctx->grid_max_occ;
@@ -6275,10 +6287,13 @@ static int m2_geom(const tspgpu_ctx *ctx, int what)
 static int nl_launch_sweep(tspgpu_ctx *ctx, int slot);      // (tspgpu_nl2opt.inc's driver, below)
 static int ornl_launch_sweep(tspgpu_ctx *ctx, int slot);    // (tspgpu_ornl.inc's driver, below)
 static int ornl_launch_apply(tspgpu_ctx *ctx, int slot);
+static int nl3_launch_sweep(tspgpu_ctx *ctx, int slot);     // (tspgpu_nl3opt.inc's driver, below)
+static int nl3_launch_apply(tspgpu_ctx *ctx, int slot);
 
 // where the candidates of a sweep come from and what an accepted one is: every b of the parallel-move 2-opt, the neighbour
-// lists' 2-opt pairs (k_nl_sweep), or the neighbour lists' Or-opt segment moves (k_ornl_sweep, with its own compaction and apply)
-enum M2Kind { M2_FULL, M2_NL, M2_ORNL };
+// lists' 2-opt pairs (k_nl_sweep), the neighbour lists' Or-opt segment moves (k_ornl_sweep, with its own compaction and apply), or
+// the neighbour lists' 3-opt chains (k_nl3_sweep, likewise)
+enum M2Kind { M2_FULL, M2_NL, M2_ORNL, M2_NL3 };
 
 // the candidate sweep and the selection of one sweep (matrix-free mode: behind the gather of the successors' points)
 static int m2_launch_select(tspgpu_ctx *ctx, int slot, const SweepGeom &P, bool gather = true, M2Kind kind = M2_FULL)
@@ -6290,6 +6305,8 @@ static int m2_launch_select(tspgpu_ctx *ctx, int slot, const SweepGeom &P, bool 
         if ((rc = nl_launch_sweep(ctx, slot))) return rc;
     } else if (kind == M2_ORNL) {
         if ((rc = ornl_launch_sweep(ctx, slot))) return rc;
+    } else if (kind == M2_NL3) {
+        if ((rc = nl3_launch_sweep(ctx, slot))) return rc;
     } else if (ctx->otf) {
         if (gather && (rc = launch_spts_gather(ctx, slot, &ctl->stop))) return rc;
         kind_switch(ctx, [&](auto kind, auto *pts, auto *spts) {
@@ -6305,6 +6322,7 @@ static int m2_launch_select(tspgpu_ctx *ctx, int slot, const SweepGeom &P, bool 
     }
     HIP_TRY(hipGetLastError());
     if (kind == M2_ORNL) hipLaunchKernelGGL(k_ornl_compact, dim3(1), dim3(1024), 0, ctx->stream, ctx->S, n, slot, ctx->m2, ctx->d_m2);
+    else if (kind == M2_NL3) hipLaunchKernelGGL(k_nl3_compact, dim3(1), dim3(1024), 0, ctx->stream, ctx->S, n, slot, ctx->nl, ctx->m2, ctx->d_m2);
     else hipLaunchKernelGGL(k_m2_compact, dim3(1), dim3(1024), 0, ctx->stream, ctx->S, n, slot, ctx->m2, ctx->d_m2);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(k_m2_select, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->m2, ctl);
@@ -6315,6 +6333,7 @@ static int m2_launch_select(tspgpu_ctx *ctx, int slot, const SweepGeom &P, bool 
 static int m2_launch_apply(tspgpu_ctx *ctx, int slot, M2Kind kind = M2_FULL)
 {
     if (kind == M2_ORNL) return ornl_launch_apply(ctx, slot);
+    if (kind == M2_NL3) return nl3_launch_apply(ctx, slot);
     const int n = ctx->n, G = std::min(M2_APPLY_WGS, (n + 1) / 2);
     if (ctx->otf)
         kind_switch(ctx, [&](auto kind, auto *pts, auto *) {
@@ -6345,6 +6364,7 @@ static void m2_record(tspgpu_ctx *ctx, const M2Ctl &C, M2Kind kind = M2_FULL)
     // (a phase's polish is counted behind it, tspgpu_two_opt_nl: until then the phase has none)
     if (kind == M2_NL) { ctx->nl_sweeps = (long)C.sweeps; ctx->nl_moves = (long)C.moves; ctx->nl_polish_sweeps = 0; }
     else if (kind == M2_ORNL) { ctx->ornl_sweeps = (long)C.sweeps; ctx->ornl_moves = (long)C.moves; ctx->ornl_max_k = C.max_k; }
+    else if (kind == M2_NL3) { ctx->nl3_sweeps = (long)C.sweeps; ctx->nl3_moves = (long)C.moves; ctx->nl3_max_k = C.max_k; }
     else { ctx->m2_sweeps = (long)C.sweeps; ctx->m2_moves = (long)C.moves; ctx->m2_max_k = C.max_k; }
 }
 
@@ -6399,10 +6419,14 @@ int tspgpu_two_opt_multi(tspgpu_ctx *ctx, int *path, double *cost, double time_l
 
 static int nl_check(tspgpu_ctx *ctx);
 static int ornl_check(tspgpu_ctx *ctx);
-static int m2_kind_check(tspgpu_ctx *ctx, M2Kind kind) { return kind == M2_ORNL ? ornl_check(ctx) : kind == M2_NL ? nl_check(ctx) : m2_check(ctx); }
+static int nl3_check(tspgpu_ctx *ctx);
+static int m2_kind_check(tspgpu_ctx *ctx, M2Kind kind)
+{
+    return kind == M2_NL3 ? nl3_check(ctx) : kind == M2_ORNL ? ornl_check(ctx) : kind == M2_NL ? nl_check(ctx) : m2_check(ctx);
+}
 
 // one sweep on a host tour (tspgpu_two_opt_multi_once, tspgpu_two_opt_nl_once: moves_ab holds a, b per move;
-// tspgpu_or_opt_nl_once: s, L, q, rev per move)
+// tspgpu_or_opt_nl_once: s, L, q, rev per move; tspgpu_three_opt_nl_once: i, j, k, kind per move)
 static int m2_once(tspgpu_ctx *ctx, int *path, double *cost, int *nmoves, int *moves_ab, double *deltas, int cap, M2Kind kind)
 {
     if (!ctx) return E_UNAVAILABLE;
@@ -6418,8 +6442,16 @@ static int m2_once(tspgpu_ctx *ctx, int *path, double *cost, int *nmoves, int *m
     M2Ctl C;
     if ((rc = ctl_get(ctx, &C, ctx->d_m2.p))) return rc;
     const size_t m = (size_t)C.m;
-    std::vector<int> acc(m), a(m), b(m);
+    std::vector<int> acc(m), a(m), b(m), ri, rk, rjk;
     std::vector<double> d(m);
+    if (m && kind == M2_NL3) {              // the range and (j, kind) of every candidate, while the tour still stands
+        ri.resize(m); rk.resize(m); rjk.resize(m);
+        hipLaunchKernelGGL(k_nl3_describe, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, ctx->S, ctx->n, 0, ctx->nl, ctx->m2, ctx->d_m2);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(ri.data(), ctx->m2.i, m * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(rk.data(), ctx->m2.j, m * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(rjk.data(), ctx->m2.raw_b, m * 4, hipMemcpyDeviceToHost, ctx->stream));
+    }
     if (m) {
         HIP_TRY(hipMemcpyAsync(acc.data(), ctx->m2.acc, m * 4, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipMemcpyAsync(a.data(), ctx->m2.a, m * 4, hipMemcpyDeviceToHost, ctx->stream));
@@ -6439,7 +6471,9 @@ static int m2_once(tspgpu_ctx *ctx, int *path, double *cost, int *nmoves, int *m
     for (size_t k = 0; k < idx.size(); k++) {
         const int x = idx[k];
         deltas[k] = d[x];
-        if (kind == M2_ORNL) {              // a = s < b = the packed (L, q, rev): the order above is (delta, s, L, q, rev)
+        if (kind == M2_NL3) {               // a = t1 < b = the code: the order above is (delta, t1, code)
+            moves_ab[4 * k] = ri[x]; moves_ab[4 * k + 1] = rjk[x] >> 2; moves_ab[4 * k + 2] = rk[x]; moves_ab[4 * k + 3] = rjk[x] & 3;
+        } else if (kind == M2_ORNL) {       // a = s < b = the packed (L, q, rev): the order above is (delta, s, L, q, rev)
             moves_ab[4 * k] = a[x]; moves_ab[4 * k + 1] = b[x] >> ORNL_LSHIFT;
             moves_ab[4 * k + 2] = (b[x] >> 1) & (int)OR_QM; moves_ab[4 * k + 3] = b[x] & 1;
         } else {
@@ -6455,7 +6489,7 @@ static int m2_once(tspgpu_ctx *ctx, int *path, double *cost, int *nmoves, int *m
 }
 
 // the candidate sweep and the selection `reps` times, nothing applied (tspgpu_time_multi_sweep, tspgpu_time_nl_sweep,
-// tspgpu_time_or_nl_sweep)
+// tspgpu_time_or_nl_sweep, tspgpu_time_three_nl_sweep)
 static int m2_time(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean, M2Kind kind)
 {
     if (!ctx) return E_UNAVAILABLE;
@@ -6724,6 +6758,152 @@ int tspgpu_tour_local_search_nl(tspgpu_ctx *ctx, int slot, double time_left_s, l
 int tspgpu_time_or_nl_sweep(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean)
 {
     return m2_time(ctx, slot, reps, ms_mean, M2_ORNL);
+}
+
+} // extern "C"
+
+// ---- neighbour-list 3-opt and the descent with a 3-opt phase (tspgpu_nl3opt.inc) -----------------------------------------
+
+// what the neighbour-list Or-opt needs (the descent runs its alternation on the same slot), and a width of 1 .. 16: W is the
+// part of every list the chains are drawn from
+static int nl3_check(tspgpu_ctx *ctx)
+{
+    if (ctx->nl3_width < 1 || ctx->nl3_width > NL_KMAX)
+        return fail(ctx, E_INVALID, "neighbour-list 3-opt takes a width of 1 to %d list entries, got %d", NL_KMAX, ctx->nl3_width);
+    const int rc = ornl_check(ctx);
+    if (rc) return rc;
+    ctx->nl3_w = std::min(ctx->nl3_width, ctx->nl.K);
+    return E_OK;
+}
+
+static int nl3_launch_sweep(tspgpu_ctx *ctx, int slot)
+{
+    const int n = ctx->n, W = ctx->nl3_w;
+    const dim3 grid((n + NL3_NODES - 1) / NL3_NODES), block(NL3_NODES * 64);
+    const M2Ctl *ctl = ctx->d_m2;
+    if (ctx->otf)
+        kind_switch(ctx, [&](auto kind, auto *pts, auto *) {
+            hipLaunchKernelGGL((k_nl3_sweep_otf<kind()>), grid, block, 0, ctx->stream, ctx->S, pts, n, slot, ctx->nl, W, ctx->m2, ctl);
+        });
+    else
+        ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_nl3_sweep<T>), grid, block, 0, ctx->stream, ctx->S, (const T *)ctx->d_mat.p, n, ctx->ld, slot,
+                                                     ctx->nl, W, ctx->m2, ctl));
+    HIP_TRY(hipGetLastError());
+    return E_OK;
+}
+
+static int nl3_launch_apply(tspgpu_ctx *ctx, int slot)
+{
+    const int n = ctx->n, G = std::min(M2_APPLY_WGS, (n + 2) / 3);     // a range holds three positions at least
+    if (ctx->otf)
+        kind_switch(ctx, [&](auto kind, auto *pts, auto *) {
+            hipLaunchKernelGGL((k_nl3_apply_otf<kind()>), dim3(G), dim3(NL3_APPLY_BT), 0, ctx->stream, ctx->S, pts, n, slot, ctx->nl, ctx->m2, ctx->d_m2);
+        });
+    else
+        ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_nl3_apply<T>), dim3(G), dim3(NL3_APPLY_BT), 0, ctx->stream, ctx->S,
+                                                     (const T *)ctx->d_mat.p, n, ctx->ld, slot, ctx->nl, ctx->m2, ctx->d_m2));
+    HIP_TRY(hipGetLastError());
+    return E_OK;
+}
+
+struct Descent3 { long ts = 0, tm = 0; int np = 0; };
+
+// the descent of tspgpu_local_search_nl3 on a slot: { the alternation of ornl_descent to its end; neighbour-list 3-opt until a
+// sweep accepts nothing } until a 3-opt phase applies nothing.  The counters of "Neighbour-list Or-opt" hold the totals
+static int nl3_descent(tspgpu_ctx *ctx, int slot, double time_left_s, Descent *out, Descent3 *out3, bool *late)
+{
+    const double t_end = deadline_of(time_left_s);
+    Descent D;
+    Descent3 D3;
+    long mk = 0, omk = 0;
+    int rc = E_OK;
+    *late = false;
+    ctx->nl3_sweeps = ctx->nl3_moves = ctx->nl3_max_k = 0;
+    for (;;) {
+        Descent d;
+        rc = ornl_descent(ctx, slot, t_end >= 0 ? std::max(0.0, t_end - now_s()) : -1.0, &d, late);
+        D += d; omk = std::max(omk, ctx->ornl_max_k);
+        if (rc || *late) break;
+        long s = 0, m = 0;
+        if ((rc = m2_run(ctx, slot, -1, t_end, &s, &m, late, M2_NL3))) break;
+        D3.ts += s; D3.tm += m; D3.np++; mk = std::max(mk, ctx->nl3_max_k);
+        if (*late || m == 0) break;
+    }
+    ctx->ornl_sweeps = D.os; ctx->ornl_moves = D.om; ctx->ornl_max_k = omk; ctx->ornl_rounds = D.nr;
+    ctx->nl3_sweeps = D3.ts; ctx->nl3_moves = D3.tm; ctx->nl3_max_k = mk; ctx->nl3_phases = D3.np;
+    *out = D; *out3 = D3;
+    return rc;
+}
+
+static void descent3_out(const Descent3 &D3, long *three_sweeps, long *three_moves, int *three_phases)
+{
+    if (three_sweeps) *three_sweeps = D3.ts;
+    if (three_moves) *three_moves = D3.tm;
+    if (three_phases) *three_phases = D3.np;
+}
+
+extern "C" {
+
+int tspgpu_three_opt_nl_once(tspgpu_ctx *ctx, int width, int *path, double *cost, int *nmoves, int *moves, double *deltas, int cap)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    ctx->nl3_width = width;
+    return m2_once(ctx, path, cost, nmoves, moves, deltas, cap, M2_NL3);
+}
+
+int tspgpu_three_opt_nl(tspgpu_ctx *ctx, int width, int *path, double *cost, double time_left_s, long *sweeps, long *moves)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    if (!path || !cost) return fail(ctx, E_INVALID, "null argument");
+    ctx->nl3_width = width;
+    return with_host_tour(ctx, path, cost, true, nl3_check,
+                          [&](bool *late) { return m2_run(ctx, 0, -1, deadline_of(time_left_s), sweeps, moves, late, M2_NL3); });
+}
+
+int tspgpu_tour_three_opt_nl(tspgpu_ctx *ctx, int slot, int width, long max_sweeps, double time_left_s, long *sweeps, long *moves)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    ctx->nl3_width = width;
+    return with_slot(ctx, slot, nl3_check,
+                     [&](bool *late) { return m2_run(ctx, slot, max_sweeps, deadline_of(time_left_s), sweeps, moves, late, M2_NL3); });
+}
+
+int tspgpu_local_search_nl3(tspgpu_ctx *ctx, int width, int *path, double *cost, double time_left_s, long *two_opt_sweeps, long *two_opt_moves,
+                            long *or_sweeps, long *or_moves, int *rounds, long *three_sweeps, long *three_moves, int *three_phases)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    if (!path || !cost) return fail(ctx, E_INVALID, "null argument");
+    ctx->nl3_width = width;
+    return with_host_tour(ctx, path, cost, false, nl3_check, [&](bool *late) {
+        Descent D;
+        Descent3 D3;
+        const int rc = nl3_descent(ctx, 0, time_left_s, &D, &D3, late);
+        descent_out(&D, 1, two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds);
+        descent3_out(D3, three_sweeps, three_moves, three_phases);
+        return rc;
+    });
+}
+
+int tspgpu_tour_local_search_nl3(tspgpu_ctx *ctx, int slot, int width, double time_left_s, long *two_opt_sweeps, long *two_opt_moves,
+                                 long *or_sweeps, long *or_moves, int *rounds, long *three_sweeps, long *three_moves, int *three_phases)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    ctx->nl3_width = width;
+    return with_slot(ctx, slot, nl3_check, [&](bool *late) {
+        Descent D;
+        Descent3 D3;
+        const int rc = nl3_descent(ctx, slot, time_left_s, &D, &D3, late);
+        descent_out(&D, 1, two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds);
+        descent3_out(D3, three_sweeps, three_moves, three_phases);
+        return rc;
+    });
+}
+
+int tspgpu_time_three_nl_sweep(tspgpu_ctx *ctx, int slot, int width, int reps, float *ms_mean)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    ctx->nl3_width = width;
+    return m2_time(ctx, slot, reps, ms_mean, M2_NL3);
 }
 
 } // extern "C"

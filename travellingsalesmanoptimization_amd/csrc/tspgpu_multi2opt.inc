@@ -292,6 +292,25 @@ __device__ __forceinline__ void m2_close(const Tours &S, int t, M2Ctl *ctl, doub
     if (stop) { ctl->stop = 1; S.done[t] = 1; }
 }
 
+// the cells at the forward positions F + 1 .. F + M and the M - 1 edge costs between them, swapped end for end in place by
+// the threads of one workgroup (tspgpu_nl3opt.inc composes its moves of these; the caller's barriers stand around it)
+template <typename AT>
+__device__ __forceinline__ void m2_reverse_cells(int *ord, int *pos, AT *dp, int n, int dir, int F, int M)
+{
+    const int tid = threadIdx.x, BT = blockDim.x;
+    for (int k = tid; k < M / 2; k += BT) {
+        const int pk = or_cell(F + 1 + k, n, dir), qk = or_cell(F + M - k, n, dir);
+        const int u = ord[pk], v = ord[qk];
+        ord[pk] = v; ord[qk] = u;
+        pos[v] = pk; pos[u] = qk;
+    }
+    for (int k = tid; k < (M - 1) / 2; k += BT) {           // the M - 1 inner edges F + 1 .. F + M - 1
+        const int pe = or_ecell(F + 1 + k, n, dir), qe = or_ecell(F + M - 1 - k, n, dir);
+        const AT eu = dp[pe], ev = dp[qe];
+        dp[pe] = ev; dp[qe] = eu;
+    }
+}
+
 template <typename T, typename CS, typename CTL>
 __device__ __forceinline__ void m2_apply_tour(const Tours &S, const CS cs, int n, int t, const M2Buf &B, CTL *ctl)
 {
@@ -330,17 +349,7 @@ __device__ __forceinline__ void m2_apply_tour(const Tours &S, const CS cs, int n
             dnb[v] = w;
         }
         __syncthreads();                    // every read of the old ord / dpos of this range is complete
-        for (int k = tid; k < M / 2; k += BT) {
-            const int pk = or_cell(F + 1 + k, n, dir), qk = or_cell(F + M - k, n, dir);
-            const int u = ord[pk], v = ord[qk];
-            ord[pk] = v; ord[qk] = u;
-            pos[v] = pk; pos[u] = qk;
-        }
-        for (int k = tid; k < (M - 1) / 2; k += BT) {       // the M - 1 inner edges F + 1 .. F + M - 1
-            const int pe = or_ecell(F + 1 + k, n, dir), qe = or_ecell(F + M - 1 - k, n, dir);
-            const AT eu = dp[pe], ev = dp[qe];
-            dp[pe] = ev; dp[qe] = eu;
-        }
+        m2_reverse_cells(ord, pos, dp, n, dir, F, M);
         if (tid == 0) {
             const AT wab = cs(a, b), wss = cs(sa, sb);
             dp[or_ecell(F, n, dir)] = wab;

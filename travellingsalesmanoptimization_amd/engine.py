@@ -57,7 +57,8 @@ class Engine:
                  "or_nl_sweeps", "or_nl_moves", "or_nl_max_moves", "or_nl_rounds", "or_nl_starts",
                  "nl_batch_tours", "nl_batch_launches", "nl_batch_max_live", "nl_batch_wgs",
                  "vns_nl_walks", "vns_nl_iterations", "vns_nl_rounds", "vns_nl_max_live", "vns_nl_dry",
-                 "persist_shaped"]
+                 "persist_shaped",
+                 "three_nl_w", "three_nl_sweeps", "three_nl_moves", "three_nl_max_moves", "three_nl_phases", "three_nl_nodes"]
         return {k: int(self.L.tspgpu_info(self.ctx, i)) for i, k in enumerate(names)}
 
     # ---- instance
@@ -214,6 +215,35 @@ class Engine:
                                                     C.byref(om), C.byref(nr)), ok=(T_OK, DEADLINE_EXCEEDED))
         return {"cost": c.value, "two_opt_sweeps": tw.value, "two_opt_moves": tm.value, "or_sweeps": os_.value, "or_moves": om.value,
                 "rounds": nr.value, "rc": rc}
+
+    def three_opt_nl_once(self, path, cost, width, cap=None):
+        """one neighbour-list 3-opt sweep over the first `width` list entries (include/tspgpu.h "Neighbour-list 3-opt"); path in
+        place -> (cost, moves, deltas): moves an array [k][4] of i, j, k, kind in ascending key order, deltas [k] (k = 0: nothing
+        improves).  More than `cap` (default n) accepted moves: RESOURCE_EXHAUSTED, nothing applied."""
+        cap = self.n if cap is None else int(cap)
+        c, k = C.c_double(cost), C.c_int()
+        mv = np.empty(4 * max(cap, 1), dtype=np.int32)
+        dl = np.empty(max(cap, 1), dtype=np.float64)
+        self._ck(self.L.tspgpu_three_opt_nl_once(self.ctx, int(width), path, C.byref(c), C.byref(k), mv, dl, cap))
+        return c.value, mv[:4 * k.value].reshape(-1, 4).copy(), dl[:k.value].copy()
+
+    def three_opt_nl(self, path, cost, width, time_left_s=-1.0):
+        """neighbour-list 3-opt sweeps until one accepts nothing; path in place -> (cost, sweeps, moves, rc)."""
+        c, s, m = C.c_double(cost), C.c_long(), C.c_long()
+        rc = self._ck(self.L.tspgpu_three_opt_nl(self.ctx, int(width), path, C.byref(c), float(time_left_s), C.byref(s), C.byref(m)),
+                      ok=(T_OK, DEADLINE_EXCEEDED))
+        return c.value, s.value, m.value, rc
+
+    def local_search_nl3(self, path, width, time_left_s=-1.0):
+        """the descent of local_search_nl and a neighbour-list 3-opt phase in turn until a 3-opt phase applies nothing; path in
+        place -> dict(cost, two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds, three_sweeps, three_moves, three_phases, rc)."""
+        c, tw, tm, os_, om, nr = C.c_double(), C.c_long(), C.c_long(), C.c_long(), C.c_long(), C.c_int()
+        ts, tv, tp = C.c_long(), C.c_long(), C.c_int()
+        rc = self._ck(self.L.tspgpu_local_search_nl3(self.ctx, int(width), path, C.byref(c), float(time_left_s), C.byref(tw), C.byref(tm),
+                                                     C.byref(os_), C.byref(om), C.byref(nr), C.byref(ts), C.byref(tv), C.byref(tp)),
+                      ok=(T_OK, DEADLINE_EXCEEDED))
+        return {"cost": c.value, "two_opt_sweeps": tw.value, "two_opt_moves": tm.value, "or_sweeps": os_.value, "or_moves": om.value,
+                "rounds": nr.value, "three_sweeps": ts.value, "three_moves": tv.value, "three_phases": tp.value, "rc": rc}
 
     def local_search(self, path, time_left_s=-1.0):
         """2-opt and Or-opt in turn until neither improves; path in place ->
@@ -422,6 +452,29 @@ class Engine:
                                                           os_.ctypes.data, om.ctypes.data, nr.ctypes.data),
                       ok=(T_OK, DEADLINE_EXCEEDED))
         return {"two_opt_sweeps": tw, "two_opt_moves": tm, "or_sweeps": os_, "or_moves": om, "rounds": nr, "rc": rc}
+
+    def tour_three_opt_nl(self, slot, width, max_sweeps=-1, time_left_s=-1.0):
+        """neighbour-list 3-opt sweeps on a slot -> (sweeps, moves, rc)."""
+        s, m = C.c_long(), C.c_long()
+        rc = self._ck(self.L.tspgpu_tour_three_opt_nl(self.ctx, int(slot), int(width), int(max_sweeps), float(time_left_s), C.byref(s),
+                                                      C.byref(m)), ok=(T_OK, DEADLINE_EXCEEDED))
+        return s.value, m.value, rc
+
+    def tour_local_search_nl3(self, slot, width, time_left_s=-1.0):
+        """the descent of local_search_nl3 on a slot -> dict(two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds,
+        three_sweeps, three_moves, three_phases, rc)."""
+        tw, tm, os_, om, nr = C.c_long(), C.c_long(), C.c_long(), C.c_long(), C.c_int()
+        ts, tv, tp = C.c_long(), C.c_long(), C.c_int()
+        rc = self._ck(self.L.tspgpu_tour_local_search_nl3(self.ctx, int(slot), int(width), float(time_left_s), C.byref(tw), C.byref(tm),
+                                                          C.byref(os_), C.byref(om), C.byref(nr), C.byref(ts), C.byref(tv), C.byref(tp)),
+                      ok=(T_OK, DEADLINE_EXCEEDED))
+        return {"two_opt_sweeps": tw.value, "two_opt_moves": tm.value, "or_sweeps": os_.value, "or_moves": om.value, "rounds": nr.value,
+                "three_sweeps": ts.value, "three_moves": tv.value, "three_phases": tp.value, "rc": rc}
+
+    def time_three_nl_sweep(self, slot, width, reps):
+        ms = C.c_float()
+        self._ck(self.L.tspgpu_time_three_nl_sweep(self.ctx, int(slot), int(width), int(reps), C.byref(ms)))
+        return ms.value
 
     def time_or_nl_sweep(self, slot, reps):
         ms = C.c_float()

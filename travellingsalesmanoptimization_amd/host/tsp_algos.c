@@ -781,6 +781,9 @@ static int or_opt_refusal(ERROR_CODE e)
 /* TSP_OR_OPT_NEIGHBOURS=K, K in 1..16 (tsp_run_algorithm): the polish runs the descent over neighbour lists of K nodes
  * (tspgpu_local_search_nl) instead of tspgpu_local_search; it takes a matrix-free instance as it is */
 static int or_opt_nl_k = 0;
+/* TSP_3OPT_WIDTH=W, W in 1..16 (tsp_run_algorithm), with the two switches above: that descent gets a neighbour-list 3-opt phase
+ * over the first W list entries (tspgpu_local_search_nl3) */
+static int three_opt_width = 0;
 
 ERROR_CODE tsp_or_opt_polish(tsp_solution *solution)
 {
@@ -793,12 +796,21 @@ ERROR_CODE tsp_or_opt_polish(tsp_solution *solution)
     if (or_opt_nl_k) {
         /* the lists belong to the costs in place: built when the context holds none of that length */
         const int kp = or_opt_nl_k < tsp_inst.nnodes - 1 ? or_opt_nl_k : tsp_inst.nnodes - 1;
-        long or_sweeps = 0, two_opt_moves = 0;
+        long or_sweeps = 0, two_opt_moves = 0, three_sweeps = 0, three_moves = 0;
+        int three_phases = 0;
+        const char *call = three_opt_width ? "tspgpu_local_search_nl3" : "tspgpu_local_search_nl";
         int rc = tspgpu_info(g, 42) == kp ? 0 : tspgpu_neighbours_build(g, or_opt_nl_k);
-        if (rc == 0)
+        if (rc == 0 && three_opt_width)
+            rc = tspgpu_local_search_nl3(g, three_opt_width, solution->path, &solution->cost, time_left(), &sweeps, &two_opt_moves, &or_sweeps,
+                                         &moves, &rounds, &three_sweeps, &three_moves, &three_phases);
+        else if (rc == 0)
             rc = tspgpu_local_search_nl(g, solution->path, &solution->cost, time_left(), &sweeps, &two_opt_moves, &or_sweeps, &moves, &rounds);
-        if (or_opt_refusal(from_rc(rc))) log_warn("tspgpu_local_search_nl: %s", tspgpu_last_error(g));
-        else if (rc != 0 && rc != DEADLINE_EXCEEDED) log_error("tspgpu_local_search_nl: %s", tspgpu_last_error(g));
+        if (or_opt_refusal(from_rc(rc))) log_warn("%s: %s", call, tspgpu_last_error(g));
+        else if (rc != 0 && rc != DEADLINE_EXCEEDED) log_error("%s: %s", call, tspgpu_last_error(g));
+        else if (three_opt_width)
+            log_debug("Or-opt polish over lists of %d with 3-opt over %d: %d rounds, %ld 2-opt sweeps (%ld moves), %ld Or-opt sweeps (%ld moves), "
+                      "%d 3-opt phases, %ld sweeps (%ld moves), cost %f", or_opt_nl_k, three_opt_width, rounds, sweeps, two_opt_moves, or_sweeps,
+                      moves, three_phases, three_sweeps, three_moves, solution->cost);
         else log_debug("Or-opt polish over lists of %d: %d rounds, %ld 2-opt sweeps (%ld moves), %ld Or-opt sweeps (%ld moves), cost %f",
                        or_opt_nl_k, rounds, sweeps, two_opt_moves, or_sweeps, moves, solution->cost);
         thread_done(lease);
@@ -918,7 +930,8 @@ static int env_switch(const char *name)
     return -1;
 }
 
-/* TSP_2OPT_NEIGHBOURS, TSP_OR_OPT_NEIGHBOURS: unset or 0 = off, 1..16 = the list length; anything else is an error (-1) */
+/* TSP_2OPT_NEIGHBOURS, TSP_OR_OPT_NEIGHBOURS, and TSP_3OPT_WIDTH (the part of a list the 3-opt chains use): unset or 0 = off,
+ * 1..16 = the list length; anything else is an error (-1) */
 static int env_neighbours(const char *name)
 {
     const char *v = getenv(name);
@@ -947,6 +960,9 @@ ERROR_CODE tsp_run_algorithm(void)
     /* TSP_EVERY_START_NEIGHBOURS=K (env_neighbours): -alg 2OPT_GREEDY runs h_greedy_local_search_nl over lists of K nodes */
     const int es_k = env_neighbours("TSP_EVERY_START_NEIGHBOURS");
     if (es_k < 0) return INVALID_ARGUMENT;
+    /* TSP_3OPT_WIDTH=W (env_neighbours): the TSP_OR_OPT polish over the lists gets a 3-opt phase over their first W entries */
+    const int width3 = env_neighbours("TSP_3OPT_WIDTH");
+    if (width3 < 0) return INVALID_ARGUMENT;
     if (es_k && ((nl_k && nl_k != es_k) || (or_nl_k && or_nl_k != es_k))) {
         fprintf(stderr, "tsp: TSP_EVERY_START_NEIGHBOURS=%d and TSP_%s_NEIGHBOURS=%d: the list lengths must be equal\n", es_k,
                 nl_k && nl_k != es_k ? "2OPT" : "OR_OPT", nl_k && nl_k != es_k ? nl_k : or_nl_k);
@@ -989,6 +1005,8 @@ ERROR_CODE tsp_run_algorithm(void)
     else if (es_k) log_warn("TSP_EVERY_START_NEIGHBOURS=%d has no effect without -alg 2OPT_GREEDY", es_k);
     or_opt_nl_k = polish > 0 ? or_nl_k : 0;
     if (or_nl_k && !polish) log_warn("TSP_OR_OPT_NEIGHBOURS=%d has no effect without TSP_OR_OPT=1", or_nl_k);
+    three_opt_width = or_opt_nl_k ? width3 : 0;
+    if (width3 && !or_opt_nl_k) log_warn("TSP_3OPT_WIDTH=%d has no effect without TSP_OR_OPT=1 and TSP_OR_OPT_NEIGHBOURS=K", width3);
     two_opt_multi_on = multi;
     two_opt_nl_k = nl_k;
     two_opt_nl_polish = nl_polish;
