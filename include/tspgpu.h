@@ -380,6 +380,11 @@ int tspgpu_timing_read(tspgpu_ctx *ctx, double *sweep_ms_total, long *sweep_laun
 /* diagnostics: 64 wall-clock stamps (10 ns ticks) per sweep workgroup of the last launch
  * made while stamping was enabled (tools/stamps.py); not part of the reference's surface */
 int tspgpu_debug_stamps(tspgpu_ctx *ctx, unsigned long long *out, int capacity_words);
+/* diagnostics: the first `cells` cells of the tour-ordered matrix copy that the last LDS-resident
+ * descent kept (row of node x, n cells: c[x][node at array cell q], the cell of x itself 16383);
+ * tspgpu_info 68 tells whether the last LDS-resident descent kept it up to date; error 9
+ * (failed precondition) when no descent has kept one yet */
+int tspgpu_debug_tmat(tspgpu_ctx *ctx, unsigned short *out, size_t cells);
 /* with TSPGPU_OPT_HISTORY: the recorded moves of slot 0; returns count in *count */
 int tspgpu_history(tspgpu_ctx *ctx, int *a, int *b, double *delta, int capacity, int *count);
 

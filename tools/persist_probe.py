@@ -1,14 +1,17 @@
 #!/usr/bin/env python3
 """Times the single-tour descent with and without the LDS-resident kernel (TSPGPU_OPT_PERSIST) on uniform-random
-instances:  python tools/persist_probe.py [n ...]"""
+instances:  python tools/persist_probe.py [--no-tmat] [n ...]
+--no-tmat: the shaped k_lds2opt that reloads moved rows from the matrix (option 88), not from the tour-ordered copy"""
 import sys, time
 import numpy as np
 sys.path.insert(0, ".")
 import travellingsalesmanoptimization_amd as T
 from bench import reference_points
 
-ns = [int(a) for a in sys.argv[1:]] or [4096, 1024, 2048]
+no_tmat = "--no-tmat" in sys.argv[1:]
+ns = [int(a) for a in sys.argv[1:] if a != "--no-tmat"] or [4096, 1024, 2048]
 eng = T.Engine(0)
+eng.set_option(88, 1 if no_tmat else 0)
 for n in ns:
     eng.set_option(T.OPT_ELEM, T.ELEM_U16)
     eng.set_points(reference_points(n, 123)); eng.build_costs()
@@ -24,7 +27,7 @@ for n in ns:
             ts.append(time.perf_counter() - t0)
         _, cost, _ = eng.tour_store(1, want_path=False)
         best = min(ts[1:])
-        print(f"n={n} persist={mode} edges={edges} used={eng.info()['persist']} sweeps={sw} cost={cost:.0f} "
+        print(f"n={n} persist={mode} edges={edges} used={eng.info()['persist']} tmat={eng.info()['persist_tmat']} sweeps={sw} cost={cost:.0f} "
               f"best {best*1e3:.3f} ms = {best/sw*1e6:.2f} us/sweep, {T.evals_per_sweep(n)*sw/best:.3e} evals/s", flush=True)
 # phase clocks of the LDS-resident kernel (option 98): ticks of 10 ns summed per workgroup over the descent
 import ctypes as C
@@ -46,7 +49,7 @@ for n in ns[:1]:
     for i, nm in enumerate(names):
         v = st[:, i] / st[:, 8] / 100.0
         print(f"  {nm:14s} {v.mean():7.3f} {v.min():7.3f} {v.max():7.3f}")
-    for i, nm in enumerate(["  decode", "  need/mirror", "  row swaps"]):
+    for i, nm in enumerate(["  decode", "  need/mirror", "  row swaps", "write-back"]):      # (write-back: the TM instantiations only)
         v = st[:, 9 + i] / st[:, 8] / 100.0
         print(f"  {nm:14s} {v.mean():7.3f} {v.min():7.3f} {v.max():7.3f}")
     log = buf[8192 + 1:8192 + 1 + int(st[0, 8]) - 1]

@@ -37,6 +37,7 @@ INFO_VNS_NL_WALKS, INFO_VNS_NL_ITERATIONS, INFO_VNS_NL_ROUNDS, INFO_VNS_NL_MAX_L
 # ... W in effect, sweeps / moves / largest sweep of the last neighbour-list 3-opt call, 3-opt phases of the last local_search_nl3,
 # nodes per workgroup of its candidate sweep (61 is the shape-specialised LDS-resident descent's flag)
 INFO_THREE_NL_W, INFO_THREE_NL_SWEEPS, INFO_THREE_NL_MOVES, INFO_THREE_NL_MAX_MOVES, INFO_THREE_NL_PHASES, INFO_THREE_NL_NODES = 62, 63, 64, 65, 66, 67
+INFO_PERSIST_TMAT = 68                  # the last LDS-resident descent fetched moved rows from the tour-ordered matrix copy
 EM_FORM_AUTO, EM_FORM_RESIDENT, EM_FORM_PER_STEP = 0, 1, 2
 MOPT_EXCHANGE = 1000
 EXCHANGE_AUTO, EXCHANGE_HOST, EXCHANGE_RCCL = 0, 1, 2
@@ -105,6 +106,7 @@ SIGNATURES = {
     "tspgpu_time_build": (C.c_int, [_ctx, C.c_int, C.POINTER(C.c_float)]),
     "tspgpu_timing_read": (C.c_int, [_ctx, _pd, _pl, C.c_int]),
     "tspgpu_debug_stamps": (C.c_int, [_ctx, C.c_void_p, C.c_int]),
+    "tspgpu_debug_tmat": (C.c_int, [_ctx, C.c_void_p, C.c_size_t]),
     "tspgpu_history": (C.c_int, [_ctx, _ip, _ip, _dp, C.c_int, _pi]),
     "tspgpu_two_opt_multi_once": (C.c_int, [_ctx, _ip, _pd, _pi, _ip, _dp, C.c_int]),
     "tspgpu_two_opt_multi": (C.c_int, [_ctx, _ip, _pd, C.c_double, _pl, _pl]),

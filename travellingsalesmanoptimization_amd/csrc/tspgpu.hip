@@ -51,6 +51,7 @@
 
 #include "tspgpu.h"
 #include "tspgpu_relaunch.h"    // LP_ST_*, and the host's protocol over them (run_persist, run_pstream)
+#include "tspgpu_lds_tmat.h"    // index arithmetic of the tour-ordered matrix copy (k_lds2opt's TM instantiations)
 
 #ifndef TSPGPU_RPC
 #define TSPGPU_RPC 3   // rows landed per chunk in the resident bodies (tools: -DTSPGPU_RPC=2 to compare)
@@ -3136,6 +3137,7 @@ struct MEM_GROUP ContextMem {             // until tspgpu_destroy: allocated on 
     DevBuf<int> hist_a, hist_b; DevBuf<double> hist_d;
     DevBuf<unsigned long long> d_stamps;
     DevBuf<u64> d_lp_slots; PinBuf<int> h_lp;       // LDS-resident descent: exchange slots, the control words behind them
+    DevBuf<u16> d_lp_tmat;                          // ... [n][n] the matrix in tour order (the TM instantiations of k_lds2opt; filled by every launch)
     DevBuf<int> d_lp_best;      // tabu walk / VNS: the best tour by array cell [ld], its direction and flag [2]
     DevBuf<int> d_vns_rand;     // VNS: the caller's rand() values of a launch
     DevBuf<OrCtl> d_or;         // control block of the single-tour Or-opt
@@ -3297,6 +3299,8 @@ struct tspgpu_ctx : ContextMem, InstanceMem, CostMem, SlotMem {
     bool plan_otf_early = false;   // the matrix-free plan is the early-out kernel's (runs of 64 edges: plain 2-opt over integer points)
     bool lp_shaped = false;    // the last LDS-resident descent ran in a shaped instantiation of k_lds2opt
     int opt_lp_generic = 0;    // undocumented (option 89): 1 = never a shaped instantiation
+    bool lp_tmat = false;      // ... and it fetched moved rows from the tour-ordered copy (a TM instantiation)
+    int opt_lp_no_tmat = 0;    // undocumented (option 88): 1 = the shaped instantiation that reloads moved rows from the matrix
     bool max16k = false;       // every off-diagonal cell <= 16383 (packed 16-bit deltas cannot overflow)
     bool max8k = false;        // ... <= 8190 (the tabu form of the packed loop: a poisoned pair must exceed every valid delta)
 
@@ -4120,10 +4124,11 @@ static bool persist_fits_w(const tspgpu_ctx *ctx, int &E, int &W, size_t &lds, i
 }
 
 // The shaped instantiations of k_lds2opt (plain packed descent, n == nl): the one place that lists them.
-static const void *lp_shaped_fn(int n, int E)
+// tmat: the form that fetches moved rows from the tour-ordered copy (PersistArgs::tmat, n * n cells)
+static const void *lp_shaped_fn(int n, int E, bool tmat)
 {
-    if (n == 4096 && E == 16) return (const void *)k_lds2opt<true, false, false, 4096, 16>;
-    if (n == 1024 && E == 4) return (const void *)k_lds2opt<true, false, false, 1024, 4>;
+    if (n == 4096 && E == 16) return tmat ? (const void *)k_lds2opt<true, false, false, 4096, 16, true> : (const void *)k_lds2opt<true, false, false, 4096, 16>;
+    if (n == 1024 && E == 4) return tmat ? (const void *)k_lds2opt<true, false, false, 1024, 4, true> : (const void *)k_lds2opt<true, false, false, 1024, 4>;
     return nullptr;
 }
 
@@ -4235,17 +4240,21 @@ static int run_persist(tspgpu_ctx *ctx, int slot, double *time_left_io, bool *de
         {{k_lds2opt_w<false, false>, k_lds2opt_w<true, false>}, {k_lds2opt_w<false, true>, k_lds2opt_w<true, true>}, {k_lds2opt_w<false, false, true>, k_lds2opt_w<true, false, true>}}};
     // (E comes from the device's compute units: 16 / 4 on a whole MI355X; with fewer CUs E is larger, no shape is listed and
     // the generic kernel runs -- tspgpu_info 61 tells)
-    const void *const sfn = !win && !tabu && !vns && pk && !ctx->opt_lp_generic ? lp_shaped_fn(ctx->n, E) : nullptr;
+    const bool shaped = !win && !tabu && !vns && pk && !ctx->opt_lp_generic && lp_shaped_fn(ctx->n, E, false);
+    // the tour-ordered copy where a shaped form runs; without the memory for it the shaped form that needs none
+    bool tm = shaped && !ctx->opt_lp_no_tmat;
+    if (tm && ctx->d_lp_tmat.reserve((size_t)ctx->n * ctx->n) != hipSuccess) { (void)hipGetLastError(); tm = false; }
+    const void *const sfn = shaped ? lp_shaped_fn(ctx->n, E, tm) : nullptr;
     const void *const fn = sfn ? sfn : (const void *)fns[win][tabu ? 1 : vns ? 2 : 0][pk];
     if (const int rc = ensure_max_lds(ctx, fn)) return rc;
     const double t_end = deadline_of(time_left_s);
-    if (t_end >= 0 && time_left_s <= 0) { if (deadline_hit) *deadline_hit = true; *ran = true; ctx->lp_used = true; ctx->lp_window = win; ctx->lp_shaped = false; return E_OK; }
+    if (t_end >= 0 && time_left_s <= 0) { if (deadline_hit) *deadline_hit = true; *ran = true; ctx->lp_used = true; ctx->lp_window = win; ctx->lp_shaped = false; ctx->lp_tmat = false; return E_OK; }
     if (vns) vns->need_rand = false;
     // one launch: fill(A) queues what the walk needs in front of it and completes the arguments
     auto launch = [&](int budget, bool first, int &status, int &sd, auto &&fill, const double *also = nullptr) -> int {
         PersistArgs A;
         int rc = resident_args(ctx, A, slot, W, budget, first);
-        A.E = E; A.nl = (ctx->n + 7) & ~7; A.Ws = Ws; A.nstage = nstage;
+        A.E = E; A.nl = (ctx->n + 7) & ~7; A.Ws = Ws; A.nstage = nstage; A.tmat = tm ? ctx->d_lp_tmat.p : nullptr;
         if (!rc) rc = fill(A);
         return rc ? rc : launch_resident(ctx, "LDS-resident descent", fn, W, win ? LW_BT : LP_BT, lds, A, first, status, sd, also);
     };
@@ -4315,7 +4324,7 @@ static int run_persist(tspgpu_ctx *ctx, int slot, double *time_left_io, bool *de
                             [&](int budget, bool first, int &st, int &sd) { return launch(budget, first, st, sd, [](PersistArgs &) -> int { return E_OK; }); },
                             [&](int status, int sd) { return descent_completed(ctx, status, sd); }, hand_over);
     if (const int rc = resident_result(ctx, r, deadline_hit, ran); rc || !*ran) return rc;
-    ctx->lp_used = true; ctx->lp_window = win; ctx->lp_shaped = sfn != nullptr;
+    ctx->lp_used = true; ctx->lp_window = win; ctx->lp_shaped = sfn != nullptr; ctx->lp_tmat = tm;
     return E_OK;
 }
 
@@ -4935,6 +4944,7 @@ int tspgpu_set_option(tspgpu_ctx *ctx, int option, long value)
     case TSPGPU_OPT_BLOCK: if (value < 0 || value > 1024) return fail(ctx, E_INVALID, "bad block"); ctx->opt_block = (int)value; ctx->plan_kernel = 0; break;
     case TSPGPU_OPT_DEPTH: if (value < 0 || value > 8) return fail(ctx, E_INVALID, "bad depth"); ctx->opt_depth = (int)value; ctx->plan_kernel = 0; break;
     case 99: ctx->opt_ablate = (int)value; drop_graphs(ctx); break; // undocumented: kernel ablation for profiling
+    case 88: ctx->opt_lp_no_tmat = value ? 1 : 0; break; // undocumented: the shaped k_lds2opt that reloads moved rows from the matrix, not from the tour-ordered copy (tests)
     case 89: ctx->opt_lp_generic = value ? 1 : 0; break; // undocumented: the generic k_lds2opt where a shaped instantiation exists (tests)
     case 90: ctx->opt_or_otf_early = value == 1 || value == 2 ? (int)value : 0; break; // undocumented: see or_otf_early()
     case 91: ctx->opt_otf_early = value == 1 || value == 2 ? (int)value : 0; ctx->plan_kernel = 0; drop_graphs(ctx); break; // undocumented: see otf_early()
@@ -5047,6 +5057,7 @@ long tspgpu_info(const tspgpu_ctx *ctx, int what)
     case 65: return ctx->nl3_max_k;
     case 66: return ctx->nl3_phases;
     case 67: return NL3_NODES;
+    case 68: return ctx->lp_used && ctx->lp_shaped && ctx->lp_tmat ? 1 : 0;
     case 55: return ctx->have_costs && ctx->symmetric && ctx->n >= 8 ? (ctx->n + ORNL_STARTS - 1) / ORNL_STARTS : 0;
     case 12: return (ctx->built && ctx->grid_ok && ctx->opt_nn != 1 && ctx->cost_bound < 134217728.0) ? ctx->grid_G : 0;
     case 13: return ctx->grid_max_occ;
@@ -5693,6 +5704,16 @@ int tspgpu_debug_stamps(tspgpu_ctx *ctx, unsigned long long *out, int capacity_w
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     const size_t words = std::min<size_t>((size_t)capacity_words, (size_t)MAX_WGS_PER_TOUR * 64);
     HIP_TRY(hipMemcpy(out, ctx->d_stamps, words * 8, hipMemcpyDeviceToHost));
+    return E_OK;
+}
+
+int tspgpu_debug_tmat(tspgpu_ctx *ctx, unsigned short *out, size_t cells)
+{
+    if (!ctx || !out) return fail(ctx, E_INVALID, "null argument");
+    if (!ctx->d_lp_tmat) return fail(ctx, E_PRECOND, "no tour-ordered copy was kept");
+    hipSetDevice(ctx->device);
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    HIP_TRY(hipMemcpy(out, ctx->d_lp_tmat, std::min(cells, ctx->d_lp_tmat.n) * sizeof(u16), hipMemcpyDeviceToHost));
     return E_OK;
 }
 

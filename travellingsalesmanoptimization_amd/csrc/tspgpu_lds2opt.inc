@@ -71,6 +71,10 @@ struct PersistArgs {
     int vns_nrand;         // rand() values in vns_rand
     const int *vns_rand;   // the caller's random numbers in the order the reference consumes them
     int *vns_state;        // out: [0] iterations completed, [1] numbers consumed, [2] 1 = stopped in front of a kick phase for want of numbers
+    // TM instantiations of the shaped k_lds2opt: [n][n] the matrix with its columns in tour order (tspgpu_lds_tmat.h), filled by
+    // every launch.  A row is written by whichever workgroup holds its node, at different times by different ones: every access
+    // is agent scope (sc1), and a workgroup publishes its record of a sweep only behind the acknowledgement of its stores.
+    u16 *tmat;
 };
 
 static constexpr int LP_EMAX = 16, LP_BT = 512;
@@ -130,7 +134,21 @@ __device__ __forceinline__ unsigned lp_pk_min(unsigned a, unsigned b)
 // minima stay packed until a column is known to hold the workgroup's minimum, and the exchange reads its wave candidates
 // with independent wide reads.  Same algorithm, keys, records, slots and barriers; NLC == 0 is the generic kernel, unchanged.
 // (The shaped form reads A again from the kernel-argument segment at offset 0: PersistArgs must stay the ONLY argument.)
-template <bool PK16, bool TABU, bool VNS = false, int NLC = 0, int EC = 0>
+// TM: the shaped form with the rows that a move brings to a workgroup read from A.tmat -- the matrix kept in TOUR order in device
+// memory by the workgroups that hold the rows -- with plain wide loads straight into place, the reversal applied on the way in,
+// instead of read from the matrix in node order and permuted through LDS (reload: a barrier and 8 label gathers per row).
+//   * fill: behind the first reload every workgroup stores its rows 0 .. E-1 to tmat[node of the row];
+//   * write-back: behind every move every workgroup stores, for each row r < E it holds NOW, the aligned 8-cell chunks that
+//     overlap the reversed range -- each node sits at one cell, so each row of tmat has one writer per sweep;
+//   * fetch: a needed row r < E of node x is read from tmat[x], which nobody but this workgroup touches in this sweep and which
+//     is still in the order before the move: cell q takes the cell tspgpu_lds_tmat.h's src_cell names.  A thread's chunk is
+//     fetched whole (as it is, or the mirrored 8 cells reversed in registers) unless it is one of the at most three chunks a
+//     row has that mix both kinds or whose mirrored run crosses the array end: those go cell by cell, one lane a cell;
+//   * row E, the copy of the neighbour's first row, keeps reload()'s path through the matrix: its owner reads and rewrites
+//     tmat[x] in this very sweep;
+//   * every thread waits for its stores (vmcnt(0)) in front of the last barrier before the exchange: a published record implies
+//     that the workgroup's tmat is up to date, and a row is read only behind the exchange of the sweep that moves it.
+template <bool PK16, bool TABU, bool VNS = false, int NLC = 0, int EC = 0, bool TM = false>
 __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -139,6 +157,7 @@ __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
     constexpr int WC = NLC / (EC > 0 ? EC : 1);             // workgroups of the shaped form
     typedef __attribute__((address_space(4))) const PersistArgs c_PersistArgs;      // (the kernel arguments where they lie)
     static_assert(!SH || (PK16 && !TABU && !VNS), "the shaped form is the plain packed descent");
+    static_assert(!TM || SH, "the tour-ordered copy needs the shaped form: n == nl a power of two, k0 = wg * E, no overlapping workgroup");
     static_assert(!SH || ((NLC & (NLC - 1)) == 0 && NLC % 16 == 0 && NLC / 8 <= LP_BT), "shaped n: a power of two, at most 8 cells a thread");
     static_assert(!SH || (EC >= 2 && EC % 2 == 0 && EC <= LP_EMAX && NLC % EC == 0 && NLC / EC <= 256), "shaped E: even, W = n / E <= 256");
     constexpr unsigned POISON = PK16 ? 16383u : 65535u;     // on the diagonal: delta(k, k) = 2 POISON - 2 w[k] >= 0
@@ -266,7 +285,7 @@ __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
         }
         // (shaped form: the row mask is opaque from here on, so that its bits are tested again where the rows are written and
         // not kept as 17 lane masks across the loads)
-        if constexpr (SH) asm volatile("" : "+s"(need));
+        if constexpr (SH && !TM) asm volatile("" : "+s"(need));
         const int last = 31 - __builtin_clz(need);
         int left = __builtin_popcount(need);                       // rows still to be written to a buffer
         unsigned char *bufT = reinterpret_cast<unsigned char *>(rows + (size_t)last * nl);
@@ -320,6 +339,110 @@ __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
     };
     const unsigned allrows = (2u << E) - 1u;
     reload(allrows);
+    // TM: the descriptor of A.tmat (out-of-range offsets are dropped by the hardware), built where it is used from the
+    // kernel arguments where they lie (see the tour state's write-back below): nothing of it lives across the sweep loop
+    auto tm_rsrc = [&]() __attribute__((always_inline)) {
+        c_PersistArgs *Ak = (c_PersistArgs *)__builtin_amdgcn_kernarg_segment_ptr();
+        asm volatile("" : "+s"(Ak));
+        return __builtin_amdgcn_make_buffer_rsrc(Ak->tmat, 0, NLC * NLC * 2, 0x00020000);
+    };
+    constexpr int TM_SC1 = 16;                        // (the cache-policy word of the buffer builtins: agent scope)
+    if constexpr (TM) {                               // fill: the own rows 0 .. E-1 as they lie in LDS
+        const auto rs = tm_rsrc();
+#pragma unroll 4
+        for (int i = tid; i < EC * (NLC / 8); i += BT) {
+            const int row = i / (NLC / 8), c = i & (NLC / 8 - 1);
+            const unsigned x = wt16[2 * (k0 + row) + 1];
+            const v4u32 v = *reinterpret_cast<const v4u32 *>(rows + (size_t)row * NLC + 8 * c);
+            __builtin_amdgcn_raw_buffer_store_b128(v, rs, (int)((x * NLC + 8 * c) * 2), 0, TM_SC1);
+        }
+    }
+    // TM: the rows in `need` behind the move that reversed [lo, lo + M) -- labels, edge costs and the rows that stay are final
+    // (tidv: the thread index, opaque inside a sweep -- LP_TID -- so that the lane masks of the cell-by-cell pass are computed here)
+    auto fetch_tm = [&](unsigned need, int lo, int M, int tidv) __attribute__((always_inline)) {
+        if constexpr (!TM) return;
+        const auto rs = tm_rsrc();
+        const int lane = tid & 63;
+        const unsigned ownlab = wt16[2 * ((k0 + min(lane, EC)) & (NLC - 1)) + 1];      // lane r: the node at the own cell r
+        int start = 0;
+        const int cls = act ? lds_tmat::chunk_class(m0, lo, M, NLC, start) : (int)lds_tmat::CELLWISE;
+        v4u32 R[EC > 0 ? EC : 1], Rc = {0, 0, 0, 0};
+#pragma unroll
+        for (int r = 0; r < EC; r++)                  // (every thread loads: a chunk that goes cell by cell is loaded and dropped)
+            if ((need >> r) & 1)
+                R[r] = __builtin_amdgcn_raw_buffer_load_b128(rs, start * 2, __builtin_amdgcn_readlane((int)ownlab, r) * (NLC * 2), TM_SC1);
+        asm volatile("" : "+s"(need));                // (as in reload(): the bits are tested again where the rows are written)
+        const bool copy = (need >> EC) & 1;
+        const unsigned xc = (unsigned)__builtin_amdgcn_readlane((int)ownlab, EC);
+        if (copy && act) {                            // (matrix and stride from the kernel arguments as well; xc * ld < 2^32)
+            c_PersistArgs *Ak = (c_PersistArgs *)__builtin_amdgcn_kernarg_segment_ptr();
+            asm volatile("" : "+s"(Ak));
+            Rc = *reinterpret_cast<const v4u32 *>(Ak->mat + (size_t)(xc * (unsigned)Ak->ld) + m0);
+        }
+        // the cells of the three chunks that may not go whole: 24 lanes a row
+        int cw[3];
+        lds_tmat::cellwise_chunks(lo, M, NLC, cw);
+        const int sr = tidv / 24, si = tidv - sr * 24;
+        const bool sact = sr < EC && ((need >> sr) & 1);
+        const int sq = (si < 8 ? cw[0] : si < 16 ? cw[1] : cw[2]) * 8 + (si & 7);
+        const unsigned sx = wt16[2 * (k0 + min(sr, EC - 1)) + 1];
+        const u16 sv = __builtin_amdgcn_raw_buffer_load_b16(rs, (int)((sx * NLC + lds_tmat::src_cell(sq, lo, M, NLC)) * 2), 0, TM_SC1);
+#pragma unroll
+        for (int r = 0; r < EC; r++) {
+            if ((need >> r) & 1) {
+                const v4u32 v = R[r];
+                const v4u32 m = {__builtin_amdgcn_alignbit(v.w, v.w, 16), __builtin_amdgcn_alignbit(v.z, v.z, 16),
+                                 __builtin_amdgcn_alignbit(v.y, v.y, 16), __builtin_amdgcn_alignbit(v.x, v.x, 16)};
+                if (cls != lds_tmat::CELLWISE) *reinterpret_cast<v4u32 *>(rows + (size_t)r * NLC + m0) = cls == lds_tmat::MIRROR ? m : v;
+            }
+        }
+        if (sact) rows[(size_t)sr * NLC + sq] = sv;
+        // (the cell's load has landed in EVERY lane from here on: a load left pending in the idle lanes would make the compiler
+        // wait for all memory operations -- the write-back's stores among them -- where its register is used next)
+        asm volatile("" :: "v"((unsigned)sv));
+        if (copy) {                                 // as reload(): in node order to the staging row, gathered by the labels
+            if (act) {
+                v4u32 v = Rc;
+                if ((int)(xc >> 3) == tid) {
+                    const unsigned sel = (xc & 7u) >> 1;
+                    unsigned c[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+                    for (int q = 0; q < 4; q++)
+                        if ((unsigned)q == sel) c[q] = (xc & 1u) ? (c[q] & 0xffffu) | (POISON << 16) : (c[q] & 0xffff0000u) | POISON;
+                    v = v4u32{c[0], c[1], c[2], c[3]};
+                }
+                *reinterpret_cast<v4u32 *>(stage + m0) = v;
+            }
+            __syncthreads();
+            if (act) {
+                const v4u32 la = *reinterpret_cast<const v4u32 *>(wt + m0), lb = *reinterpret_cast<const v4u32 *>(wt + m0 + 4);
+                const unsigned l[8] = {la.x >> 16, la.y >> 16, la.z >> 16, la.w >> 16, lb.x >> 16, lb.y >> 16, lb.z >> 16, lb.w >> 16};
+                unsigned g[8];
+#pragma unroll
+                for (int v = 0; v < 8; v++) g[v] = stage[l[v]];
+                const v4u32 out = {g[0] | g[1] << 16, g[2] | g[3] << 16, g[4] | g[5] << 16, g[6] | g[7] << 16};
+                *reinterpret_cast<v4u32 *>(rows + (size_t)EC * NLC + m0) = out;
+            }
+        }
+        __syncthreads();
+    };
+    // TM: behind the move, the chunks of the rows 0 .. E-1 that overlap the reversed range, from LDS to the rows' nodes in tmat
+    // (2^lg >= the chunk count threads a row, 512 >> lg rows a pass)
+    auto write_back_tm = [&](int lo, int M, int tidv) __attribute__((always_inline)) {
+        if constexpr (!TM) return;
+        const auto rs = tm_rsrc();
+        const int nch = lds_tmat::wb_count(lo, M), c0 = lds_tmat::wb_first(lo);
+        const int lg = nch > 1 ? 32 - __builtin_clz(nch - 1) : 0;
+        const int j = tidv & ((1 << lg) - 1), rpi = BT >> lg;
+        if (j < nch) {
+            const int c = (c0 + j) & (NLC / 8 - 1);
+            for (int row = tidv >> lg; row < EC; row += rpi) {
+                const unsigned x = wt16[2 * (k0 + row) + 1];
+                const v4u32 v = *reinterpret_cast<const v4u32 *>(rows + (size_t)row * NLC + 8 * c);
+                __builtin_amdgcn_raw_buffer_store_b128(v, rs, (int)((x * NLC + 8 * c) * 2), 0, TM_SC1);
+            }
+        }
+    };
 
     int status = LP_ST_RUNNING;
     if (cap >= 0 && kd >= cap) status = LP_ST_CAPPED;        // (cap 0: not one sweep)
@@ -609,6 +732,8 @@ __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
             }
             if (mykey != ~0ull) __hip_atomic_fetch_min(&scr[0], mykey, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         }
+        // TM: every thread's stores to tmat (the fill, the last move's write-back) acknowledged before the record goes out
+        if constexpr (TM) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
         const u64 kmin = scr[0];
         const bool have = found ? mykey == kmin : LP_TID == 0;
@@ -818,8 +943,12 @@ __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
             __syncthreads();
         }
         LP_PHASE(3);                                  // reversal
-        if (need) { reload(need); nreload++; nrows += __builtin_popcount(need); }
+        if (need) {
+            if constexpr (TM) fetch_tm(need, lo, M, LP_TID); else reload(need);
+            nreload++; nrows += __builtin_popcount(need);
+        }
         LP_PHASE(4);                                  // rows fetched
+        if constexpr (TM) { write_back_tm(lo, M, LP_TID); LP_PHASE2(3); }
         if (clk && wg == 0 && sdone < 4000) A.stamps[8192 + sdone] = ((unsigned long long)M << 48) | (wall_clock64() & 0xFFFFFFFFFFFFull);
         }   // (!nomove)
         if constexpr (TABU) {
@@ -884,7 +1013,7 @@ __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
     }
     if constexpr (SH) {
         // (the kernel-argument segment begins with the explicit arguments: PersistArgs, the only one, lies at offset 0)
-        static_assert(std::is_same_v<decltype(&k_lds2opt<PK16, TABU, VNS, NLC, EC>), void (*)(PersistArgs)>, "PersistArgs must stay the kernel's only argument");
+        static_assert(std::is_same_v<decltype(&k_lds2opt<PK16, TABU, VNS, NLC, EC, TM>), void (*)(PersistArgs)>, "PersistArgs must stay the kernel's only argument");
         c_PersistArgs *Ak = (c_PersistArgs *)__builtin_amdgcn_kernarg_segment_ptr();
         asm volatile("" : "+s"(Ak));
         const int tk = Ak->slot;
