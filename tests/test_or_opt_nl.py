@@ -30,7 +30,7 @@ from make_golden_or_opt_nl import model_ls_descent, model_or_sweep, unpack  # no
 from make_golden_two_opt_nl import digest, model_lists, model_sweep  # noqa: E402
 from test_two_opt_multi import (CEIL_2D, EPS, EUC_2D, MODES, engine_for, nn0, points_for, random_tour,  # noqa: E402
                                 sym_int_matrix, symmetric_noise, tour_cost, weight_matrix)
-from test_two_opt_nl import brute_lists, restricted_improving_pairs, source_of, stripe_tour  # noqa: E402
+from test_two_opt_nl import brute_lists, check_cap_refusal, restricted_improving_pairs, source_of, stripe_tour  # noqa: E402
 
 DATA = os.path.join(ROOT, "tests", "golden", "data")
 GOLDEN = os.path.join(ROOT, "tests", "golden", "golden_or_opt_nl.json")
@@ -353,6 +353,13 @@ def test_gpu_move_by_move(mode, n):
     eng, multi = run_phases(mode, n, (1, 8, 16))
     assert n < 40 or multi >= 1
     eng.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode,seed", [("u16", 2), ("mf_euc", 2)])
+def test_gpu_cap_below_the_accepted_count(mode, seed):
+    check_cap_refusal(mode, seed, 4, model_or_sweep,
+                      lambda eng, *a: eng.L.tspgpu_or_opt_nl_once(eng.ctx, *a), lambda eng, p, c, cap: eng.or_opt_nl_once(p, c, cap=cap))
 
 
 @pytest.mark.gpu

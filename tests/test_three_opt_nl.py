@@ -33,7 +33,7 @@ from make_golden_three_opt_nl import model_ls3_descent, model_three_sweep, pack 
 from make_golden_two_opt_nl import digest, model_lists  # noqa: E402
 from test_two_opt_multi import (EPS, EUC_2D, MODES, engine_for, nn0, points_for, random_tour, sym_int_matrix,  # noqa: E402
                                 symmetric_noise, tour_cost, weight_matrix)
-from test_two_opt_nl import brute_lists, source_of, stripe_tour  # noqa: E402
+from test_two_opt_nl import brute_lists, check_cap_refusal, source_of, stripe_tour  # noqa: E402
 from test_or_opt_nl import rect_lattice, run_tsp, tour_from_zero  # noqa: E402
 
 DATA = os.path.join(ROOT, "tests", "golden", "data")
@@ -395,6 +395,15 @@ def test_gpu_move_by_move(mode, n):
     eng, multi = run_phases(mode, n, KW)
     assert n < 40 or multi >= 1
     eng.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode,seed", [("u16", 26), ("mf_euc", 26)])
+def test_gpu_cap_below_the_accepted_count(mode, seed):
+    """(width 8 = K: every list entry)"""
+    check_cap_refusal(mode, seed, 4, lambda p, c, nodes, **src: model_three_sweep(p, c, nodes, 8, **src),
+                      lambda eng, *a: eng.L.tspgpu_three_opt_nl_once(eng.ctx, 8, *a),
+                      lambda eng, p, c, cap: eng.three_opt_nl_once(p, c, 8, cap=cap))
 
 
 @pytest.mark.gpu

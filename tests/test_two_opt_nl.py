@@ -451,6 +451,48 @@ def test_gpu_move_by_move_large(mode, n, start):
     eng.close()
 
 
+CAP_N, CAP_K = 40, 8
+
+
+def cap_case(mode, seed, sweep):
+    """40 random points and a random start; `sweep` is a module's model of one sweep -> (xy, kind, nodes, start, the model's
+    record of the first sweep, the path behind it)"""
+    xy, kind = points_for(mode, CAP_N, seed)
+    src = source_of(mode, xy, kind, weight_matrix(xy, kind))
+    nodes, _ = model_lists(CAP_K, **src)
+    start = random_tour(CAP_N, np.random.default_rng(seed))
+    want = start.copy()
+    r = sweep(want, 123.0, nodes, **src)
+    return xy, kind, nodes, start, r, want
+
+
+def check_cap_refusal(mode, seed, ints, sweep, raw_once, once):
+    """the caller's arrays hold one move less than the sweep accepts: 8, nothing applied and nothing written; they hold exactly
+    as many: the model's sweep.  raw_once(eng, path, cost, cnt, mv, dl, cap) is the C entry point, once(eng, path, cost, cap)
+    the engine's method.  The seed is chosen on the CPU so that the model accepts k >= 2 moves"""
+    xy, kind, _, start, r, want = cap_case(mode, seed, sweep)
+    k = len(r["moves"])
+    assert k >= 2, (mode, seed, k)
+    eng = engine_for(mode, xy, kind)
+    eng.neighbours_build(CAP_K)
+    path = start.copy()
+    mv, dl = np.full(ints * CAP_N, -7, np.int32), np.full(CAP_N, -7.0)
+    cost, cnt = C.c_double(123.0), C.c_int(-7)
+    assert raw_once(eng, path, C.byref(cost), C.byref(cnt), mv, dl, k - 1) == 8
+    assert np.array_equal(path, start) and cost.value == 123.0 and cnt.value == -7 and np.all(mv == -7) and np.all(dl == -7.0)
+    got, mv, dl = once(eng, path, 123.0, k)
+    assert np.array_equal(mv, r["moves"]) and np.array_equal(dl, r["deltas"])
+    assert np.array_equal(path, want) and got == r["cost"]
+    eng.close()
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode,seed", [("u16", 1), ("mf_euc", 1)])
+def test_gpu_cap_below_the_accepted_count(mode, seed):
+    check_cap_refusal(mode, seed, 2, model_sweep,
+                      lambda eng, *a: eng.L.tspgpu_two_opt_nl_once(eng.ctx, *a), lambda eng, p, c, cap: eng.two_opt_nl_once(p, c, cap=cap))
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode", ["u16", "i32", "f64", "mf_euc", "mf_ceil_int"])
 def test_gpu_full_lists_equal_the_parallel_move_sweep(mode):

@@ -51,6 +51,7 @@
 
 #include "tspgpu.h"
 #include "tspgpu_relaunch.h"    // LP_ST_*, and the host's protocol over them (run_persist, run_pstream)
+#include "tspgpu_looks.h"       // rounds of launches between looks at a control block (m2_run, or_run, the batched descents)
 #include "tspgpu_lds_tmat.h"    // index arithmetic of the tour-ordered matrix copy (k_lds2opt's TM instantiations)
 
 #ifndef TSPGPU_RPC
@@ -3234,6 +3235,8 @@ struct MEM_GROUP SlotMem {                // of one slot capacity: ensure_tours 
     ~SlotMem() { reset(); }
 };
 
+struct M2Counters { long sweeps = 0, moves = 0, max_k = 0; };    // what tspgpu_info keeps of a parallel-move family's last call
+
 struct tspgpu_ctx : ContextMem, InstanceMem, CostMem, SlotMem {
     int device = 0;
     hipStream_t stream = nullptr;
@@ -3317,19 +3320,17 @@ struct tspgpu_ctx : ContextMem, InstanceMem, CostMem, SlotMem {
     int or_otf_form = 0;       // how the last matrix-free Or-opt sweep ran: 0 none, 1 every candidate, 2 with the early-out
     int or_otf_R = 0;          // its tour positions per workgroup
 
-    // parallel-move 2-opt (tspgpu_multi2opt.inc)
-    long m2_sweeps = 0, m2_moves = 0, m2_max_k = 0;    // the last parallel-move descent
+    // the parallel-move families (M2Family): the last call's sweeps, moves and largest sweep (a descent: over its rounds or phases)
+    M2Counters m2_count, nl_count, ornl_count, nl3_count;
 
     // neighbour-list 2-opt (tspgpu_nl2opt.inc)
     bool nl_dropped = false;   // a new cost source took the lists away (the refusal says so)
-    long nl_sweeps = 0, nl_moves = 0, nl_polish_sweeps = 0;     // the last neighbour-list phase and its polish
-    // neighbour-list Or-opt (tspgpu_ornl.inc): the last call's sweeps, moves and largest sweep (a descent: over its rounds)
-    long ornl_sweeps = 0, ornl_moves = 0, ornl_max_k = 0;
+    long nl_polish_sweeps = 0; // the polish of the last neighbour-list phase
+    // neighbour-list Or-opt (tspgpu_ornl.inc)
     int ornl_rounds = 0;       // rounds of the last tspgpu_local_search_nl
-    // neighbour-list 3-opt (tspgpu_nl3opt.inc): the width asked for and W = min(width, K') in effect; the last call's sweeps,
-    // moves and largest sweep (a descent: over its phases), and the 3-opt phases of the last tspgpu_local_search_nl3
+    // neighbour-list 3-opt (tspgpu_nl3opt.inc): the width asked for and W = min(width, K') in effect, and the 3-opt phases of
+    // the last tspgpu_local_search_nl3
     int nl3_width = 0, nl3_w = 0;
-    long nl3_sweeps = 0, nl3_moves = 0, nl3_max_k = 0;
     int nl3_phases = 0;
     // batched neighbour-list descent (tspgpu_nlbatch.inc)
     long nlb_tours = 0, nlb_launches = 0, nlb_max_live = 0;     // the last batched descent: tours, sweeps launched, most tours in one
@@ -3470,6 +3471,15 @@ template <typename F> static void kind_switch(const tspgpu_ctx *ctx, F &&f)
     else if (ctx->kind == TSPGPU_ATT) f(std::integral_constant<int, TSPGPU_ATT>{}, pts, spts);
     else f(std::integral_constant<int, TSPGPU_CEIL_2D>{}, pts, spts);
 }
+
+// one launch from whichever cost source the context has: K<T>(S, mat, n, ld, ...) or K_otf<KIND>(S, pts, n, ...)
+#define LAUNCH_BY_COST(K, grid, block, ...)                                                                                               \
+    do {                                                                                                                                  \
+        if (ctx->otf) kind_switch(ctx, [&](auto kind, auto *pts, auto *) {                                                                \
+            hipLaunchKernelGGL((K##_otf<kind()>), grid, block, 0, ctx->stream, ctx->S, pts, ctx->n, __VA_ARGS__); });                      \
+        else ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((K<T>), grid, block, 0, ctx->stream, ctx->S, (const T *)ctx->d_mat.p, ctx->n,  \
+                                                          ctx->ld, __VA_ARGS__));                                                         \
+    } while (0)
 
 // room for `points` gathered successor points
 static int ensure_spts(tspgpu_ctx *ctx, size_t points)
@@ -5026,20 +5036,20 @@ long tspgpu_info(const tspgpu_ctx *ctx, int what)
     case 33: return or_single_geom(ctx, true);
     case 34: return ctx->or_otf_form;
     case 35: return ctx->or_otf_R;
-    case 36: return ctx->m2_sweeps;
-    case 37: return ctx->m2_moves;
-    case 38: return ctx->m2_max_k;
+    case 36: return ctx->m2_count.sweeps;
+    case 37: return ctx->m2_count.moves;
+    case 38: return ctx->m2_count.max_k;
     case 39: return m2_geom(ctx, 0);
     case 40: return m2_geom(ctx, 1);
     case 41: return m2_geom(ctx, 2);
     case 42: return ctx->nl.K;
-    case 43: return ctx->nl_sweeps;
-    case 44: return ctx->nl_moves;
+    case 43: return ctx->nl_count.sweeps;
+    case 44: return ctx->nl_count.moves;
     case 45: return ctx->nl_polish_sweeps;
     case 46: return NL_NODES;
-    case 47: return ctx->ornl_sweeps;
-    case 48: return ctx->ornl_moves;
-    case 49: return ctx->ornl_max_k;
+    case 47: return ctx->ornl_count.sweeps;
+    case 48: return ctx->ornl_count.moves;
+    case 49: return ctx->ornl_count.max_k;
     case 50: return ctx->ornl_rounds;
     case 51: return ORNL_STARTS;
     case 52: return ctx->nlb_tours;
@@ -5052,9 +5062,9 @@ long tspgpu_info(const tspgpu_ctx *ctx, int what)
     case 60: return ctx->nlv_dry;
     case 61: return ctx->lp_used && ctx->lp_shaped ? 1 : 0;
     case 62: return ctx->nl3_w;
-    case 63: return ctx->nl3_sweeps;
-    case 64: return ctx->nl3_moves;
-    case 65: return ctx->nl3_max_k;
+    case 63: return ctx->nl3_count.sweeps;
+    case 64: return ctx->nl3_count.moves;
+    case 65: return ctx->nl3_count.max_k;
     case 66: return ctx->nl3_phases;
     case 67: return NL3_NODES;
     case 68: return ctx->lp_used && ctx->lp_shaped && ctx->lp_tmat ? 1 : 0;
@@ -5979,13 +5989,7 @@ static int or_launch_sweep(tspgpu_ctx *ctx, int slot, const SweepGeom &P, bool g
 static int or_launch_apply(tspgpu_ctx *ctx, int slot, const SweepGeom &P)
 {
     const int BT = std::min(1024, std::max(64, pow2_ceil(ctx->n / 8)));
-    if (ctx->otf)
-        kind_switch(ctx, [&](auto kind, auto *pts, auto *) {
-            hipLaunchKernelGGL((k_oropt_apply_otf<kind()>), dim3(1), dim3(BT), 0, ctx->stream, ctx->S, pts, ctx->n, slot, P.W, ctx->d_or);
-        });
-    else
-        ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_oropt_apply<T>), dim3(1), dim3(BT), 0, ctx->stream, ctx->S, (const T *)ctx->d_mat.p,
-                                                     ctx->n, ctx->ld, slot, P.W, ctx->d_or));
+    LAUNCH_BY_COST(k_oropt_apply, dim3(1), dim3(BT), slot, P.W, ctx->d_or);
     HIP_TRY(hipGetLastError());
     return E_OK;
 }
@@ -6006,16 +6010,13 @@ static int or_run(tspgpu_ctx *ctx, int slot, long max_moves, double t_end, long 
     int rc = ctl_put(ctx, ctx->d_or.p, C);
     if (rc) return rc;
     const SweepGeom P = or_plan(ctx);
-    for (;;) {
-        if (t_end >= 0 && now_s() >= t_end) { if (late) *late = true; break; }
-        const int K = t_end >= 0 ? 1 : 8;
-        for (int i = 0; i < K; i++) {
-            if ((rc = or_launch_sweep(ctx, slot, P))) return rc;
-            if ((rc = or_launch_apply(ctx, slot, P))) return rc;
-        }
-        if ((rc = ctl_get(ctx, &C, ctx->d_or.p))) return rc;
-        if (C.stop) break;
-    }
+    const looks::Result r = looks::drive(
+        now_s, t_end, 8,
+        [&] { const int e = or_launch_sweep(ctx, slot, P); return e ? e : or_launch_apply(ctx, slot, P); },
+        [&] { const int e = ctl_get(ctx, &C, ctx->d_or.p); return e ? e : C.stop ? (int)looks::STOP : (int)looks::GO_ON; });
+    if (r.code) return r.code;
+    if (late) *late = r.late;
+    if (r.late && (rc = ctl_get(ctx, &C, ctx->d_or.p))) return rc;      // (as m2_run: every round under a deadline has its look, so C stands)
     if (moves) *moves = (long)C.moves;
     if (last) *last = C;
     return E_OK;
@@ -6123,22 +6124,15 @@ static int or_descent_batch(tspgpu_ctx *ctx, int slot0, int count, double time_l
         // the Or-opt phase of the live tours (the list uploaded above is still theirs)
         hipLaunchKernelGGL(k_or_arm, dim3((nl + 255) / 256), dim3(256), 0, ctx->stream, ctx->d_or_ctl, (const int *)ctx->d_live, nl);
         HIP_TRY(hipGetLastError());
-        act = live;
-        bool fresh = true;      // d_live holds `act`
-        while (!act.empty()) {
-            if (t_end >= 0 && now_s() >= t_end) { *late = true; break; }
-            if (!fresh && (rc = set_live(ctx, act))) return rc;
-            fresh = false;
-            const SweepGeom P = or_plan_batch(ctx, (int)act.size());
-            if (!ctx->or_batch_R) ctx->or_batch_R = P.R;
-            const int K = t_end >= 0 ? 1 : 8;
-            for (int i = 0; i < K; i++)
-                if ((rc = or_launch_round(ctx, (int)act.size(), P))) return rc;
-            if ((rc = read_ctl())) return rc;
-            size_t k = 0;
-            for (int t : act) if (!hc[t - slot0].stop) act[k++] = t;
-            act.resize(k);
-        }
+        act = live;             // d_live holds `act`, and only set_live writes it: a list that did not shrink is not uploaded again
+        SweepGeom P{};
+        const looks::Result r = looks::drive_live(
+            now_s, t_end, 8, act,
+            [&](int len) { P = or_plan_batch(ctx, len); if (!ctx->or_batch_R) ctx->or_batch_R = P.R; },
+            [&](int len) { return or_launch_round(ctx, len, P); }, read_ctl, [&](int t) { return hc[t - slot0].stop != 0; },
+            [&](const std::vector<int> &list) { return set_live(ctx, list); });
+        if (r.code) return r.code;
+        *late = r.late;
         if (*late && (rc = read_ctl())) return rc;
         size_t k = 0;
         for (int t : live) {
@@ -6305,30 +6299,32 @@ static int m2_geom(const tspgpu_ctx *ctx, int what)
     return what == 0 ? P.R : what == 1 ? P.BT : P.NCH;
 }
 
-static int nl_launch_sweep(tspgpu_ctx *ctx, int slot);      // (tspgpu_nl2opt.inc's driver, below)
-static int ornl_launch_sweep(tspgpu_ctx *ctx, int slot);    // (tspgpu_ornl.inc's driver, below)
-static int ornl_launch_apply(tspgpu_ctx *ctx, int slot);
-static int nl3_launch_sweep(tspgpu_ctx *ctx, int slot);     // (tspgpu_nl3opt.inc's driver, below)
-static int nl3_launch_apply(tspgpu_ctx *ctx, int slot);
+// the host's copy of a sweep's compacted list, as far as a family's `put` reads it.  The names are the device buffers': a, b the
+// candidate as M2Buf holds it; i, j the two ends of its range (for the 3-opt: the rule's i and k); jk what k_nl3_describe left
+// in raw_b, the 3-opt's middle position and kind as j << 2 | kind
+struct M2Moves { std::vector<int> a, b, i, j, jk; };
 
-// where the candidates of a sweep come from and what an accepted one is: every b of the parallel-move 2-opt, the neighbour
-// lists' 2-opt pairs (k_nl_sweep), the neighbour lists' Or-opt segment moves (k_ornl_sweep, with its own compaction and apply), or
-// the neighbour lists' 3-opt chains (k_nl3_sweep, likewise)
-enum M2Kind { M2_FULL, M2_NL, M2_ORNL, M2_NL3 };
+// A parallel-move family: where the candidates of a sweep come from and what an accepted one is.  The drivers below (m2_run,
+// m2_once, m2_time) know a family only through this; the four instances stand behind their families' launch functions
+struct M2Family {
+    int (*check)(tspgpu_ctx *);
+    int (*sweep)(tspgpu_ctx *, int slot, const SweepGeom &P, bool gather);      // the candidate sweep (P, gather: the full family's)
+    void (*compact)(tspgpu_ctx *, int slot);                                    // the launch of its compaction
+    int (*apply)(tspgpu_ctx *, int slot);
+    int ints;                                                                   // ints per move in the caller's `moves` array
+    int (*describe)(tspgpu_ctx *, size_t m, M2Moves &L);    // queues what `put` needs beyond a and b, while the tour still stands (or null)
+    void (*put)(int *out, const M2Moves &L, int x);         // candidate x into the caller's array
+    M2Counters tspgpu_ctx::*count;
+    long tspgpu_ctx::*voids;                                // a descent's counter that a new run of the family takes back to 0 (or null)
+};
 
-// the candidate sweep and the selection of one sweep (matrix-free mode: behind the gather of the successors' points)
-static int m2_launch_select(tspgpu_ctx *ctx, int slot, const SweepGeom &P, bool gather = true, M2Kind kind = M2_FULL)
+// every b of every node (k_m2_sweep; matrix-free mode: behind the gather of the successors' points)
+static int m2_sweep_full(tspgpu_ctx *ctx, int slot, const SweepGeom &P, bool gather)
 {
     const int n = ctx->n;
     const M2Ctl *ctl = ctx->d_m2;
     int rc;
-    if (kind == M2_NL) {
-        if ((rc = nl_launch_sweep(ctx, slot))) return rc;
-    } else if (kind == M2_ORNL) {
-        if ((rc = ornl_launch_sweep(ctx, slot))) return rc;
-    } else if (kind == M2_NL3) {
-        if ((rc = nl3_launch_sweep(ctx, slot))) return rc;
-    } else if (ctx->otf) {
+    if (ctx->otf) {
         if (gather && (rc = launch_spts_gather(ctx, slot, &ctl->stop))) return rc;
         kind_switch(ctx, [&](auto kind, auto *pts, auto *spts) {
             hipLaunchKernelGGL((k_m2_sweep_otf<kind()>), dim3(P.W), dim3(P.BT), 0, ctx->stream, ctx->S, pts, spts, n, slot, ctx->m2, ctl);
@@ -6341,28 +6337,35 @@ static int m2_launch_select(tspgpu_ctx *ctx, int slot, const SweepGeom &P, bool 
                                     else if (P.NCH == 4) M2_SWEEP(T, 4); else M2_SWEEP(T, 10); });
 #undef M2_SWEEP
     }
-    HIP_TRY(hipGetLastError());
-    if (kind == M2_ORNL) hipLaunchKernelGGL(k_ornl_compact, dim3(1), dim3(1024), 0, ctx->stream, ctx->S, n, slot, ctx->m2, ctx->d_m2);
-    else if (kind == M2_NL3) hipLaunchKernelGGL(k_nl3_compact, dim3(1), dim3(1024), 0, ctx->stream, ctx->S, n, slot, ctx->nl, ctx->m2, ctx->d_m2);
-    else hipLaunchKernelGGL(k_m2_compact, dim3(1), dim3(1024), 0, ctx->stream, ctx->S, n, slot, ctx->m2, ctx->d_m2);
-    HIP_TRY(hipGetLastError());
-    hipLaunchKernelGGL(k_m2_select, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->m2, ctl);
+    return E_OK;
+}
+
+static void m2_compact_pairs(tspgpu_ctx *ctx, int slot)
+{
+    hipLaunchKernelGGL(k_m2_compact, dim3(1), dim3(1024), 0, ctx->stream, ctx->S, ctx->n, slot, ctx->m2, ctx->d_m2);
+}
+
+static int m2_apply_pairs(tspgpu_ctx *ctx, int slot)
+{
+    const int G = std::min(M2_APPLY_WGS, (ctx->n + 1) / 2);
+    LAUNCH_BY_COST(k_m2_apply, dim3(G), dim3(256), slot, ctx->m2, ctx->d_m2);
     HIP_TRY(hipGetLastError());
     return E_OK;
 }
 
-static int m2_launch_apply(tspgpu_ctx *ctx, int slot, M2Kind kind = M2_FULL)
+static void m2_put_pair(int *out, const M2Moves &L, int x) { out[0] = L.a[x]; out[1] = L.b[x]; }
+
+static const M2Family M2_FULL = {m2_check, m2_sweep_full, m2_compact_pairs, m2_apply_pairs, 2, nullptr, m2_put_pair, &tspgpu_ctx::m2_count, nullptr};
+
+// the candidate sweep and the selection of one sweep
+static int m2_launch_select(tspgpu_ctx *ctx, int slot, const SweepGeom &P, bool gather, const M2Family &F)
 {
-    if (kind == M2_ORNL) return ornl_launch_apply(ctx, slot);
-    if (kind == M2_NL3) return nl3_launch_apply(ctx, slot);
-    const int n = ctx->n, G = std::min(M2_APPLY_WGS, (n + 1) / 2);
-    if (ctx->otf)
-        kind_switch(ctx, [&](auto kind, auto *pts, auto *) {
-            hipLaunchKernelGGL((k_m2_apply_otf<kind()>), dim3(G), dim3(256), 0, ctx->stream, ctx->S, pts, n, slot, ctx->m2, ctx->d_m2);
-        });
-    else
-        ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_m2_apply<T>), dim3(G), dim3(256), 0, ctx->stream, ctx->S, (const T *)ctx->d_mat.p,
-                                                     n, ctx->ld, slot, ctx->m2, ctx->d_m2));
+    const int rc = F.sweep(ctx, slot, P, gather);
+    if (rc) return rc;
+    HIP_TRY(hipGetLastError());
+    F.compact(ctx, slot);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_m2_select, dim3((ctx->n + 255) / 256), dim3(256), 0, ctx->stream, ctx->m2, (const M2Ctl *)ctx->d_m2);
     HIP_TRY(hipGetLastError());
     return E_OK;
 }
@@ -6380,43 +6383,36 @@ static int m2_arm(tspgpu_ctx *ctx, int slot, long budget)
     return E_OK;
 }
 
-static void m2_record(tspgpu_ctx *ctx, const M2Ctl &C, M2Kind kind = M2_FULL)
+static void m2_record(tspgpu_ctx *ctx, const M2Ctl &C, const M2Family &F)
 {
-    // (a phase's polish is counted behind it, tspgpu_two_opt_nl: until then the phase has none)
-    if (kind == M2_NL) { ctx->nl_sweeps = (long)C.sweeps; ctx->nl_moves = (long)C.moves; ctx->nl_polish_sweeps = 0; }
-    else if (kind == M2_ORNL) { ctx->ornl_sweeps = (long)C.sweeps; ctx->ornl_moves = (long)C.moves; ctx->ornl_max_k = C.max_k; }
-    else if (kind == M2_NL3) { ctx->nl3_sweeps = (long)C.sweeps; ctx->nl3_moves = (long)C.moves; ctx->nl3_max_k = C.max_k; }
-    else { ctx->m2_sweeps = (long)C.sweeps; ctx->m2_moves = (long)C.moves; ctx->m2_max_k = C.max_k; }
+    ctx->*F.count = M2Counters{(long)C.sweeps, (long)C.moves, (long)C.max_k};
+    if (F.voids) ctx->*F.voids = 0;
 }
 
 // sweeps on `slot` until one accepts nothing, max_sweeps (< 0: no cap) have run or t_end (< 0: none) passes; per sweep the
-// launches of m2_launch_select and m2_launch_apply, four sweeps between looks at the control block (one under a deadline)
-static int m2_run(tspgpu_ctx *ctx, int slot, long max_sweeps, double t_end, long *sweeps, long *moves, bool *late, M2Kind kind = M2_FULL)
+// launches of m2_launch_select and the family's apply, four sweeps between looks at the control block (looks::drive)
+static int m2_run(tspgpu_ctx *ctx, int slot, long max_sweeps, double t_end, long *sweeps, long *moves, bool *late, const M2Family &F)
 {
     M2Ctl C;
     memset(&C, 0, sizeof C);
     *late = false;
     if (sweeps) *sweeps = 0;
     if (moves) *moves = 0;
-    m2_record(ctx, C, kind);
+    m2_record(ctx, C, F);
     if (max_sweeps == 0) return E_OK;
     int rc = m2_arm(ctx, slot, max_sweeps);
     if (rc) return rc;
     const SweepGeom P = m2_plan(ctx);
-    for (;;) {
-        if (t_end >= 0 && now_s() >= t_end) { *late = true; break; }
-        const int K = t_end >= 0 ? 1 : 4;
-        for (int i = 0; i < K; i++) {
-            if ((rc = m2_launch_select(ctx, slot, P, true, kind))) return rc;
-            if ((rc = m2_launch_apply(ctx, slot, kind))) return rc;
-        }
-        if ((rc = ctl_get(ctx, &C, ctx->d_m2.p))) return rc;
-        if (C.stop) break;
-    }
-    if (*late && (rc = ctl_get(ctx, &C, ctx->d_m2.p))) return rc;
+    const looks::Result r = looks::drive(
+        now_s, t_end, 4,
+        [&] { const int e = m2_launch_select(ctx, slot, P, true, F); return e ? e : F.apply(ctx, slot); },
+        [&] { const int e = ctl_get(ctx, &C, ctx->d_m2.p); return e ? e : C.stop ? (int)looks::STOP : (int)looks::GO_ON; });
+    if (r.code) return r.code;
+    *late = r.late;
+    if (r.late && (rc = ctl_get(ctx, &C, ctx->d_m2.p))) return rc;
     if (sweeps) *sweeps = (long)C.sweeps;
     if (moves) *moves = (long)C.moves;
-    m2_record(ctx, C, kind);
+    m2_record(ctx, C, F);
     return E_OK;
 }
 
@@ -6425,7 +6421,8 @@ extern "C" {
 int tspgpu_tour_two_opt_multi(tspgpu_ctx *ctx, int slot, long max_sweeps, double time_left_s, long *sweeps, long *moves)
 {
     if (!ctx) return E_UNAVAILABLE;
-    return with_slot(ctx, slot, m2_check, [&](bool *late) { return m2_run(ctx, slot, max_sweeps, deadline_of(time_left_s), sweeps, moves, late); });
+    return with_slot(ctx, slot, m2_check,
+                     [&](bool *late) { return m2_run(ctx, slot, max_sweeps, deadline_of(time_left_s), sweeps, moves, late, M2_FULL); });
 }
 
 int tspgpu_two_opt_multi(tspgpu_ctx *ctx, int *path, double *cost, double time_left_s, long *sweeps, long *moves)
@@ -6433,50 +6430,37 @@ int tspgpu_two_opt_multi(tspgpu_ctx *ctx, int *path, double *cost, double time_l
     if (!ctx) return E_UNAVAILABLE;
     if (!path || !cost) return fail(ctx, E_INVALID, "null argument");
     return with_host_tour(ctx, path, cost, false, m2_check,
-                          [&](bool *late) { return m2_run(ctx, 0, -1, deadline_of(time_left_s), sweeps, moves, late); });
+                          [&](bool *late) { return m2_run(ctx, 0, -1, deadline_of(time_left_s), sweeps, moves, late, M2_FULL); });
 }
 
 } // extern "C"
 
-static int nl_check(tspgpu_ctx *ctx);
-static int ornl_check(tspgpu_ctx *ctx);
-static int nl3_check(tspgpu_ctx *ctx);
-static int m2_kind_check(tspgpu_ctx *ctx, M2Kind kind)
-{
-    return kind == M2_NL3 ? nl3_check(ctx) : kind == M2_ORNL ? ornl_check(ctx) : kind == M2_NL ? nl_check(ctx) : m2_check(ctx);
-}
-
-// one sweep on a host tour (tspgpu_two_opt_multi_once, tspgpu_two_opt_nl_once: moves_ab holds a, b per move;
-// tspgpu_or_opt_nl_once: s, L, q, rev per move; tspgpu_three_opt_nl_once: i, j, k, kind per move)
-static int m2_once(tspgpu_ctx *ctx, int *path, double *cost, int *nmoves, int *moves_ab, double *deltas, int cap, M2Kind kind)
+// one sweep of family F on a host tour, `F.ints` ints per move in `moves` (tspgpu_two_opt_multi_once, tspgpu_two_opt_nl_once,
+// tspgpu_or_opt_nl_once, tspgpu_three_opt_nl_once)
+static int m2_once(tspgpu_ctx *ctx, int *path, double *cost, int *nmoves, int *moves, double *deltas, int cap, const M2Family &F)
 {
     if (!ctx) return E_UNAVAILABLE;
-    if (!path || !cost || cap < 0 || (cap > 0 && (!moves_ab || !deltas))) return fail(ctx, E_INVALID, "bad argument");
+    if (!path || !cost || cap < 0 || (cap > 0 && (!moves || !deltas))) return fail(ctx, E_INVALID, "bad argument");
     hipSetDevice(ctx->device);
-    int rc = m2_kind_check(ctx, kind);
+    int rc = F.check(ctx);
     if (rc) return rc;
     if ((rc = load_path(ctx, 0, path, -1))) return rc;
     HIP_TRY(hipMemcpyAsync(ctx->S.cost, cost, 8, hipMemcpyHostToDevice, ctx->stream));     // the caller's running cost, as ref_2opt_once
     if ((rc = m2_arm(ctx, 0, 1))) return rc;
-    if ((rc = m2_launch_select(ctx, 0, m2_plan(ctx), true, kind))) return rc;
+    if ((rc = m2_launch_select(ctx, 0, m2_plan(ctx), true, F))) return rc;
     // the accepted list comes back before anything is applied: a list longer than `cap` leaves the tour as it is
     M2Ctl C;
     if ((rc = ctl_get(ctx, &C, ctx->d_m2.p))) return rc;
     const size_t m = (size_t)C.m;
-    std::vector<int> acc(m), a(m), b(m), ri, rk, rjk;
+    M2Moves L;
+    L.a.resize(m); L.b.resize(m);
+    std::vector<int> acc(m);
     std::vector<double> d(m);
-    if (m && kind == M2_NL3) {              // the range and (j, kind) of every candidate, while the tour still stands
-        ri.resize(m); rk.resize(m); rjk.resize(m);
-        hipLaunchKernelGGL(k_nl3_describe, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, ctx->S, ctx->n, 0, ctx->nl, ctx->m2, ctx->d_m2);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(ri.data(), ctx->m2.i, m * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(rk.data(), ctx->m2.j, m * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(rjk.data(), ctx->m2.raw_b, m * 4, hipMemcpyDeviceToHost, ctx->stream));
-    }
     if (m) {
+        if (F.describe && (rc = F.describe(ctx, m, L))) return rc;
         HIP_TRY(hipMemcpyAsync(acc.data(), ctx->m2.acc, m * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(a.data(), ctx->m2.a, m * 4, hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipMemcpyAsync(b.data(), ctx->m2.b, m * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(L.a.data(), ctx->m2.a, m * 4, hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(L.b.data(), ctx->m2.b, m * 4, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipMemcpyAsync(d.data(), ctx->m2.d, m * 8, hipMemcpyDeviceToHost, ctx->stream));
         HIP_TRY(hipStreamSynchronize(ctx->stream));
     }
@@ -6486,44 +6470,36 @@ static int m2_once(tspgpu_ctx *ctx, int *path, double *cost, int *nmoves, int *m
         return fail(ctx, E_EXHAUSTED, "the sweep accepts %d moves, the caller's arrays hold %d: nothing was applied", (int)idx.size(), cap);
     std::sort(idx.begin(), idx.end(), [&](int x, int y) {
         if (d[x] != d[y]) return d[x] < d[y];
-        const int lx = std::min(a[x], b[x]), ly = std::min(a[y], b[y]);
-        return lx != ly ? lx < ly : std::max(a[x], b[x]) < std::max(a[y], b[y]);
+        const int lx = std::min(L.a[x], L.b[x]), ly = std::min(L.a[y], L.b[y]);
+        return lx != ly ? lx < ly : std::max(L.a[x], L.b[x]) < std::max(L.a[y], L.b[y]);
     });
     for (size_t k = 0; k < idx.size(); k++) {
-        const int x = idx[k];
-        deltas[k] = d[x];
-        if (kind == M2_NL3) {               // a = t1 < b = the code: the order above is (delta, t1, code)
-            moves_ab[4 * k] = ri[x]; moves_ab[4 * k + 1] = rjk[x] >> 2; moves_ab[4 * k + 2] = rk[x]; moves_ab[4 * k + 3] = rjk[x] & 3;
-        } else if (kind == M2_ORNL) {       // a = s < b = the packed (L, q, rev): the order above is (delta, s, L, q, rev)
-            moves_ab[4 * k] = a[x]; moves_ab[4 * k + 1] = b[x] >> ORNL_LSHIFT;
-            moves_ab[4 * k + 2] = (b[x] >> 1) & (int)OR_QM; moves_ab[4 * k + 3] = b[x] & 1;
-        } else {
-            moves_ab[2 * k] = a[x]; moves_ab[2 * k + 1] = b[x];
-        }
+        deltas[k] = d[idx[k]];
+        F.put(moves + (size_t)F.ints * k, L, idx[k]);
     }
     if (nmoves) *nmoves = (int)idx.size();
-    if ((rc = m2_launch_apply(ctx, 0, kind))) return rc;
+    if ((rc = F.apply(ctx, 0))) return rc;
     if ((rc = store_path(ctx, 0, path, cost, nullptr))) return rc;
     if ((rc = ctl_get(ctx, &C, ctx->d_m2.p))) return rc;
-    m2_record(ctx, C, kind);
+    m2_record(ctx, C, F);
     return E_OK;
 }
 
 // the candidate sweep and the selection `reps` times, nothing applied (tspgpu_time_multi_sweep, tspgpu_time_nl_sweep,
 // tspgpu_time_or_nl_sweep, tspgpu_time_three_nl_sweep)
-static int m2_time(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean, M2Kind kind)
+static int m2_time(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean, const M2Family &F)
 {
     if (!ctx) return E_UNAVAILABLE;
     if (!ms_mean || reps <= 0) return fail(ctx, E_INVALID, "bad argument");
     hipSetDevice(ctx->device);
-    int rc = m2_kind_check(ctx, kind);
+    int rc = F.check(ctx);
     if (rc) return rc;
     if ((rc = need_slot(ctx, slot))) return rc;
     HIP_TRY(hipMemsetAsync(ctx->d_m2, 0, sizeof(M2Ctl), ctx->stream));
     const SweepGeom P = m2_plan(ctx);
     // warm: in matrix-free mode with its gather; the timed launches go without
-    return time_launches(ctx, reps, [&] { return m2_launch_select(ctx, slot, P, true, kind); },
-                         [&] { return m2_launch_select(ctx, slot, P, false, kind); }, ms_mean);
+    return time_launches(ctx, reps, [&] { return m2_launch_select(ctx, slot, P, true, F); },
+                         [&] { return m2_launch_select(ctx, slot, P, false, F); }, ms_mean);
 }
 
 extern "C" {
@@ -6553,21 +6529,18 @@ static int nl_check(tspgpu_ctx *ctx)
     return E_OK;
 }
 
-static int nl_launch_sweep(tspgpu_ctx *ctx, int slot)
+static int nl_launch_sweep(tspgpu_ctx *ctx, int slot, const SweepGeom &, bool)
 {
-    const int n = ctx->n;
-    const dim3 grid((n + NL_NODES - 1) / NL_NODES), block(NL_NODES * 32);
-    const M2Ctl *ctl = ctx->d_m2;
-    if (ctx->otf)
-        kind_switch(ctx, [&](auto kind, auto *pts, auto *) {
-            hipLaunchKernelGGL((k_nl_sweep_otf<kind()>), grid, block, 0, ctx->stream, ctx->S, pts, n, slot, ctx->nl, ctx->m2, ctl);
-        });
-    else
-        ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_nl_sweep<T>), grid, block, 0, ctx->stream, ctx->S, (const T *)ctx->d_mat.p, n, ctx->ld, slot,
-                                                     ctx->nl, ctx->m2, ctl));
+    const dim3 grid((ctx->n + NL_NODES - 1) / NL_NODES), block(NL_NODES * 32);
+    LAUNCH_BY_COST(k_nl_sweep, grid, block, slot, ctx->nl, ctx->m2, (const M2Ctl *)ctx->d_m2);
     HIP_TRY(hipGetLastError());
     return E_OK;
 }
+
+// the lists' 2-opt pairs: compaction, apply and move layout are the full family's.  (A phase's polish is counted behind it,
+// tspgpu_two_opt_nl: until then the phase has none)
+static const M2Family M2_NL = {nl_check, nl_launch_sweep, m2_compact_pairs, m2_apply_pairs, 2, nullptr, m2_put_pair, &tspgpu_ctx::nl_count,
+                               &tspgpu_ctx::nl_polish_sweeps};
 
 extern "C" {
 
@@ -6647,7 +6620,7 @@ int tspgpu_two_opt_nl(tspgpu_ctx *ctx, int *path, double *cost, double time_left
         int rc = m2_run(ctx, 0, -1, t_end, sweeps, moves, late, M2_NL);
         if (rc) return rc;
         if (polish && !*late) {                 // the parallel-move descent goes on from the slot as it stands
-            if ((rc = m2_run(ctx, 0, -1, t_end, &ps, &pm, late))) return rc;
+            if ((rc = m2_run(ctx, 0, -1, t_end, &ps, &pm, late, M2_FULL))) return rc;
             ctx->nl_polish_sweeps = ps;
         }
         if (polish_sweeps) *polish_sweeps = ps;
@@ -6675,35 +6648,36 @@ static int ornl_check(tspgpu_ctx *ctx)
     return nl_check(ctx);
 }
 
-static int ornl_launch_sweep(tspgpu_ctx *ctx, int slot)
+static int ornl_launch_sweep(tspgpu_ctx *ctx, int slot, const SweepGeom &, bool)
 {
-    const int n = ctx->n;
-    const dim3 grid((n + ORNL_STARTS - 1) / ORNL_STARTS), block(ORNL_STARTS * 64);
-    const M2Ctl *ctl = ctx->d_m2;
-    if (ctx->otf)
-        kind_switch(ctx, [&](auto kind, auto *pts, auto *) {
-            hipLaunchKernelGGL((k_ornl_sweep_otf<kind()>), grid, block, 0, ctx->stream, ctx->S, pts, n, slot, ctx->nl, ctx->m2, ctl);
-        });
-    else
-        ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_ornl_sweep<T>), grid, block, 0, ctx->stream, ctx->S, (const T *)ctx->d_mat.p, n, ctx->ld, slot,
-                                                     ctx->nl, ctx->m2, ctl));
+    const dim3 grid((ctx->n + ORNL_STARTS - 1) / ORNL_STARTS), block(ORNL_STARTS * 64);
+    LAUNCH_BY_COST(k_ornl_sweep, grid, block, slot, ctx->nl, ctx->m2, (const M2Ctl *)ctx->d_m2);
     HIP_TRY(hipGetLastError());
     return E_OK;
 }
 
 static int ornl_launch_apply(tspgpu_ctx *ctx, int slot)
 {
-    const int n = ctx->n, G = std::min(M2_APPLY_WGS, (n + 1) / 2);
-    if (ctx->otf)
-        kind_switch(ctx, [&](auto kind, auto *pts, auto *) {
-            hipLaunchKernelGGL((k_ornl_apply_otf<kind()>), dim3(G), dim3(ORNL_APPLY_BT), 0, ctx->stream, ctx->S, pts, n, slot, ctx->m2, ctx->d_m2);
-        });
-    else
-        ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_ornl_apply<T>), dim3(G), dim3(ORNL_APPLY_BT), 0, ctx->stream, ctx->S,
-                                                     (const T *)ctx->d_mat.p, n, ctx->ld, slot, ctx->m2, ctx->d_m2));
+    const int G = std::min(M2_APPLY_WGS, (ctx->n + 1) / 2);
+    LAUNCH_BY_COST(k_ornl_apply, dim3(G), dim3(ORNL_APPLY_BT), slot, ctx->m2, ctx->d_m2);
     HIP_TRY(hipGetLastError());
     return E_OK;
 }
+
+static void ornl_launch_compact(tspgpu_ctx *ctx, int slot)
+{
+    hipLaunchKernelGGL(k_ornl_compact, dim3(1), dim3(1024), 0, ctx->stream, ctx->S, ctx->n, slot, ctx->m2, ctx->d_m2);
+}
+
+// s, L, q, rev of a = s < b = the packed (L, q, rev): m2_once's order (delta, a, b) is (delta, s, L, q, rev)
+static void ornl_put(int *out, const M2Moves &L, int x)
+{
+    const int b = L.b[x];
+    out[0] = L.a[x]; out[1] = b >> ORNL_LSHIFT; out[2] = (b >> 1) & (int)OR_QM; out[3] = b & 1;
+}
+
+static const M2Family M2_ORNL = {ornl_check, ornl_launch_sweep, ornl_launch_compact, ornl_launch_apply, 4, nullptr, ornl_put, &tspgpu_ctx::ornl_count,
+                                 nullptr};
 
 // the descent of tspgpu_local_search_nl on a slot: { neighbour-list 2-opt to its end; neighbour-list Or-opt until a sweep accepts
 // nothing } until an Or-opt phase applies nothing
@@ -6714,17 +6688,17 @@ static int ornl_descent(tspgpu_ctx *ctx, int slot, double time_left_s, Descent *
     long mk = 0;
     int rc = E_OK;
     *late = false;
-    ctx->ornl_sweeps = ctx->ornl_moves = ctx->ornl_max_k = 0;
+    ctx->ornl_count = M2Counters{};
     for (;;) {
         long s = 0, m = 0;
         if ((rc = m2_run(ctx, slot, -1, t_end, &s, &m, late, M2_NL))) break;
         D.tw += s; D.tm += m; D.nr++;
         if (*late) break;
         if ((rc = m2_run(ctx, slot, -1, t_end, &s, &m, late, M2_ORNL))) break;
-        D.os += s; D.om += m; mk = std::max(mk, ctx->ornl_max_k);
+        D.os += s; D.om += m; mk = std::max(mk, ctx->ornl_count.max_k);
         if (*late || m == 0) break;
     }
-    ctx->ornl_sweeps = D.os; ctx->ornl_moves = D.om; ctx->ornl_max_k = mk; ctx->ornl_rounds = D.nr;
+    ctx->ornl_count = M2Counters{D.os, D.om, mk}; ctx->ornl_rounds = D.nr;
     *out = D;
     return rc;
 }
@@ -6797,35 +6771,47 @@ static int nl3_check(tspgpu_ctx *ctx)
     return E_OK;
 }
 
-static int nl3_launch_sweep(tspgpu_ctx *ctx, int slot)
+static int nl3_launch_sweep(tspgpu_ctx *ctx, int slot, const SweepGeom &, bool)
 {
-    const int n = ctx->n, W = ctx->nl3_w;
-    const dim3 grid((n + NL3_NODES - 1) / NL3_NODES), block(NL3_NODES * 64);
-    const M2Ctl *ctl = ctx->d_m2;
-    if (ctx->otf)
-        kind_switch(ctx, [&](auto kind, auto *pts, auto *) {
-            hipLaunchKernelGGL((k_nl3_sweep_otf<kind()>), grid, block, 0, ctx->stream, ctx->S, pts, n, slot, ctx->nl, W, ctx->m2, ctl);
-        });
-    else
-        ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_nl3_sweep<T>), grid, block, 0, ctx->stream, ctx->S, (const T *)ctx->d_mat.p, n, ctx->ld, slot,
-                                                     ctx->nl, W, ctx->m2, ctl));
+    const dim3 grid((ctx->n + NL3_NODES - 1) / NL3_NODES), block(NL3_NODES * 64);
+    LAUNCH_BY_COST(k_nl3_sweep, grid, block, slot, ctx->nl, ctx->nl3_w, ctx->m2, (const M2Ctl *)ctx->d_m2);
     HIP_TRY(hipGetLastError());
     return E_OK;
 }
 
 static int nl3_launch_apply(tspgpu_ctx *ctx, int slot)
 {
-    const int n = ctx->n, G = std::min(M2_APPLY_WGS, (n + 2) / 3);     // a range holds three positions at least
-    if (ctx->otf)
-        kind_switch(ctx, [&](auto kind, auto *pts, auto *) {
-            hipLaunchKernelGGL((k_nl3_apply_otf<kind()>), dim3(G), dim3(NL3_APPLY_BT), 0, ctx->stream, ctx->S, pts, n, slot, ctx->nl, ctx->m2, ctx->d_m2);
-        });
-    else
-        ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_nl3_apply<T>), dim3(G), dim3(NL3_APPLY_BT), 0, ctx->stream, ctx->S,
-                                                     (const T *)ctx->d_mat.p, n, ctx->ld, slot, ctx->nl, ctx->m2, ctx->d_m2));
+    const int G = std::min(M2_APPLY_WGS, (ctx->n + 2) / 3);     // a range holds three positions at least
+    LAUNCH_BY_COST(k_nl3_apply, dim3(G), dim3(NL3_APPLY_BT), slot, ctx->nl, ctx->m2, ctx->d_m2);
     HIP_TRY(hipGetLastError());
     return E_OK;
 }
+
+static void nl3_launch_compact(tspgpu_ctx *ctx, int slot)
+{
+    hipLaunchKernelGGL(k_nl3_compact, dim3(1), dim3(1024), 0, ctx->stream, ctx->S, ctx->n, slot, ctx->nl, ctx->m2, ctx->d_m2);
+}
+
+// the range and (j, kind) of every candidate of slot 0, while the tour still stands
+static int nl3_describe(tspgpu_ctx *ctx, size_t m, M2Moves &L)
+{
+    L.i.resize(m); L.j.resize(m); L.jk.resize(m);
+    hipLaunchKernelGGL(k_nl3_describe, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, ctx->S, ctx->n, 0, ctx->nl, ctx->m2, ctx->d_m2);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(L.i.data(), ctx->m2.i, m * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(L.j.data(), ctx->m2.j, m * 4, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(L.jk.data(), ctx->m2.raw_b, m * 4, hipMemcpyDeviceToHost, ctx->stream));
+    return E_OK;
+}
+
+// i, j, k, kind of a = t1 < b = the code: m2_once's order (delta, a, b) is (delta, t1, code)
+static void nl3_put(int *out, const M2Moves &L, int x)
+{
+    out[0] = L.i[x]; out[1] = L.jk[x] >> 2; out[2] = L.j[x]; out[3] = L.jk[x] & 3;
+}
+
+static const M2Family M2_NL3 = {nl3_check, nl3_launch_sweep, nl3_launch_compact, nl3_launch_apply, 4, nl3_describe, nl3_put, &tspgpu_ctx::nl3_count,
+                                nullptr};
 
 struct Descent3 { long ts = 0, tm = 0; int np = 0; };
 
@@ -6839,19 +6825,19 @@ static int nl3_descent(tspgpu_ctx *ctx, int slot, double time_left_s, Descent *o
     long mk = 0, omk = 0;
     int rc = E_OK;
     *late = false;
-    ctx->nl3_sweeps = ctx->nl3_moves = ctx->nl3_max_k = 0;
+    ctx->nl3_count = M2Counters{};
     for (;;) {
         Descent d;
         rc = ornl_descent(ctx, slot, t_end >= 0 ? std::max(0.0, t_end - now_s()) : -1.0, &d, late);
-        D += d; omk = std::max(omk, ctx->ornl_max_k);
+        D += d; omk = std::max(omk, ctx->ornl_count.max_k);
         if (rc || *late) break;
         long s = 0, m = 0;
         if ((rc = m2_run(ctx, slot, -1, t_end, &s, &m, late, M2_NL3))) break;
-        D3.ts += s; D3.tm += m; D3.np++; mk = std::max(mk, ctx->nl3_max_k);
+        D3.ts += s; D3.tm += m; D3.np++; mk = std::max(mk, ctx->nl3_count.max_k);
         if (*late || m == 0) break;
     }
-    ctx->ornl_sweeps = D.os; ctx->ornl_moves = D.om; ctx->ornl_max_k = omk; ctx->ornl_rounds = D.nr;
-    ctx->nl3_sweeps = D3.ts; ctx->nl3_moves = D3.tm; ctx->nl3_max_k = mk; ctx->nl3_phases = D3.np;
+    ctx->ornl_count = M2Counters{D.os, D.om, omk}; ctx->ornl_rounds = D.nr;
+    ctx->nl3_count = M2Counters{D3.ts, D3.tm, mk}; ctx->nl3_phases = D3.np;
     *out = D; *out3 = D3;
     return rc;
 }
@@ -7001,21 +6987,14 @@ static int nlb_descent(tspgpu_ctx *ctx, int slot0, int count, double time_left_s
     std::vector<int> live((size_t)count);
     for (int i = 0; i < count; i++) live[i] = slot0 + i;
     if ((rc = set_live(ctx, live))) return rc;
-    while (!live.empty()) {
-        if (t_end >= 0 && now_s() >= t_end) { *late = true; break; }
-        const int K = t_end >= 0 ? 1 : 4;
-        ctx->nlb_max_live = std::max(ctx->nlb_max_live, (long)live.size());
-        for (int i = 0; i < K; i++) {
-            if ((rc = nlb_launch_sweep(ctx, slot0, (int)live.size()))) return rc;
-            ctx->nlb_launches++;
-        }
-        if ((rc = ctl_get(ctx, hc.data(), ctx->d_nlb_ctl, (size_t)count))) return rc;
-        size_t k = 0;
-        for (int t : live) if (!hc[t - slot0].stop) live[k++] = t;
-        if (k == live.size()) continue;
-        live.resize(k);
-        if (k && (rc = set_live(ctx, live))) return rc;
-    }
+    const looks::Result r = looks::drive_live(
+        now_s, t_end, 4, live, [](int) {},
+        [&](int len) { const int e = nlb_launch_sweep(ctx, slot0, len); ctx->nlb_launches += !e; return e; },
+        [&] { return ctl_get(ctx, hc.data(), ctx->d_nlb_ctl, (size_t)count); }, [&](int t) { return hc[t - slot0].stop != 0; },
+        [&](const std::vector<int> &list) { return set_live(ctx, list); });
+    ctx->nlb_max_live = r.max_live;
+    if (r.code) return r.code;
+    *late = r.late;
     for (int i = 0; i < count; i++) {
         D[i].tw = (long)hc[i].two_opt_sweeps; D[i].tm = (long)hc[i].two_opt_moves;
         D[i].os = (long)hc[i].or_sweeps; D[i].om = (long)hc[i].or_moves; D[i].nr = hc[i].rounds;
@@ -7143,25 +7122,19 @@ static int nlv_walks(tspgpu_ctx *ctx, int walks, int k, double time_left_s, int 
     HIP_TRY(hipMemcpyAsync(ctx->d_nlv_ctl, hv.data(), W * sizeof(NlvCtl), hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));             // (the copies read pageable memory of this call)
 
-    bool late = false;
     if (!live.empty() && (rc = set_live(ctx, live))) return rc;
-    while (!live.empty()) {
-        if (t_end >= 0 && now_s() >= t_end) { late = true; break; }
-        const int K = t_end >= 0 ? 1 : 4;
-        ctx->nlv_max_live = std::max(ctx->nlv_max_live, (long)live.size());
-        for (int i = 0; i < K; i++) {
-            if ((rc = nlb_launch_sweep(ctx, 0, (int)live.size()))) return rc;
-            if ((rc = nlv_launch_step(ctx, (int)live.size(), trace != nullptr))) return rc;
-            ctx->nlv_rounds++;
-        }
-        HIP_TRY(hipMemcpyAsync(hv.data(), ctx->d_nlv_ctl, W * sizeof(NlvCtl), hipMemcpyDeviceToHost, ctx->stream));
-        HIP_TRY(hipStreamSynchronize(ctx->stream));
-        size_t m = 0;
-        for (int t : live) if (!hv[t].halt) live[m++] = t;
-        if (m == live.size()) continue;
-        live.resize(m);
-        if (m && (rc = set_live(ctx, live))) return rc;
-    }
+    const looks::Result r = looks::drive_live(
+        now_s, t_end, 4, live, [](int) {},
+        [&](int len) {
+            int e = nlb_launch_sweep(ctx, 0, len);
+            if (!e && !(e = nlv_launch_step(ctx, len, trace != nullptr))) ctx->nlv_rounds++;
+            return e;
+        },
+        [&] { return ctl_get(ctx, hv.data(), ctx->d_nlv_ctl, W); }, [&](int w) { return hv[w].halt != 0; },
+        [&](const std::vector<int> &list) { return set_live(ctx, list); });
+    ctx->nlv_max_live = r.max_live;
+    if (r.code) return r.code;
+    const bool late = r.late;
 
     std::vector<double> tr(trace ? W * (size_t)k : 0);
     HIP_TRY(hipMemcpyAsync(hc.data(), ctx->d_nlb_ctl, W * sizeof(NlbCtl), hipMemcpyDeviceToHost, ctx->stream));

@@ -192,10 +192,12 @@ __global__ void __launch_bounds__(256) k_m2_sweep_otf(Tours S, const typename Or
     }
 }
 
-// one workgroup of 1024 threads; thread k owns the nodes [k C, k C + C)
-// (the body, for the control block of a single descent or of a tour of a batch: tspgpu_nlbatch.inc; cnts: [1024] in LDS)
-template <typename CTL>
-__device__ __forceinline__ void m2_compact_tour(const Tours &S, int n, int t, const M2Buf &B, CTL *ctl, int *cnts)
+// The counted scan of every family's compaction.  One workgroup of 1024 threads; thread k owns the nodes [k C, k C + C), counts
+// those that are valid(node), and after an inclusive scan over cnts ([1024] in LDS) calls emit(node, at) for each of them with
+// its place in the list: node order, the same in every run.  valid runs twice per node.  ctl->m := the length of the list, 0
+// once `stop` is up.  For the control block of a single descent or of a tour of a batch (tspgpu_nlbatch.inc)
+template <typename CTL, typename Valid, typename Emit>
+__device__ __forceinline__ void m2_counted_scan(int n, CTL *ctl, int *cnts, Valid valid, Emit emit)
 {
     const int tid = threadIdx.x;
     if (ctl->stop) {
@@ -203,10 +205,6 @@ __device__ __forceinline__ void m2_compact_tour(const Tours &S, int n, int t, co
         return;
     }
     const int C = (n + 1023) / 1024, a0 = min(n, tid * C), a1 = min(n, a0 + C);
-    auto valid = [&](int a) {
-        const int b = B.raw_b[a];
-        return b >= 0 && B.raw_d[a] < TWO_OPT_EPS && !(B.raw_b[b] == a && b < a);   // mutual choice: the same pair, the same delta
-    };
     int c = 0;
     for (int a = a0; a < a1; a++) c += valid(a) ? 1 : 0;
     cnts[tid] = c;
@@ -218,24 +216,37 @@ __device__ __forceinline__ void m2_compact_tour(const Tours &S, int n, int t, co
         __syncthreads();
     }
     int at = cnts[tid] - c;
+    for (int a = a0; a < a1; a++)
+        if (valid(a)) emit(a, at++);
+    if (tid == 1023) ctl->m = cnts[1023];
+}
+
+// the improving candidates, once per pair, with their ranges from pos, dir and pos[0].  (dir and pos[0] are read in front of
+// the scan's `stop` test, here and in the other two callers: a few loads of valid slot memory that a stopped tour does not need)
+template <typename CTL>
+__device__ __forceinline__ void m2_compact_tour(const Tours &S, int n, int t, const M2Buf &B, CTL *ctl, int *cnts)
+{
     const int *pos = S.pos + (size_t)t * n;
     const int dir = S.dir[t];
     const int f0 = dir > 0 ? pos[0] : n - 1 - pos[0];
-    for (int a = a0; a < a1; a++) {
-        if (!valid(a)) continue;
-        const int b = B.raw_b[a];
-        int pa = (dir > 0 ? pos[a] : n - 1 - pos[a]) - f0, pb = (dir > 0 ? pos[b] : n - 1 - pos[b]) - f0;
-        if (pa < 0) pa += n;
-        if (pb < 0) pb += n;
-        const bool ab = pa < pb;
-        B.d[at] = B.raw_d[a];
-        B.a[at] = ab ? a : b;
-        B.b[at] = ab ? b : a;
-        B.i[at] = ab ? pa : pb;
-        B.j[at] = ab ? pb : pa;
-        at++;
-    }
-    if (tid == 1023) ctl->m = cnts[1023];
+    m2_counted_scan(
+        n, ctl, cnts,
+        [&](int a) {
+            const int b = B.raw_b[a];
+            return b >= 0 && B.raw_d[a] < TWO_OPT_EPS && !(B.raw_b[b] == a && b < a);   // mutual choice: the same pair, the same delta
+        },
+        [&](int a, int at) {
+            const int b = B.raw_b[a];
+            int pa = (dir > 0 ? pos[a] : n - 1 - pos[a]) - f0, pb = (dir > 0 ? pos[b] : n - 1 - pos[b]) - f0;
+            if (pa < 0) pa += n;
+            if (pb < 0) pb += n;
+            const bool ab = pa < pb;
+            B.d[at] = B.raw_d[a];
+            B.a[at] = ab ? a : b;
+            B.b[at] = ab ? b : a;
+            B.i[at] = ab ? pa : pb;
+            B.j[at] = ab ? pb : pa;
+        });
 }
 
 __global__ void __launch_bounds__(1024) k_m2_compact(Tours S, int n, int t, M2Buf B, M2Ctl *ctl)
@@ -311,28 +322,37 @@ __device__ __forceinline__ void m2_reverse_cells(int *ord, int *pos, AT *dp, int
     }
 }
 
+// Workgroup 0's part of every family's apply launch, by BT <= 256 threads: sum, minimum and count of the m candidates' accepted
+// deltas -- strided per thread, then a halving tree of fixed shape, so the double sum is the same in every run -- and the
+// close of the sweep.  false: `stop` is up, the launch has nothing to do
+template <typename CTL>
+__device__ __forceinline__ bool m2_sum_close(const Tours &S, int t, const M2Buf &B, CTL *ctl, int m, int BT)
+{
+    __shared__ double rs[256], rm[256];
+    __shared__ int rk[256];
+    const int tid = threadIdx.x;
+    if (ctl->stop) return false;
+    double s = 0.0, mn = 0.0;
+    int k = 0;
+    for (int x = tid; x < m; x += BT)
+        if (B.acc[x]) { const double d = B.d[x]; s += d; mn = fmin(mn, d); k++; }
+    rs[tid] = s; rm[tid] = mn; rk[tid] = k;
+    __syncthreads();
+    for (int off = BT >> 1; off > 0; off >>= 1) {
+        if (tid < off) { rs[tid] += rs[tid + off]; rm[tid] = fmin(rm[tid], rm[tid + off]); rk[tid] += rk[tid + off]; }
+        __syncthreads();
+    }
+    if (tid == 0) m2_close(S, t, ctl, rs[0], rm[0], rk[0]);
+    return true;
+}
+
 template <typename T, typename CS, typename CTL>
 __device__ __forceinline__ void m2_apply_tour(const Tours &S, const CS cs, int n, int t, const M2Buf &B, CTL *ctl)
 {
     typedef typename Elem<T>::acc AT;
-    __shared__ double rs[256], rm[256];
-    __shared__ int rk[256];
     const int tid = threadIdx.x, BT = blockDim.x;
     const int m = ctl->m;                   // (0 once `stop` is up: k_m2_compact)
-    if (blockIdx.x == 0) {
-        if (ctl->stop) return;
-        double s = 0.0, mn = 0.0;
-        int k = 0;
-        for (int x = tid; x < m; x += BT)
-            if (B.acc[x]) { const double d = B.d[x]; s += d; mn = fmin(mn, d); k++; }
-        rs[tid] = s; rm[tid] = mn; rk[tid] = k;
-        __syncthreads();
-        for (int off = BT >> 1; off > 0; off >>= 1) {
-            if (tid < off) { rs[tid] += rs[tid + off]; rm[tid] = fmin(rm[tid], rm[tid + off]); rk[tid] += rk[tid + off]; }
-            __syncthreads();
-        }
-        if (tid == 0) m2_close(S, t, ctl, rs[0], rm[0], rk[0]);
-    }
+    if (blockIdx.x == 0 && !m2_sum_close(S, t, B, ctl, m, BT)) return;
     int *ord = S.ord + (size_t)t * n, *pos = S.pos + (size_t)t * n, *succ = S.succ + (size_t)t * n;
     AT *dp = dpos_of<AT>(S, t, n), *dnb = dnb_of<AT>(S, t, n);
     const int dir = S.dir[t];

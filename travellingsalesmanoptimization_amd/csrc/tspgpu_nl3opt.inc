@@ -2,7 +2,7 @@
 // Neighbour-list 3-opt: the pure 3-opt moves (segment insertion of any length, the double reversal and the two mixed forms)
 // whose new edges come from the K-nearest-neighbour lists, and every accepted move of a sweep applied in one launch.
 // Included by tspgpu.hip behind tspgpu_ornl.inc (uses Tours, Elem, wave_argmin, key_better, or_cell / or_ecell, OrMatCost /
-// OrPtsCost, M2Buf, M2Ctl, NlBuf, m2_close, m2_reverse_cells, k_m2_select).  The rule is in include/tspgpu.h
+// OrPtsCost, M2Buf, M2Ctl, NlBuf, m2_counted_scan, m2_sum_close, m2_reverse_cells, k_m2_select).  The rule is in include/tspgpu.h
 // ("Neighbour-list 3-opt") and DESIGN 4.19; conflict and selection are those of tspgpu_multi2opt.inc.
 //
 // A candidate is a chain t1 .. t6: the tour edges {t1,t2}, {t3,t4}, {t5,t6} go, {t2,t3}, {t4,t5}, {t6,t1} come; t3 is among
@@ -17,7 +17,7 @@
 //                                   source; succ and pred come from pos, ord and dir.  The kind test runs only for a chain
 //                                   that would beat the lane's best so far.  A DPP argmin by (delta, code) leaves
 //                                   raw_d[t1] / raw_b[t1].  No LDS.
-//   k_nl3_compact                   one workgroup: the counted scan of k_ornl_compact; the chain of (t1, code) is decoded to
+//   k_nl3_compact                   one workgroup: m2_counted_scan over the improving nodes; the chain of (t1, code) is decoded to
 //                                   its three edge positions, counted from node 0 in the slot's direction.
 //   k_m2_select                     unchanged.
 //   k_nl3_apply / k_nl3_apply_otf   workgroup per accepted move (grid-stride).  The chain is decoded again; the new order of
@@ -163,41 +163,22 @@ __global__ void __launch_bounds__(256) k_nl3_sweep_otf(Tours S, const typename O
     nl3_sweep_node<int>(S, OrPtsCost<KIND>{pts}, n, t, NL, W, B);
 }
 
-// one workgroup of 1024 threads; thread k owns the nodes [k C, k C + C) (the scan of ornl_compact_tour; cnts: [1024] in LDS)
+// the improving candidates through m2_counted_scan, with the ranges of their decoded chains
 __global__ void __launch_bounds__(1024) k_nl3_compact(Tours S, int n, int t, NlBuf NL, M2Buf B, M2Ctl *ctl)
 {
     __shared__ int cnts[1024];
-    const int tid = threadIdx.x;
-    if (ctl->stop) {
-        if (tid == 0) ctl->m = 0;
-        return;
-    }
-    const int C = (n + 1023) / 1024, a0 = min(n, tid * C), a1 = min(n, a0 + C);
-    auto valid = [&](int s) { return B.raw_b[s] >= 0 && B.raw_d[s] < TWO_OPT_EPS; };
-    int c = 0;
-    for (int s = a0; s < a1; s++) c += valid(s) ? 1 : 0;
-    cnts[tid] = c;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        const int v = tid >= off ? cnts[tid - off] : 0;
-        __syncthreads();
-        cnts[tid] += v;
-        __syncthreads();
-    }
-    int at = cnts[tid] - c;
     const Nl3Pos T = nl3_pos(S, n, t);
-    for (int s = a0; s < a1; s++) {
-        if (!valid(s)) continue;
-        const int code = B.raw_b[s];
-        const Nl3Move M = nl3_decode(T, NL, s, code);
-        B.d[at] = B.raw_d[s];
-        B.a[at] = s;
-        B.b[at] = code;
-        B.i[at] = M.i;                      // 0 <= i < k <= n - 1: no range wraps
-        B.j[at] = M.k;
-        at++;
-    }
-    if (tid == 1023) ctl->m = cnts[1023];
+    m2_counted_scan(
+        n, ctl, cnts, [&](int s) { return B.raw_b[s] >= 0 && B.raw_d[s] < TWO_OPT_EPS; },
+        [&](int s, int at) {
+            const int code = B.raw_b[s];
+            const Nl3Move M = nl3_decode(T, NL, s, code);
+            B.d[at] = B.raw_d[s];
+            B.a[at] = s;
+            B.b[at] = code;
+            B.i[at] = M.i;                  // 0 <= i < k <= n - 1: no range wraps
+            B.j[at] = M.k;
+        });
 }
 
 // j << 2 | kind of candidate x into raw_b[x] (the sweep's raw_b is spent once the compaction has run)
@@ -215,24 +196,9 @@ template <typename T, typename CS>
 __device__ __forceinline__ void nl3_apply_tour(const Tours &S, const CS cs, int n, int t, const NlBuf &NL, const M2Buf &B, M2Ctl *ctl)
 {
     typedef typename Elem<T>::acc AT;
-    __shared__ double rs[NL3_APPLY_BT], rm[NL3_APPLY_BT];
-    __shared__ int rk[NL3_APPLY_BT];
     const int tid = threadIdx.x, BT = NL3_APPLY_BT;
     const int m = ctl->m;                   // (0 once `stop` is up: k_nl3_compact)
-    if (blockIdx.x == 0) {                  // the close of k_m2_apply: a tree of fixed shape over the accepted deltas
-        if (ctl->stop) return;
-        double s = 0.0, mn = 0.0;
-        int k = 0;
-        for (int x = tid; x < m; x += BT)
-            if (B.acc[x]) { const double d = B.d[x]; s += d; mn = fmin(mn, d); k++; }
-        rs[tid] = s; rm[tid] = mn; rk[tid] = k;
-        __syncthreads();
-        for (int off = BT >> 1; off > 0; off >>= 1) {
-            if (tid < off) { rs[tid] += rs[tid + off]; rm[tid] = fmin(rm[tid], rm[tid + off]); rk[tid] += rk[tid + off]; }
-            __syncthreads();
-        }
-        if (tid == 0) m2_close(S, t, ctl, rs[0], rm[0], rk[0]);
-    }
+    if (blockIdx.x == 0 && !m2_sum_close(S, t, B, ctl, m, BT)) return;      // the close of k_m2_apply
     int *ord = S.ord + (size_t)t * n, *pos = S.pos + (size_t)t * n, *succ = S.succ + (size_t)t * n;
     AT *dp = dpos_of<AT>(S, t, n), *dnb = dnb_of<AT>(S, t, n);
     const Nl3Pos T0 = nl3_pos(S, n, t);     // node 0 is in no moved range: its cell stays

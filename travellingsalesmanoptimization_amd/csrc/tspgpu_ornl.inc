@@ -2,7 +2,7 @@
 // Neighbour-list Or-opt: the candidates of a segment start come from the K-nearest-neighbour lists of the segment's ends,
 // and every accepted move of a sweep is applied in one launch.
 // Included by tspgpu.hip behind tspgpu_nl2opt.inc (uses Tours, Elem, wave_argmin, key_better, or_cell / or_ecell, OR_QB,
-// OrMatCost / OrPtsCost, M2Buf, M2Ctl, NlBuf, k_m2_select).  The rule is in include/tspgpu.h ("Neighbour-list Or-opt") and
+// OrMatCost / OrPtsCost, M2Buf, M2Ctl, NlBuf, m2_counted_scan, m2_sum_close, k_m2_select).  The rule is in include/tspgpu.h ("Neighbour-list Or-opt") and
 // DESIGN 4.15; move and delta are those of tspgpu_oropt.inc, conflict and selection those of tspgpu_multi2opt.inc.
 //
 // Per sweep four launches on the slot's stream:
@@ -13,8 +13,8 @@
 //                                     one gather per (s, L); pred(u) comes from pos, ord and dir.  A lane keeps its best over
 //                                     the three L, a DPP argmin by (delta, L | q | rev) leaves raw_d[s] / raw_b[s].
 //                                     A segment that holds node 0 is no candidate.  No LDS.
-//   k_ornl_compact                    one workgroup: the improving candidates in node order -- the counted scan of
-//                                     k_m2_compact, without a mutual-choice rule -- with a = s, b = the packed (L, q, rev)
+//   k_ornl_compact                    one workgroup: the improving candidates in node order -- m2_counted_scan, as
+//                                     k_m2_compact but without a mutual-choice rule -- with a = s, b = the packed (L, q, rev)
 //                                     and the range [lo, hi] of positions counted from node 0.
 //   k_m2_select                       unchanged: b > a for every candidate (below), so its key (delta, min, max) is
 //                                     (delta, s, L, q, rev).
@@ -111,45 +111,26 @@ __global__ void __launch_bounds__(256) k_ornl_sweep_otf(Tours S, const typename 
     ornl_sweep_start<int>(S, OrPtsCost<KIND>{pts}, n, t, NL, B);
 }
 
-// one workgroup of 1024 threads; thread k owns the nodes [k C, k C + C) (the body, as m2_compact_tour; cnts: [1024] in LDS)
+// the improving candidates through m2_counted_scan (cnts: [1024] in LDS), with their ranges
 template <typename CTL>
 __device__ __forceinline__ void ornl_compact_tour(const Tours &S, int n, int t, const M2Buf &B, CTL *ctl, int *cnts)
 {
-    const int tid = threadIdx.x;
-    if (ctl->stop) {
-        if (tid == 0) ctl->m = 0;
-        return;
-    }
-    const int C = (n + 1023) / 1024, a0 = min(n, tid * C), a1 = min(n, a0 + C);
-    auto valid = [&](int s) { return B.raw_b[s] >= 0 && B.raw_d[s] < TWO_OPT_EPS; };
-    int c = 0;
-    for (int s = a0; s < a1; s++) c += valid(s) ? 1 : 0;
-    cnts[tid] = c;
-    __syncthreads();
-    for (int off = 1; off < 1024; off <<= 1) {
-        const int v = tid >= off ? cnts[tid - off] : 0;
-        __syncthreads();
-        cnts[tid] += v;
-        __syncthreads();
-    }
-    int at = cnts[tid] - c;
     const int *pos = S.pos + (size_t)t * n;
     const int dir = S.dir[t];
     const int f0 = ornl_fwd(pos[0], n, dir);
-    for (int s = a0; s < a1; s++) {
-        if (!valid(s)) continue;
-        const int b = B.raw_b[s], L = b >> ORNL_LSHIFT, q = (b >> 1) & (int)OR_QM;
-        int i = ornl_fwd(pos[s], n, dir) - f0, j = ornl_fwd(pos[q], n, dir) - f0;     // P(s), P(q)
-        if (i < 0) i += n;
-        if (j < 0) j += n;
-        B.d[at] = B.raw_d[s];
-        B.a[at] = s;
-        B.b[at] = b;
-        B.i[at] = min(i - 1, j);            // node 0 is in no segment: 1 <= i, i + L - 1 <= n - 1, no range wraps
-        B.j[at] = max(i + L - 1, j);
-        at++;
-    }
-    if (tid == 1023) ctl->m = cnts[1023];
+    m2_counted_scan(
+        n, ctl, cnts, [&](int s) { return B.raw_b[s] >= 0 && B.raw_d[s] < TWO_OPT_EPS; },
+        [&](int s, int at) {
+            const int b = B.raw_b[s], L = b >> ORNL_LSHIFT, q = (b >> 1) & (int)OR_QM;
+            int i = ornl_fwd(pos[s], n, dir) - f0, j = ornl_fwd(pos[q], n, dir) - f0;     // P(s), P(q)
+            if (i < 0) i += n;
+            if (j < 0) j += n;
+            B.d[at] = B.raw_d[s];
+            B.a[at] = s;
+            B.b[at] = b;
+            B.i[at] = min(i - 1, j);        // node 0 is in no segment: 1 <= i, i + L - 1 <= n - 1, no range wraps
+            B.j[at] = max(i + L - 1, j);
+        });
 }
 
 __global__ void __launch_bounds__(1024) k_ornl_compact(Tours S, int n, int t, M2Buf B, M2Ctl *ctl)
@@ -162,24 +143,9 @@ template <typename T, typename CS, typename CTL>
 __device__ __forceinline__ void ornl_apply_tour(const Tours &S, const CS cs, int n, int t, const M2Buf &B, CTL *ctl)
 {
     typedef typename Elem<T>::acc AT;
-    __shared__ double rs[ORNL_APPLY_BT], rm[ORNL_APPLY_BT];
-    __shared__ int rk[ORNL_APPLY_BT];
     const int tid = threadIdx.x, BT = ORNL_APPLY_BT;
     const int m = ctl->m;                   // (0 once `stop` is up: k_ornl_compact)
-    if (blockIdx.x == 0) {                  // the close of k_m2_apply: a tree of fixed shape over the accepted deltas
-        if (ctl->stop) return;
-        double s = 0.0, mn = 0.0;
-        int k = 0;
-        for (int x = tid; x < m; x += BT)
-            if (B.acc[x]) { const double d = B.d[x]; s += d; mn = fmin(mn, d); k++; }
-        rs[tid] = s; rm[tid] = mn; rk[tid] = k;
-        __syncthreads();
-        for (int off = BT >> 1; off > 0; off >>= 1) {
-            if (tid < off) { rs[tid] += rs[tid + off]; rm[tid] = fmin(rm[tid], rm[tid + off]); rk[tid] += rk[tid + off]; }
-            __syncthreads();
-        }
-        if (tid == 0) m2_close(S, t, ctl, rs[0], rm[0], rk[0]);
-    }
+    if (blockIdx.x == 0 && !m2_sum_close(S, t, B, ctl, m, BT)) return;      // the close of k_m2_apply
     int *ord = S.ord + (size_t)t * n, *pos = S.pos + (size_t)t * n, *succ = S.succ + (size_t)t * n;
     AT *dp = dpos_of<AT>(S, t, n), *dnb = dnb_of<AT>(S, t, n);
     const int dir = S.dir[t];
