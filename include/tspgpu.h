@@ -124,7 +124,8 @@ int  tspgpu_set_option(tspgpu_ctx *ctx, int option, long value);
  * evaluated, 2 with the exact early-out), 35 tour positions per workgroup of that sweep (0 where 34 is 0); 36 .. 60 in the
  * sections below; 61 the last LDS-resident descent ran in an instantiation of k_lds2opt compiled for its shape (plain 2-opt,
  * packed 16-bit costs, (n, edges per workgroup) = (4096, 16) or (1024, 4); 0: the generic kernel); 62 .. 67 in
- * "Neighbour-list 3-opt" below */
+ * "Neighbour-list 3-opt" below; 68 with tspgpu_debug_tmat below; 69 the last LDS-resident descent, tabu walk or VNS walk (whole rows or
+ * half-window rows) ran the loop over packed 16-bit deltas (every cost <= 16383; the tabu walk: <= 8190), 0: 32-bit deltas */
 long tspgpu_info(const tspgpu_ctx *ctx, int what);
 
 /* ---- instance / cost matrix ------------------------------------------- */

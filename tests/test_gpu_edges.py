@@ -1,7 +1,8 @@
 """The sweep kernels where they change representation, and deep in the two large descents (on an MI355X).
 
 - weight width: instances whose bounding box puts cost_bound (include/tspgpu.h: the largest weight the points can
-  produce) on each side of every threshold the engine switches at -- 65 534 (uint16 -> int32 cells), 2^22 (CEIL_2D's
+  produce) on each side of every threshold the engine switches at -- 8 190 (the packed tabu form of the LDS-resident
+  kernels -> their 32-bit form), 16 383 (packed 16-bit deltas -> 32-bit deltas), 65 534 (uint16 -> int32 cells), 2^22 (CEIL_2D's
   integer ceil-sqrt -> the generic double form), 2^25 (k_sweep_otf8 -> k_sweep_otf), 2^27 (int32 -> f64 cells; the
   matrix-free mode refuses) -- through every path that admits them, move by move against the oracle;
 - label width: n = 65 535 / 65 536 (the largest matrix-mode instances), n past 65 536 in the automatic mode, n = 131 071 /
@@ -22,6 +23,8 @@ from conftest import GOLDEN_DIR, data_path
 pytestmark = pytest.mark.gpu
 
 U16_MAX, CEIL_INT_BOUND, OTF8_BOUND, I32_BOUND = 65534.0, 4194304.0, 33554432.0, 134217728.0
+PK16_MAX, PK8_MAX = 16383.0, 8190.0
+LE_THRESHOLDS = (U16_MAX, PK16_MAX, PK8_MAX)        # bound <= threshold is the low side; the others: bound < threshold
 
 
 @pytest.fixture(scope="module")
@@ -77,7 +80,8 @@ def _history(eng, cap):
 # regime -> (threshold, side): cost_bound just below / just above it
 REGIMES = {"u16_top": (U16_MAX, -1), "i32_bottom": (U16_MAX, +1), "ceil_int_top": (CEIL_INT_BOUND, -1),
            "ceil_generic": (CEIL_INT_BOUND, +1), "otf8_top": (OTF8_BOUND, -1), "otf_bottom": (OTF8_BOUND, +1),
-           "i32_top": (I32_BOUND, -1), "f64_bottom": (I32_BOUND, +1)}
+           "i32_top": (I32_BOUND, -1), "f64_bottom": (I32_BOUND, +1),
+           "pk16_top": (PK16_MAX, -1), "pk16_bottom": (PK16_MAX, +1), "pk8_top": (PK8_MAX, -1), "pk8_bottom": (PK8_MAX, +1)}
 KINDS = ["EUC_2D", "CEIL_2D", "ATT"]
 
 
@@ -87,7 +91,7 @@ def _edge_instance(inst, kind, regime):
     thr, side = REGIMES[regime]
     att = math.sqrt(10.0) if kind == 1 else 1.0
     if side < 0:
-        want = (thr - 2.0 - (0.0 if thr == U16_MAX else 0.5)) * att       # u16: bound <= 65534; else bound < thr
+        want = (thr - 2.0 - (0.0 if thr in LE_THRESHOLDS else 0.5)) * att       # 65534, 16383, 8190: bound <= thr; else bound < thr
     else:
         want = (thr - 2.0 + 0.5) * att
     if inst in ("lattice", "lattice_frac"):        # grid20 scaled: ties everywhere, kept by the scaling
@@ -118,7 +122,8 @@ def _edge_instance(inst, kind, regime):
             xy = np.concatenate([[[0.0, 0.0], [s, s]], r.uniform(0, s, size=(698, 2))])
     xy = np.ascontiguousarray(xy, dtype=np.float64)
     b = _cost_bound(xy, kind)
-    assert (b <= thr if thr == U16_MAX else b < thr) if side < 0 else (b > thr if thr == U16_MAX else b >= thr), (inst, regime, b)
+    le = thr in LE_THRESHOLDS
+    assert (b <= thr if le else b < thr) if side < 0 else (b > thr if le else b >= thr), (inst, regime, b)
     return xy
 
 
@@ -141,8 +146,8 @@ PATHS = {"default": {}, "one_launch": {16: 0}, "split": {16: 0, 12: 0},
 def test_weight_width_edges(clean, T, O, regime, kind, inst):
     """one instance on one side of one threshold: on every admissible path the NN tour, every move of the 2-opt descent from
     it, a 150-move tabu walk from the oracle's optimum -- against the oracle's matrix of the same kind --, info() naming the
-    storage and the sweep kernel that ran; one matrix-free VNS walk on the glibc stream; the matrix-free mode refuses past
-    2^27 with code 8"""
+    storage, the sweep kernel and (LDS-resident: persist_packed) the packed or the 32-bit form that ran; one matrix-free VNS
+    walk on the glibc stream; the matrix-free mode refuses past 2^27 with code 8"""
     eng = clean
     k = getattr(O, kind)
     xy = _edge_instance(inst, k, regime)
@@ -197,6 +202,7 @@ def test_weight_width_edges(clean, T, O, regime, kind, inst):
                 assert info["matrix_free"] == 0 and info["elem"] == elem and info["otf_kernel"] == 0, (path, info)
                 if path == "default" and elem == 3:
                     assert info["persist"] == 1, info          # k_lds2opt
+                    assert info["persist_packed"] == int(bound <= PK16_MAX), (info, bound)     # packed 16-bit deltas
                 if path == "split":
                     assert info["fused"] == 0, info
             # the tabu walk
@@ -205,6 +211,9 @@ def test_weight_width_edges(clean, T, O, regime, kind, inst):
             bad = np.nonzero(trace != otabu[3])[0]
             assert len(bad) == 0, (path, bad[:5], trace[bad[:5]], otabu[3][bad[:5]])
             assert final == otabu[2] and best_cost == otabu[1] and np.array_equal(best, otabu[0]), path
+            if path == "default" and elem == 3:
+                info = eng.info()
+                assert info["persist"] == 1 and info["persist_packed"] == int(bound <= PK8_MAX), (info, bound)   # the tabu form
             if mf:
                 info = eng.info()
                 assert info["otf_kernel"] == (1 if bound >= OTF8_BOUND else 2), (path, info)   # the tabu form: never early-out

@@ -38,6 +38,7 @@ INFO_VNS_NL_WALKS, INFO_VNS_NL_ITERATIONS, INFO_VNS_NL_ROUNDS, INFO_VNS_NL_MAX_L
 # nodes per workgroup of its candidate sweep (61 is the shape-specialised LDS-resident descent's flag)
 INFO_THREE_NL_W, INFO_THREE_NL_SWEEPS, INFO_THREE_NL_MOVES, INFO_THREE_NL_MAX_MOVES, INFO_THREE_NL_PHASES, INFO_THREE_NL_NODES = 62, 63, 64, 65, 66, 67
 INFO_PERSIST_TMAT = 68                  # the last LDS-resident descent fetched moved rows from the tour-ordered matrix copy
+INFO_PERSIST_PACKED = 69                # the last LDS-resident descent / tabu walk / VNS walk ran the packed 16-bit loop
 EM_FORM_AUTO, EM_FORM_RESIDENT, EM_FORM_PER_STEP = 0, 1, 2
 MOPT_EXCHANGE = 1000
 EXCHANGE_AUTO, EXCHANGE_HOST, EXCHANGE_RCCL = 0, 1, 2

@@ -3304,6 +3304,7 @@ struct tspgpu_ctx : ContextMem, InstanceMem, CostMem, SlotMem {
     int opt_lp_generic = 0;    // undocumented (option 89): 1 = never a shaped instantiation
     bool lp_tmat = false;      // ... and it fetched moved rows from the tour-ordered copy (a TM instantiation)
     int opt_lp_no_tmat = 0;    // undocumented (option 88): 1 = the shaped instantiation that reloads moved rows from the matrix
+    bool lp_packed = false;    // the last LDS-resident descent / tabu walk / VNS walk ran the packed 16-bit loop (pk in run_persist)
     bool max16k = false;       // every off-diagonal cell <= 16383 (packed 16-bit deltas cannot overflow)
     bool max8k = false;        // ... <= 8190 (the tabu form of the packed loop: a poisoned pair must exceed every valid delta)
 
@@ -4258,7 +4259,7 @@ static int run_persist(tspgpu_ctx *ctx, int slot, double *time_left_io, bool *de
     const void *const fn = sfn ? sfn : (const void *)fns[win][tabu ? 1 : vns ? 2 : 0][pk];
     if (const int rc = ensure_max_lds(ctx, fn)) return rc;
     const double t_end = deadline_of(time_left_s);
-    if (t_end >= 0 && time_left_s <= 0) { if (deadline_hit) *deadline_hit = true; *ran = true; ctx->lp_used = true; ctx->lp_window = win; ctx->lp_shaped = false; ctx->lp_tmat = false; return E_OK; }
+    if (t_end >= 0 && time_left_s <= 0) { if (deadline_hit) *deadline_hit = true; *ran = true; ctx->lp_used = true; ctx->lp_window = win; ctx->lp_shaped = false; ctx->lp_tmat = false; ctx->lp_packed = pk != 0; return E_OK; }
     if (vns) vns->need_rand = false;
     // one launch: fill(A) queues what the walk needs in front of it and completes the arguments
     auto launch = [&](int budget, bool first, int &status, int &sd, auto &&fill, const double *also = nullptr) -> int {
@@ -4334,7 +4335,7 @@ static int run_persist(tspgpu_ctx *ctx, int slot, double *time_left_io, bool *de
                             [&](int budget, bool first, int &st, int &sd) { return launch(budget, first, st, sd, [](PersistArgs &) -> int { return E_OK; }); },
                             [&](int status, int sd) { return descent_completed(ctx, status, sd); }, hand_over);
     if (const int rc = resident_result(ctx, r, deadline_hit, ran); rc || !*ran) return rc;
-    ctx->lp_used = true; ctx->lp_window = win; ctx->lp_shaped = sfn != nullptr; ctx->lp_tmat = tm;
+    ctx->lp_used = true; ctx->lp_window = win; ctx->lp_shaped = sfn != nullptr; ctx->lp_tmat = tm; ctx->lp_packed = pk != 0;
     return E_OK;
 }
 
@@ -5068,6 +5069,7 @@ long tspgpu_info(const tspgpu_ctx *ctx, int what)
     case 66: return ctx->nl3_phases;
     case 67: return NL3_NODES;
     case 68: return ctx->lp_used && ctx->lp_shaped && ctx->lp_tmat ? 1 : 0;
+    case 69: return ctx->lp_used && ctx->lp_packed ? 1 : 0;
     case 55: return ctx->have_costs && ctx->symmetric && ctx->n >= 8 ? (ctx->n + ORNL_STARTS - 1) / ORNL_STARTS : 0;
     case 12: return (ctx->built && ctx->grid_ok && ctx->opt_nn != 1 && ctx->cost_bound < 134217728.0) ? ctx->grid_G : 0;
     case 13: return ctx->grid_max_occ;

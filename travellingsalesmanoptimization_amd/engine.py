@@ -59,7 +59,7 @@ class Engine:
                  "vns_nl_walks", "vns_nl_iterations", "vns_nl_rounds", "vns_nl_max_live", "vns_nl_dry",
                  "persist_shaped",
                  "three_nl_w", "three_nl_sweeps", "three_nl_moves", "three_nl_max_moves", "three_nl_phases", "three_nl_nodes",
-                 "persist_tmat"]
+                 "persist_tmat", "persist_packed"]
         return {k: int(self.L.tspgpu_info(self.ctx, i)) for i, k in enumerate(names)}
 
     # ---- instance
