@@ -616,6 +616,80 @@ int tspgpu_tour_local_search_nl3(tspgpu_ctx *ctx, int slot, int width, double ti
  * nothing applied */
 int tspgpu_time_three_nl_sweep(tspgpu_ctx *ctx, int slot, int width, int reps, float *ms_mean);
 
+/* ---- Don't-look bits (an extension: the neighbour-list sweeps evaluate only the nodes near a changed edge; a kick on a slot) ----
+ * A sweep of "Neighbour-list 2-opt", "Neighbour-list Or-opt" and "Neighbour-list 3-opt" evaluates every node.  With looks it
+ * evaluates the nodes near an edge that changed since they were last evaluated without result.  Opt-in: no other entry point
+ * changes.  "Unit v" is what a family's sweep evaluates for node v: cand(a) of "Neighbour-list 2-opt", cand(s) of rule 2 of
+ * "Neighbour-list Or-opt", cand(t1) of rule 4 of "Neighbour-list 3-opt".  P is the position function of those sections.
+ * Preconditions and codes of every _dl entry point: those of its plain counterpart.
+ *   1. State.  Per slot three sets of awake nodes, A2, AO and A3, one per family (family 0, 1, 2).  A slot that has just been
+ *      loaded (tspgpu_tour_load, tspgpu_tour_nn, every host-tour entry point) has every node awake in all three;
+ *      tspgpu_tour_copy copies the sets; every slot call outside this section that can rewrite a tour leaves every node awake
+ *      in all three.  A slot for which nothing was ever allocated counts as all awake.
+ *   2. Looked units of a sweep of family f.  Q = { v : one of the nodes at the positions P(v), .., P(v) + fwd (mod n) is in
+ *      A_f }, fwd = 0 for the 2-opt, 2 for Or-opt (a changed edge (t, x) reaches the units s whose segments end in t), 0 for
+ *      the 3-opt.
+ *   3. Candidates.  cand(v) is the family's own for v in Q and "none" for every other node.  Range, conflict, the one
+ *      selection round, apply and the cost sum are the family's rules on those candidates, unchanged.
+ *   4. The new set.  A_f' = carry + ends.  carry: for every unit with a candidate (delta < -1e-7), accepted or not, read on
+ *      the tour as it stood before the apply -- 2-opt: a and succ(a) (after a reversal the same tour edge is keyed on its
+ *      other end); Or-opt: the nodes s .. t of the candidate's segment; 3-opt: t1.  ends: for every accepted move the end
+ *      nodes of its removed edges (4, 6 and 6 nodes: a, succ a, b, succ b; p, s, t, x, q, q'; t1 .. t6).  The other two
+ *      families g: A_g' = A_g + ends.
+ *   5. Count.  `looked` grows by |Q|.  A sweep with |Q| = n is a full sweep.
+ *   6. Phase with looks, with a flag `closing`.  A_f empty on entry: closing == 0 runs no sweep and every counter stays 0;
+ *      closing != 0 wakes every node of A_f, so one full sweep runs.  Otherwise sweeps run until one accepts nothing; that
+ *      sweep is counted.  If it was full the phase ends.  If not: closing != 0 wakes every node of A_f and the phase goes on
+ *      (a phase cut by max_sweeps at that sweep still wakes them); closing == 0 ends the phase.  At the end of a phase that
+ *      neither max_sweeps nor the deadline cut, A_f is empty: a sweep that accepts nothing had no candidate, because the
+ *      smallest key is always accepted.
+ *   7. Consequences.  (a) A first sweep with every node awake is the plain sweep move for move.  (b) With closing != 0 a
+ *      phase ends exactly where the plain phase's end condition holds: the family's plain _once call on the result accepts
+ *      nothing.  (c) With closing == 0 the result is the classic approximation: a sleeping unit whose far side (the q, q' or
+ *      t3 .. t6 part) changed is not looked at again.  (d) The trajectory is in general not the plain one, and the final cost
+ *      may be higher or lower.
+ *   8. Descent.  Rule 10 of "Neighbour-list 3-opt" with every phase a phase with looks and one `closing` for all of them;
+ *      width == 0 means no 3-opt phase, which is rule 8 of "Neighbour-list Or-opt".  The host-tour form recomputes the cost
+ *      first, as the plain one does; the slot form takes the cost as it stands.
+ *   9. Kick.  tspgpu_tour_kick applies the move (i, j, k, kind 1) of rule 2 of "Neighbour-list 3-opt" -- B, A: the segment
+ *      swap of mh_VNS's kick -- whatever its delta, 0 <= i < j < k <= n - 1.  The slot's cost grows by
+ *          ((c[a][b'] + c[c][a']) + c[b][c']) - ((c[a][a'] + c[b][b']) + c[c][c'])                 in this order
+ *      which is also the slot's last delta, and a, a', b, b', c, c' join A2, AO and A3.  It needs n >= 8 and symmetric costs
+ *      (or matrix-free mode), and no lists.
+ * Codes: no context 14; lists not built or invalidated 9 (the text of "Neighbour-list 2-opt"); n < 5 (2-opt) / n < 8 3; a
+ * width outside 1 .. 16 (the descents: 0 .. 16) 3; a slot that holds no tour 9; bad kick positions 3; a node outside
+ * 0 .. n - 1 in tspgpu_tour_wake 3 (nothing changed); a family outside 0 .. 2 3; a deadline that passed 4 (with a valid tour).
+ * Memory: at the first call of this section 3 n bytes per slot (the sets; they grow with the slots) and 4 n bytes per
+ * context (the queue of looked units), all of it or none.
+ * tspgpu_info: 70 `looked` of the last call with looks (a descent: the total), 71 its full sweeps, 72 the largest |Q| of one
+ * of its sweeps that was not full, 73 the most workgroups a queued sweep runs (each takes the units of tspgpu_info 46 / 51 /
+ * 67 per pass and strides over Q).  The plain families' counters (43-45, 47-50, 63-66) are left by a _dl call as its plain
+ * counterpart leaves them, with the _dl call's own sweeps and moves. */
+/* count < 0: every node of the slot wakes in all three sets; else nodes[0 .. count) join them */
+int tspgpu_tour_wake(tspgpu_ctx *ctx, int slot, const int *nodes, int count);
+/* all three sets empty */
+int tspgpu_tour_sleep(tspgpu_ctx *ctx, int slot);
+/* the set of `family` (0 2-opt, 1 Or-opt, 2 3-opt): out[v] = 1 iff v is awake (may be NULL), *count their number (may be NULL) */
+int tspgpu_tour_awake(tspgpu_ctx *ctx, int slot, int family, unsigned char *out /* [n] */, int *count);
+/* rule 9 */
+int tspgpu_tour_kick(tspgpu_ctx *ctx, int slot, int i, int j, int k);
+/* the phase with looks (rule 6) of each family on a slot: at most max_sweeps sweeps (< 0: no cap); *sweeps, *moves and
+ * *looked (each may be NULL) are totals over the phase */
+int tspgpu_tour_two_opt_nl_dl(tspgpu_ctx *ctx, int slot, int closing, long max_sweeps, double time_left_s,
+                              long *sweeps, long *moves, long *looked);
+int tspgpu_tour_or_opt_nl_dl(tspgpu_ctx *ctx, int slot, int closing, long max_sweeps, double time_left_s,
+                             long *sweeps, long *moves, long *looked);
+int tspgpu_tour_three_opt_nl_dl(tspgpu_ctx *ctx, int slot, int width, int closing, long max_sweeps, double time_left_s,
+                                long *sweeps, long *moves, long *looked);
+/* the descent (rule 8) on a slot and on a host tour; the nine counters of tspgpu_tour_local_search_nl3, then the units
+ * looked at and the full sweeps over the whole descent (each may be NULL) */
+int tspgpu_tour_local_search_nl3_dl(tspgpu_ctx *ctx, int slot, int width, int closing, double time_left_s,
+                                    long *two_opt_sweeps, long *two_opt_moves, long *or_sweeps, long *or_moves, int *rounds,
+                                    long *three_sweeps, long *three_moves, int *three_phases, long *looked, long *full_sweeps);
+int tspgpu_local_search_nl3_dl(tspgpu_ctx *ctx, int width, int closing, int *path, double *cost, double time_left_s,
+                               long *two_opt_sweeps, long *two_opt_moves, long *or_sweeps, long *or_moves, int *rounds,
+                               long *three_sweeps, long *three_moves, int *three_phases, long *looked, long *full_sweeps);
+
 /* ---- Batched neighbour-list descent (an extension: the descent over the lists on a batch of tours, and the multi-start) ----
  * The descent of "Neighbour-list Or-opt" (rule 8) on many tours at once: every launch serves every tour of the batch that
  * is still descending.  For each tour of the batch the descent is exactly rule 8, run on that tour alone:

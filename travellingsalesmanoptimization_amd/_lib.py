@@ -39,6 +39,9 @@ INFO_VNS_NL_WALKS, INFO_VNS_NL_ITERATIONS, INFO_VNS_NL_ROUNDS, INFO_VNS_NL_MAX_L
 INFO_THREE_NL_W, INFO_THREE_NL_SWEEPS, INFO_THREE_NL_MOVES, INFO_THREE_NL_MAX_MOVES, INFO_THREE_NL_PHASES, INFO_THREE_NL_NODES = 62, 63, 64, 65, 66, 67
 INFO_PERSIST_TMAT = 68                  # the last LDS-resident descent fetched moved rows from the tour-ordered matrix copy
 INFO_PERSIST_PACKED = 69                # the last LDS-resident descent / tabu walk / VNS walk ran the packed 16-bit loop
+# ... units looked at, full sweeps and the largest sweep that was not full of the last call with don't-look bits; the most
+# workgroups of a queued sweep
+INFO_DL_LOOKED, INFO_DL_FULL_SWEEPS, INFO_DL_MAX_QUEUE, INFO_DL_MAX_WGS = 70, 71, 72, 73
 EM_FORM_AUTO, EM_FORM_RESIDENT, EM_FORM_PER_STEP = 0, 1, 2
 MOPT_EXCHANGE = 1000
 EXCHANGE_AUTO, EXCHANGE_HOST, EXCHANGE_RCCL = 0, 1, 2
@@ -135,6 +138,15 @@ SIGNATURES = {
     "tspgpu_multistart_local_search_nl": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_double, _ip, _pd, _pi, _pl, _pl, _pl, _pl, C.c_void_p]),
     "tspgpu_vns_walks_nl": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_double, _ip, _dp, C.c_void_p, C.c_long, C.c_void_p, _ip, _ip, _ip, _dp,
                                       C.c_void_p, C.c_void_p]),
+    "tspgpu_tour_wake": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_int]),
+    "tspgpu_tour_sleep": (C.c_int, [_ctx, C.c_int]),
+    "tspgpu_tour_awake": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, _pi]),
+    "tspgpu_tour_kick": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "tspgpu_tour_two_opt_nl_dl": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_long, C.c_double, _pl, _pl, _pl]),
+    "tspgpu_tour_or_opt_nl_dl": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_long, C.c_double, _pl, _pl, _pl]),
+    "tspgpu_tour_three_opt_nl_dl": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_long, C.c_double, _pl, _pl, _pl]),
+    "tspgpu_tour_local_search_nl3_dl": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_double, _pl, _pl, _pl, _pl, _pi, _pl, _pl, _pi, _pl, _pl]),
+    "tspgpu_local_search_nl3_dl": (C.c_int, [_ctx, C.c_int, C.c_int, _ip, _pd, C.c_double, _pl, _pl, _pl, _pl, _pi, _pl, _pl, _pi, _pl, _pl]),
     "tspgpu_multi_neighbours_build": (C.c_int, [_ctx, C.c_int]),
     "tspgpu_multi_multistart_local_search_nl": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_double, _ip, _pd, _pi, _pl, _pl, _pl, _pl]),
 }

@@ -3111,6 +3111,7 @@ __global__ void k_cap_now(Tours S, int slot0, int count)
 #include "tspgpu_nl2opt.inc"
 #include "tspgpu_ornl.inc"
 #include "tspgpu_nl3opt.inc"
+#include "tspgpu_looks_dl.inc"
 #include "tspgpu_nlbatch.inc"
 #include "tspgpu_nlvns.inc"
 
@@ -3163,7 +3164,13 @@ struct MEM_GROUP InstanceMem {            // of one n: new_instance drops it
     DevBuf<double2> d_gxy; DevBuf<int> d_gidx, d_gpos, d_cstart, d_gcell;
     DevBuf<unsigned> d_knn;     // [n][NN_K] neighbour lists of k_nn_grid's KNN form (built at the first single-tour NN)
     int grid_G = 0; bool grid_ok = false;
+    // don't-look bits (tspgpu_looks_dl.inc): the queue of looked units [n] and the control block of a phase with looks; both, with
+    // the slots' sets (SlotMem::d_awake), at the first call of "Don't-look bits", or none
+    int *d_lq = nullptr;
+    LookCtl *d_look = nullptr;
 
+    Rows look_ctx_rows(size_t n) { return {{&d_lq, n * 4}, {&d_look, sizeof(LookCtl), 0, 0}}; }
+    void drop_look_ctx() { tspmem::free_rows<HipMem>(look_ctx_rows(0)); }
     static Rows m2_rows(M2Buf &B, size_t n)
     {
         return {{&B.raw_d, n * 8}, {&B.raw_b, n * 4}, {&B.d, n * 8}, {&B.a, n * 4}, {&B.b, n * 4}, {&B.i, n * 4}, {&B.j, n * 4}, {&B.acc, n * 4}};
@@ -3173,7 +3180,7 @@ struct MEM_GROUP InstanceMem {            // of one n: new_instance drops it
     void drop_nlv() { tspmem::free_rows<HipMem>(nlv_rows(0)); nlv_cap = 0; tspmem::reset_all(d_nlv_rand, d_nlv_trace); }
     void drop_nlb() { tspmem::free_rows<HipMem>(nlb_rows(0)); nlb_cap = 0; drop_nlv(); }
     void drop_grid() { tspmem::reset_all(d_gxy, d_gidx, d_gpos, d_cstart, d_gcell, d_knn); grid_G = 0; grid_ok = false; }
-    void reset() { tspmem::free_rows<HipMem>(m2_rows(m2, 0)); drop_nlb(); drop_grid(); }
+    void reset() { tspmem::free_rows<HipMem>(m2_rows(m2, 0)); drop_look_ctx(); drop_nlb(); drop_grid(); }
     ~InstanceMem() { reset(); }
 };
 
@@ -3200,6 +3207,11 @@ struct MEM_GROUP SlotMem {                // of one slot capacity: ensure_tours 
     TabuState *d_tabu = nullptr;
     Fused F{};                  // fused path state (allocated on first use, capacity fcap)
     int fcap = 0;
+    // don't-look bits: awake[slot][family][n] bytes for lcap slots (0: not allocated), grown with the slots; new slots are all awake
+    unsigned char *d_awake = nullptr;
+    int lcap = 0;
+    Rows look_rows(size_t n) { return {{&d_awake, 3 * n, 0, 1, true}}; }
+    void drop_looks() { tspmem::free_rows<HipMem>(look_rows(0)); lcap = 0; }
 
     // per slot; new slots are zero-filled (no sweep cap: 0xff) and the old ones copied
     Rows tour_rows(size_t n, size_t pstride)
@@ -3231,7 +3243,7 @@ struct MEM_GROUP SlotMem {                // of one slot capacity: ensure_tours 
         return r;
     }
     void drop_fused() { tspmem::free_rows<HipMem>(fused_rows(0, 0)); fcap = 0; }
-    void reset() { tspmem::free_rows<HipMem>(tour_rows(0, 0)); drop_fused(); S.pstride = 0; tcap = 0; }
+    void reset() { tspmem::free_rows<HipMem>(tour_rows(0, 0)); drop_fused(); drop_looks(); S.pstride = 0; tcap = 0; }
     ~SlotMem() { reset(); }
 };
 
@@ -3264,6 +3276,9 @@ struct tspgpu_ctx : ContextMem, InstanceMem, CostMem, SlotMem {
 
     // tours
     std::vector<unsigned char> slot_valid;   // [tcap] host side: the slot holds a complete tour state
+    // don't-look bits: 1 = every node of the slot is awake in all three sets, whatever d_awake holds (a loaded slot, and any
+    // slot a call outside "Don't-look bits" may have rewritten)
+    std::vector<unsigned char> look_all;     // [tcap] host side
     hipEvent_t ev_ord = nullptr; bool ord_pending = false;   // guards the reuse of h_ord
 
     // launch plan
@@ -3333,6 +3348,8 @@ struct tspgpu_ctx : ContextMem, InstanceMem, CostMem, SlotMem {
     // the last tspgpu_local_search_nl3
     int nl3_width = 0, nl3_w = 0;
     int nl3_phases = 0;
+    // don't-look bits (tspgpu_looks_dl.inc): units looked at, full sweeps and the largest sweep that was not full of the last call
+    long dl_looked = 0, dl_full = 0, dl_max_q = 0;
     // batched neighbour-list descent (tspgpu_nlbatch.inc)
     long nlb_tours = 0, nlb_launches = 0, nlb_max_live = 0;     // the last batched descent: tours, sweeps launched, most tours in one
     // neighbour-list VNS (tspgpu_nlvns.inc): the last call's walks, iterations completed, sweep rounds, most walks live in one, dry walks
@@ -3397,6 +3414,11 @@ static int ensure_tours(tspgpu_ctx *ctx, int want)
     if (want <= ctx->tcap) return E_OK;
     want = std::max(want, 16);
     const int pstride = std::max(MAX_WGS_PER_TOUR, (ctx->n + 7) / 8 + 8); // the matrix-free sweep runs n/8 workgroups per tour
+    // (the awake sets first, where they exist: if the slots then fail to grow, the sets merely have room to spare)
+    if (ctx->lcap && ctx->lcap < want) {
+        HIP_TRY(tspmem::grow(HipMem{ctx->stream}, ctx->look_rows((size_t)ctx->n), (size_t)ctx->lcap, (size_t)want));
+        ctx->lcap = want;
+    }
     HIP_TRY(tspmem::grow(HipMem{ctx->stream}, ctx->tour_rows((size_t)ctx->n, (size_t)pstride), (size_t)ctx->tcap, (size_t)want));
     ctx->S.pstride = pstride;
     if (ctx->tcap) {
@@ -3405,12 +3427,20 @@ static int ensure_tours(tspgpu_ctx *ctx, int want)
     }
     ctx->tcap = want;
     ctx->slot_valid.resize((size_t)want, 0);
+    ctx->look_all.resize((size_t)want, 1);
     return E_OK;
+}
+
+// don't-look bits: the slots' tours were, or may have been, rewritten outside "Don't-look bits": every node is awake
+static void wake_slots(tspgpu_ctx *ctx, int slot0, int count)
+{
+    for (int i = slot0; i < slot0 + count && i < (int)ctx->look_all.size(); i++) ctx->look_all[i] = 1;
 }
 
 static void mark_slots(tspgpu_ctx *ctx, int slot0, int count, bool valid)
 {
     for (int i = slot0; i < slot0 + count && i < (int)ctx->slot_valid.size(); i++) ctx->slot_valid[i] = valid ? 1 : 0;
+    wake_slots(ctx, slot0, count);
 }
 
 // a slot entry point was handed `slot`: it must exist and hold a tour
@@ -3440,6 +3470,7 @@ static int new_instance(tspgpu_ctx *ctx, int n)
     ctx->SlotMem::reset();
     ctx->InstanceMem::reset(); // (the grid is the old points': tspgpu_set_points builds the new one)
     ctx->slot_valid.clear();
+    ctx->look_all.clear();
     drop_graphs(ctx);
     ctx->grid_max_occ = 0;
     ctx->n = n;
@@ -4816,13 +4847,15 @@ template <typename B> static int with_host_tour(tspgpu_ctx *ctx, int *path, doub
     return done_code(late);
 }
 
-// the same on a slot that must hold a tour: the family's check, the slot's, body(&late)
-template <typename B> static int with_slot(tspgpu_ctx *ctx, int slot, int (*check)(tspgpu_ctx *), B &&body)
+// the same on a slot that must hold a tour: the family's check, the slot's, body(&late).  keeps_looks: the body keeps the
+// slot's awake sets itself ("Don't-look bits"); after any other body every node is awake
+template <typename B> static int with_slot(tspgpu_ctx *ctx, int slot, int (*check)(tspgpu_ctx *), B &&body, bool keeps_looks = false)
 {
     hipSetDevice(ctx->device);
     int rc = check(ctx);
     if (rc) return rc;
     if ((rc = need_slot(ctx, slot))) return rc;
+    if (!keeps_looks) wake_slots(ctx, slot, 1);
     bool late = false;
     if ((rc = body(&late))) return rc;
     return done_code(late);
@@ -5070,6 +5103,10 @@ long tspgpu_info(const tspgpu_ctx *ctx, int what)
     case 67: return NL3_NODES;
     case 68: return ctx->lp_used && ctx->lp_shaped && ctx->lp_tmat ? 1 : 0;
     case 69: return ctx->lp_used && ctx->lp_packed ? 1 : 0;
+    case 70: return ctx->dl_looked;
+    case 71: return ctx->dl_full;
+    case 72: return ctx->dl_max_q;
+    case 73: return (long)LOOK_WGS_PER_CU * ctx->cus;
     case 55: return ctx->have_costs && ctx->symmetric && ctx->n >= 8 ? (ctx->n + ORNL_STARTS - 1) / ORNL_STARTS : 0;
     case 12: return (ctx->built && ctx->grid_ok && ctx->opt_nn != 1 && ctx->cost_bound < 134217728.0) ? ctx->grid_G : 0;
     case 13: return ctx->grid_max_occ;
@@ -5310,7 +5347,14 @@ int tspgpu_tour_copy(tspgpu_ctx *ctx, int dst, int src)
     if ((rc = ensure_tours(ctx, dst + 1))) return rc;
     hipLaunchKernelGGL(k_copy_tour, dim3(std::max(1, ctx->n / 256)), dim3(256), 0, ctx->stream, ctx->S, ctx->n, dst, src);
     HIP_TRY(hipGetLastError());
+    const bool src_all = ctx->look_all[src] != 0;
     mark_slots(ctx, dst, 1, true);
+    if (!src_all) {                         // the awake sets travel with the tour (d_awake exists: something cleared the flag)
+        const size_t bytes = 3 * (size_t)ctx->n;
+        if (dst != src)
+            HIP_TRY(hipMemcpyAsync(ctx->d_awake + dst * bytes, ctx->d_awake + src * bytes, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+        ctx->look_all[dst] = 0;
+    }
     return E_OK;
 }
 
@@ -5321,6 +5365,7 @@ int tspgpu_tour_two_opt(tspgpu_ctx *ctx, int slot, long max_sweeps, double time_
     int rc = need_costs(ctx);
     if (rc) return rc;
     if ((rc = need_slot(ctx, slot))) return rc;
+    wake_slots(ctx, slot, 1);
     hipLaunchKernelGGL(k_rearm, dim3(1), dim3(64), 0, ctx->stream, ctx->S, slot, 1, (int)std::min<long>(max_sweeps, INT_MAX));
     HIP_TRY(hipGetLastError());
     bool late = false;
@@ -5664,6 +5709,7 @@ int tspgpu_tour_apply_move(tspgpu_ctx *ctx, int slot, int a, int b, double delta
     int rc = need_costs(ctx);
     if (rc) return rc;
     if ((rc = need_slot(ctx, slot))) return rc;
+    wake_slots(ctx, slot, 1);
     if ((rc = ensure_plan(ctx, 1, false))) return rc;
     const int G = ctx->plan_G;
     const u64 key = delta < TWO_OPT_EPS ? (a < b ? ((u64)(unsigned)a << 32) | (unsigned)b : ((u64)(unsigned)b << 32) | (unsigned)a) : 0;
@@ -6156,6 +6202,7 @@ static int or_batch_args(tspgpu_ctx *ctx, int slot0, int count)
         const int rc = need_slot(ctx, slot0 + i);
         if (rc) return rc;
     }
+    wake_slots(ctx, slot0, count);      // (a batched descent rewrites them)
     return E_OK;
 }
 
@@ -6318,6 +6365,11 @@ struct M2Family {
     void (*put)(int *out, const M2Moves &L, int x);         // candidate x into the caller's array
     M2Counters tspgpu_ctx::*count;
     long tspgpu_ctx::*voids;                                // a descent's counter that a new run of the family takes back to 0 (or null)
+    // "Don't-look bits" (null / -1: the family has none): its set, the queue pass over its window with the queued sweep behind
+    // it, and the wake pass that goes between the selection and the apply
+    int look_set = -1;
+    int (*qsweep)(tspgpu_ctx *, int slot, const LookBuf &K, int closing) = nullptr;
+    int (*wake)(tspgpu_ctx *, int slot, const LookBuf &K) = nullptr;
 };
 
 // every b of every node (k_m2_sweep; matrix-free mode: behind the gather of the successors' points)
@@ -6539,10 +6591,41 @@ static int nl_launch_sweep(tspgpu_ctx *ctx, int slot, const SweepGeom &, bool)
     return E_OK;
 }
 
+// "Don't-look bits": the workgroups of a queued sweep with `per_wg` units each, and of the wake pass: fixed from n and the chip
+static dim3 look_grid(const tspgpu_ctx *ctx, int per_wg)
+{
+    return dim3((unsigned)std::max(1, std::min((ctx->n + per_wg - 1) / per_wg, LOOK_WGS_PER_CU * ctx->cus)));
+}
+
+// the queue pass of family F over a window of FWD positions behind the unit
+template <int F, int FWD> static int look_launch_queue(tspgpu_ctx *ctx, int slot, const LookBuf &K, int closing)
+{
+    hipLaunchKernelGGL((k_look_queue<F, FWD>), dim3(1), dim3(1024), 0, ctx->stream, ctx->S, ctx->n, slot, K, ctx->m2, (M2Ctl *)ctx->d_m2, closing);
+    HIP_TRY(hipGetLastError());
+    return E_OK;
+}
+
+template <int F> static int look_launch_wake(tspgpu_ctx *ctx, int slot, const LookBuf &K)
+{
+    hipLaunchKernelGGL((k_look_wake<F>), look_grid(ctx, 256), dim3(256), 0, ctx->stream, ctx->S, ctx->n, slot, ctx->nl, K, ctx->m2,
+                       (const M2Ctl *)ctx->d_m2);
+    HIP_TRY(hipGetLastError());
+    return E_OK;
+}
+
+static int nl_launch_qsweep(tspgpu_ctx *ctx, int slot, const LookBuf &K, int closing)
+{
+    const int rc = look_launch_queue<0, 0>(ctx, slot, K, closing);
+    if (rc) return rc;
+    LAUNCH_BY_COST(k_nl_qsweep, look_grid(ctx, NL_NODES), dim3(NL_NODES * 32), slot, ctx->nl, ctx->m2, (const M2Ctl *)ctx->d_m2, K);
+    HIP_TRY(hipGetLastError());
+    return E_OK;
+}
+
 // the lists' 2-opt pairs: compaction, apply and move layout are the full family's.  (A phase's polish is counted behind it,
 // tspgpu_two_opt_nl: until then the phase has none)
 static const M2Family M2_NL = {nl_check, nl_launch_sweep, m2_compact_pairs, m2_apply_pairs, 2, nullptr, m2_put_pair, &tspgpu_ctx::nl_count,
-                               &tspgpu_ctx::nl_polish_sweeps};
+                               &tspgpu_ctx::nl_polish_sweeps, 0, nl_launch_qsweep, look_launch_wake<0>};
 
 extern "C" {
 
@@ -6658,6 +6741,15 @@ static int ornl_launch_sweep(tspgpu_ctx *ctx, int slot, const SweepGeom &, bool)
     return E_OK;
 }
 
+static int ornl_launch_qsweep(tspgpu_ctx *ctx, int slot, const LookBuf &K, int closing)
+{
+    const int rc = look_launch_queue<1, 2>(ctx, slot, K, closing);     // a changed edge (t, x) reaches the units whose segments end in t
+    if (rc) return rc;
+    LAUNCH_BY_COST(k_ornl_qsweep, look_grid(ctx, ORNL_STARTS), dim3(ORNL_STARTS * 64), slot, ctx->nl, ctx->m2, (const M2Ctl *)ctx->d_m2, K);
+    HIP_TRY(hipGetLastError());
+    return E_OK;
+}
+
 static int ornl_launch_apply(tspgpu_ctx *ctx, int slot)
 {
     const int G = std::min(M2_APPLY_WGS, (ctx->n + 1) / 2);
@@ -6679,7 +6771,7 @@ static void ornl_put(int *out, const M2Moves &L, int x)
 }
 
 static const M2Family M2_ORNL = {ornl_check, ornl_launch_sweep, ornl_launch_compact, ornl_launch_apply, 4, nullptr, ornl_put, &tspgpu_ctx::ornl_count,
-                                 nullptr};
+                                 nullptr, 1, ornl_launch_qsweep, look_launch_wake<1>};
 
 // the descent of tspgpu_local_search_nl on a slot: { neighbour-list 2-opt to its end; neighbour-list Or-opt until a sweep accepts
 // nothing } until an Or-opt phase applies nothing
@@ -6781,6 +6873,15 @@ static int nl3_launch_sweep(tspgpu_ctx *ctx, int slot, const SweepGeom &, bool)
     return E_OK;
 }
 
+static int nl3_launch_qsweep(tspgpu_ctx *ctx, int slot, const LookBuf &K, int closing)
+{
+    const int rc = look_launch_queue<2, 0>(ctx, slot, K, closing);
+    if (rc) return rc;
+    LAUNCH_BY_COST(k_nl3_qsweep, look_grid(ctx, NL3_NODES), dim3(NL3_NODES * 64), slot, ctx->nl, ctx->nl3_w, ctx->m2, (const M2Ctl *)ctx->d_m2, K);
+    HIP_TRY(hipGetLastError());
+    return E_OK;
+}
+
 static int nl3_launch_apply(tspgpu_ctx *ctx, int slot)
 {
     const int G = std::min(M2_APPLY_WGS, (ctx->n + 2) / 3);     // a range holds three positions at least
@@ -6813,7 +6914,7 @@ static void nl3_put(int *out, const M2Moves &L, int x)
 }
 
 static const M2Family M2_NL3 = {nl3_check, nl3_launch_sweep, nl3_launch_compact, nl3_launch_apply, 4, nl3_describe, nl3_put, &tspgpu_ctx::nl3_count,
-                                nullptr};
+                                nullptr, 2, nl3_launch_qsweep, look_launch_wake<2>};
 
 struct Descent3 { long ts = 0, tm = 0; int np = 0; };
 
@@ -6913,6 +7014,313 @@ int tspgpu_time_three_nl_sweep(tspgpu_ctx *ctx, int slot, int width, int reps, f
     if (!ctx) return E_UNAVAILABLE;
     ctx->nl3_width = width;
     return m2_time(ctx, slot, reps, ms_mean, M2_NL3);
+}
+
+} // extern "C"
+
+// ---- don't-look bits for the neighbour-list families, and the kick on a slot (tspgpu_looks_dl.inc) --------------------------
+
+// The queue and the control block (by n) and the slots' awake sets (3 n bytes per slot): all of them at the first call of
+// "Don't-look bits", or none.  They go where the M2Buf and the slot arrays go (InstanceMem, SlotMem) and grow with the slots
+static int ensure_looks(tspgpu_ctx *ctx)
+{
+    const size_t n = (size_t)ctx->n;
+    const bool fresh = !ctx->d_lq;
+    if (fresh) HIP_TRY(tspmem::grow(HipMem{ctx->stream}, ctx->look_ctx_rows(n), 0, 1));
+    if (!ctx->lcap) {
+        const hipError_t e = tspmem::grow(HipMem{ctx->stream}, ctx->look_rows(n), 0, (size_t)ctx->tcap);
+        if (e != hipSuccess) {
+            if (fresh) ctx->drop_look_ctx();
+            return fail(ctx, E_INTERNAL, "the awake sets of %d slots: %s", ctx->tcap, hipGetErrorString(e));
+        }
+        ctx->lcap = ctx->tcap;
+    }
+    return E_OK;
+}
+
+// the look state of a slot that holds a tour; a slot flagged "all awake" has its sets filled first (sets != 0), so that the
+// device arrays are what counts from here on
+static int look_buf(tspgpu_ctx *ctx, int slot, bool sets, LookBuf *K)
+{
+    const int rc = ensure_looks(ctx);
+    if (rc) return rc;
+    const size_t n = (size_t)ctx->n;
+    *K = LookBuf{ctx->d_awake + (size_t)slot * 3 * n, ctx->d_lq, ctx->d_look};
+    if (sets && ctx->look_all[slot]) {
+        HIP_TRY(hipMemsetAsync(K->awake, 1, 3 * n, ctx->stream));
+        ctx->look_all[slot] = 0;
+    }
+    return E_OK;
+}
+
+struct DlCount {
+    long looked = 0, full = 0, max_q = 0;
+    void operator+=(const DlCount &d) { looked += d.looked; full += d.full; max_q = std::max(max_q, d.max_q); }
+};
+
+// The phase with looks of family F on `slot`: m2_run with the queue pass in front of the sweep and the wake pass in front of
+// the apply.  The host decides at its look what a stopped phase does next (looks::after_stop); the counters are totals over
+// the phase, the deadline is m2_run's
+static int dl_run(tspgpu_ctx *ctx, int slot, int closing, long max_sweeps, double t_end, long *sweeps, long *moves, DlCount *dl, bool *late,
+                  const M2Family &F)
+{
+    M2Ctl C;
+    LookCtl LC;
+    memset(&C, 0, sizeof C);
+    memset(&LC, 0, sizeof LC);
+    *late = false;
+    *dl = DlCount{};
+    if (sweeps) *sweeps = 0;
+    if (moves) *moves = 0;
+    m2_record(ctx, C, F);
+    if (max_sweeps == 0) return E_OK;
+    LookBuf K;
+    int rc = look_buf(ctx, slot, true, &K);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(ctx->d_look, 0, sizeof(LookCtl), ctx->stream));
+    if ((rc = m2_arm(ctx, slot, max_sweeps))) return rc;
+    const int n = ctx->n;
+    const looks::Result r = looks::drive(
+        now_s, t_end, 4,
+        [&]() -> int {
+            int e = F.qsweep(ctx, slot, K, closing);
+            if (e) return e;
+            F.compact(ctx, slot);
+            HIP_TRY(hipGetLastError());
+            hipLaunchKernelGGL(k_m2_select, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->m2, (const M2Ctl *)ctx->d_m2);
+            HIP_TRY(hipGetLastError());
+            if ((e = F.wake(ctx, slot, K))) return e;
+            return F.apply(ctx, slot);
+        },
+        [&]() -> int {
+            int e = ctl_get(ctx, &C, ctx->d_m2.p);
+            if (e) return e;
+            if (!C.stop) return (int)looks::GO_ON;
+            if ((e = ctl_get(ctx, &LC, (const LookCtl *)ctx->d_look))) return e;
+            const looks::AfterStop next = looks::after_stop(closing != 0, C.sweeps, C.last_k, LC.last_q, n, C.budget);
+            if (next == looks::AfterStop::END) return (int)looks::STOP;
+            HIP_TRY(hipMemsetAsync(K.awake + (size_t)F.look_set * n, 1, (size_t)n, ctx->stream));
+            if (next == looks::AfterStop::WAKE_END) return (int)looks::STOP;
+            HIP_TRY(hipMemsetAsync(&ctx->d_m2.p->stop, 0, sizeof(int), ctx->stream));
+            return (int)looks::GO_ON;
+        });
+    if (r.code) return r.code;
+    *late = r.late;
+    if (r.late && (rc = ctl_get(ctx, &C, ctx->d_m2.p))) return rc;
+    if ((rc = ctl_get(ctx, &LC, (const LookCtl *)ctx->d_look))) return rc;
+    if (sweeps) *sweeps = (long)C.sweeps;
+    if (moves) *moves = (long)C.moves;
+    *dl = DlCount{(long)LC.looked, (long)LC.full, (long)LC.max_q};
+    m2_record(ctx, C, F);
+    return E_OK;
+}
+
+static void dl_record(tspgpu_ctx *ctx, const DlCount &dl) { ctx->dl_looked = dl.looked; ctx->dl_full = dl.full; ctx->dl_max_q = dl.max_q; }
+
+// a single phase with looks on a slot (tspgpu_tour_two_opt_nl_dl, _or_opt_nl_dl, _three_opt_nl_dl)
+static int dl_phase(tspgpu_ctx *ctx, int slot, int closing, long max_sweeps, double time_left_s, long *sweeps, long *moves, long *looked,
+                    const M2Family &F)
+{
+    return with_slot(ctx, slot, F.check, [&](bool *late) {
+        DlCount dl;
+        const int rc = dl_run(ctx, slot, closing, max_sweeps, deadline_of(time_left_s), sweeps, moves, &dl, late, F);
+        if (rc) return rc;
+        dl_record(ctx, dl);
+        if (looked) *looked = dl.looked;
+        return (int)E_OK;
+    }, true);
+}
+
+// the descent of tspgpu_local_search_nl3_dl on a slot: nl3_descent with every phase a phase with looks; width == 0: no 3-opt
+// phase, which is ornl_descent.  The plain families' counters hold what the plain descents leave
+static int dl_descent(tspgpu_ctx *ctx, int slot, int width, int closing, double time_left_s, Descent *out, Descent3 *out3, DlCount *dl, bool *late)
+{
+    const double t_end = deadline_of(time_left_s);
+    Descent D;
+    Descent3 D3;
+    DlCount total, d;
+    long mk = 0, omk = 0;
+    int rc = E_OK;
+    *late = false;
+    ctx->ornl_count = M2Counters{};
+    ctx->nl3_count = M2Counters{};
+    for (bool more = true; more && !rc && !*late;) {
+        for (;;) {                          // rule 8 of "Neighbour-list Or-opt"
+            long s = 0, m = 0;
+            if ((rc = dl_run(ctx, slot, closing, -1, t_end, &s, &m, &d, late, M2_NL))) break;
+            D.tw += s; D.tm += m; D.nr++; total += d;
+            if (*late) break;
+            if ((rc = dl_run(ctx, slot, closing, -1, t_end, &s, &m, &d, late, M2_ORNL))) break;
+            D.os += s; D.om += m; total += d; omk = std::max(omk, ctx->ornl_count.max_k);
+            if (*late || m == 0) break;
+        }
+        if (rc || *late || width == 0) break;
+        long s = 0, m = 0;
+        if ((rc = dl_run(ctx, slot, closing, -1, t_end, &s, &m, &d, late, M2_NL3))) break;
+        D3.ts += s; D3.tm += m; D3.np++; total += d; mk = std::max(mk, ctx->nl3_count.max_k);
+        more = m != 0;
+    }
+    ctx->ornl_count = M2Counters{D.os, D.om, omk}; ctx->ornl_rounds = D.nr;
+    if (width) { ctx->nl3_count = M2Counters{D3.ts, D3.tm, mk}; ctx->nl3_phases = D3.np; }
+    *out = D; *out3 = D3; *dl = total;
+    return rc;
+}
+
+// a width of 0 .. 16; 0: the checks of the descent without a 3-opt phase
+static int dl_descent_check(tspgpu_ctx *ctx)
+{
+    if (ctx->nl3_width == 0) return ornl_check(ctx);
+    return nl3_check(ctx);
+}
+
+static int kick_check(tspgpu_ctx *ctx)
+{
+    const int rc = need_costs(ctx);
+    if (rc) return rc;
+    if (ctx->n < 8) return fail(ctx, E_INVALID, "a kick needs at least 8 nodes, got %d", ctx->n);
+    if (!ctx->symmetric) return fail(ctx, E_PRECOND, "a kick needs a symmetric cost matrix");
+    return E_OK;
+}
+
+// the slot entry points of the awake sets: a context, costs, a tour in the slot
+static int look_slot_check(tspgpu_ctx *ctx) { return need_costs(ctx); }
+
+extern "C" {
+
+int tspgpu_tour_wake(tspgpu_ctx *ctx, int slot, const int *nodes, int count)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    if (count > 0 && !nodes) return fail(ctx, E_INVALID, "null argument");
+    return with_slot(ctx, slot, look_slot_check, [&](bool *) {
+        for (int x = 0; x < count; x++)
+            if (nodes[x] < 0 || nodes[x] >= ctx->n) return fail(ctx, E_INVALID, "node %d outside 0 .. %d: nothing was changed", nodes[x], ctx->n - 1);
+        LookBuf K;
+        int rc = look_buf(ctx, slot, count >= 0, &K);
+        if (rc) return rc;
+        if (count < 0) { wake_slots(ctx, slot, 1); return (int)E_OK; }
+        if (count == 0) return (int)E_OK;
+        DevBuf<int> d_nodes;
+        HIP_TRY(d_nodes.alloc((size_t)count));
+        HIP_TRY(hipMemcpyAsync(d_nodes, nodes, (size_t)count * 4, hipMemcpyHostToDevice, ctx->stream));
+        hipLaunchKernelGGL(k_look_set, dim3((unsigned)std::min(256, (count + 255) / 256)), dim3(256), 0, ctx->stream, K.awake, ctx->n,
+                           (const int *)d_nodes, count);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(ctx->stream));     // (d_nodes and the caller's array are free again)
+        return (int)E_OK;
+    }, true);
+}
+
+int tspgpu_tour_sleep(tspgpu_ctx *ctx, int slot)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    return with_slot(ctx, slot, look_slot_check, [&](bool *) {
+        LookBuf K;
+        const int rc = look_buf(ctx, slot, false, &K);
+        if (rc) return rc;
+        HIP_TRY(hipMemsetAsync(K.awake, 0, 3 * (size_t)ctx->n, ctx->stream));
+        ctx->look_all[slot] = 0;
+        return (int)E_OK;
+    }, true);
+}
+
+int tspgpu_tour_awake(tspgpu_ctx *ctx, int slot, int family, unsigned char *out, int *count)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    if (family < 0 || family > 2) return fail(ctx, E_INVALID, "family %d: 0 the 2-opt, 1 Or-opt, 2 the 3-opt", family);
+    return with_slot(ctx, slot, look_slot_check, [&](bool *) {
+        LookBuf K;
+        const int rc = look_buf(ctx, slot, false, &K);
+        if (rc) return rc;
+        const size_t n = (size_t)ctx->n;
+        std::vector<unsigned char> h(n, 1);
+        if (!ctx->look_all[slot]) {
+            HIP_TRY(hipMemcpyAsync(h.data(), K.awake + (size_t)family * n, n, hipMemcpyDeviceToHost, ctx->stream));
+            HIP_TRY(hipStreamSynchronize(ctx->stream));
+        }
+        int c = 0;
+        for (size_t v = 0; v < n; v++) { c += h[v] != 0; if (out) out[v] = h[v] != 0; }
+        if (count) *count = c;
+        return (int)E_OK;
+    }, true);
+}
+
+int tspgpu_tour_kick(tspgpu_ctx *ctx, int slot, int i, int j, int k)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    return with_slot(ctx, slot, kick_check, [&](bool *) {
+        if (!(0 <= i && i < j && j < k && k <= ctx->n - 1))
+            return fail(ctx, E_INVALID, "a kick takes edge positions 0 <= i < j < k <= n - 1, got %d, %d, %d (n = %d)", i, j, k, ctx->n);
+        LookBuf K;
+        const int rc = look_buf(ctx, slot, false, &K);
+        if (rc) return rc;
+        unsigned char *awake = ctx->look_all[slot] ? nullptr : K.awake;    // (all awake: the six nodes are awake already)
+        LAUNCH_BY_COST(k_tour_kick, dim3(1), dim3(256), slot, i, j, k, awake);
+        HIP_TRY(hipGetLastError());
+        return (int)E_OK;
+    }, true);
+}
+
+int tspgpu_tour_two_opt_nl_dl(tspgpu_ctx *ctx, int slot, int closing, long max_sweeps, double time_left_s, long *sweeps, long *moves, long *looked)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    return dl_phase(ctx, slot, closing, max_sweeps, time_left_s, sweeps, moves, looked, M2_NL);
+}
+
+int tspgpu_tour_or_opt_nl_dl(tspgpu_ctx *ctx, int slot, int closing, long max_sweeps, double time_left_s, long *sweeps, long *moves, long *looked)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    return dl_phase(ctx, slot, closing, max_sweeps, time_left_s, sweeps, moves, looked, M2_ORNL);
+}
+
+int tspgpu_tour_three_opt_nl_dl(tspgpu_ctx *ctx, int slot, int width, int closing, long max_sweeps, double time_left_s, long *sweeps, long *moves,
+                                long *looked)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    ctx->nl3_width = width;
+    return dl_phase(ctx, slot, closing, max_sweeps, time_left_s, sweeps, moves, looked, M2_NL3);
+}
+
+int tspgpu_tour_local_search_nl3_dl(tspgpu_ctx *ctx, int slot, int width, int closing, double time_left_s, long *two_opt_sweeps, long *two_opt_moves,
+                                    long *or_sweeps, long *or_moves, int *rounds, long *three_sweeps, long *three_moves, int *three_phases,
+                                    long *looked, long *full_sweeps)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    if (width < 0 || width > NL_KMAX) return fail(ctx, E_INVALID, "the descent with looks takes a width of 0 to %d list entries, got %d", NL_KMAX, width);
+    ctx->nl3_width = width;
+    return with_slot(ctx, slot, dl_descent_check, [&](bool *late) {
+        Descent D;
+        Descent3 D3;
+        DlCount dl;
+        const int rc = dl_descent(ctx, slot, width, closing, time_left_s, &D, &D3, &dl, late);
+        descent_out(&D, 1, two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds);
+        descent3_out(D3, three_sweeps, three_moves, three_phases);
+        dl_record(ctx, dl);
+        if (looked) *looked = dl.looked;
+        if (full_sweeps) *full_sweeps = dl.full;
+        return rc;
+    }, true);
+}
+
+int tspgpu_local_search_nl3_dl(tspgpu_ctx *ctx, int width, int closing, int *path, double *cost, double time_left_s, long *two_opt_sweeps,
+                               long *two_opt_moves, long *or_sweeps, long *or_moves, int *rounds, long *three_sweeps, long *three_moves,
+                               int *three_phases, long *looked, long *full_sweeps)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    if (!path || !cost) return fail(ctx, E_INVALID, "null argument");
+    if (width < 0 || width > NL_KMAX) return fail(ctx, E_INVALID, "the descent with looks takes a width of 0 to %d list entries, got %d", NL_KMAX, width);
+    ctx->nl3_width = width;
+    return with_host_tour(ctx, path, cost, false, dl_descent_check, [&](bool *late) {
+        Descent D;
+        Descent3 D3;
+        DlCount dl;
+        const int rc = dl_descent(ctx, 0, width, closing, time_left_s, &D, &D3, &dl, late);
+        descent_out(&D, 1, two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds);
+        descent3_out(D3, three_sweeps, three_moves, three_phases);
+        dl_record(ctx, dl);
+        if (looked) *looked = dl.looked;
+        if (full_sweeps) *full_sweeps = dl.full;
+        return rc;
+    });
 }
 
 } // extern "C"

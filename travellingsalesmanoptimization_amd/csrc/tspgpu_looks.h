@@ -40,6 +40,19 @@ Result drive(Clock &&now, double t_end, int per_look, Round &&round, Look &&look
     return drive(now, t_end, per_look, [](Result &) {}, round, look);
 }
 
+// What the host does when it finds a phase with looks ("Don't-look bits") stopped, from the control blocks it read: the phase's
+// sweeps and budget left (< 0: no cap), the moves of its last sweep and that sweep's |Q|.
+//   END      the phase is over: nothing ran, the last sweep accepted something (so the budget ended it), the last sweep was
+//            full, or the phase does not close
+//   WAKE_END the last sweep accepted nothing and was not full, and the phase closes: every node wakes, but the budget is spent
+//   WAKE_GO  ... and the phase goes on
+enum class AfterStop { END, WAKE_END, WAKE_GO };
+inline AfterStop after_stop(bool closing, long long sweeps, int last_k, int last_q, int n, long long budget)
+{
+    if (!closing || sweeps == 0 || last_k != 0 || last_q >= n) return AfterStop::END;
+    return budget == 0 ? AfterStop::WAKE_END : AfterStop::WAKE_GO;
+}
+
 // The same over a list of live entries, until it is empty (an empty list on entry launches nothing).  group(len) runs at the
 // head of a group; round(len) launches for the first len entries; read() fetches the control blocks (an error code or 0);
 // stopped(entry) says whether an entry leaves.  The list keeps its order, and set_live(list) uploads it (an error code or 0)

@@ -134,9 +134,9 @@ __device__ __forceinline__ void half_argmin(double &d, u64 &key)
 }
 
 template <typename AT, typename CS>
-__device__ __forceinline__ void nl_sweep_node(const Tours &S, const CS cs, int n, int t, const NlBuf &L, const M2Buf &B)
+__device__ __forceinline__ void nl_sweep_unit(const Tours &S, const CS cs, int n, int t, const NlBuf &L, const M2Buf &B, int a)
 {
-    const int l = threadIdx.x & 31, a = (int)blockIdx.x * NL_NODES + (threadIdx.x >> 5);
+    const int l = threadIdx.x & 31;         // a: this half-wave's node; a >= n: it has none (the queued sweep's tail)
     // (no early return: the DPP steps read lanes of both halves; a lane without a candidate carries "none")
     double dd = DBL_MAX;
     u64 key = KEY_NONE;
@@ -172,6 +172,13 @@ __device__ __forceinline__ void nl_sweep_node(const Tours &S, const CS cs, int n
         B.raw_d[a] = dd;
         B.raw_b[a] = key == KEY_NONE ? -1 : (int)key;
     }
+}
+
+// the plain sweep: workgroup g takes the nodes g NL_NODES .. g NL_NODES + NL_NODES - 1
+template <typename AT, typename CS>
+__device__ __forceinline__ void nl_sweep_node(const Tours &S, const CS cs, int n, int t, const NlBuf &L, const M2Buf &B)
+{
+    nl_sweep_unit<AT>(S, cs, n, t, L, B, (int)blockIdx.x * NL_NODES + (threadIdx.x >> 5));
 }
 
 template <typename T>

@@ -104,10 +104,9 @@ __device__ __forceinline__ Nl3Move nl3_decode(const Nl3Pos &T, const NlBuf &NL, 
 }
 
 template <typename AT, typename CS>
-__device__ __forceinline__ void nl3_sweep_node(const Tours &S, const CS cs, int n, int t, const NlBuf &NL, int W, const M2Buf &B)
+__device__ __forceinline__ void nl3_sweep_unit(const Tours &S, const CS cs, int n, int t, const NlBuf &NL, int W, const M2Buf &B, int t1)
 {
-    const int lane = threadIdx.x & 63, t1 = (int)blockIdx.x * NL3_NODES + (threadIdx.x >> 6);
-    if (t1 >= n) return;                    // (a whole wave: no barrier below)
+    const int lane = threadIdx.x & 63;      // t1: this wave's node, 0 <= t1 < n
     const Nl3Pos T = nl3_pos(S, n, t);
     const AT *dnb = dnb_of<AT>(S, t, n), *lw = reinterpret_cast<const AT *>(NL.w);
     const int K = NL.K, F = 4 * W, per = 64 / F;            // lanes per first-level choice: 1 at W = 16, 16 at W = 1
@@ -146,6 +145,15 @@ __device__ __forceinline__ void nl3_sweep_node(const Tours &S, const CS cs, int 
         B.raw_d[t1] = bd;
         B.raw_b[t1] = bk == KEY_NONE ? -1 : (int)bk;
     }
+}
+
+// the plain sweep: workgroup g takes the nodes g NL3_NODES .. g NL3_NODES + NL3_NODES - 1
+template <typename AT, typename CS>
+__device__ __forceinline__ void nl3_sweep_node(const Tours &S, const CS cs, int n, int t, const NlBuf &NL, int W, const M2Buf &B)
+{
+    const int t1 = (int)blockIdx.x * NL3_NODES + (threadIdx.x >> 6);
+    if (t1 >= n) return;                    // (a whole wave: no barrier below)
+    nl3_sweep_unit<AT>(S, cs, n, t, NL, W, B, t1);
 }
 
 template <typename T>

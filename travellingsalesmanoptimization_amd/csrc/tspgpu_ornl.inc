@@ -41,10 +41,9 @@ __device__ __forceinline__ int ornl_pack(int L, int q, int rev) { return L << OR
 __device__ __forceinline__ int ornl_fwd(int c, int n, int dir) { return dir > 0 ? c : n - 1 - c; }
 
 template <typename AT, typename CS>
-__device__ __forceinline__ void ornl_sweep_start(const Tours &S, const CS cs, int n, int t, const NlBuf &NL, const M2Buf &B)
+__device__ __forceinline__ void ornl_sweep_unit(const Tours &S, const CS cs, int n, int t, const NlBuf &NL, const M2Buf &B, int s)
 {
-    const int lane = threadIdx.x & 63, s = (int)blockIdx.x * ORNL_STARTS + (threadIdx.x >> 6);
-    if (s >= n) return;                     // (a whole wave: no barrier below)
+    const int lane = threadIdx.x & 63;      // s: this wave's segment start, 0 <= s < n
     const int *ord = S.ord + (size_t)t * n, *pos = S.pos + (size_t)t * n, *succ = S.succ + (size_t)t * n;
     const AT *dnb = dnb_of<AT>(S, t, n), *lw = reinterpret_cast<const AT *>(NL.w);
     const int K = NL.K, dir = S.dir[t];
@@ -94,6 +93,15 @@ __device__ __forceinline__ void ornl_sweep_start(const Tours &S, const CS cs, in
         B.raw_d[s] = bd;
         B.raw_b[s] = bk == KEY_NONE ? -1 : (int)bk;
     }
+}
+
+// the plain sweep: workgroup g takes the starts g ORNL_STARTS .. g ORNL_STARTS + ORNL_STARTS - 1
+template <typename AT, typename CS>
+__device__ __forceinline__ void ornl_sweep_start(const Tours &S, const CS cs, int n, int t, const NlBuf &NL, const M2Buf &B)
+{
+    const int s = (int)blockIdx.x * ORNL_STARTS + (threadIdx.x >> 6);
+    if (s >= n) return;                     // (a whole wave: no barrier below)
+    ornl_sweep_unit<AT>(S, cs, n, t, NL, B, s);
 }
 
 template <typename T>

@@ -59,7 +59,8 @@ class Engine:
                  "vns_nl_walks", "vns_nl_iterations", "vns_nl_rounds", "vns_nl_max_live", "vns_nl_dry",
                  "persist_shaped",
                  "three_nl_w", "three_nl_sweeps", "three_nl_moves", "three_nl_max_moves", "three_nl_phases", "three_nl_nodes",
-                 "persist_tmat", "persist_packed"]
+                 "persist_tmat", "persist_packed",
+                 "dl_looked", "dl_full_sweeps", "dl_max_queue", "dl_max_wgs"]
         return {k: int(self.L.tspgpu_info(self.ctx, i)) for i, k in enumerate(names)}
 
     # ---- instance
@@ -471,6 +472,68 @@ class Engine:
                       ok=(T_OK, DEADLINE_EXCEEDED))
         return {"two_opt_sweeps": tw.value, "two_opt_moves": tm.value, "or_sweeps": os_.value, "or_moves": om.value, "rounds": nr.value,
                 "three_sweeps": ts.value, "three_moves": tv.value, "three_phases": tp.value, "rc": rc}
+
+    # ---- don't-look bits (include/tspgpu.h "Don't-look bits")
+    def tour_wake(self, slot, nodes=None):
+        """nodes join the slot's three awake sets; None: every node wakes."""
+        if nodes is None:
+            self._ck(self.L.tspgpu_tour_wake(self.ctx, int(slot), None, -1))
+            return
+        a = np.ascontiguousarray(nodes, dtype=np.int32)
+        self._ck(self.L.tspgpu_tour_wake(self.ctx, int(slot), a.ctypes.data, len(a)))
+
+    def tour_sleep(self, slot):
+        self._ck(self.L.tspgpu_tour_sleep(self.ctx, int(slot)))
+
+    def tour_awake(self, slot, family):
+        """the awake set of family 0 (2-opt), 1 (Or-opt) or 2 (3-opt) -> uint8 [n]."""
+        out, cnt = np.empty(self.n, dtype=np.uint8), C.c_int()
+        self._ck(self.L.tspgpu_tour_awake(self.ctx, int(slot), int(family), out.ctypes.data, C.byref(cnt)))
+        assert cnt.value == int(out.sum())
+        return out
+
+    def tour_kick(self, slot, i, j, k):
+        """the segment swap at the edge positions i < j < k, whatever its delta."""
+        self._ck(self.L.tspgpu_tour_kick(self.ctx, int(slot), int(i), int(j), int(k)))
+
+    def _tour_dl(self, fn, slot, head, closing, max_sweeps, time_left_s):
+        s, m, q = C.c_long(), C.c_long(), C.c_long()
+        rc = self._ck(fn(self.ctx, int(slot), *head, int(closing), int(max_sweeps), float(time_left_s), C.byref(s), C.byref(m), C.byref(q)),
+                      ok=(T_OK, DEADLINE_EXCEEDED))
+        return s.value, m.value, q.value, rc
+
+    def tour_two_opt_nl_dl(self, slot, closing=1, max_sweeps=-1, time_left_s=-1.0):
+        """the neighbour-list 2-opt phase with looks on a slot -> (sweeps, moves, looked, rc)."""
+        return self._tour_dl(self.L.tspgpu_tour_two_opt_nl_dl, slot, (), closing, max_sweeps, time_left_s)
+
+    def tour_or_opt_nl_dl(self, slot, closing=1, max_sweeps=-1, time_left_s=-1.0):
+        return self._tour_dl(self.L.tspgpu_tour_or_opt_nl_dl, slot, (), closing, max_sweeps, time_left_s)
+
+    def tour_three_opt_nl_dl(self, slot, width, closing=1, max_sweeps=-1, time_left_s=-1.0):
+        return self._tour_dl(self.L.tspgpu_tour_three_opt_nl_dl, slot, (int(width),), closing, max_sweeps, time_left_s)
+
+    def _descent_dl(self, call):
+        tw, tm, os_, om, nr = C.c_long(), C.c_long(), C.c_long(), C.c_long(), C.c_int()
+        ts, tv, tp, lk, fs = C.c_long(), C.c_long(), C.c_int(), C.c_long(), C.c_long()
+        rc = self._ck(call(C.byref(tw), C.byref(tm), C.byref(os_), C.byref(om), C.byref(nr), C.byref(ts), C.byref(tv), C.byref(tp),
+                           C.byref(lk), C.byref(fs)), ok=(T_OK, DEADLINE_EXCEEDED))
+        return {"two_opt_sweeps": tw.value, "two_opt_moves": tm.value, "or_sweeps": os_.value, "or_moves": om.value, "rounds": nr.value,
+                "three_sweeps": ts.value, "three_moves": tv.value, "three_phases": tp.value, "looked": lk.value, "full_sweeps": fs.value,
+                "rc": rc}
+
+    def tour_local_search_nl3_dl(self, slot, width, closing=1, time_left_s=-1.0):
+        """the descent over the lists with looks on a slot (width 0: no 3-opt phase) -> dict(the counters of
+        tour_local_search_nl3, looked, full_sweeps, rc)."""
+        return self._descent_dl(lambda *out: self.L.tspgpu_tour_local_search_nl3_dl(self.ctx, int(slot), int(width), int(closing),
+                                                                                    float(time_left_s), *out))
+
+    def local_search_nl3_dl(self, path, width, closing=1, time_left_s=-1.0):
+        """the same on a host tour, path in place -> the dict with cost."""
+        c = C.c_double()
+        r = self._descent_dl(lambda *out: self.L.tspgpu_local_search_nl3_dl(self.ctx, int(width), int(closing), path, C.byref(c),
+                                                                            float(time_left_s), *out))
+        r["cost"] = c.value
+        return r
 
     def time_three_nl_sweep(self, slot, width, reps):
         ms = C.c_float()

@@ -784,6 +784,9 @@ static int or_opt_nl_k = 0;
 /* TSP_3OPT_WIDTH=W, W in 1..16 (tsp_run_algorithm), with the two switches above: that descent gets a neighbour-list 3-opt phase
  * over the first W list entries (tspgpu_local_search_nl3) */
 static int three_opt_width = 0;
+/* TSP_DONT_LOOK=1 (tsp_run_algorithm), with TSP_OR_OPT=1 and TSP_OR_OPT_NEIGHBOURS=K [and TSP_3OPT_WIDTH=W]: that descent runs
+ * with don't-look bits and a closing full sweep per phase (tspgpu_local_search_nl3_dl, closing = 1; W = 0: no 3-opt phase) */
+static int dont_look_on = 0;
 
 ERROR_CODE tsp_or_opt_polish(tsp_solution *solution)
 {
@@ -798,15 +801,28 @@ ERROR_CODE tsp_or_opt_polish(tsp_solution *solution)
         const int kp = or_opt_nl_k < tsp_inst.nnodes - 1 ? or_opt_nl_k : tsp_inst.nnodes - 1;
         long or_sweeps = 0, two_opt_moves = 0, three_sweeps = 0, three_moves = 0;
         int three_phases = 0;
-        const char *call = three_opt_width ? "tspgpu_local_search_nl3" : "tspgpu_local_search_nl";
+        long looked = 0, full_sweeps = 0;
+        const char *call = dont_look_on ? "tspgpu_local_search_nl3_dl" : three_opt_width ? "tspgpu_local_search_nl3" : "tspgpu_local_search_nl";
         int rc = tspgpu_info(g, 42) == kp ? 0 : tspgpu_neighbours_build(g, or_opt_nl_k);
-        if (rc == 0 && three_opt_width)
+        if (rc == 0 && dont_look_on)
+            rc = tspgpu_local_search_nl3_dl(g, three_opt_width, 1, solution->path, &solution->cost, time_left(), &sweeps, &two_opt_moves,
+                                            &or_sweeps, &moves, &rounds, &three_sweeps, &three_moves, &three_phases, &looked, &full_sweeps);
+        else if (rc == 0 && three_opt_width)
             rc = tspgpu_local_search_nl3(g, three_opt_width, solution->path, &solution->cost, time_left(), &sweeps, &two_opt_moves, &or_sweeps,
                                          &moves, &rounds, &three_sweeps, &three_moves, &three_phases);
         else if (rc == 0)
             rc = tspgpu_local_search_nl(g, solution->path, &solution->cost, time_left(), &sweeps, &two_opt_moves, &or_sweeps, &moves, &rounds);
         if (or_opt_refusal(from_rc(rc))) log_warn("%s: %s", call, tspgpu_last_error(g));
         else if (rc != 0 && rc != DEADLINE_EXCEEDED) log_error("%s: %s", call, tspgpu_last_error(g));
+        else if (dont_look_on && !three_opt_width)
+            log_debug("Or-opt polish over lists of %d with don't-look bits: %d rounds, %ld 2-opt sweeps (%ld moves), %ld Or-opt sweeps (%ld moves), "
+                      "%ld units looked at, %ld full sweeps, cost %f", or_opt_nl_k, rounds, sweeps, two_opt_moves, or_sweeps, moves, looked,
+                      full_sweeps, solution->cost);
+        else if (dont_look_on)
+            log_debug("Or-opt polish over lists of %d with 3-opt over %d and don't-look bits: %d rounds, %ld 2-opt sweeps (%ld moves), %ld Or-opt "
+                      "sweeps (%ld moves), %d 3-opt phases, %ld sweeps (%ld moves), %ld units looked at, %ld full sweeps, cost %f", or_opt_nl_k,
+                      three_opt_width, rounds, sweeps, two_opt_moves, or_sweeps, moves, three_phases, three_sweeps, three_moves, looked, full_sweeps,
+                      solution->cost);
         else if (three_opt_width)
             log_debug("Or-opt polish over lists of %d with 3-opt over %d: %d rounds, %ld 2-opt sweeps (%ld moves), %ld Or-opt sweeps (%ld moves), "
                       "%d 3-opt phases, %ld sweeps (%ld moves), cost %f", or_opt_nl_k, three_opt_width, rounds, sweeps, two_opt_moves, or_sweeps,
@@ -963,6 +979,9 @@ ERROR_CODE tsp_run_algorithm(void)
     /* TSP_3OPT_WIDTH=W (env_neighbours): the TSP_OR_OPT polish over the lists gets a 3-opt phase over their first W entries */
     const int width3 = env_neighbours("TSP_3OPT_WIDTH");
     if (width3 < 0) return INVALID_ARGUMENT;
+    /* TSP_DONT_LOOK=1 (env_switch): that polish over the lists runs with don't-look bits */
+    const int dont_look = env_switch("TSP_DONT_LOOK");
+    if (dont_look < 0) return INVALID_ARGUMENT;
     if (es_k && ((nl_k && nl_k != es_k) || (or_nl_k && or_nl_k != es_k))) {
         fprintf(stderr, "tsp: TSP_EVERY_START_NEIGHBOURS=%d and TSP_%s_NEIGHBOURS=%d: the list lengths must be equal\n", es_k,
                 nl_k && nl_k != es_k ? "2OPT" : "OR_OPT", nl_k && nl_k != es_k ? nl_k : or_nl_k);
@@ -1007,6 +1026,8 @@ ERROR_CODE tsp_run_algorithm(void)
     if (or_nl_k && !polish) log_warn("TSP_OR_OPT_NEIGHBOURS=%d has no effect without TSP_OR_OPT=1", or_nl_k);
     three_opt_width = or_opt_nl_k ? width3 : 0;
     if (width3 && !or_opt_nl_k) log_warn("TSP_3OPT_WIDTH=%d has no effect without TSP_OR_OPT=1 and TSP_OR_OPT_NEIGHBOURS=K", width3);
+    dont_look_on = or_opt_nl_k ? dont_look : 0;
+    if (dont_look && !or_opt_nl_k) log_warn("TSP_DONT_LOOK=1 has no effect without TSP_OR_OPT=1 and TSP_OR_OPT_NEIGHBOURS=K");
     two_opt_multi_on = multi;
     two_opt_nl_k = nl_k;
     two_opt_nl_polish = nl_polish;
