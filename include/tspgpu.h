@@ -690,6 +690,42 @@ int tspgpu_local_search_nl3_dl(tspgpu_ctx *ctx, int width, int closing, int *pat
                                long *two_opt_sweeps, long *two_opt_moves, long *or_sweeps, long *or_moves, int *rounds,
                                long *three_sweeps, long *three_moves, int *three_phases, long *looked, long *full_sweeps);
 
+/* ---- Greedy-edge construction (an extension: the greedy-edge tour over the neighbour lists, built on the device) ----------
+ * A second single-tour construction next to tspgpu_tour_nn: the usual start of list-based 2-opt / 3-opt with don't-look bits.
+ * Opt-in: no other entry point changes.
+ * Preconditions: those of "Neighbour-list 2-opt" -- costs or points in place, a symmetric matrix, lists built for the cost
+ * source in place with K' = min(K, n - 1), n >= 5 -- without that section's row-in-LDS limit.
+ *   1. Edges and keys.  An edge is an unordered pair {a, b}, a < b; its key is (c[a][b], a, b), compared lexicographically, the
+ *      cost exactly as the lists compare it (integers for uint16 / int32 cells and in matrix-free mode, doubles for f64 cells).
+ *      Keys are distinct, so the order is total.
+ *   2. State.  A set S of accepted edges in which every node has degree <= 2 and which has no cycle: a set of paths
+ *      ("fragments"); a node of degree 0 is a fragment of its own.  An edge {a, b} is valid if both ends have degree < 2 and a
+ *      and b are not the two ends of the same fragment.
+ *   3. Phase 1 (list edges).  E1 = { {v, u} : u in N(v) }, membership in either direction.  S is the result of the sequential
+ *      greedy over E1: the edges in ascending key order, each accepted iff it is valid when it is reached.
+ *   4. Phase 2 (joining).  E2 = all pairs of nodes that have degree < 2 after phase 1.  The same sequential greedy goes on over
+ *      E2 in ascending key order until a single fragment covers all n nodes; the edge between its two ends closes the tour.
+ *   5. Orientation.  The slot's order starts at node 0, and the successor of node 0 is the smaller-numbered of its two tour
+ *      neighbours.  The slot is then initialised as a loaded tour is: dir = +1, the cost recomputed in node order as ref_2opt
+ *      does (refinment.c:6-9), last delta 0, every node awake in all three sets of "Don't-look bits".
+ *   6. Equality with plain greedy edge.  With K' = n - 1 (n <= 17 at K = 16) E1 is every pair, and the result is the textbook
+ *      greedy-edge tour under the key order.
+ *   7. Rounds.  The device computes S without sorting, in rounds of locally dominant edges: best(v) is the smallest key among the
+ *      valid edges of the phase's edge set at v, a fragment's best the smaller of its two ends' bests, and an edge is accepted
+ *      iff it is the best of both fragments it joins.  This is the sequential result: an accepted edge is smaller than every
+ *      valid edge at the four ends of its two fragments, and whatever could block it in the sequential order would be such an
+ *      edge.  The globally smallest valid edge is always accepted, so a phase has at most n - 1 rounds; the counters below count
+ *      the rounds that accepted an edge.
+ * Codes: no context 14; a null argument or a negative slot 3; n < 5 3; no costs 9; an asymmetric matrix 9; lists not built or
+ * invalidated 9 (the text of "Neighbour-list 2-opt").
+ * Memory: 80 n bytes per context at the first construction, all of it or none; dropped with the lists and with the instance.
+ * tspgpu_info: 74 / 75 the rounds of phase 1 / phase 2 of the last construction, 76 the edges phase 1 accepted, 77 the free
+ * nodes (degree < 2) entering phase 2. */
+/* the greedy-edge tour straight into a slot, as tspgpu_tour_nn (the slot array grows on demand) */
+int tspgpu_tour_greedy(tspgpu_ctx *ctx, int slot);
+/* the same into host arrays (successor array and cost), slot 0 as scratch */
+int tspgpu_greedy_tour(tspgpu_ctx *ctx, int *path /* [n] */, double *cost);
+
 /* ---- Batched neighbour-list descent (an extension: the descent over the lists on a batch of tours, and the multi-start) ----
  * The descent of "Neighbour-list Or-opt" (rule 8) on many tours at once: every launch serves every tour of the batch that
  * is still descending.  For each tour of the batch the descent is exactly rule 8, run on that tour alone:

@@ -42,6 +42,8 @@ INFO_PERSIST_PACKED = 69                # the last LDS-resident descent / tabu w
 # ... units looked at, full sweeps and the largest sweep that was not full of the last call with don't-look bits; the most
 # workgroups of a queued sweep
 INFO_DL_LOOKED, INFO_DL_FULL_SWEEPS, INFO_DL_MAX_QUEUE, INFO_DL_MAX_WGS = 70, 71, 72, 73
+# ... the last greedy-edge construction: rounds of phase 1 and of phase 2, edges phase 1 accepted, free nodes entering phase 2
+INFO_GREEDY_ROUNDS1, INFO_GREEDY_ROUNDS2, INFO_GREEDY_EDGES1, INFO_GREEDY_FREE = 74, 75, 76, 77
 EM_FORM_AUTO, EM_FORM_RESIDENT, EM_FORM_PER_STEP = 0, 1, 2
 MOPT_EXCHANGE = 1000
 EXCHANGE_AUTO, EXCHANGE_HOST, EXCHANGE_RCCL = 0, 1, 2
@@ -147,6 +149,8 @@ SIGNATURES = {
     "tspgpu_tour_three_opt_nl_dl": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_long, C.c_double, _pl, _pl, _pl]),
     "tspgpu_tour_local_search_nl3_dl": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_double, _pl, _pl, _pl, _pl, _pi, _pl, _pl, _pi, _pl, _pl]),
     "tspgpu_local_search_nl3_dl": (C.c_int, [_ctx, C.c_int, C.c_int, _ip, _pd, C.c_double, _pl, _pl, _pl, _pl, _pi, _pl, _pl, _pi, _pl, _pl]),
+    "tspgpu_tour_greedy": (C.c_int, [_ctx, C.c_int]),
+    "tspgpu_greedy_tour": (C.c_int, [_ctx, _ip, _pd]),
     "tspgpu_multi_neighbours_build": (C.c_int, [_ctx, C.c_int]),
     "tspgpu_multi_multistart_local_search_nl": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_double, _ip, _pd, _pi, _pl, _pl, _pl, _pl]),
 }

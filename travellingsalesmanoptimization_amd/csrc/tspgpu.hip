@@ -3112,6 +3112,7 @@ __global__ void k_cap_now(Tours S, int slot0, int count)
 #include "tspgpu_ornl.inc"
 #include "tspgpu_nl3opt.inc"
 #include "tspgpu_looks_dl.inc"
+#include "tspgpu_greedy.inc"
 #include "tspgpu_nlbatch.inc"
 #include "tspgpu_nlvns.inc"
 
@@ -3169,6 +3170,16 @@ struct MEM_GROUP InstanceMem {            // of one n: new_instance drops it
     int *d_lq = nullptr;
     LookCtl *d_look = nullptr;
 
+    // greedy-edge construction (tspgpu_greedy.inc): best keys, adjacency, degrees, other_end, accept flags, the free list, the
+    // rank buffers and the control block, 80 n bytes: all of them at the first construction, or none; dropped with the lists
+    GeBuf ge{};
+    Rows ge_rows(size_t n)
+    {
+        return {{&ge.bw, n * 8}, {&ge.be, n * 8}, {&ge.adj, n * 8}, {&ge.deg, n * 4}, {&ge.oe, n * 4}, {&ge.acc, n * 4}, {&ge.fl, n * 4},
+                {&ge.nxt, n * 16}, {&ge.dist, n * 16}, {&ge.ctl, sizeof(GeCtl), 0, 0}};
+    }
+    void drop_greedy() { tspmem::free_rows<HipMem>(ge_rows(0)); }
+
     Rows look_ctx_rows(size_t n) { return {{&d_lq, n * 4}, {&d_look, sizeof(LookCtl), 0, 0}}; }
     void drop_look_ctx() { tspmem::free_rows<HipMem>(look_ctx_rows(0)); }
     static Rows m2_rows(M2Buf &B, size_t n)
@@ -3180,7 +3191,7 @@ struct MEM_GROUP InstanceMem {            // of one n: new_instance drops it
     void drop_nlv() { tspmem::free_rows<HipMem>(nlv_rows(0)); nlv_cap = 0; tspmem::reset_all(d_nlv_rand, d_nlv_trace); }
     void drop_nlb() { tspmem::free_rows<HipMem>(nlb_rows(0)); nlb_cap = 0; drop_nlv(); }
     void drop_grid() { tspmem::reset_all(d_gxy, d_gidx, d_gpos, d_cstart, d_gcell, d_knn); grid_G = 0; grid_ok = false; }
-    void reset() { tspmem::free_rows<HipMem>(m2_rows(m2, 0)); drop_look_ctx(); drop_nlb(); drop_grid(); }
+    void reset() { tspmem::free_rows<HipMem>(m2_rows(m2, 0)); drop_look_ctx(); drop_greedy(); drop_nlb(); drop_grid(); }
     ~InstanceMem() { reset(); }
 };
 
@@ -3350,6 +3361,8 @@ struct tspgpu_ctx : ContextMem, InstanceMem, CostMem, SlotMem {
     int nl3_phases = 0;
     // don't-look bits (tspgpu_looks_dl.inc): units looked at, full sweeps and the largest sweep that was not full of the last call
     long dl_looked = 0, dl_full = 0, dl_max_q = 0;
+    // greedy-edge construction (tspgpu_greedy.inc): the last one's rounds per phase, phase-1 edges, free nodes entering phase 2
+    long ge_rounds1 = 0, ge_rounds2 = 0, ge_edges1 = 0, ge_free = 0;
     // batched neighbour-list descent (tspgpu_nlbatch.inc)
     long nlb_tours = 0, nlb_launches = 0, nlb_max_live = 0;     // the last batched descent: tours, sweeps launched, most tours in one
     // neighbour-list VNS (tspgpu_nlvns.inc): the last call's walks, iterations completed, sweep rounds, most walks live in one, dry walks
@@ -3389,6 +3402,7 @@ static void drop_graphs(tspgpu_ctx *ctx)
 static void free_matrix(tspgpu_ctx *ctx)
 {
     if (ctx->nl.K) ctx->nl_dropped = true;  // the neighbour lists belong to the old costs
+    ctx->drop_greedy();                     // (the construction's scratch goes with them)
     ctx->CostMem::reset();
     ctx->have_costs = false;
     ctx->or_otf_form = ctx->or_otf_R = 0;
@@ -5107,6 +5121,10 @@ long tspgpu_info(const tspgpu_ctx *ctx, int what)
     case 71: return ctx->dl_full;
     case 72: return ctx->dl_max_q;
     case 73: return (long)LOOK_WGS_PER_CU * ctx->cus;
+    case 74: return ctx->ge_rounds1;
+    case 75: return ctx->ge_rounds2;
+    case 76: return ctx->ge_edges1;
+    case 77: return ctx->ge_free;
     case 55: return ctx->have_costs && ctx->symmetric && ctx->n >= 8 ? (ctx->n + ORNL_STARTS - 1) / ORNL_STARTS : 0;
     case 12: return (ctx->built && ctx->grid_ok && ctx->opt_nn != 1 && ctx->cost_bound < 134217728.0) ? ctx->grid_G : 0;
     case 13: return ctx->grid_max_occ;
@@ -6633,7 +6651,7 @@ int tspgpu_neighbours_build(tspgpu_ctx *ctx, int K)
 {
     if (!ctx) return E_UNAVAILABLE;
     hipSetDevice(ctx->device);
-    if (K == 0) { ctx->drop_nl(); ctx->nl_dropped = false; return E_OK; }
+    if (K == 0) { ctx->drop_nl(); ctx->drop_greedy(); ctx->nl_dropped = false; return E_OK; }
     if (K < 0 || K > NL_KMAX) return fail(ctx, E_INVALID, "neighbour lists hold 1 to %d nodes, got K = %d", NL_KMAX, K);
     int rc = need_costs(ctx);
     if (rc) return rc;
@@ -7321,6 +7339,129 @@ int tspgpu_local_search_nl3_dl(tspgpu_ctx *ctx, int width, int closing, int *pat
         if (full_sweeps) *full_sweeps = dl.full;
         return rc;
     });
+}
+
+} // extern "C"
+
+// ---- greedy-edge construction over the neighbour lists (tspgpu_greedy.inc) ---------------------------------------------------
+
+// the preconditions of "Neighbour-list 2-opt" without its row-in-LDS limit: no kernel here holds a matrix row
+static int greedy_check(tspgpu_ctx *ctx)
+{
+    const int rc = need_costs(ctx);
+    if (rc) return rc;
+    if (ctx->n < 5) return fail(ctx, E_INVALID, "the greedy-edge construction needs at least 5 nodes, got %d", ctx->n);
+    if (!ctx->symmetric) return fail(ctx, E_PRECOND, "the greedy-edge construction needs a symmetric cost matrix");
+    if (!ctx->nl.K)
+        return fail(ctx, E_PRECOND, ctx->nl_dropped ? "the neighbour lists were invalidated by a new cost source: call tspgpu_neighbours_build again"
+                                                    : "no neighbour lists: call tspgpu_neighbours_build first");
+    return E_OK;
+}
+
+// rounds of one phase in batches of GE_ROUNDS_PER_LOOK behind one another on the stream; the host reads the control block per
+// batch.  A phase has at most n - 1 rounds that accept an edge and one that does not
+constexpr int GE_ROUNDS_PER_LOOK = 16;
+
+template <typename R> static int greedy_phase(tspgpu_ctx *ctx, int ph, GeCtl *C, R &&round)
+{
+    int r = 0;
+    const looks::Result res = looks::drive(
+        now_s, -1.0, GE_ROUNDS_PER_LOOK,
+        [&]() -> int {
+            const int rc = round(r);
+            r++;
+            return rc;
+        },
+        [&]() -> int {
+            const int rc = ctl_get(ctx, C, (const GeCtl *)ctx->ge.ctl);
+            if (rc) return rc;
+            if (C->done[ph]) return (int)looks::STOP;
+            if (r > ctx->n + GE_ROUNDS_PER_LOOK) return fail(ctx, E_INTERNAL, "greedy-edge phase %d did not end within %d rounds", ph + 1, r);
+            return (int)looks::GO_ON;
+        });
+    return res.code;
+}
+
+// the greedy-edge tour of the cost source in place into `slot` (checked, and the slot array grown, by the caller)
+static int greedy_build(tspgpu_ctx *ctx, int slot)
+{
+    const int n = ctx->n;
+    if (!ctx->ge.ctl) HIP_TRY(tspmem::grow(HipMem{ctx->stream}, ctx->ge_rows((size_t)n), 0, 1));
+    const GeBuf G = ctx->ge;
+    const NlBuf L = ctx->nl;
+    const dim3 nodes((n + GE_BT - 1) / GE_BT), darts((2 * n + GE_BT - 1) / GE_BT), block(GE_BT);
+    hipStream_t st = ctx->stream;
+    HIP_TRY(hipMemsetAsync(G.ctl, 0, sizeof(GeCtl), st));
+    hipLaunchKernelGGL(k_ge_init, nodes, block, 0, st, G, n);
+    HIP_TRY(hipGetLastError());
+    GeCtl C;
+    memset(&C, 0, sizeof C);
+    const bool f64 = ctx->elem == TSPGPU_ELEM_F64;
+    int rc = greedy_phase(ctx, 0, &C, [&](int r) -> int {
+        if (f64) {
+            hipLaunchKernelGGL((k_ge_p1<double, 0>), nodes, block, 0, st, G, L, n);
+            hipLaunchKernelGGL((k_ge_p1<double, 1>), nodes, block, 0, st, G, L, n);
+        } else {
+            hipLaunchKernelGGL((k_ge_p1<int, 0>), nodes, block, 0, st, G, L, n);
+            hipLaunchKernelGGL((k_ge_p1<int, 1>), nodes, block, 0, st, G, L, n);
+        }
+        hipLaunchKernelGGL(k_ge_accept, nodes, block, 0, st, G, n, 0, r & 1);
+        hipLaunchKernelGGL(k_ge_link, nodes, block, 0, st, G, n, 0, r);
+        HIP_TRY(hipGetLastError());
+        return E_OK;
+    });
+    if (rc) return rc;
+    const dim3 scan((unsigned)std::max(1, std::min((n + 3) / 4, 4 * ctx->cus)));    // a wave per free node, striding
+    rc = greedy_phase(ctx, 1, &C, [&](int r) -> int {
+        hipLaunchKernelGGL(k_ge_p2_compact, nodes, block, 0, st, G, n, r & 1);
+        ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_ge_p2_best<T>), scan, block, 0, st, G, (const T *)ctx->d_mat.p, ctx->d_pts, ctx->kind,
+                                                     ctx->ld, n, r & 1));
+        hipLaunchKernelGGL(k_ge_accept, nodes, block, 0, st, G, n, 1, r & 1);
+        hipLaunchKernelGGL(k_ge_link, nodes, block, 0, st, G, n, 1, r);
+        HIP_TRY(hipGetLastError());
+        return E_OK;
+    });
+    if (rc) return rc;
+    if (C.edges[0] + C.edges[1] != (unsigned)(n - 1))
+        return fail(ctx, E_INTERNAL, "the greedy-edge construction ended with %u edges of %d", C.edges[0] + C.edges[1], n - 1);
+    ctx->ge_rounds1 = C.rounds[0]; ctx->ge_rounds2 = C.rounds[1]; ctx->ge_edges1 = C.edges[0]; ctx->ge_free = C.free_in;
+    // the order: close the path, rank the darts (ceil(log2 n) jumps between the two halves of the rank buffers), write ord[]
+    hipLaunchKernelGGL(k_ge_close, nodes, block, 0, st, G, n);
+    hipLaunchKernelGGL(k_ge_rank_init, darts, block, 0, st, G, n);
+    int cur = 0;
+    for (int reach = 1; reach < n; reach *= 2, cur ^= 1)
+        hipLaunchKernelGGL(k_ge_rank_jump, darts, block, 0, st, G.nxt + (size_t)cur * 2 * n, G.dist + (size_t)cur * 2 * n,
+                           G.nxt + (size_t)(cur ^ 1) * 2 * n, G.dist + (size_t)(cur ^ 1) * 2 * n, 2 * n);
+    hipLaunchKernelGGL(k_ge_rank_out, darts, block, 0, st, G, G.nxt + (size_t)cur * 2 * n, G.dist + (size_t)cur * 2 * n, ctx->S, slot, n);
+    HIP_TRY(hipGetLastError());
+    if ((rc = init_slots(ctx, slot, 1, -1))) return rc;
+    mark_slots(ctx, slot, 1, true);
+    return E_OK;
+}
+
+extern "C" {
+
+int tspgpu_tour_greedy(tspgpu_ctx *ctx, int slot)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    if (slot < 0) return fail(ctx, E_INVALID, "bad slot %d", slot);
+    hipSetDevice(ctx->device);
+    int rc = greedy_check(ctx);
+    if (rc) return rc;
+    if ((rc = ensure_tours(ctx, slot + 1))) return rc;
+    return greedy_build(ctx, slot);
+}
+
+int tspgpu_greedy_tour(tspgpu_ctx *ctx, int *path, double *cost)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    if (!path || !cost) return fail(ctx, E_INVALID, "null argument");
+    hipSetDevice(ctx->device);
+    int rc = greedy_check(ctx);
+    if (rc) return rc;
+    if ((rc = ensure_tours(ctx, 1))) return rc;
+    if ((rc = greedy_build(ctx, 0))) return rc;
+    return store_path(ctx, 0, path, cost, nullptr);
 }
 
 } // extern "C"

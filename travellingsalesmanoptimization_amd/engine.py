@@ -60,7 +60,8 @@ class Engine:
                  "persist_shaped",
                  "three_nl_w", "three_nl_sweeps", "three_nl_moves", "three_nl_max_moves", "three_nl_phases", "three_nl_nodes",
                  "persist_tmat", "persist_packed",
-                 "dl_looked", "dl_full_sweeps", "dl_max_queue", "dl_max_wgs"]
+                 "dl_looked", "dl_full_sweeps", "dl_max_queue", "dl_max_wgs",
+                 "greedy_rounds1", "greedy_rounds2", "greedy_edges1", "greedy_free"]
         return {k: int(self.L.tspgpu_info(self.ctx, i)) for i, k in enumerate(names)}
 
     # ---- instance
@@ -534,6 +535,17 @@ class Engine:
                                                                             float(time_left_s), *out))
         r["cost"] = c.value
         return r
+
+    # ---- greedy-edge construction (include/tspgpu.h "Greedy-edge construction")
+    def tour_greedy(self, slot):
+        """the greedy-edge tour over the neighbour lists into a slot, as tour_nn."""
+        self._ck(self.L.tspgpu_tour_greedy(self.ctx, int(slot)))
+
+    def greedy_tour(self):
+        """the same into host arrays -> (path, cost)."""
+        path, c = np.empty(self.n, dtype=np.int32), C.c_double()
+        self._ck(self.L.tspgpu_greedy_tour(self.ctx, path, C.byref(c)))
+        return path, c.value
 
     def time_three_nl_sweep(self, slot, width, reps):
         ms = C.c_float()

@@ -260,13 +260,34 @@ ERROR_CODE h_greedyutil(int starting_node, tsp_solution *solution, double *costs
     return from_rc(rc);
 }
 
+/* TSP_GREEDY_EDGE_NEIGHBOURS=K (tsp_run_algorithm): h_Greedy builds the greedy-edge tour over neighbour lists of K nodes
+ * (tspgpu_greedy_tour) instead of the nearest-neighbour tour; an extension, the reference has no such construction */
+static int greedy_edge_k = 0;
+
+static ERROR_CODE greedy_edge_tour(tsp_solution *solution)
+{
+    if (past_deadline()) { log_warn("time limit exceeded in the greedy-edge construction"); return DEADLINE_EXCEEDED; }
+    thread_ctx *lease;
+    tspgpu_ctx *g = ctx_for(tsp_inst.costs, &lease);
+    if (!g) return UNAVAILABLE;
+    /* the lists belong to the costs in place: built when the context holds none of that length */
+    const int kp = greedy_edge_k < tsp_inst.nnodes - 1 ? greedy_edge_k : tsp_inst.nnodes - 1;
+    int rc = tspgpu_info(g, 42) == kp ? 0 : tspgpu_neighbours_build(g, greedy_edge_k);
+    if (rc == 0) rc = tspgpu_greedy_tour(g, solution->path, &solution->cost);
+    if (rc) log_error("tspgpu_greedy_tour: %s", tspgpu_last_error(g));
+    else log_debug("greedy-edge tour over lists of %d: %ld + %ld rounds, %ld list edges, %ld free nodes joined, cost %f", greedy_edge_k,
+                   tspgpu_info(g, 74), tspgpu_info(g, 75), tspgpu_info(g, 76), tspgpu_info(g, 77), solution->cost);
+    thread_done(lease);
+    return from_rc(rc);
+}
+
 /* heuristics.c:12-32 */
 ERROR_CODE h_Greedy(void)
 {
-    log_info("running Nearest Neighbour");
+    log_info(greedy_edge_k ? "running Greedy Edge" : "running Nearest Neighbour");
     tsp_solution s;
     tsp_init_solution(tsp_inst.nnodes, &s);
-    ERROR_CODE e = h_greedyutil(tsp_inst.starting_node, &s, tsp_inst.costs);
+    ERROR_CODE e = greedy_edge_k ? greedy_edge_tour(&s) : h_greedyutil(tsp_inst.starting_node, &s, tsp_inst.costs);
     if (!err_ok(e)) log_error("code %d : greedy did not finish correctly", e);
     else {
         e = tsp_update_best_solution(&s);
@@ -999,6 +1020,23 @@ ERROR_CODE tsp_run_algorithm(void)
                 nl_k && nl_k != vns_k ? "2OPT" : "OR_OPT", nl_k && nl_k != vns_k ? nl_k : or_nl_k);
         return INVALID_ARGUMENT;
     }
+    /* TSP_GREEDY_EDGE_NEIGHBOURS=K (env_neighbours): -alg GREEDY builds the greedy-edge tour over lists of K nodes */
+    const int ge_k = env_neighbours("TSP_GREEDY_EDGE_NEIGHBOURS");
+    if (ge_k < 0) return INVALID_ARGUMENT;
+    {
+        const struct { const char *name; int k; } others[] = {{"2OPT", nl_k}, {"OR_OPT", or_nl_k}, {"EVERY_START", es_k}, {"VNS", vns_k}};
+        for (size_t x = 0; ge_k && x < sizeof others / sizeof others[0]; x++)
+            if (others[x].k && others[x].k != ge_k) {
+                fprintf(stderr, "tsp: TSP_GREEDY_EDGE_NEIGHBOURS=%d and TSP_%s_NEIGHBOURS=%d: the list lengths must be equal\n", ge_k,
+                        others[x].name, others[x].k);
+                return INVALID_ARGUMENT;
+            }
+    }
+    greedy_edge_k = tsp_inst.alg == ALG_GREEDY ? ge_k : 0;
+    if (ge_k && tsp_inst.alg == ALG_GREEDY)
+        log_warn("TSP_GREEDY_EDGE_NEIGHBOURS=%d: -alg GREEDY builds the greedy-edge tour, not the nearest-neighbour tour; results differ from "
+                 "the reference's", ge_k);
+    else if (ge_k) log_warn("TSP_GREEDY_EDGE_NEIGHBOURS=%d has no effect without -alg GREEDY", ge_k);
     int vns_w = 1;
     {
         const char *v = getenv("TSP_VNS_WALKS");
