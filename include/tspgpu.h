@@ -125,7 +125,8 @@ int  tspgpu_set_option(tspgpu_ctx *ctx, int option, long value);
  * sections below; 61 the last LDS-resident descent ran in an instantiation of k_lds2opt compiled for its shape (plain 2-opt,
  * packed 16-bit costs, (n, edges per workgroup) = (4096, 16) or (1024, 4); 0: the generic kernel); 62 .. 67 in
  * "Neighbour-list 3-opt" below; 68 with tspgpu_debug_tmat below; 69 the last LDS-resident descent, tabu walk or VNS walk (whole rows or
- * half-window rows) ran the loop over packed 16-bit deltas (every cost <= 16383; the tabu walk: <= 8190), 0: 32-bit deltas */
+ * half-window rows) ran the loop over packed 16-bit deltas (every cost <= 16383; the tabu walk: <= 8190), 0: 32-bit deltas; 70 .. 77 in
+ * the sections below; 78 .. 81 in "Batched neighbour-list 3-opt" below */
 long tspgpu_info(const tspgpu_ctx *ctx, int what);
 
 /* ---- instance / cost matrix ------------------------------------------- */
@@ -813,6 +814,57 @@ int tspgpu_vns_walks_nl(tspgpu_ctx *ctx, int walks, int k, double time_left_s,
                         int *best_paths /* [walks][n] in/out */, double *best_costs /* [walks] in/out */,
                         double *trace /* [walks][k] or NULL; only the iterations this call completes are written */,
                         long *totals /* [walks][6] or NULL: two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds, kicks of this call */);
+
+/* ---- Batched neighbour-list 3-opt (an extension: the descent with a 3-opt phase on a batch of tours, the multi-start, the walks) ----
+ * The descent of "Neighbour-list 3-opt" (rule 10) on many tours at once, in the way of "Batched neighbour-list descent": every
+ * launch serves every tour of the batch that is still descending.  For each tour of the batch the descent is exactly rule 10,
+ * run on that tour alone with the slot's cost taken as it stands:
+ *   1. the neighbour-list 2-opt phase runs until a sweep accepts nothing; that sweep is counted;
+ *   2. the neighbour-list Or-opt phase runs until a sweep accepts nothing; that sweep is counted;
+ *   3. 1 and 2 repeat until an Or-opt phase applies nothing: a part of rule 8 has ended;
+ *   4. the neighbour-list 3-opt phase (rule 9, W = min(width, K')) runs until a sweep accepts nothing; that sweep is counted;
+ *   5. 1 to 4 repeat until a 3-opt phase applies nothing.
+ * Tours do not interact, and a tour's phases advance on the device without a host read in between.  At the close of a sweep
+ * that accepted nothing (phase 0 = 2-opt, 1 = Or-opt, 2 = 3-opt): 0 -> 1;  1 -> 0 with rounds += 1 if the Or-opt phase applied
+ * something, 1 -> 2 with three_phases += 1 if it applied nothing;  2 -> 0 with rounds += 1 if the 3-opt phase applied something
+ * (a new part of rule 8 begins at its round 1, and `rounds` sums the rounds of the parts), and the descent ends behind a 3-opt
+ * phase that applied nothing.  Each slot ends exactly as tspgpu_tour_local_search_nl3 would leave it: the successor array, the
+ * cost (bit-equal for double cells as well: the same tree of fixed shape sums a sweep's accepted deltas) and the last delta as
+ * tspgpu_tour_store shows them, the eight counters, and a slot that every later slot call can use.
+ * Matrix mode (uint16, int32, f64 cells) and matrix-free mode.
+ * Preconditions, memory and codes: those of "Batched neighbour-list descent" (the walks: of "Neighbour-list VNS"), and a width
+ * outside 1 .. 16 is 3.
+ * tspgpu_info: 52 .. 55 describe the last batched list descent of either kind; 78 the W in effect of the last batched list
+ * descent (0: it had no 3-opt phase), 79 / 80 its 3-opt sweeps / moves summed over the tours, 81 the most moves one tour's
+ * 3-opt sweep accepted. */
+/* the descent on slots slot0 .. slot0+count-1 at once; per-slot outputs, [count] each (each may be NULL) */
+int tspgpu_tours_local_search_nl3(tspgpu_ctx *ctx, int slot0, int count, int width, double time_left_s,
+                                  long *two_opt_sweeps, long *two_opt_moves, long *or_sweeps, long *or_moves, int *rounds,
+                                  long *three_sweeps, long *three_moves, int *three_phases);
+/* tspgpu_multistart_local_search_nl with this descent: its chunks, its winner (strict <, ties to the earliest entry), its
+ * refusal of a sweep cap and its deadline behaviour */
+int tspgpu_multistart_local_search_nl3(tspgpu_ctx *ctx, int width, const int *starts, int nstarts, double time_left_s,
+                                       int *best_path, double *best_cost, int *best_start,
+                                       long *total_two_opt_sweeps, long *total_two_opt_moves,
+                                       long *total_or_sweeps, long *total_or_moves,
+                                       long *total_three_sweeps, long *total_three_moves, double *costs_out);
+/* ... sharded as tspgpu_multi_multistart_local_search_nl is (entry p of the list on device p mod G, the same exchange) */
+int tspgpu_multi_multistart_local_search_nl3(tspgpu_multi *m, int width, const int *starts, int nstarts, double time_left_s,
+                                             int *best_path, double *best_cost, int *best_start,
+                                             long *total_two_opt_sweeps, long *total_two_opt_moves,
+                                             long *total_or_sweeps, long *total_or_moves,
+                                             long *total_three_sweeps, long *total_three_moves);
+/* tspgpu_vns_walks_nl with this descent in step 1: every rule of "Neighbour-list VNS" holds with rule 10 of "Neighbour-list
+ * 3-opt" in the place of rule 8, so every iteration equals tspgpu_tour_load + tspgpu_tour_local_search_nl3 on the kicked tour,
+ * bit for bit */
+int tspgpu_vns_walks_nl3(tspgpu_ctx *ctx, int width, int walks, int k, double time_left_s,
+                         int *paths /* [walks][n] in/out */, double *costs /* [walks] out: cost of paths[w] */,
+                         const int *rand_values /* [walks][nrand] */, long nrand, long *consumed /* [walks] out */,
+                         int *iterations /* [walks] in/out */, int *kick_pending /* [walks] in/out */,
+                         int *best_paths /* [walks][n] in/out */, double *best_costs /* [walks] in/out */,
+                         double *trace /* [walks][k] or NULL; only the iterations this call completes are written */,
+                         long *totals /* [walks][9] or NULL: two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds, kicks,
+                                         three_sweeps, three_moves, three_phases of this call */);
 
 #ifdef __cplusplus
 }

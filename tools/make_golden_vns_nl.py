@@ -34,6 +34,7 @@ OUT = os.path.join(ROOT, "tests", "golden", "golden_vns_nl.json")
 K = 8
 CASES = (("pr1002", 16, 12), ("d1291", 3, 5), ("fnl4461", 2, 3))        # instance, walks, iterations
 TOTALS = ("two_opt_sweeps", "two_opt_moves", "or_sweeps", "or_moves", "rounds", "kicks")
+THREE_TOTALS = ("three_sweeps", "three_moves", "three_phases")       # ... of a walk whose descent has a 3-opt phase
 _libc = C.CDLL(None)
 
 
@@ -121,18 +122,20 @@ def consumed_of(rv, nxt, nxt2):
     return at[0]
 
 
-def model_walk(start, best_cost, nodes, k, seed, kick=None, **src):
-    """k iterations from `start` on glibc's stream of `seed`; kick(succ) draws from that stream itself (None: kick_port) ->
-    dict(path, best_path, best_cost, trace, consumed, and the six totals)"""
+def model_walk(start, best_cost, nodes, k, seed, kick=None, descent=None, **src):
+    """k iterations from `start` on glibc's stream of `seed`; kick(succ) draws from that stream itself (None: kick_port);
+    descent(path, nodes, **src) is the descent of an iteration (None: model_ls_descent; one that also answers three_sweeps,
+    three_moves and three_phases has them summed too) -> dict(path, best_path, best_cost, trace, consumed, and the totals)"""
     rv = libc_draws(seed, draws_for(k))
     libc_srand(seed)
     path, best = start.copy(), start.copy()
     out = {t: 0 for t in TOTALS}
     trace = []
     for _ in range(k):
-        r = model_ls_descent(path, nodes, **src)
-        for t in TOTALS[:5]:
-            out[t] += r[t]
+        r = (descent or model_ls_descent)(path, nodes, **src)
+        for t in TOTALS[:5] + THREE_TOTALS:
+            if t in r:
+                out[t] = out.get(t, 0) + r[t]
         trace.append(r["cost"])
         if r["cost"] < best_cost:
             best_cost, best = r["cost"], path.copy()

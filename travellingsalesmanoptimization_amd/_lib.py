@@ -44,6 +44,9 @@ INFO_PERSIST_PACKED = 69                # the last LDS-resident descent / tabu w
 INFO_DL_LOOKED, INFO_DL_FULL_SWEEPS, INFO_DL_MAX_QUEUE, INFO_DL_MAX_WGS = 70, 71, 72, 73
 # ... the last greedy-edge construction: rounds of phase 1 and of phase 2, edges phase 1 accepted, free nodes entering phase 2
 INFO_GREEDY_ROUNDS1, INFO_GREEDY_ROUNDS2, INFO_GREEDY_EDGES1, INFO_GREEDY_FREE = 74, 75, 76, 77
+# ... the last batched neighbour-list descent: its 3-opt width in effect (0: two phases), 3-opt sweeps / moves over the tours, and the
+# most moves one tour's 3-opt sweep accepted
+INFO_NL3_BATCH_W, INFO_NL3_BATCH_SWEEPS, INFO_NL3_BATCH_MOVES, INFO_NL3_BATCH_MAX_MOVES = 78, 79, 80, 81
 EM_FORM_AUTO, EM_FORM_RESIDENT, EM_FORM_PER_STEP = 0, 1, 2
 MOPT_EXCHANGE = 1000
 EXCHANGE_AUTO, EXCHANGE_HOST, EXCHANGE_RCCL = 0, 1, 2
@@ -153,6 +156,14 @@ SIGNATURES = {
     "tspgpu_greedy_tour": (C.c_int, [_ctx, _ip, _pd]),
     "tspgpu_multi_neighbours_build": (C.c_int, [_ctx, C.c_int]),
     "tspgpu_multi_multistart_local_search_nl": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_double, _ip, _pd, _pi, _pl, _pl, _pl, _pl]),
+    "tspgpu_tours_local_search_nl3": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "tspgpu_multistart_local_search_nl3": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_int, C.c_double, _ip, _pd, _pi, _pl, _pl, _pl, _pl, _pl, _pl,
+                                                     C.c_void_p]),
+    "tspgpu_multi_multistart_local_search_nl3": (C.c_int, [_ctx, C.c_int, C.c_void_p, C.c_int, C.c_double, _ip, _pd, _pi, _pl, _pl, _pl, _pl,
+                                                           _pl, _pl]),
+    "tspgpu_vns_walks_nl3": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_double, _ip, _dp, C.c_void_p, C.c_long, C.c_void_p, _ip, _ip, _ip, _dp,
+                                       C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

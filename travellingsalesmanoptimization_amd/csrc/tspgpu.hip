@@ -52,6 +52,7 @@
 #include "tspgpu.h"
 #include "tspgpu_relaunch.h"    // LP_ST_*, and the host's protocol over them (run_persist, run_pstream)
 #include "tspgpu_looks.h"       // rounds of launches between looks at a control block (m2_run, or_run, the batched descents)
+#include "tspgpu_nlphase.h"     // NlbCtl and the phase machine of a tour of a batched neighbour-list descent (tspgpu_nlbatch.inc)
 #include "tspgpu_lds_tmat.h"    // index arithmetic of the tour-ordered matrix copy (k_lds2opt's TM instantiations)
 
 #ifndef TSPGPU_RPC
@@ -3365,6 +3366,8 @@ struct tspgpu_ctx : ContextMem, InstanceMem, CostMem, SlotMem {
     long ge_rounds1 = 0, ge_rounds2 = 0, ge_edges1 = 0, ge_free = 0;
     // batched neighbour-list descent (tspgpu_nlbatch.inc)
     long nlb_tours = 0, nlb_launches = 0, nlb_max_live = 0;     // the last batched descent: tours, sweeps launched, most tours in one
+    long nlb_w3 = 0, nlb_three_sweeps = 0, nlb_three_moves = 0, nlb_three_max_k = 0;    // ... its 3-opt width in effect (0: none), 3-opt sweeps and
+                                                                                        // moves over the tours, most moves of one tour's 3-opt sweep
     // neighbour-list VNS (tspgpu_nlvns.inc): the last call's walks, iterations completed, sweep rounds, most walks live in one, dry walks
     long nlv_walks = 0, nlv_iterations = 0, nlv_rounds = 0, nlv_max_live = 0, nlv_dry = 0;
 
@@ -4830,7 +4833,9 @@ static int launch_nn(tspgpu_ctx *ctx, int slot0, const int *h_starts, int count)
 struct Descent {
     long tw = 0, tm = 0, os = 0, om = 0;
     int nr = 0;
-    void operator+=(const Descent &d) { tw += d.tw; tm += d.tm; os += d.os; om += d.om; nr += d.nr; }
+    long hs = 0, hm = 0;    // 3-opt sweeps and moves, 3-opt phases: the batched descent with a 3-opt phase alone fills them
+    int np = 0;
+    void operator+=(const Descent &d) { tw += d.tw; tm += d.tm; os += d.os; om += d.om; nr += d.nr; hs += d.hs; hm += d.hm; np += d.np; }
 };
 
 // D[0 .. count) to the caller's arrays, each of them optional
@@ -5125,6 +5130,10 @@ long tspgpu_info(const tspgpu_ctx *ctx, int what)
     case 75: return ctx->ge_rounds2;
     case 76: return ctx->ge_edges1;
     case 77: return ctx->ge_free;
+    case 78: return ctx->nlb_w3;
+    case 79: return ctx->nlb_three_sweeps;
+    case 80: return ctx->nlb_three_moves;
+    case 81: return ctx->nlb_three_max_k;
     case 55: return ctx->have_costs && ctx->symmetric && ctx->n >= 8 ? (ctx->n + ORNL_STARTS - 1) / ORNL_STARTS : 0;
     case 12: return (ctx->built && ctx->grid_ok && ctx->opt_nn != 1 && ctx->cost_bound < 134217728.0) ? ctx->grid_G : 0;
     case 13: return ctx->grid_max_occ;
@@ -7485,8 +7494,10 @@ static int nlb_ensure(tspgpu_ctx *ctx, int count)
     return E_OK;
 }
 
-// one sweep of every tour of the first `live` slots of the list: the four launches, grid rows in runs of at most 65 535
-static int nlb_launch_sweep(tspgpu_ctx *ctx, int slot0, int live)
+// one sweep of every tour of the first `live` slots of the list: the four launches, grid rows in runs of at most 65 535.
+// THREE: the instantiations with the 3-opt phase, at width w3
+template <bool THREE>
+static int nlb_launch_sweep_as(tspgpu_ctx *ctx, int slot0, int live, int w3)
 {
     const int n = ctx->n, W = (n + ORNL_STARTS - 1) / ORNL_STARTS, G = std::min(NLB_APPLY_WGS, (n + 1) / 2);
     NlbCtl *ctl = ctx->d_nlb_ctl;
@@ -7496,37 +7507,46 @@ static int nlb_launch_sweep(tspgpu_ctx *ctx, int slot0, int live)
         const int *list = ctx->d_live + off;
         if (ctx->otf)
             kind_switch(ctx, [&](auto kind, auto *pts, auto *) {
-                hipLaunchKernelGGL((k_nlb_sweep_otf<kind()>), dim3(W, rows), dim3(256), 0, ctx->stream, ctx->S, pts, n, list, slot0, ctx->nl, ctx->nlb,
-                                   (const NlbCtl *)ctl);
+                hipLaunchKernelGGL((k_nlb_sweep_otf<kind(), THREE>), dim3(W, rows), dim3(256), 0, ctx->stream, ctx->S, pts, n, list, slot0, ctx->nl,
+                                   ctx->nlb, (const NlbCtl *)ctl, w3);
             });
         else
-            ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_nlb_sweep<T>), dim3(W, rows), dim3(256), 0, ctx->stream, ctx->S, (const T *)ctx->d_mat.p, n,
-                                                         ctx->ld, list, slot0, ctx->nl, ctx->nlb, (const NlbCtl *)ctl));
+            ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_nlb_sweep<T, THREE>), dim3(W, rows), dim3(256), 0, ctx->stream, ctx->S,
+                                                         (const T *)ctx->d_mat.p, n, ctx->ld, list, slot0, ctx->nl, ctx->nlb, (const NlbCtl *)ctl, w3));
         HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(k_nlb_compact, dim3(1, rows), dim3(1024), 0, ctx->stream, ctx->S, n, list, slot0, ctx->nlb, ctl);
+        hipLaunchKernelGGL(k_nlb_compact<THREE>, dim3(1, rows), dim3(1024), 0, ctx->stream, ctx->S, n, list, slot0, ctx->nlb, ctl, ctx->nl);
         HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_nlb_select, dim3((n + 255) / 256, rows), dim3(256), 0, ctx->stream, n, list, slot0, ctx->nlb, (const NlbCtl *)ctl);
         HIP_TRY(hipGetLastError());
         if (ctx->otf)
             kind_switch(ctx, [&](auto kind, auto *pts, auto *) {
-                hipLaunchKernelGGL((k_nlb_apply_otf<kind()>), dim3(G, rows), dim3(256), 0, ctx->stream, ctx->S, pts, n, list, slot0, ctx->nlb, ctl);
+                hipLaunchKernelGGL((k_nlb_apply_otf<kind(), THREE>), dim3(G, rows), dim3(256), 0, ctx->stream, ctx->S, pts, n, list, slot0, ctx->nlb,
+                                   ctl, ctx->nl);
             });
         else
-            ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_nlb_apply<T>), dim3(G, rows), dim3(256), 0, ctx->stream, ctx->S, (const T *)ctx->d_mat.p, n,
-                                                         ctx->ld, list, slot0, ctx->nlb, ctl));
+            ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_nlb_apply<T, THREE>), dim3(G, rows), dim3(256), 0, ctx->stream, ctx->S,
+                                                         (const T *)ctx->d_mat.p, n, ctx->ld, list, slot0, ctx->nlb, ctl, ctx->nl));
         HIP_TRY(hipGetLastError());
     }
     return E_OK;
 }
 
-// ornl_descent on the slots slot0 .. slot0 + count - 1 at once.  The control blocks are armed (2-opt phase, round 1) and the
-// slots re-armed as m2_arm does; then sweeps of all live tours -- four between looks at the control blocks, one under a
-// deadline, as m2_run -- and the tours whose descent has ended leave the list.  D: per-slot counters, [count]
-static int nlb_descent(tspgpu_ctx *ctx, int slot0, int count, double time_left_s, Descent *D, bool *late)
+// w3: the width of the 3-opt phase, 0: the descent has none
+static int nlb_launch_sweep(tspgpu_ctx *ctx, int slot0, int live, int w3)
+{
+    return w3 > 0 ? nlb_launch_sweep_as<true>(ctx, slot0, live, w3) : nlb_launch_sweep_as<false>(ctx, slot0, live, 0);
+}
+
+// ornl_descent (w3 > 0: nl3_descent at that width) on the slots slot0 .. slot0 + count - 1 at once.  The control blocks are
+// armed (2-opt phase, round 1) and the slots re-armed as m2_arm does; then sweeps of all live tours -- four between looks at
+// the control blocks, one under a deadline, as m2_run -- and the tours whose descent has ended leave the list.  D: per-slot
+// counters, [count]
+static int nlb_descent(tspgpu_ctx *ctx, int slot0, int count, int w3, double time_left_s, Descent *D, bool *late)
 {
     const double t_end = deadline_of(time_left_s);
     *late = false;
     ctx->nlb_tours = count; ctx->nlb_launches = 0; ctx->nlb_max_live = 0;
+    ctx->nlb_w3 = w3; ctx->nlb_three_sweeps = ctx->nlb_three_moves = ctx->nlb_three_max_k = 0;
     int rc = nlb_ensure(ctx, count);
     if (rc) return rc;
     std::vector<NlbCtl> hc((size_t)count);
@@ -7540,7 +7560,7 @@ static int nlb_descent(tspgpu_ctx *ctx, int slot0, int count, double time_left_s
     if ((rc = set_live(ctx, live))) return rc;
     const looks::Result r = looks::drive_live(
         now_s, t_end, 4, live, [](int) {},
-        [&](int len) { const int e = nlb_launch_sweep(ctx, slot0, len); ctx->nlb_launches += !e; return e; },
+        [&](int len) { const int e = nlb_launch_sweep(ctx, slot0, len, w3); ctx->nlb_launches += !e; return e; },
         [&] { return ctl_get(ctx, hc.data(), ctx->d_nlb_ctl, (size_t)count); }, [&](int t) { return hc[t - slot0].stop != 0; },
         [&](const std::vector<int> &list) { return set_live(ctx, list); });
     ctx->nlb_max_live = r.max_live;
@@ -7549,7 +7569,25 @@ static int nlb_descent(tspgpu_ctx *ctx, int slot0, int count, double time_left_s
     for (int i = 0; i < count; i++) {
         D[i].tw = (long)hc[i].two_opt_sweeps; D[i].tm = (long)hc[i].two_opt_moves;
         D[i].os = (long)hc[i].or_sweeps; D[i].om = (long)hc[i].or_moves; D[i].nr = hc[i].rounds;
+        D[i].hs = (long)hc[i].three_sweeps; D[i].hm = (long)hc[i].three_moves; D[i].np = hc[i].three_phases;
+        ctx->nlb_three_sweeps += D[i].hs; ctx->nlb_three_moves += D[i].hm;
+        ctx->nlb_three_max_k = std::max(ctx->nlb_three_max_k, (long)hc[i].three_max_k);
     }
+    return E_OK;
+}
+
+// the range of a batched descent over the lists, behind the family's check: count slots from slot0, each with a tour
+static int nlb_range(tspgpu_ctx *ctx, int slot0, int count)
+{
+    if (slot0 < 0 || count <= 0 || count > ctx->tcap || slot0 > ctx->tcap - count)      // (the range first: a slot past the end is no slot without a tour)
+        return fail(ctx, E_INVALID, "bad slot range: slot0 %d, count %d of %d slots", slot0, count, ctx->tcap);
+    return or_batch_args(ctx, slot0, count);
+}
+
+static int nlb_no_cap(tspgpu_ctx *ctx)
+{
+    if (ctx->opt_sweep_cap != -1)
+        return fail(ctx, E_INVALID, "TSPGPU_OPT_SWEEP_CAP = %d: the descent over the neighbour lists runs every phase to its end", ctx->opt_sweep_cap);
     return E_OK;
 }
 
@@ -7562,13 +7600,32 @@ int tspgpu_tours_local_search_nl(tspgpu_ctx *ctx, int slot0, int count, double t
     hipSetDevice(ctx->device);
     int rc = ornl_check(ctx);
     if (rc) return rc;
-    if (slot0 < 0 || count <= 0 || count > ctx->tcap || slot0 > ctx->tcap - count)      // (the range first: a slot past the end is no slot without a tour)
-        return fail(ctx, E_INVALID, "bad slot range: slot0 %d, count %d of %d slots", slot0, count, ctx->tcap);
-    if ((rc = or_batch_args(ctx, slot0, count))) return rc;
+    if ((rc = nlb_range(ctx, slot0, count))) return rc;
     std::vector<Descent> D(count);
     bool late = false;
-    if ((rc = nlb_descent(ctx, slot0, count, time_left_s, D.data(), &late))) return rc;
+    if ((rc = nlb_descent(ctx, slot0, count, 0, time_left_s, D.data(), &late))) return rc;
     descent_out(D.data(), count, two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds);
+    return done_code(late);
+}
+
+int tspgpu_tours_local_search_nl3(tspgpu_ctx *ctx, int slot0, int count, int width, double time_left_s, long *two_opt_sweeps, long *two_opt_moves,
+                                  long *or_sweeps, long *or_moves, int *rounds, long *three_sweeps, long *three_moves, int *three_phases)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    hipSetDevice(ctx->device);
+    ctx->nl3_width = width;
+    int rc = nl3_check(ctx);
+    if (rc) return rc;
+    if ((rc = nlb_range(ctx, slot0, count))) return rc;
+    std::vector<Descent> D(count);
+    bool late = false;
+    if ((rc = nlb_descent(ctx, slot0, count, ctx->nl3_w, time_left_s, D.data(), &late))) return rc;
+    descent_out(D.data(), count, two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds);
+    for (int i = 0; i < count; i++) {
+        if (three_sweeps) three_sweeps[i] = D[i].hs;
+        if (three_moves) three_moves[i] = D[i].hm;
+        if (three_phases) three_phases[i] = D[i].np;
+    }
     return done_code(late);
 }
 
@@ -7581,13 +7638,35 @@ int tspgpu_multistart_local_search_nl(tspgpu_ctx *ctx, const int *starts, int ns
     hipSetDevice(ctx->device);
     int rc = ornl_check(ctx);
     if (rc) return rc;
-    if (ctx->opt_sweep_cap != -1)
-        return fail(ctx, E_INVALID, "TSPGPU_OPT_SWEEP_CAP = %d: the descent over the neighbour lists runs every phase to its end", ctx->opt_sweep_cap);
+    if ((rc = nlb_no_cap(ctx))) return rc;
     MultiStart ms;
     rc = multistart(ctx, starts, nstarts, time_left_s, -1, best_path, best_cost, best_start, costs_out, &ms,
-                    [&](int m, double left, bool *late, Descent *D) { return nlb_descent(ctx, 0, m, left, D, late); });
+                    [&](int m, double left, bool *late, Descent *D) { return nlb_descent(ctx, 0, m, 0, left, D, late); });
     if (rc && rc != E_DEADLINE) return rc;
     descent_out(&ms.total, 1, total_two_opt_sweeps, total_two_opt_moves, total_or_sweeps, total_or_moves, nullptr);
+    return rc;
+}
+
+int tspgpu_multistart_local_search_nl3(tspgpu_ctx *ctx, int width, const int *starts, int nstarts, double time_left_s, int *best_path,
+                                       double *best_cost, int *best_start, long *total_two_opt_sweeps, long *total_two_opt_moves,
+                                       long *total_or_sweeps, long *total_or_moves, long *total_three_sweeps, long *total_three_moves,
+                                       double *costs_out)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    if (!best_path || !best_cost || !best_start || nstarts <= 0) return fail(ctx, E_INVALID, "bad argument");
+    hipSetDevice(ctx->device);
+    ctx->nl3_width = width;
+    int rc = nl3_check(ctx);
+    if (rc) return rc;
+    if ((rc = nlb_no_cap(ctx))) return rc;
+    const int w3 = ctx->nl3_w;
+    MultiStart ms;
+    rc = multistart(ctx, starts, nstarts, time_left_s, -1, best_path, best_cost, best_start, costs_out, &ms,
+                    [&](int m, double left, bool *late, Descent *D) { return nlb_descent(ctx, 0, m, w3, left, D, late); });
+    if (rc && rc != E_DEADLINE) return rc;
+    descent_out(&ms.total, 1, total_two_opt_sweeps, total_two_opt_moves, total_or_sweeps, total_or_moves, nullptr);
+    if (total_three_sweeps) *total_three_sweeps = ms.total.hs;
+    if (total_three_moves) *total_three_moves = ms.total.hm;
     return rc;
 }
 
@@ -7632,7 +7711,7 @@ static int nlv_launch_step(tspgpu_ctx *ctx, int live, bool trace)
 
 // the walks on slots 0 .. walks-1: upload, arm, sweep rounds of five launches (the four of the batched descent and the step)
 // -- four rounds between looks at the control blocks, one under a deadline, as nlb_descent --, download
-static int nlv_walks(tspgpu_ctx *ctx, int walks, int k, double time_left_s, int *paths, double *costs, const int *rand_values, long nrand,
+static int nlv_walks(tspgpu_ctx *ctx, int w3, int walks, int k, double time_left_s, int *paths, double *costs, const int *rand_values, long nrand,
                      long *consumed, int *iterations, int *kick_pending, int *best_paths, double *best_costs, double *trace, long *totals)
 {
     const double t_end = deadline_of(time_left_s);
@@ -7677,7 +7756,7 @@ static int nlv_walks(tspgpu_ctx *ctx, int walks, int k, double time_left_s, int 
     const looks::Result r = looks::drive_live(
         now_s, t_end, 4, live, [](int) {},
         [&](int len) {
-            int e = nlb_launch_sweep(ctx, 0, len);
+            int e = nlb_launch_sweep(ctx, 0, len, w3);
             if (!e && !(e = nlv_launch_step(ctx, len, trace != nullptr))) ctx->nlv_rounds++;
             return e;
         },
@@ -7702,9 +7781,10 @@ static int nlv_walks(tspgpu_ctx *ctx, int walks, int k, double time_left_s, int 
         for (size_t i = 0; i < tr.size() / W; i++)
             if (tr[w * k + i] == tr[w * k + i]) trace[w * k + i] = tr[w * k + i];
         if (totals) {
-            long *o = totals + 6 * w;
+            long *o = totals + (w3 > 0 ? 9 : 6) * w;
             o[0] = (long)hc[w].two_opt_sweeps; o[1] = (long)hc[w].two_opt_moves; o[2] = (long)hc[w].or_sweeps; o[3] = (long)hc[w].or_moves;
             o[4] = hc[w].rounds; o[5] = (long)hv[w].kicks;
+            if (w3 > 0) { o[6] = (long)hc[w].three_sweeps; o[7] = (long)hc[w].three_moves; o[8] = hc[w].three_phases; }
         }
     }
     if (late) return E_DEADLINE;
@@ -7728,8 +7808,26 @@ int tspgpu_vns_walks_nl(tspgpu_ctx *ctx, int walks, int k, double time_left_s, i
     if (rc) return rc;
     for (int w = 0; w < walks; w++)
         if (iterations[w] < 0 || iterations[w] > k) return fail(ctx, E_INVALID, "iterations[%d] = %d is outside [0, %d]", w, iterations[w], k);
-    return nlv_walks(ctx, walks, k, time_left_s, paths, costs, rand_values, nrand, consumed, iterations, kick_pending, best_paths, best_costs,
+    return nlv_walks(ctx, 0, walks, k, time_left_s, paths, costs, rand_values, nrand, consumed, iterations, kick_pending, best_paths, best_costs,
                      trace, totals);
+}
+
+int tspgpu_vns_walks_nl3(tspgpu_ctx *ctx, int width, int walks, int k, double time_left_s, int *paths, double *costs, const int *rand_values,
+                         long nrand, long *consumed, int *iterations, int *kick_pending, int *best_paths, double *best_costs, double *trace,
+                         long *totals)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    if (walks <= 0 || k < 0 || nrand < 0 || !paths || !costs || !consumed || !iterations || !kick_pending || !best_paths || !best_costs ||
+        (nrand > 0 && !rand_values))
+        return fail(ctx, E_INVALID, "bad argument");
+    hipSetDevice(ctx->device);
+    ctx->nl3_width = width;
+    const int rc = nl3_check(ctx);
+    if (rc) return rc;
+    for (int w = 0; w < walks; w++)
+        if (iterations[w] < 0 || iterations[w] > k) return fail(ctx, E_INVALID, "iterations[%d] = %d is outside [0, %d]", w, iterations[w], k);
+    return nlv_walks(ctx, ctx->nl3_w, walks, k, time_left_s, paths, costs, rand_values, nrand, consumed, iterations, kick_pending, best_paths,
+                     best_costs, trace, totals);
 }
 
 } // extern "C"

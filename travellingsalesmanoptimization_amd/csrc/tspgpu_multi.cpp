@@ -228,6 +228,7 @@ struct Local {           // one device's result
     long pos = -1;       // position in the caller's start list of the device's winner (-1: none)
     int start = -1;
     long tw = 0, tm = 0, os = 0, om = 0;    // 2-opt sweeps and moves, Or-opt sweeps and moves (a family without one leaves it 0)
+    long hs = 0, hm = 0;                    // 3-opt sweeps and moves
     int done = 0;        // starts processed (tspgpu_multi_nn_all)
     std::vector<int> path;
     std::string err;
@@ -345,6 +346,7 @@ int sharded(tspgpu_multi *m, const int *starts, int nstarts, int *best_path, dou
     for (const Local &l : L) {
         late |= l.rc == E_DEADLINE;
         total->tw += l.tw; total->tm += l.tm; total->os += l.os; total->om += l.om; total->done += l.done;
+        total->hs += l.hs; total->hm += l.hm;
     }
     *best_cost = owner >= 0 ? cost : DBL_MAX;
     *best_start = owner >= 0 ? L[owner].start : -1;
@@ -530,6 +532,28 @@ int tspgpu_multi_multistart_local_search_nl(tspgpu_multi *m, const int *starts, 
     if (total_two_opt_moves) *total_two_opt_moves = T.tm;
     if (total_or_sweeps) *total_or_sweeps = T.os;
     if (total_or_moves) *total_or_moves = T.om;
+    return rc;
+}
+
+// ... and with the 3-opt phase at `width` (tspgpu_multistart_local_search_nl3 per device)
+int tspgpu_multi_multistart_local_search_nl3(tspgpu_multi *m, int width, const int *starts, int nstarts, double time_left_s, int *best_path,
+                                             double *best_cost, int *best_start, long *total_two_opt_sweeps, long *total_two_opt_moves,
+                                             long *total_or_sweeps, long *total_or_moves, long *total_three_sweeps, long *total_three_moves)
+{
+    if (!m) return E_UNAVAILABLE;
+    if (!best_path || !best_cost || !best_start || nstarts <= 0) return mfail(m, E_INVALID, "bad argument");
+    Local T;
+    const int rc = sharded(m, starts, nstarts, best_path, best_cost, best_start, &T, [&](tspgpu_ctx *ctx, const int *list, int count, Local &l) {
+        return tspgpu_multistart_local_search_nl3(ctx, width, list, count, time_left_s, l.path.data(), &l.cost, &l.start, &l.tw, &l.tm, &l.os,
+                                                  &l.om, &l.hs, &l.hm, nullptr);
+    });
+    if (rc && rc != E_DEADLINE) return rc;
+    if (total_two_opt_sweeps) *total_two_opt_sweeps = T.tw;
+    if (total_two_opt_moves) *total_two_opt_moves = T.tm;
+    if (total_or_sweeps) *total_or_sweeps = T.os;
+    if (total_or_moves) *total_or_moves = T.om;
+    if (total_three_sweeps) *total_three_sweeps = T.hs;
+    if (total_three_moves) *total_three_moves = T.hm;
     return rc;
 }
 

@@ -171,10 +171,11 @@ __global__ void __launch_bounds__(256) k_nl3_sweep_otf(Tours S, const typename O
     nl3_sweep_node<int>(S, OrPtsCost<KIND>{pts}, n, t, NL, W, B);
 }
 
-// the improving candidates through m2_counted_scan, with the ranges of their decoded chains
-__global__ void __launch_bounds__(1024) k_nl3_compact(Tours S, int n, int t, NlBuf NL, M2Buf B, M2Ctl *ctl)
+// the improving candidates through m2_counted_scan, with the ranges of their decoded chains.  For the control block of a single
+// descent or of a tour of a batch (tspgpu_nlbatch.inc)
+template <typename CTL>
+__device__ __forceinline__ void nl3_compact_tour(const Tours &S, int n, int t, const NlBuf &NL, const M2Buf &B, CTL *ctl, int *cnts)
 {
-    __shared__ int cnts[1024];
     const Nl3Pos T = nl3_pos(S, n, t);
     m2_counted_scan(
         n, ctl, cnts, [&](int s) { return B.raw_b[s] >= 0 && B.raw_d[s] < TWO_OPT_EPS; },
@@ -189,6 +190,12 @@ __global__ void __launch_bounds__(1024) k_nl3_compact(Tours S, int n, int t, NlB
         });
 }
 
+__global__ void __launch_bounds__(1024) k_nl3_compact(Tours S, int n, int t, NlBuf NL, M2Buf B, M2Ctl *ctl)
+{
+    __shared__ int cnts[1024];
+    nl3_compact_tour(S, n, t, NL, B, ctl, cnts);
+}
+
 // j << 2 | kind of candidate x into raw_b[x] (the sweep's raw_b is spent once the compaction has run)
 __global__ void __launch_bounds__(256) k_nl3_describe(Tours S, int n, int t, NlBuf NL, M2Buf B, const M2Ctl *ctl)
 {
@@ -200,8 +207,10 @@ __global__ void __launch_bounds__(256) k_nl3_describe(Tours S, int n, int t, NlB
     }
 }
 
-template <typename T, typename CS>
-__device__ __forceinline__ void nl3_apply_tour(const Tours &S, const CS cs, int n, int t, const NlBuf &NL, const M2Buf &B, M2Ctl *ctl)
+// (every return and `continue` in front of a barrier is block-uniform: the trip count of the move loop depends only on
+// blockIdx.x, gridDim.x and m, and acc[y] is one cell for the whole workgroup)
+template <typename T, typename CS, typename CTL>
+__device__ __forceinline__ void nl3_apply_tour(const Tours &S, const CS cs, int n, int t, const NlBuf &NL, const M2Buf &B, CTL *ctl)
 {
     typedef typename Elem<T>::acc AT;
     const int tid = threadIdx.x, BT = NL3_APPLY_BT;

@@ -61,7 +61,8 @@ class Engine:
                  "three_nl_w", "three_nl_sweeps", "three_nl_moves", "three_nl_max_moves", "three_nl_phases", "three_nl_nodes",
                  "persist_tmat", "persist_packed",
                  "dl_looked", "dl_full_sweeps", "dl_max_queue", "dl_max_wgs",
-                 "greedy_rounds1", "greedy_rounds2", "greedy_edges1", "greedy_free"]
+                 "greedy_rounds1", "greedy_rounds2", "greedy_edges1", "greedy_free",
+                 "nl3_batch_w", "nl3_batch_sweeps", "nl3_batch_moves", "nl3_batch_max_moves"]
         return {k: int(self.L.tspgpu_info(self.ctx, i)) for i, k in enumerate(names)}
 
     # ---- instance
@@ -284,12 +285,7 @@ class Engine:
         return {"rc": rc, "cost": c.value, "best_cost": bc.value, "iterations": it.value, "kick_pending": kp.value,
                 "consumed": used.value, "trace": trace}
 
-    def vns_walks_nl(self, paths, k, rand_values, best_paths, best_costs, iterations=None, kick_pending=None, time_left_s=-1.0,
-                     want_trace=False):
-        """W walks of the neighbour-list VNS (include/tspgpu.h "Neighbour-list VNS").  paths, best_paths [W][n] int32 and
-        best_costs [W] float64 in place; rand_values [W][nrand]; iterations, kick_pending [W] (default: zeros) are copied ->
-        dict(rc, costs, best_costs, iterations, kick_pending, consumed, trace [W][k] (NaN: not written by this call) or None,
-        totals: dict of [W] arrays two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds, kicks)."""
+    def _vns_walks(self, fn, head, names, paths, k, rand_values, best_paths, best_costs, iterations, kick_pending, time_left_s, want_trace):
         W = paths.shape[0]
         assert paths.dtype == np.int32 and best_paths.dtype == np.int32 and best_costs.dtype == np.float64
         assert paths.flags.c_contiguous and best_paths.flags.c_contiguous and best_costs.flags.c_contiguous
@@ -299,15 +295,32 @@ class Engine:
         kp = np.zeros(W, dtype=np.int32) if kick_pending is None else np.array(kick_pending, dtype=np.int32)
         costs = np.zeros(W, dtype=np.float64)
         used = np.zeros(W, dtype=np.int64)
-        totals = np.zeros((W, 6), dtype=np.int64)
+        totals = np.zeros((W, len(names)), dtype=np.int64)
         trace = np.full((W, max(int(k), 1)), np.nan, dtype=np.float64) if want_trace else None
-        rc = self._ck(self.L.tspgpu_vns_walks_nl(self.ctx, W, int(k), float(time_left_s), paths.reshape(-1), costs, rv.ctypes.data, rv.shape[1],
-                                                 used.ctypes.data, it, kp, best_paths.reshape(-1), best_costs,
-                                                 trace.ctypes.data if want_trace else None, totals.ctypes.data),
+        rc = self._ck(fn(self.ctx, *head, W, int(k), float(time_left_s), paths.reshape(-1), costs, rv.ctypes.data, rv.shape[1],
+                         used.ctypes.data, it, kp, best_paths.reshape(-1), best_costs,
+                         trace.ctypes.data if want_trace else None, totals.ctypes.data),
                       ok=(T_OK, DEADLINE_EXCEEDED, 8))
-        names = ("two_opt_sweeps", "two_opt_moves", "or_sweeps", "or_moves", "rounds", "kicks")
         return {"rc": rc, "costs": costs, "best_costs": best_costs, "iterations": it, "kick_pending": kp, "consumed": used,
                 "trace": trace[:, :int(k)] if want_trace else None, "totals": {nm: totals[:, i].copy() for i, nm in enumerate(names)}}
+
+    def vns_walks_nl(self, paths, k, rand_values, best_paths, best_costs, iterations=None, kick_pending=None, time_left_s=-1.0,
+                     want_trace=False):
+        """W walks of the neighbour-list VNS (include/tspgpu.h "Neighbour-list VNS").  paths, best_paths [W][n] int32 and
+        best_costs [W] float64 in place; rand_values [W][nrand]; iterations, kick_pending [W] (default: zeros) are copied ->
+        dict(rc, costs, best_costs, iterations, kick_pending, consumed, trace [W][k] (NaN: not written by this call) or None,
+        totals: dict of [W] arrays two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds, kicks)."""
+        names = ("two_opt_sweeps", "two_opt_moves", "or_sweeps", "or_moves", "rounds", "kicks")
+        return self._vns_walks(self.L.tspgpu_vns_walks_nl, (), names, paths, k, rand_values, best_paths, best_costs, iterations, kick_pending,
+                               time_left_s, want_trace)
+
+    def vns_walks_nl3(self, paths, k, rand_values, best_paths, best_costs, width, iterations=None, kick_pending=None, time_left_s=-1.0,
+                      want_trace=False):
+        """vns_walks_nl with the descent of local_search_nl3 at `width` (include/tspgpu.h "Batched neighbour-list 3-opt"); totals
+        gains three_sweeps, three_moves, three_phases."""
+        names = ("two_opt_sweeps", "two_opt_moves", "or_sweeps", "or_moves", "rounds", "kicks", "three_sweeps", "three_moves", "three_phases")
+        return self._vns_walks(self.L.tspgpu_vns_walks_nl3, (int(width),), names, paths, k, rand_values, best_paths, best_costs, iterations,
+                               kick_pending, time_left_s, want_trace)
 
     # ---- multi-start
     @staticmethod
@@ -374,6 +387,20 @@ class Engine:
                       ok=(T_OK, DEADLINE_EXCEEDED))
         return {"path": best, "cost": c.value, "start": s.value, "two_opt_sweeps": tw.value, "two_opt_moves": tm.value,
                 "or_sweeps": os_.value, "or_moves": om.value, "costs": costs, "rc": rc}
+
+    def multistart_local_search_nl3(self, width, starts=None, time_left_s=-1.0):
+        """multistart_local_search_nl with the 3-opt phase at `width` -> its dict with three_sweeps, three_moves added."""
+        p, m, keep = self._starts(starts, self.n)
+        best = np.empty(self.n, dtype=np.int32)
+        c, s = C.c_double(), C.c_int()
+        tw, tm, os_, om, ts, tv = (C.c_long() for _ in range(6))
+        costs = np.full(m, np.nan, dtype=np.float64)
+        rc = self._ck(self.L.tspgpu_multistart_local_search_nl3(self.ctx, int(width), p, m, float(time_left_s), best, C.byref(c), C.byref(s),
+                                                                C.byref(tw), C.byref(tm), C.byref(os_), C.byref(om), C.byref(ts), C.byref(tv),
+                                                                costs.ctypes.data),
+                      ok=(T_OK, DEADLINE_EXCEEDED))
+        return {"path": best, "cost": c.value, "start": s.value, "two_opt_sweeps": tw.value, "two_opt_moves": tm.value,
+                "or_sweeps": os_.value, "or_moves": om.value, "three_sweeps": ts.value, "three_moves": tv.value, "costs": costs, "rc": rc}
 
     # ---- device-resident
     def tour_load(self, slot, path):
@@ -455,6 +482,20 @@ class Engine:
                                                           os_.ctypes.data, om.ctypes.data, nr.ctypes.data),
                       ok=(T_OK, DEADLINE_EXCEEDED))
         return {"two_opt_sweeps": tw, "two_opt_moves": tm, "or_sweeps": os_, "or_moves": om, "rounds": nr, "rc": rc}
+
+    def tours_local_search_nl3(self, slot0, count, width, time_left_s=-1.0):
+        """the descent of tour_local_search_nl3 on slots slot0 .. slot0+count-1 at once ->
+        dict(two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds, three_sweeps, three_moves, three_phases: arrays of count
+        entries, rc)."""
+        count = int(count)
+        tw, tm, os_, om, ts, tv = (np.zeros(max(count, 0), dtype=np.int64) for _ in range(6))
+        nr, tp = (np.zeros(max(count, 0), dtype=np.int32) for _ in range(2))
+        rc = self._ck(self.L.tspgpu_tours_local_search_nl3(self.ctx, int(slot0), count, int(width), float(time_left_s), tw.ctypes.data,
+                                                           tm.ctypes.data, os_.ctypes.data, om.ctypes.data, nr.ctypes.data, ts.ctypes.data,
+                                                           tv.ctypes.data, tp.ctypes.data),
+                      ok=(T_OK, DEADLINE_EXCEEDED))
+        return {"two_opt_sweeps": tw, "two_opt_moves": tm, "or_sweeps": os_, "or_moves": om, "rounds": nr,
+                "three_sweeps": ts, "three_moves": tv, "three_phases": tp, "rc": rc}
 
     def tour_three_opt_nl(self, slot, width, max_sweeps=-1, time_left_s=-1.0):
         """neighbour-list 3-opt sweeps on a slot -> (sweeps, moves, rc)."""
@@ -701,6 +742,20 @@ class MultiEngine:
                       ok=(T_OK, DEADLINE_EXCEEDED))
         return {"path": best, "cost": c.value, "start": s.value, "two_opt_sweeps": tw.value, "two_opt_moves": tm.value,
                 "or_sweeps": os_.value, "or_moves": om.value, "rc": rc}
+
+    def multistart_local_search_nl3(self, width, starts=None, time_left_s=-1.0):
+        """Engine.multistart_local_search_nl3 over every device ->
+        dict(path, cost, start, two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, three_sweeps, three_moves, rc)."""
+        p, m, keep = Engine._starts(starts, self.n)
+        best = np.empty(self.n, dtype=np.int32)
+        c, s = C.c_double(), C.c_int()
+        tw, tm, os_, om, ts, tv = (C.c_long() for _ in range(6))
+        rc = self._ck(self.L.tspgpu_multi_multistart_local_search_nl3(self.m, int(width), p, m, float(time_left_s), best, C.byref(c),
+                                                                      C.byref(s), C.byref(tw), C.byref(tm), C.byref(os_), C.byref(om),
+                                                                      C.byref(ts), C.byref(tv)),
+                      ok=(T_OK, DEADLINE_EXCEEDED))
+        return {"path": best, "cost": c.value, "start": s.value, "two_opt_sweeps": tw.value, "two_opt_moves": tm.value,
+                "or_sweeps": os_.value, "or_moves": om.value, "three_sweeps": ts.value, "three_moves": tv.value, "rc": rc}
 
     def nn_all(self, starts=None, time_left_s=-1.0):
         """h_Greedy_iterative (heuristics.c:34-72) over every device -> (best_path, best_cost, best_start, done, rc)."""

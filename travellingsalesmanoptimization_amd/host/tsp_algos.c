@@ -643,8 +643,9 @@ ERROR_CODE tabu_make_move(int *prev, tsp_solution *solution, int bestCase, int i
 }
 
 /* TSP_VNS_NEIGHBOURS=K, K in 1..16 (tsp_run_algorithm): mh_VNS runs TSP_VNS_WALKS walks of the neighbour-list VNS
- * (tspgpu_vns_walks_nl) over lists of K nodes instead of its own loop */
-static int vns_nl_k = 0, vns_nl_walks = 1;
+ * (tspgpu_vns_walks_nl) over lists of K nodes instead of its own loop.
+ * TSP_VNS_3OPT_WIDTH=W, W in 1..16, with it: the walks' descent gets the 3-opt phase over the first W entries (tspgpu_vns_walks_nl3) */
+static int vns_nl_k = 0, vns_nl_walks = 1, vns_nl_width3 = 0;
 enum { VNS_NL_NUMBERS = 1 << 22 };              /* random numbers drawn ahead per call, over all walks */
 
 /* mh_VNS over the neighbour lists.  Every walk starts from the tour in *best (the All-NN tour).  Per call at most C
@@ -689,7 +690,9 @@ static ERROR_CODE vns_nl_loop(tsp_solution *best, FILE *f)
         const int *rv = tsp_rand_peek(per * W);
         if (!rv) { log_fatal("out of memory for %ld random numbers", per * W); tsp_handlefatal(); }
         if (trace) for (long i = 0; i < (long)W * kk; i++) trace[i] = NAN;
-        rc = tspgpu_vns_walks_nl(g, W, kk, time_left(), paths, costs, rv, per, used, itl, pending, bests, bcosts, trace, NULL);
+        rc = vns_nl_width3
+                 ? tspgpu_vns_walks_nl3(g, vns_nl_width3, W, kk, time_left(), paths, costs, rv, per, used, itl, pending, bests, bcosts, trace, NULL)
+                 : tspgpu_vns_walks_nl(g, W, kk, time_left(), paths, costs, rv, per, used, itl, pending, bests, bcosts, trace, NULL);
         tsp_rand_consume(W == 1 ? used[0] : per * W);
         /* RESOURCE_EXHAUSTED with progress: walks ran dry in front of a kick phase, come back with more (see mh_VNS) */
         int progress = 0;
@@ -907,8 +910,10 @@ ERROR_CODE h_greedy_local_search(void)
  * from EVERY start (tspgpu_multistart_local_search_nl: the starts of a chunk descend together, every launch serves all of them
  * that still descend).  It takes a matrix-free instance as it is; the incumbent, starting_node and the deadline are handled as
  * in h_greedy_2opt.  An instance the descent does not take (fewer than 8 nodes, an asymmetric matrix) gets a warning and the
- * plain h_greedy_2opt. */
-static int every_start_nl_k = 0;
+ * plain h_greedy_2opt.
+ * TSP_EVERY_START_3OPT_WIDTH=W, W in 1..16, with it: that descent gets the 3-opt phase over the first W list entries
+ * (tspgpu_multistart_local_search_nl3). */
+static int every_start_nl_k = 0, every_start_width3 = 0;
 
 ERROR_CODE h_greedy_local_search_nl(void)
 {
@@ -920,13 +925,19 @@ ERROR_CODE h_greedy_local_search_nl(void)
     tsp_solution s;
     tsp_init_solution(tsp_inst.nnodes, &s);
     int start = -1;
-    long sweeps = 0, two_opt_moves = 0, or_sweeps = 0, moves = 0;
+    long sweeps = 0, two_opt_moves = 0, or_sweeps = 0, moves = 0, three_sweeps = 0, three_moves = 0;
+    const int w3 = every_start_width3;
     const double t0 = utils_timeelapsed(&tsp_inst.c);
     /* the lists belong to the costs in place: built when the context holds none of that length */
     const int kp = every_start_nl_k < tsp_inst.nnodes - 1 ? every_start_nl_k : tsp_inst.nnodes - 1;
     int rc = m ? tspgpu_multi_neighbours_build(m, every_start_nl_k)
                : tspgpu_info(g, 42) == kp ? 0 : tspgpu_neighbours_build(g, every_start_nl_k);
-    if (rc == 0)
+    if (rc == 0 && w3)
+        rc = m ? tspgpu_multi_multistart_local_search_nl3(m, w3, NULL, tsp_inst.nnodes, time_left(), s.path, &s.cost, &start, &sweeps,
+                                                          &two_opt_moves, &or_sweeps, &moves, &three_sweeps, &three_moves)
+               : tspgpu_multistart_local_search_nl3(g, w3, NULL, tsp_inst.nnodes, time_left(), s.path, &s.cost, &start, &sweeps, &two_opt_moves,
+                                                    &or_sweeps, &moves, &three_sweeps, &three_moves, NULL);
+    else if (rc == 0)
         rc = m ? tspgpu_multi_multistart_local_search_nl(m, NULL, tsp_inst.nnodes, time_left(), s.path, &s.cost, &start, &sweeps,
                                                          &two_opt_moves, &or_sweeps, &moves)
                : tspgpu_multistart_local_search_nl(g, NULL, tsp_inst.nnodes, time_left(), s.path, &s.cost, &start, &sweeps, &two_opt_moves,
@@ -938,7 +949,7 @@ ERROR_CODE h_greedy_local_search_nl(void)
         free(s.path); free(s.comp);
         return h_greedy_2opt();
     }
-    multi_stats("h_greedy_local_search_nl", m, tsp_inst.nnodes, sweeps + or_sweeps, utils_timeelapsed(&tsp_inst.c) - t0, s.cost);
+    multi_stats("h_greedy_local_search_nl", m, tsp_inst.nnodes, sweeps + or_sweeps + three_sweeps, utils_timeelapsed(&tsp_inst.c) - t0, s.cost);
     if (rc != 0 && rc != DEADLINE_EXCEEDED) {
         log_error("tspgpu_multistart_local_search_nl: %s", m ? tspgpu_multi_last_error(m) : tspgpu_last_error(g));
     } else {
@@ -946,8 +957,8 @@ ERROR_CODE h_greedy_local_search_nl(void)
         if (!err_ok(u)) log_error("code %d : Error in neighbour-list local search solution update", u);
         if (rc == 0) tsp_inst.starting_node = tsp_inst.nnodes - 1;
         else log_warn("time limit exceeded in greedy neighbour-list local search");
-        log_debug("best start %d, cost %f, %ld 2-opt sweeps (%ld moves), %ld Or-opt sweeps (%ld moves)", start, s.cost, sweeps, two_opt_moves,
-                  or_sweeps, moves);
+        log_debug("best start %d, cost %f, %ld 2-opt sweeps (%ld moves), %ld Or-opt sweeps (%ld moves), %ld 3-opt sweeps (%ld moves)", start,
+                  s.cost, sweeps, two_opt_moves, or_sweeps, moves, three_sweeps, three_moves);
     }
     free(s.path); free(s.comp);
     return e;
@@ -967,7 +978,8 @@ static int env_switch(const char *name)
     return -1;
 }
 
-/* TSP_2OPT_NEIGHBOURS, TSP_OR_OPT_NEIGHBOURS, and TSP_3OPT_WIDTH (the part of a list the 3-opt chains use): unset or 0 = off,
+/* TSP_2OPT_NEIGHBOURS, TSP_OR_OPT_NEIGHBOURS, and TSP_3OPT_WIDTH, TSP_EVERY_START_3OPT_WIDTH, TSP_VNS_3OPT_WIDTH (the part of a
+ * list the 3-opt chains use: in the TSP_OR_OPT polish, in the multi-start over the lists, in the walks over the lists): unset or 0 = off,
  * 1..16 = the list length; anything else is an error (-1) */
 static int env_neighbours(const char *name)
 {
@@ -1020,6 +1032,10 @@ ERROR_CODE tsp_run_algorithm(void)
                 nl_k && nl_k != vns_k ? "2OPT" : "OR_OPT", nl_k && nl_k != vns_k ? nl_k : or_nl_k);
         return INVALID_ARGUMENT;
     }
+    /* TSP_EVERY_START_3OPT_WIDTH=W / TSP_VNS_3OPT_WIDTH=W (env_neighbours): the multi-start / the walks over the lists run the
+     * descent with the 3-opt phase over the first W list entries */
+    const int es_w3 = env_neighbours("TSP_EVERY_START_3OPT_WIDTH"), vns_w3 = env_neighbours("TSP_VNS_3OPT_WIDTH");
+    if (es_w3 < 0 || vns_w3 < 0) return INVALID_ARGUMENT;
     /* TSP_GREEDY_EDGE_NEIGHBOURS=K (env_neighbours): -alg GREEDY builds the greedy-edge tour over lists of K nodes */
     const int ge_k = env_neighbours("TSP_GREEDY_EDGE_NEIGHBOURS");
     if (ge_k < 0) return INVALID_ARGUMENT;
@@ -1055,11 +1071,16 @@ ERROR_CODE tsp_run_algorithm(void)
                  vns_k, vns_w, vns_w == 1 ? "" : "s");
     else if (vns_k) log_warn("TSP_VNS_NEIGHBOURS=%d has no effect without -alg VNS", vns_k);
     else if (getenv("TSP_VNS_WALKS")) log_warn("TSP_VNS_WALKS has no effect without TSP_VNS_NEIGHBOURS");
+    vns_nl_width3 = vns_nl_k ? vns_w3 : 0;
+    if (vns_w3 && !vns_nl_k) log_warn("TSP_VNS_3OPT_WIDTH=%d has no effect without -alg VNS and TSP_VNS_NEIGHBOURS=K", vns_w3);
     every_start_nl_k = es_k;
     if (es_k && tsp_inst.alg == ALG_2OPT_GREEDY)
         log_warn("TSP_EVERY_START_NEIGHBOURS=%d: every start runs the descent over the neighbour lists; results differ from the reference's trajectory",
                  es_k);
     else if (es_k) log_warn("TSP_EVERY_START_NEIGHBOURS=%d has no effect without -alg 2OPT_GREEDY", es_k);
+    every_start_width3 = es_k && tsp_inst.alg == ALG_2OPT_GREEDY ? es_w3 : 0;
+    if (es_w3 && !every_start_width3)
+        log_warn("TSP_EVERY_START_3OPT_WIDTH=%d has no effect without -alg 2OPT_GREEDY and TSP_EVERY_START_NEIGHBOURS=K", es_w3);
     or_opt_nl_k = polish > 0 ? or_nl_k : 0;
     if (or_nl_k && !polish) log_warn("TSP_OR_OPT_NEIGHBOURS=%d has no effect without TSP_OR_OPT=1", or_nl_k);
     three_opt_width = or_opt_nl_k ? width3 : 0;
