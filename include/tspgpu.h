@@ -866,6 +866,63 @@ int tspgpu_vns_walks_nl3(tspgpu_ctx *ctx, int width, int walks, int k, double ti
                          long *totals /* [walks][9] or NULL: two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds, kicks,
                                          three_sweeps, three_moves, three_phases of this call */);
 
+/* ---- Batched don't-look bits (an extension: the descent with looks on a batch of tours, the multi-start, the walks) ----
+ * Rule 8 of "Don't-look bits" on many tours at once, in the way of "Batched neighbour-list 3-opt": every launch serves every
+ * tour of the batch that is still descending, and a tour's phases and its `closing` decisions advance on the device without a
+ * host read in between.  Everything here is opt-in: no other entry point changes.
+ *
+ * Batch.  For each slot of the range, alone, tspgpu_tours_local_search_nl3_dl runs rule 8 of "Don't-look bits" from the slot's
+ * three sets as they stand; width == 0: no 3-opt phase.  Each slot ends exactly as tspgpu_tour_local_search_nl3_dl with the same
+ * width and closing leaves it: the successor array, the cost (bit-equal for double cells as well: the same tree of fixed
+ * shape sums a sweep's accepted deltas), the last delta, the ten counters, the three sets as tspgpu_tour_awake shows them, and
+ * a finished slot.  A phase whose set is empty and that does not close ends with no sweep counted and counts as a phase that
+ * applied nothing, so `rounds` and `three_phases` are what the single-slot descent reports; a tour whose three sets are empty
+ * ends within one sweep launch.  In a closing phase a sweep that accepted nothing and was not full wakes every node of the
+ * phase's set, and the phase goes on with one full sweep.
+ * A slot of the range whose host flag says "every node is awake" (a loaded, built or copied tour, and any slot another kind
+ * of call has rewritten) has its sets filled first.  This entry point does not set that flag; the plain batched entry points
+ * still do.
+ *
+ * Multi-start.  tspgpu_multistart_local_search_nl3_dl is tspgpu_multistart_local_search_nl3 with this descent: every start is
+ * loaded all awake; the chunks, the winner (strict <, ties to the earliest entry), the refusal of a sweep cap and the deadline
+ * behaviour are its; two more totals, `looked` and `full_sweeps`.  There is no sharded form.
+ *
+ * Walks.  tspgpu_vns_walks_nl3_dl takes the arguments of tspgpu_vns_walks_nl3 and `closing`.  Every rule of "Neighbour-list
+ * VNS" holds, with two changes.  Step 1 is rule 8 of "Don't-look bits".  Rule 7 becomes: after a kick phase the slot is what
+ * tspgpu_tour_load of the kicked successor array leaves (order from node 0, direction +1, cost recomputed in the load's
+ * summation order), the three sets are equal, and they hold exactly the nodes v whose unordered pair {pred v, succ v} differs
+ * between the local optimum in front of the kick phase and the tour behind it (one proper segment swap: its six end nodes).
+ * A walk that enters in front of a descent (kick_pending == 0, or left there by a deadline) starts all awake.  A walk that
+ * enters in front of a kick phase, and a dry walk resumed, takes its paths[w] as the local optimum.  So every iteration equals
+ * tspgpu_tour_load + tspgpu_tour_sleep + tspgpu_tour_wake(D) + tspgpu_tour_local_search_nl3_dl on the kicked tour, bit for
+ * bit, and a resumed dry walk equals the uninterrupted one.
+ *
+ * Codes: those of the plain counterparts and of "Don't-look bits" (a width outside 0 .. 16 is 3).
+ * Memory beyond theirs: 4 n bytes of queue and one look-control block per slot of the range (and the sets of "Don't-look
+ * bits"), all or none; 8 carries the byte count.  It is dropped where the batch's candidate arrays are dropped.
+ * tspgpu_info: 82 `looked` of the last batched descent with looks, summed over its tours, 83 its full sweeps (summed), 84 the
+ * largest |Q| of one of its sweeps that was not full (over the tours), 85 the workgroups per tour its queued sweep launches
+ * on the instance in place, min(16, ceil(n / 4)) (each takes the units of tspgpu_info 46 / 51 / 67 per pass; 0: no instance
+ * the descent takes). */
+/* the descent on slots slot0 .. slot0+count-1 at once; per-slot outputs, [count] each (each may be NULL) */
+int tspgpu_tours_local_search_nl3_dl(tspgpu_ctx *ctx, int slot0, int count, int width, int closing, double time_left_s,
+                                     long *two_opt_sweeps, long *two_opt_moves, long *or_sweeps, long *or_moves, int *rounds,
+                                     long *three_sweeps, long *three_moves, int *three_phases,
+                                     long *looked, long *full_sweeps);
+int tspgpu_multistart_local_search_nl3_dl(tspgpu_ctx *ctx, int width, int closing, const int *starts, int nstarts,
+                                          double time_left_s, int *best_path, double *best_cost, int *best_start,
+                                          long *total_two_opt_sweeps, long *total_two_opt_moves,
+                                          long *total_or_sweeps, long *total_or_moves,
+                                          long *total_three_sweeps, long *total_three_moves,
+                                          long *total_looked, long *total_full_sweeps, double *costs_out);
+int tspgpu_vns_walks_nl3_dl(tspgpu_ctx *ctx, int width, int closing, int walks, int k, double time_left_s,
+                            int *paths /* [walks][n] in/out */, double *costs /* [walks] out: cost of paths[w] */,
+                            const int *rand_values /* [walks][nrand] */, long nrand, long *consumed /* [walks] out */,
+                            int *iterations /* [walks] in/out */, int *kick_pending /* [walks] in/out */,
+                            int *best_paths /* [walks][n] in/out */, double *best_costs /* [walks] in/out */,
+                            double *trace /* [walks][k] or NULL; only the iterations this call completes are written */,
+                            long *totals /* [walks][11] or NULL: the nine of tspgpu_vns_walks_nl3, then looked, full sweeps */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -164,6 +164,11 @@ SIGNATURES = {
                                                            _pl, _pl]),
     "tspgpu_vns_walks_nl3": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_double, _ip, _dp, C.c_void_p, C.c_long, C.c_void_p, _ip, _ip, _ip, _dp,
                                        C.c_void_p, C.c_void_p]),
+    "tspgpu_tours_local_search_nl3_dl": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double] + [C.c_void_p] * 10),
+    "tspgpu_multistart_local_search_nl3_dl": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_double, _ip, _pd, _pi, _pl, _pl, _pl, _pl,
+                                                        _pl, _pl, _pl, _pl, C.c_void_p]),
+    "tspgpu_vns_walks_nl3_dl": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _ip, _dp, C.c_void_p, C.c_long, C.c_void_p, _ip, _ip,
+                                          _ip, _dp, C.c_void_p, C.c_void_p]),
 }
 
 _lib = None

@@ -3115,6 +3115,7 @@ __global__ void k_cap_now(Tours S, int slot0, int count)
 #include "tspgpu_looks_dl.inc"
 #include "tspgpu_greedy.inc"
 #include "tspgpu_nlbatch.inc"
+#include "tspgpu_nlbatch_dl.inc"
 #include "tspgpu_nlvns.inc"
 
 // ===========================================================================
@@ -3156,6 +3157,11 @@ struct MEM_GROUP InstanceMem {            // of one n: new_instance drops it
     M2Buf nlb{};
     NlbCtl *d_nlb_ctl = nullptr;
     int nlb_cap = 0;
+    // ... with don't-look bits (tspgpu_nlbatch_dl.inc): a queue [n] and a look block per slot of a range of nlbq_cap slots, at the
+    // first batched call with looks; both, or none.  They go where the candidate arrays go
+    int *d_nlb_queue = nullptr;
+    LookCtl *d_nlb_look = nullptr;
+    int nlbq_cap = 0;
     // neighbour-list VNS (tspgpu_nlvns.inc): per walk a second order array, the incumbent and a control block, for nlv_cap walks;
     // the walks' number blocks and trace rows of the call in hand.  All of them, or none
     int *d_nlv_ord = nullptr, *d_nlv_best = nullptr;
@@ -3190,7 +3196,9 @@ struct MEM_GROUP InstanceMem {            // of one n: new_instance drops it
     Rows nlb_rows(size_t n) { Rows r = m2_rows(nlb, n); r.push_back({&d_nlb_ctl, sizeof(NlbCtl)}); return r; }     // per slot
     Rows nlv_rows(size_t n) { return {{&d_nlv_ord, n * 4}, {&d_nlv_best, n * 4}, {&d_nlv_ctl, sizeof(NlvCtl)}}; }           // per walk
     void drop_nlv() { tspmem::free_rows<HipMem>(nlv_rows(0)); nlv_cap = 0; tspmem::reset_all(d_nlv_rand, d_nlv_trace); }
-    void drop_nlb() { tspmem::free_rows<HipMem>(nlb_rows(0)); nlb_cap = 0; drop_nlv(); }
+    Rows nlbq_rows(size_t n) { return {{&d_nlb_queue, n * 4}, {&d_nlb_look, sizeof(LookCtl)}}; }                           // per slot
+    void drop_nlbq() { tspmem::free_rows<HipMem>(nlbq_rows(0)); nlbq_cap = 0; }
+    void drop_nlb() { tspmem::free_rows<HipMem>(nlb_rows(0)); nlb_cap = 0; drop_nlbq(); drop_nlv(); }
     void drop_grid() { tspmem::reset_all(d_gxy, d_gidx, d_gpos, d_cstart, d_gcell, d_knn); grid_G = 0; grid_ok = false; }
     void reset() { tspmem::free_rows<HipMem>(m2_rows(m2, 0)); drop_look_ctx(); drop_greedy(); drop_nlb(); drop_grid(); }
     ~InstanceMem() { reset(); }
@@ -3362,6 +3370,7 @@ struct tspgpu_ctx : ContextMem, InstanceMem, CostMem, SlotMem {
     int nl3_phases = 0;
     // don't-look bits (tspgpu_looks_dl.inc): units looked at, full sweeps and the largest sweep that was not full of the last call
     long dl_looked = 0, dl_full = 0, dl_max_q = 0;
+    long nlb_dl_looked = 0, nlb_dl_full = 0, nlb_dl_max_q = 0;  // the last batched descent with looks: sums and the maximum over its tours
     // greedy-edge construction (tspgpu_greedy.inc): the last one's rounds per phase, phase-1 edges, free nodes entering phase 2
     long ge_rounds1 = 0, ge_rounds2 = 0, ge_edges1 = 0, ge_free = 0;
     // batched neighbour-list descent (tspgpu_nlbatch.inc)
@@ -4835,7 +4844,11 @@ struct Descent {
     int nr = 0;
     long hs = 0, hm = 0;    // 3-opt sweeps and moves, 3-opt phases: the batched descent with a 3-opt phase alone fills them
     int np = 0;
-    void operator+=(const Descent &d) { tw += d.tw; tm += d.tm; os += d.os; om += d.om; nr += d.nr; hs += d.hs; hm += d.hm; np += d.np; }
+    long lk = 0, lf = 0;    // looked units and full sweeps: the batched descent with looks alone fills them
+    void operator+=(const Descent &d)
+    {
+        tw += d.tw; tm += d.tm; os += d.os; om += d.om; nr += d.nr; hs += d.hs; hm += d.hm; np += d.np; lk += d.lk; lf += d.lf;
+    }
 };
 
 // D[0 .. count) to the caller's arrays, each of them optional
@@ -5134,6 +5147,10 @@ long tspgpu_info(const tspgpu_ctx *ctx, int what)
     case 79: return ctx->nlb_three_sweeps;
     case 80: return ctx->nlb_three_moves;
     case 81: return ctx->nlb_three_max_k;
+    case 82: return ctx->nlb_dl_looked;
+    case 83: return ctx->nlb_dl_full;
+    case 84: return ctx->nlb_dl_max_q;
+    case 85: return ctx->have_costs && ctx->n >= 8 ? std::min(NLB_QSWEEP_WGS, (ctx->n + ORNL_STARTS - 1) / ORNL_STARTS) : 0;
     case 55: return ctx->have_costs && ctx->symmetric && ctx->n >= 8 ? (ctx->n + ORNL_STARTS - 1) / ORNL_STARTS : 0;
     case 12: return (ctx->built && ctx->grid_ok && ctx->opt_nn != 1 && ctx->cost_bound < 134217728.0) ? ctx->grid_G : 0;
     case 13: return ctx->grid_max_occ;
@@ -6222,14 +6239,14 @@ static int or_descent_batch(tspgpu_ctx *ctx, int slot0, int count, double time_l
 }
 
 // the argument checks of the batched entry points: the slots exist and hold tours
-static int or_batch_args(tspgpu_ctx *ctx, int slot0, int count)
+static int or_batch_args(tspgpu_ctx *ctx, int slot0, int count, bool rewrites = true)
 {
     if (slot0 < 0 || count <= 0 || slot0 > INT_MAX - count) return fail(ctx, E_INVALID, "bad slot range: slot0 %d, count %d", slot0, count);
     for (int i = 0; i < count; i++) {
         const int rc = need_slot(ctx, slot0 + i);
         if (rc) return rc;
     }
-    wake_slots(ctx, slot0, count);      // (a batched descent rewrites them)
+    if (rewrites) wake_slots(ctx, slot0, count);    // (a batched descent rewrites them; one with looks keeps the sets itself)
     return E_OK;
 }
 
@@ -7494,18 +7511,68 @@ static int nlb_ensure(tspgpu_ctx *ctx, int count)
     return E_OK;
 }
 
-// one sweep of every tour of the first `live` slots of the list: the four launches, grid rows in runs of at most 65 535.
+// the looks mode of a batched descent: off, or "Batched don't-look bits" with its `closing`
+struct NlbMode { bool looks = false; int closing = 0; };
+
+// ... its memory beyond nlb_ensure's: the slots' sets (ensure_looks), and a queue of n nodes and a look block per slot of the range
+static int nlbq_ensure(tspgpu_ctx *ctx, int count)
+{
+    int rc = ensure_looks(ctx);
+    if (rc) return rc;
+    if (count <= ctx->nlbq_cap) return E_OK;
+    ctx->drop_nlbq();
+    const Rows rows = ctx->nlbq_rows((size_t)ctx->n);
+    const hipError_t e = tspmem::grow(HipMem{ctx->stream}, rows, 0, (size_t)count);
+    if (e != hipSuccess) {                  // all or none
+        (void)hipGetLastError();
+        return fail(ctx, E_EXHAUSTED, "the batched descent with don't-look bits needs %zu bytes of device memory for the queues of %d tours of %d nodes (%s)",
+                    tspmem::rows_bytes(rows, (size_t)count), count, ctx->n, hipGetErrorString(e));
+    }
+    ctx->nlbq_cap = count;
+    return E_OK;
+}
+
+// the sets of the slots slot0 .. slot0 + count - 1 as the device arrays: flagged slots ("every node is awake") are filled
+static int nlb_fill_flagged(tspgpu_ctx *ctx, int slot0, int count)
+{
+    const size_t bytes = 3 * (size_t)ctx->n;
+    for (int i = slot0; i < slot0 + count;) {
+        if (!ctx->look_all[i]) { i++; continue; }
+        int j = i;
+        while (j < slot0 + count && ctx->look_all[j]) ctx->look_all[j++] = 0;
+        HIP_TRY(hipMemsetAsync(ctx->d_awake + (size_t)i * bytes, 1, (size_t)(j - i) * bytes, ctx->stream));
+        i = j;
+    }
+    return E_OK;
+}
+
+// one sweep of every tour of the first `live` slots of the list: the four launches (six with looks: the queue pass in front
+// of the sweep, the wake pass in front of the apply), grid rows in runs of at most 65 535.
 // THREE: the instantiations with the 3-opt phase, at width w3
 template <bool THREE>
-static int nlb_launch_sweep_as(tspgpu_ctx *ctx, int slot0, int live, int w3)
+static int nlb_launch_sweep_as(tspgpu_ctx *ctx, int slot0, int live, int w3, const NlbMode &M)
 {
     const int n = ctx->n, W = (n + ORNL_STARTS - 1) / ORNL_STARTS, G = std::min(NLB_APPLY_WGS, (n + 1) / 2);
     NlbCtl *ctl = ctx->d_nlb_ctl;
+    const NlbLooks Q{ctx->d_awake, ctx->d_nlb_queue, ctx->d_nlb_look, M.closing};
     const int run = std::max(1, std::min(65535, (1 << 23) / W));    // (a grid holds fewer than 2^32 threads)
     for (int off = 0; off < live; off += run) {
         const unsigned rows = (unsigned)std::min(run, live - off);
         const int *list = ctx->d_live + off;
-        if (ctx->otf)
+        if (M.looks) {
+            const int QW = std::min(NLB_QSWEEP_WGS, W);
+            hipLaunchKernelGGL(k_nlb_queue<THREE>, dim3(rows), dim3(1024), 0, ctx->stream, ctx->S, n, list, slot0, ctx->nlb, ctl, Q);
+            HIP_TRY(hipGetLastError());
+            if (ctx->otf)
+                kind_switch(ctx, [&](auto kind, auto *pts, auto *) {
+                    hipLaunchKernelGGL((k_nlb_qsweep_otf<kind(), THREE>), dim3(QW, rows), dim3(256), 0, ctx->stream, ctx->S, pts, n, list, slot0,
+                                       ctx->nl, ctx->nlb, (const NlbCtl *)ctl, w3, Q);
+                });
+            else
+                ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_nlb_qsweep<T, THREE>), dim3(QW, rows), dim3(256), 0, ctx->stream, ctx->S,
+                                                             (const T *)ctx->d_mat.p, n, ctx->ld, list, slot0, ctx->nl, ctx->nlb,
+                                                             (const NlbCtl *)ctl, w3, Q));
+        } else if (ctx->otf)
             kind_switch(ctx, [&](auto kind, auto *pts, auto *) {
                 hipLaunchKernelGGL((k_nlb_sweep_otf<kind(), THREE>), dim3(W, rows), dim3(256), 0, ctx->stream, ctx->S, pts, n, list, slot0, ctx->nl,
                                    ctx->nlb, (const NlbCtl *)ctl, w3);
@@ -7518,7 +7585,19 @@ static int nlb_launch_sweep_as(tspgpu_ctx *ctx, int slot0, int live, int w3)
         HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(k_nlb_select, dim3((n + 255) / 256, rows), dim3(256), 0, ctx->stream, n, list, slot0, ctx->nlb, (const NlbCtl *)ctl);
         HIP_TRY(hipGetLastError());
-        if (ctx->otf)
+        if (M.looks) {
+            hipLaunchKernelGGL(k_nlb_wake<THREE>, dim3(NLB_WAKE_WGS, rows), dim3(256), 0, ctx->stream, ctx->S, n, list, slot0, ctx->nl, ctx->nlb,
+                               (const NlbCtl *)ctl, Q);
+            HIP_TRY(hipGetLastError());
+            if (ctx->otf)
+                kind_switch(ctx, [&](auto kind, auto *pts, auto *) {
+                    hipLaunchKernelGGL((k_nlb_apply_dl_otf<kind(), THREE>), dim3(G, rows), dim3(256), 0, ctx->stream, ctx->S, pts, n, list, slot0,
+                                       ctx->nlb, ctl, ctx->nl, Q);
+                });
+            else
+                ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_nlb_apply_dl<T, THREE>), dim3(G, rows), dim3(256), 0, ctx->stream, ctx->S,
+                                                             (const T *)ctx->d_mat.p, n, ctx->ld, list, slot0, ctx->nlb, ctl, ctx->nl, Q));
+        } else if (ctx->otf)
             kind_switch(ctx, [&](auto kind, auto *pts, auto *) {
                 hipLaunchKernelGGL((k_nlb_apply_otf<kind(), THREE>), dim3(G, rows), dim3(256), 0, ctx->stream, ctx->S, pts, n, list, slot0, ctx->nlb,
                                    ctl, ctx->nl);
@@ -7532,16 +7611,32 @@ static int nlb_launch_sweep_as(tspgpu_ctx *ctx, int slot0, int live, int w3)
 }
 
 // w3: the width of the 3-opt phase, 0: the descent has none
-static int nlb_launch_sweep(tspgpu_ctx *ctx, int slot0, int live, int w3)
+static int nlb_launch_sweep(tspgpu_ctx *ctx, int slot0, int live, int w3, const NlbMode &M = NlbMode{})
 {
-    return w3 > 0 ? nlb_launch_sweep_as<true>(ctx, slot0, live, w3) : nlb_launch_sweep_as<false>(ctx, slot0, live, 0);
+    return w3 > 0 ? nlb_launch_sweep_as<true>(ctx, slot0, live, w3, M) : nlb_launch_sweep_as<false>(ctx, slot0, live, 0, M);
+}
+
+// the look blocks of the first `count` places of a range into D (lk, lf) and the context's totals
+static int nlb_looks_out(tspgpu_ctx *ctx, int count, Descent *D)
+{
+    std::vector<LookCtl> hl((size_t)count);
+    const int rc = ctl_get(ctx, hl.data(), (const LookCtl *)ctx->d_nlb_look, (size_t)count);
+    if (rc) return rc;
+    ctx->nlb_dl_looked = ctx->nlb_dl_full = ctx->nlb_dl_max_q = 0;
+    for (int i = 0; i < count; i++) {
+        if (D) { D[i].lk = (long)hl[i].looked; D[i].lf = (long)hl[i].full; }
+        ctx->nlb_dl_looked += (long)hl[i].looked; ctx->nlb_dl_full += (long)hl[i].full;
+        ctx->nlb_dl_max_q = std::max(ctx->nlb_dl_max_q, (long)hl[i].max_q);
+    }
+    return E_OK;
 }
 
 // ornl_descent (w3 > 0: nl3_descent at that width) on the slots slot0 .. slot0 + count - 1 at once.  The control blocks are
 // armed (2-opt phase, round 1) and the slots re-armed as m2_arm does; then sweeps of all live tours -- four between looks at
 // the control blocks, one under a deadline, as m2_run -- and the tours whose descent has ended leave the list.  D: per-slot
 // counters, [count]
-static int nlb_descent(tspgpu_ctx *ctx, int slot0, int count, int w3, double time_left_s, Descent *D, bool *late)
+// M.looks: every phase is a phase with looks, from the slots' sets as they stand (flagged slots: every node awake)
+static int nlb_descent(tspgpu_ctx *ctx, int slot0, int count, int w3, double time_left_s, Descent *D, bool *late, const NlbMode &M = NlbMode{})
 {
     const double t_end = deadline_of(time_left_s);
     *late = false;
@@ -7549,6 +7644,11 @@ static int nlb_descent(tspgpu_ctx *ctx, int slot0, int count, int w3, double tim
     ctx->nlb_w3 = w3; ctx->nlb_three_sweeps = ctx->nlb_three_moves = ctx->nlb_three_max_k = 0;
     int rc = nlb_ensure(ctx, count);
     if (rc) return rc;
+    if (M.looks) {
+        if ((rc = nlbq_ensure(ctx, count))) return rc;
+        if ((rc = nlb_fill_flagged(ctx, slot0, count))) return rc;
+        HIP_TRY(hipMemsetAsync(ctx->d_nlb_look, 0, (size_t)count * sizeof(LookCtl), ctx->stream));
+    }
     std::vector<NlbCtl> hc((size_t)count);
     memset(hc.data(), 0, hc.size() * sizeof(NlbCtl));
     for (NlbCtl &c : hc) c.rounds = 1;
@@ -7560,7 +7660,7 @@ static int nlb_descent(tspgpu_ctx *ctx, int slot0, int count, int w3, double tim
     if ((rc = set_live(ctx, live))) return rc;
     const looks::Result r = looks::drive_live(
         now_s, t_end, 4, live, [](int) {},
-        [&](int len) { const int e = nlb_launch_sweep(ctx, slot0, len, w3); ctx->nlb_launches += !e; return e; },
+        [&](int len) { const int e = nlb_launch_sweep(ctx, slot0, len, w3, M); ctx->nlb_launches += !e; return e; },
         [&] { return ctl_get(ctx, hc.data(), ctx->d_nlb_ctl, (size_t)count); }, [&](int t) { return hc[t - slot0].stop != 0; },
         [&](const std::vector<int> &list) { return set_live(ctx, list); });
     ctx->nlb_max_live = r.max_live;
@@ -7573,15 +7673,16 @@ static int nlb_descent(tspgpu_ctx *ctx, int slot0, int count, int w3, double tim
         ctx->nlb_three_sweeps += D[i].hs; ctx->nlb_three_moves += D[i].hm;
         ctx->nlb_three_max_k = std::max(ctx->nlb_three_max_k, (long)hc[i].three_max_k);
     }
+    if (M.looks && (rc = nlb_looks_out(ctx, count, D))) return rc;
     return E_OK;
 }
 
 // the range of a batched descent over the lists, behind the family's check: count slots from slot0, each with a tour
-static int nlb_range(tspgpu_ctx *ctx, int slot0, int count)
+static int nlb_range(tspgpu_ctx *ctx, int slot0, int count, bool rewrites = true)
 {
     if (slot0 < 0 || count <= 0 || count > ctx->tcap || slot0 > ctx->tcap - count)      // (the range first: a slot past the end is no slot without a tour)
         return fail(ctx, E_INVALID, "bad slot range: slot0 %d, count %d of %d slots", slot0, count, ctx->tcap);
-    return or_batch_args(ctx, slot0, count);
+    return or_batch_args(ctx, slot0, count, rewrites);
 }
 
 static int nlb_no_cap(tspgpu_ctx *ctx)
@@ -7670,6 +7771,57 @@ int tspgpu_multistart_local_search_nl3(tspgpu_ctx *ctx, int width, const int *st
     return rc;
 }
 
+int tspgpu_tours_local_search_nl3_dl(tspgpu_ctx *ctx, int slot0, int count, int width, int closing, double time_left_s, long *two_opt_sweeps,
+                                     long *two_opt_moves, long *or_sweeps, long *or_moves, int *rounds, long *three_sweeps, long *three_moves,
+                                     int *three_phases, long *looked, long *full_sweeps)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    if (width < 0 || width > NL_KMAX) return fail(ctx, E_INVALID, "the descent with looks takes a width of 0 to %d list entries, got %d", NL_KMAX, width);
+    hipSetDevice(ctx->device);
+    ctx->nl3_width = width;
+    int rc = dl_descent_check(ctx);
+    if (rc) return rc;
+    if ((rc = nlb_range(ctx, slot0, count, false))) return rc;
+    std::vector<Descent> D(count);
+    bool late = false;
+    if ((rc = nlb_descent(ctx, slot0, count, width ? ctx->nl3_w : 0, time_left_s, D.data(), &late, NlbMode{true, closing}))) return rc;
+    descent_out(D.data(), count, two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds);
+    for (int i = 0; i < count; i++) {
+        if (three_sweeps) three_sweeps[i] = D[i].hs;
+        if (three_moves) three_moves[i] = D[i].hm;
+        if (three_phases) three_phases[i] = D[i].np;
+        if (looked) looked[i] = D[i].lk;
+        if (full_sweeps) full_sweeps[i] = D[i].lf;
+    }
+    return done_code(late);
+}
+
+int tspgpu_multistart_local_search_nl3_dl(tspgpu_ctx *ctx, int width, int closing, const int *starts, int nstarts, double time_left_s,
+                                          int *best_path, double *best_cost, int *best_start, long *total_two_opt_sweeps,
+                                          long *total_two_opt_moves, long *total_or_sweeps, long *total_or_moves, long *total_three_sweeps,
+                                          long *total_three_moves, long *total_looked, long *total_full_sweeps, double *costs_out)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    if (!best_path || !best_cost || !best_start || nstarts <= 0) return fail(ctx, E_INVALID, "bad argument");
+    if (width < 0 || width > NL_KMAX) return fail(ctx, E_INVALID, "the descent with looks takes a width of 0 to %d list entries, got %d", NL_KMAX, width);
+    hipSetDevice(ctx->device);
+    ctx->nl3_width = width;
+    int rc = dl_descent_check(ctx);
+    if (rc) return rc;
+    if ((rc = nlb_no_cap(ctx))) return rc;
+    const int w3 = width ? ctx->nl3_w : 0;
+    MultiStart ms;
+    rc = multistart(ctx, starts, nstarts, time_left_s, -1, best_path, best_cost, best_start, costs_out, &ms,
+                    [&](int m, double left, bool *late, Descent *D) { return nlb_descent(ctx, 0, m, w3, left, D, late, NlbMode{true, closing}); });
+    if (rc && rc != E_DEADLINE) return rc;
+    descent_out(&ms.total, 1, total_two_opt_sweeps, total_two_opt_moves, total_or_sweeps, total_or_moves, nullptr);
+    if (total_three_sweeps) *total_three_sweeps = ms.total.hs;
+    if (total_three_moves) *total_three_moves = ms.total.hm;
+    if (total_looked) *total_looked = ms.total.lk;
+    if (total_full_sweeps) *total_full_sweeps = ms.total.lf;
+    return rc;
+}
+
 } // extern "C"
 
 // ---- neighbour-list VNS (tspgpu_nlvns.inc) -----------------------------------------------------------------------------
@@ -7695,15 +7847,20 @@ static int nlv_ensure(tspgpu_ctx *ctx, int walks, long nrand, int k)
     return E_OK;
 }
 
-static int nlv_launch_step(tspgpu_ctx *ctx, int live, bool trace)
+static int nlv_launch_step(tspgpu_ctx *ctx, int live, bool trace, bool looks)
 {
     const int n = ctx->n;
     for (int off = 0; off < live; off += 65535 * 16) {      // (a grid of 1024-thread workgroups holds fewer than 2^32 threads)
         const unsigned wgs = (unsigned)std::min(65535 * 16, live - off);
-        ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_nlv_step<T>), dim3(wgs), dim3(1024), 0, ctx->stream, ctx->S, (const T *)ctx->d_mat.p, n, ctx->ld,
-                                                     (const int *)(ctx->d_live + off), 0, ctx->nlb, ctx->d_nlb_ctl, ctx->d_nlv_ctl, ctx->d_nlv_ord,
-                                                     ctx->d_nlv_best, (const int *)ctx->d_nlv_rand.p, trace ? ctx->d_nlv_trace.p : nullptr,
-                                                     (const double2 *)ctx->d_pts.p, ctx->kind));
+#define NLV_STEP(DL)                                                                                                                      \
+    ELEM_SWITCH(ctx->elem, T, hipLaunchKernelGGL((k_nlv_step<T, DL>), dim3(wgs), dim3(1024), 0, ctx->stream, ctx->S, (const T *)ctx->d_mat.p, n,  \
+                                                 ctx->ld, (const int *)(ctx->d_live + off), 0, ctx->nlb, ctx->d_nlb_ctl, ctx->d_nlv_ctl,       \
+                                                 ctx->d_nlv_ord, ctx->d_nlv_best, (const int *)ctx->d_nlv_rand.p,                              \
+                                                 trace ? ctx->d_nlv_trace.p : nullptr, (const double2 *)ctx->d_pts.p, ctx->kind,               \
+                                                 DL ? ctx->d_awake : nullptr))
+        if (looks) NLV_STEP(true);
+        else NLV_STEP(false);
+#undef NLV_STEP
         HIP_TRY(hipGetLastError());
     }
     return E_OK;
@@ -7712,7 +7869,8 @@ static int nlv_launch_step(tspgpu_ctx *ctx, int live, bool trace)
 // the walks on slots 0 .. walks-1: upload, arm, sweep rounds of five launches (the four of the batched descent and the step)
 // -- four rounds between looks at the control blocks, one under a deadline, as nlb_descent --, download
 static int nlv_walks(tspgpu_ctx *ctx, int w3, int walks, int k, double time_left_s, int *paths, double *costs, const int *rand_values, long nrand,
-                     long *consumed, int *iterations, int *kick_pending, int *best_paths, double *best_costs, double *trace, long *totals)
+                     long *consumed, int *iterations, int *kick_pending, int *best_paths, double *best_costs, double *trace, long *totals,
+                     const NlbMode &M = NlbMode{})
 {
     const double t_end = deadline_of(time_left_s);
     const size_t n = (size_t)ctx->n, W = (size_t)walks;
@@ -7726,6 +7884,7 @@ static int nlv_walks(tspgpu_ctx *ctx, int w3, int walks, int k, double time_left
     if ((rc = ensure_tours(ctx, walks))) return rc;
     if ((rc = nlb_ensure(ctx, walks))) return rc;
     if ((rc = nlv_ensure(ctx, walks, nrand, k))) return rc;
+    if (M.looks && (rc = nlbq_ensure(ctx, walks))) return rc;
     ctx->nlv_walks = walks; ctx->nlv_iterations = ctx->nlv_rounds = ctx->nlv_max_live = ctx->nlv_dry = 0;
 
     std::vector<NlbCtl> hc(W);
@@ -7745,6 +7904,10 @@ static int nlv_walks(tspgpu_ctx *ctx, int w3, int walks, int k, double time_left
     HIP_TRY(hipMemcpyAsync(ctx->S.ord, ords.data(), W * n * 4, hipMemcpyHostToDevice, ctx->stream));
     if ((rc = init_slots(ctx, 0, walks, -1))) return rc;    // (recomputes the cost: refinment.c:6-9)
     mark_slots(ctx, 0, walks, true);
+    if (M.looks) {                          // a walk in front of a descent starts all awake; the step writes the sets behind every kick phase
+        if ((rc = nlb_fill_flagged(ctx, 0, walks))) return rc;
+        HIP_TRY(hipMemsetAsync(ctx->d_nlb_look, 0, W * sizeof(LookCtl), ctx->stream));
+    }
     HIP_TRY(hipMemcpyAsync(ctx->d_nlv_best, best_paths, W * n * 4, hipMemcpyHostToDevice, ctx->stream));
     if (nrand > 0) HIP_TRY(hipMemcpyAsync(ctx->d_nlv_rand.p, rand_values, W * (size_t)nrand * 4, hipMemcpyHostToDevice, ctx->stream));
     if (trace && k > 0) HIP_TRY(hipMemsetAsync(ctx->d_nlv_trace.p, 0xff, W * (size_t)k * 8, ctx->stream));     // (NaN: a cell not written)
@@ -7756,8 +7919,8 @@ static int nlv_walks(tspgpu_ctx *ctx, int w3, int walks, int k, double time_left
     const looks::Result r = looks::drive_live(
         now_s, t_end, 4, live, [](int) {},
         [&](int len) {
-            int e = nlb_launch_sweep(ctx, 0, len, w3);
-            if (!e && !(e = nlv_launch_step(ctx, len, trace != nullptr))) ctx->nlv_rounds++;
+            int e = nlb_launch_sweep(ctx, 0, len, w3, M);
+            if (!e && !(e = nlv_launch_step(ctx, len, trace != nullptr, M.looks))) ctx->nlv_rounds++;
             return e;
         },
         [&] { return ctl_get(ctx, hv.data(), ctx->d_nlv_ctl, W); }, [&](int w) { return hv[w].halt != 0; },
@@ -7774,6 +7937,8 @@ static int nlv_walks(tspgpu_ctx *ctx, int w3, int walks, int k, double time_left
     HIP_TRY(hipMemcpyAsync(best_paths, ctx->d_nlv_best, W * n * 4, hipMemcpyDeviceToHost, ctx->stream));
     if (!tr.empty()) HIP_TRY(hipMemcpyAsync(tr.data(), ctx->d_nlv_trace.p, tr.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
+    std::vector<Descent> DL(M.looks ? W : 0);
+    if (M.looks && (rc = nlb_looks_out(ctx, walks, DL.data()))) return rc;
     for (size_t w = 0; w < W; w++) {
         ctx->nlv_iterations += hv[w].it - iterations[w];
         if (hv[w].halt == 2) ctx->nlv_dry++;
@@ -7781,10 +7946,11 @@ static int nlv_walks(tspgpu_ctx *ctx, int w3, int walks, int k, double time_left
         for (size_t i = 0; i < tr.size() / W; i++)
             if (tr[w * k + i] == tr[w * k + i]) trace[w * k + i] = tr[w * k + i];
         if (totals) {
-            long *o = totals + (w3 > 0 ? 9 : 6) * w;
+            long *o = totals + (M.looks ? 11 : w3 > 0 ? 9 : 6) * w;
             o[0] = (long)hc[w].two_opt_sweeps; o[1] = (long)hc[w].two_opt_moves; o[2] = (long)hc[w].or_sweeps; o[3] = (long)hc[w].or_moves;
             o[4] = hc[w].rounds; o[5] = (long)hv[w].kicks;
-            if (w3 > 0) { o[6] = (long)hc[w].three_sweeps; o[7] = (long)hc[w].three_moves; o[8] = hc[w].three_phases; }
+            if (w3 > 0 || M.looks) { o[6] = (long)hc[w].three_sweeps; o[7] = (long)hc[w].three_moves; o[8] = hc[w].three_phases; }
+            if (M.looks) { o[9] = DL[w].lk; o[10] = DL[w].lf; }
         }
     }
     if (late) return E_DEADLINE;
@@ -7828,6 +7994,25 @@ int tspgpu_vns_walks_nl3(tspgpu_ctx *ctx, int width, int walks, int k, double ti
         if (iterations[w] < 0 || iterations[w] > k) return fail(ctx, E_INVALID, "iterations[%d] = %d is outside [0, %d]", w, iterations[w], k);
     return nlv_walks(ctx, ctx->nl3_w, walks, k, time_left_s, paths, costs, rand_values, nrand, consumed, iterations, kick_pending, best_paths,
                      best_costs, trace, totals);
+}
+
+int tspgpu_vns_walks_nl3_dl(tspgpu_ctx *ctx, int width, int closing, int walks, int k, double time_left_s, int *paths, double *costs,
+                            const int *rand_values, long nrand, long *consumed, int *iterations, int *kick_pending, int *best_paths,
+                            double *best_costs, double *trace, long *totals)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    if (walks <= 0 || k < 0 || nrand < 0 || !paths || !costs || !consumed || !iterations || !kick_pending || !best_paths || !best_costs ||
+        (nrand > 0 && !rand_values))
+        return fail(ctx, E_INVALID, "bad argument");
+    if (width < 0 || width > NL_KMAX) return fail(ctx, E_INVALID, "the descent with looks takes a width of 0 to %d list entries, got %d", NL_KMAX, width);
+    hipSetDevice(ctx->device);
+    ctx->nl3_width = width;
+    const int rc = dl_descent_check(ctx);
+    if (rc) return rc;
+    for (int w = 0; w < walks; w++)
+        if (iterations[w] < 0 || iterations[w] > k) return fail(ctx, E_INVALID, "iterations[%d] = %d is outside [0, %d]", w, iterations[w], k);
+    return nlv_walks(ctx, width ? ctx->nl3_w : 0, walks, k, time_left_s, paths, costs, rand_values, nrand, consumed, iterations, kick_pending,
+                     best_paths, best_costs, trace, totals, NlbMode{true, closing});
 }
 
 } // extern "C"

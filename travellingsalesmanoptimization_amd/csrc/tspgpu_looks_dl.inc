@@ -30,30 +30,18 @@
 // ---------------------------------------------------------------------------
 static constexpr int LOOK_WGS_PER_CU = 4;   // workgroups of a queued sweep and of k_look_wake: at most this many per compute unit
 
-struct LookCtl {            // one per context; reset before every phase with looks
-    int qlen;               // |Q| of the sweep in hand
-    int last_q;             // |Q| of the last sweep that ran
-    int max_q;              // the largest |Q| of a sweep that was not full
-    int pad;
-    long long looked;       // sum of |Q|
-    long long full;         // sweeps with |Q| = n
-};
-
 struct LookBuf {
     unsigned char *awake;   // [3][n]: the slot's sets
     int *queue;             // [n]
-    LookCtl *ctl;
+    LookCtl *ctl;           // (tspgpu_nlphase.h)
 };
 
-template <int F, int FWD>
-__global__ void __launch_bounds__(1024) k_look_queue(Tours S, int n, int t, LookBuf K, M2Buf B, M2Ctl *ctl, int closing)
+// The queue pass of one workgroup of 16 waves, in two halves around the caller's decision on an empty Q (k_look_queue here,
+// k_nlb_queue in tspgpu_nlbatch_dl.inc).  look_queue_scan: the window tests of set A over FWD positions into masks[], the
+// waves' counts into wcnt[16], ONE barrier; answers |Q| and, in `at`, the place of this wave's first looked unit
+__device__ __forceinline__ int look_queue_scan(const unsigned char *A, const int *succ, int n, int FWD, u64 *masks, int *wcnt, int &at)
 {
-    __shared__ u64 masks[2048];             // the window bits of 64 nodes per step: n <= 131 072 (new_instance)
-    __shared__ int wcnt[16];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-    if (ctl->stop) return;
-    unsigned char *A = K.awake + (size_t)F * n;
-    const int *succ = S.succ + (size_t)t * n;
     const int steps = (n + 63) >> 6, per = (steps + 15) / 16, s0 = min(steps, w * per), s1 = min(steps, s0 + per);
     int c = 0;
     for (int s = s0; s < s1; s++) {         // (uniform over the wave: the ballot is reached by all its lanes)
@@ -69,17 +57,23 @@ __global__ void __launch_bounds__(1024) k_look_queue(Tours S, int n, int t, Look
     }
     if (lane == 0) wcnt[w] = c;
     __syncthreads();                        // every window read of the workgroup lies in front of this barrier
-    int at = 0, total = 0;
+    int total = 0;
+    at = 0;
     for (int i = 0; i < 16; i++) {
         const int v = wcnt[i];
         if (i < w) at += v;
         total += v;
     }
-    if (total == 0 && !closing) {           // nothing is awake: the phase ends here as every phase does (stop, done), no sweep is counted
-        if (tid == 0) { ctl->stop = 1; ctl->m = 0; K.ctl->qlen = 0; S.done[t] = 1; }
-        return;
-    }
-    const bool all = total == 0;            // ... or, in a closing phase, one full sweep
+    return total;
+}
+
+// look_queue_emit: the looked units in ascending node order to queue[0 .. |Q|) (all: every node), raw_b = -1 for the others,
+// A := 0, and the look block's counts
+__device__ __forceinline__ void look_queue_emit(unsigned char *A, int n, const LookBuf &K, const M2Buf &B, const u64 *masks, int at, int total,
+                                                bool all)
+{
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    const int steps = (n + 63) >> 6, per = (steps + 15) / 16, s0 = min(steps, w * per), s1 = min(steps, s0 + per);
     for (int s = s0; s < s1; s++) {
         const int a = s * 64 + lane;
         const u64 m = masks[s];
@@ -100,6 +94,22 @@ __global__ void __launch_bounds__(1024) k_look_queue(Tours S, int n, int t, Look
         if (q == n) L->full += 1;
         else L->max_q = max(L->max_q, q);
     }
+}
+
+template <int F, int FWD>
+__global__ void __launch_bounds__(1024) k_look_queue(Tours S, int n, int t, LookBuf K, M2Buf B, M2Ctl *ctl, int closing)
+{
+    __shared__ u64 masks[2048];             // the window bits of 64 nodes per step: n <= 131 072 (new_instance)
+    __shared__ int wcnt[16];
+    if (ctl->stop) return;
+    unsigned char *A = K.awake + (size_t)F * n;
+    int at;
+    const int total = look_queue_scan(A, S.succ + (size_t)t * n, n, FWD, masks, wcnt, at);
+    if (total == 0 && !closing) {           // nothing is awake: the phase ends here as every phase does (stop, done), no sweep is counted
+        if (threadIdx.x == 0) { ctl->stop = 1; ctl->m = 0; K.ctl->qlen = 0; S.done[t] = 1; }
+        return;
+    }
+    look_queue_emit(A, n, K, B, masks, at, total, total == 0);      // (an empty Q of a closing phase: one full sweep)
 }
 
 template <typename T>
@@ -166,14 +176,14 @@ __global__ void __launch_bounds__(256) k_nl3_qsweep_otf(Tours S, const typename 
         nl3_sweep_unit<int>(S, OrPtsCost<KIND>{pts}, n, t, NL, W, B, K.queue[g]);
 }
 
-// rule 3 of "Don't-look bits", on the tour as it stands in front of the apply
+// rule 3 of "Don't-look bits", on the tour as it stands in front of the apply: the sweep of family F looked at K.ctl->qlen
+// units and has m candidates (the body of k_look_wake, and of k_nlb_wake in tspgpu_nlbatch_dl.inc)
 template <int F>
-__global__ void __launch_bounds__(256) k_look_wake(Tours S, int n, int t, NlBuf NL, LookBuf K, M2Buf B, const M2Ctl *ctl)
+__device__ __forceinline__ void look_wake_tour(const Tours &S, int n, int t, const NlBuf &NL, const LookBuf &K, const M2Buf &B, int m)
 {
-    if (ctl->stop) return;
     unsigned char *own = K.awake + (size_t)F * n, *o1 = K.awake + (size_t)((F + 1) % 3) * n, *o2 = K.awake + (size_t)((F + 2) % 3) * n;
     const int *succ = S.succ + (size_t)t * n;
-    const int qlen = K.ctl->qlen, m = ctl->m;
+    const int qlen = K.ctl->qlen;
     const int gt = (int)(blockIdx.x * blockDim.x + threadIdx.x), GT = (int)(gridDim.x * blockDim.x);
     for (int g = gt; g < qlen; g += GT) {               // carry: the looked units with a candidate
         const int v = K.queue[g], b = B.raw_b[v];
@@ -206,6 +216,13 @@ __global__ void __launch_bounds__(256) k_look_wake(Tours S, int n, int t, NlBuf 
         }
         for (int i = 0; i < ne; i++) { own[e[i]] = 1; o1[e[i]] = 1; o2[e[i]] = 1; }
     }
+}
+
+template <int F>
+__global__ void __launch_bounds__(256) k_look_wake(Tours S, int n, int t, NlBuf NL, LookBuf K, M2Buf B, const M2Ctl *ctl)
+{
+    if (ctl->stop) return;
+    look_wake_tour<F>(S, n, t, NL, K, B, ctl->m);
 }
 
 // `count` nodes join the three sets of a slot (tspgpu_tour_wake)

@@ -12,6 +12,7 @@
 //                   the incumbent (strict <, a copy of succ), the trace cell, the kick draws on thread 0 (serial by nature:
 //                   a few dozen loads from the walk's number block), every kick as an array operation of the whole workgroup
 //                   on a second order array, then the body of k_tour_init on the result and the walk's NlbCtl re-armed.
+//                   <T, true>: the walks with don't-look bits, see in front of the kernel.
 //                   The cost source is k_tour_init's: the matrix, or (mat NULL) the points.
 //
 // A kick in array form (DESIGN 4.9 (iii)): with the tour written from node 0 in its own direction and the sorted picks
@@ -53,11 +54,14 @@ __device__ __forceinline__ bool nlv_draw(const int *tour, int n, const int *__re
     return true;
 }
 
-template <typename T>
+// DL ("Batched don't-look bits", rule 7 of the walks with looks): the step also writes the walk's three sets, awake[slot][3][n]:
+// exactly the nodes whose unordered pair of tour neighbours differs between the local optimum in front of the kick phase and
+// the tour behind it.  The local optimum's neighbours are kept by node in two idle candidate arrays before the first kick
+template <typename T, bool DL>
 __global__ void __launch_bounds__(1024) k_nlv_step(Tours S, const T *__restrict__ mat, int n, int ld, const int *__restrict__ list, int slot0,
                                                    M2Buf B0, NlbCtl *ctl, NlvCtl *vctl, int *ord2, int *best_succ,
                                                    const int *__restrict__ rand_values, double *trace, const double2 *__restrict__ pts,
-                                                   int kind)
+                                                   int kind, unsigned char *awake)
 {
     __shared__ double chunk[1024];
     __shared__ int sh[4];       // the picks of a kick; [3]: kicks of the phase, then -1 once the numbers ran out
@@ -103,6 +107,13 @@ __global__ void __launch_bounds__(1024) k_nlv_step(Tours S, const T *__restrict_
     }
     __syncthreads();
     const int kicks = sh[3];
+    int *osucc = nlb_view(B0, at, n).b, *opred = nlb_view(B0, at, n).i;     // (DL; idle as Y is, and no kick writes them)
+    if (DL)                                 // X is whole behind the barrier above; its first kick writes it two barriers on
+        for (int p = tid; p < n; p += blockDim.x) {
+            const int u = X[p];
+            osucc[u] = X[p + 1 == n ? 0 : p + 1];
+            opred[u] = X[p == 0 ? n - 1 : p - 1];
+        }
     for (int j = 0; j < kicks; j++) {
         if (tid == 0) {
             int pick[3];
@@ -126,6 +137,14 @@ __global__ void __launch_bounds__(1024) k_nlv_step(Tours S, const T *__restrict_
     for (int p = tid; p < n; p += blockDim.x) ord[p] = X[p];
     __syncthreads();
     tour_init_body<T>(S, mat, n, ld, t, -1, pts, kind, chunk);
+    if (DL) {                               // one pass over the positions of the kicked tour (X: nothing wrote it since the last kick)
+        unsigned char *A = awake + (size_t)t * 3 * n;
+        for (int p = tid; p < n; p += blockDim.x) {
+            const int u = X[p], ns = X[p + 1 == n ? 0 : p + 1], np = X[p == 0 ? n - 1 : p - 1], os = osucc[u], op = opred[u];
+            const unsigned char w = (ns == os && np == op) || (ns == op && np == os) ? 0 : 1;
+            A[u] = w; A[(size_t)n + u] = w; A[2 * (size_t)n + u] = w;
+        }
+    }
     if (tid == 0) {
         v->cursor = cur;
         v->kicks += kicks;

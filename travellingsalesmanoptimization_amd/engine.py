@@ -62,7 +62,8 @@ class Engine:
                  "persist_tmat", "persist_packed",
                  "dl_looked", "dl_full_sweeps", "dl_max_queue", "dl_max_wgs",
                  "greedy_rounds1", "greedy_rounds2", "greedy_edges1", "greedy_free",
-                 "nl3_batch_w", "nl3_batch_sweeps", "nl3_batch_moves", "nl3_batch_max_moves"]
+                 "nl3_batch_w", "nl3_batch_sweeps", "nl3_batch_moves", "nl3_batch_max_moves",
+                 "nlb_dl_looked", "nlb_dl_full_sweeps", "nlb_dl_max_queue", "nlb_dl_qsweep_wgs"]
         return {k: int(self.L.tspgpu_info(self.ctx, i)) for i, k in enumerate(names)}
 
     # ---- instance
@@ -576,6 +577,44 @@ class Engine:
                                                                             float(time_left_s), *out))
         r["cost"] = c.value
         return r
+
+    # ---- batched don't-look bits (include/tspgpu.h "Batched don't-look bits")
+    def tours_local_search_nl3_dl(self, slot0, count, width, closing=0, time_left_s=-1.0):
+        """tour_local_search_nl3_dl on slots slot0 .. slot0+count-1 at once, from their sets as they stand ->
+        dict(the counters of tours_local_search_nl3, looked, full_sweeps: arrays of count entries, rc)."""
+        count = int(count)
+        tw, tm, os_, om, ts, tv, lk, fs = (np.zeros(max(count, 0), dtype=np.int64) for _ in range(8))
+        nr, tp = (np.zeros(max(count, 0), dtype=np.int32) for _ in range(2))
+        rc = self._ck(self.L.tspgpu_tours_local_search_nl3_dl(self.ctx, int(slot0), count, int(width), int(closing), float(time_left_s),
+                                                              tw.ctypes.data, tm.ctypes.data, os_.ctypes.data, om.ctypes.data, nr.ctypes.data,
+                                                              ts.ctypes.data, tv.ctypes.data, tp.ctypes.data, lk.ctypes.data, fs.ctypes.data),
+                      ok=(T_OK, DEADLINE_EXCEEDED))
+        return {"two_opt_sweeps": tw, "two_opt_moves": tm, "or_sweeps": os_, "or_moves": om, "rounds": nr,
+                "three_sweeps": ts, "three_moves": tv, "three_phases": tp, "looked": lk, "full_sweeps": fs, "rc": rc}
+
+    def multistart_local_search_nl3_dl(self, width, closing=0, starts=None, time_left_s=-1.0):
+        """multistart_local_search_nl3 with the descent with looks (every start all awake) -> its dict with looked, full_sweeps added."""
+        p, m, keep = self._starts(starts, self.n)
+        best = np.empty(self.n, dtype=np.int32)
+        c, s = C.c_double(), C.c_int()
+        tw, tm, os_, om, ts, tv, lk, fs = (C.c_long() for _ in range(8))
+        costs = np.full(m, np.nan, dtype=np.float64)
+        rc = self._ck(self.L.tspgpu_multistart_local_search_nl3_dl(self.ctx, int(width), int(closing), p, m, float(time_left_s), best,
+                                                                   C.byref(c), C.byref(s), C.byref(tw), C.byref(tm), C.byref(os_), C.byref(om),
+                                                                   C.byref(ts), C.byref(tv), C.byref(lk), C.byref(fs), costs.ctypes.data),
+                      ok=(T_OK, DEADLINE_EXCEEDED))
+        return {"path": best, "cost": c.value, "start": s.value, "two_opt_sweeps": tw.value, "two_opt_moves": tm.value,
+                "or_sweeps": os_.value, "or_moves": om.value, "three_sweeps": ts.value, "three_moves": tv.value,
+                "looked": lk.value, "full_sweeps": fs.value, "costs": costs, "rc": rc}
+
+    def vns_walks_nl3_dl(self, paths, k, rand_values, best_paths, best_costs, width, closing=0, iterations=None, kick_pending=None,
+                         time_left_s=-1.0, want_trace=False):
+        """vns_walks_nl3 with the descent with looks: behind a kick phase only the nodes whose tour neighbours changed are awake;
+        totals gains looked, full_sweeps."""
+        names = ("two_opt_sweeps", "two_opt_moves", "or_sweeps", "or_moves", "rounds", "kicks", "three_sweeps", "three_moves", "three_phases",
+                 "looked", "full_sweeps")
+        return self._vns_walks(self.L.tspgpu_vns_walks_nl3_dl, (int(width), int(closing)), names, paths, k, rand_values, best_paths,
+                               best_costs, iterations, kick_pending, time_left_s, want_trace)
 
     # ---- greedy-edge construction (include/tspgpu.h "Greedy-edge construction")
     def tour_greedy(self, slot):

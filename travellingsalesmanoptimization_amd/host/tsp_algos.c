@@ -644,8 +644,10 @@ ERROR_CODE tabu_make_move(int *prev, tsp_solution *solution, int bestCase, int i
 
 /* TSP_VNS_NEIGHBOURS=K, K in 1..16 (tsp_run_algorithm): mh_VNS runs TSP_VNS_WALKS walks of the neighbour-list VNS
  * (tspgpu_vns_walks_nl) over lists of K nodes instead of its own loop.
- * TSP_VNS_3OPT_WIDTH=W, W in 1..16, with it: the walks' descent gets the 3-opt phase over the first W entries (tspgpu_vns_walks_nl3) */
-static int vns_nl_k = 0, vns_nl_walks = 1, vns_nl_width3 = 0;
+ * TSP_VNS_3OPT_WIDTH=W, W in 1..16, with it: the walks' descent gets the 3-opt phase over the first W entries (tspgpu_vns_walks_nl3).
+ * TSP_VNS_DONT_LOOK=1, with TSP_VNS_NEIGHBOURS=K [and TSP_VNS_3OPT_WIDTH=W]: the walks run with don't-look bits
+ * (tspgpu_vns_walks_nl3_dl; W = 0: no 3-opt phase), closing = 0 unless TSP_DONT_LOOK_CLOSING=1 */
+static int vns_nl_k = 0, vns_nl_walks = 1, vns_nl_width3 = 0, vns_nl_dont_look = 0, batch_dl_closing = 0;
 enum { VNS_NL_NUMBERS = 1 << 22 };              /* random numbers drawn ahead per call, over all walks */
 
 /* mh_VNS over the neighbour lists.  Every walk starts from the tour in *best (the All-NN tour).  Per call at most C
@@ -690,7 +692,10 @@ static ERROR_CODE vns_nl_loop(tsp_solution *best, FILE *f)
         const int *rv = tsp_rand_peek(per * W);
         if (!rv) { log_fatal("out of memory for %ld random numbers", per * W); tsp_handlefatal(); }
         if (trace) for (long i = 0; i < (long)W * kk; i++) trace[i] = NAN;
-        rc = vns_nl_width3
+        rc = vns_nl_dont_look
+                 ? tspgpu_vns_walks_nl3_dl(g, vns_nl_width3, batch_dl_closing, W, kk, time_left(), paths, costs, rv, per, used, itl, pending, bests,
+                                           bcosts, trace, NULL)
+             : vns_nl_width3
                  ? tspgpu_vns_walks_nl3(g, vns_nl_width3, W, kk, time_left(), paths, costs, rv, per, used, itl, pending, bests, bcosts, trace, NULL)
                  : tspgpu_vns_walks_nl(g, W, kk, time_left(), paths, costs, rv, per, used, itl, pending, bests, bcosts, trace, NULL);
         tsp_rand_consume(W == 1 ? used[0] : per * W);
@@ -912,8 +917,11 @@ ERROR_CODE h_greedy_local_search(void)
  * in h_greedy_2opt.  An instance the descent does not take (fewer than 8 nodes, an asymmetric matrix) gets a warning and the
  * plain h_greedy_2opt.
  * TSP_EVERY_START_3OPT_WIDTH=W, W in 1..16, with it: that descent gets the 3-opt phase over the first W list entries
- * (tspgpu_multistart_local_search_nl3). */
-static int every_start_nl_k = 0, every_start_width3 = 0;
+ * (tspgpu_multistart_local_search_nl3).
+ * TSP_EVERY_START_DONT_LOOK=1, with TSP_EVERY_START_NEIGHBOURS=K [and TSP_EVERY_START_3OPT_WIDTH=W]: every start descends with
+ * don't-look bits (tspgpu_multistart_local_search_nl3_dl, on one device: it has no sharded form), closing = 0 unless
+ * TSP_DONT_LOOK_CLOSING=1 */
+static int every_start_nl_k = 0, every_start_width3 = 0, every_start_dont_look = 0;
 
 ERROR_CODE h_greedy_local_search_nl(void)
 {
@@ -921,18 +929,21 @@ ERROR_CODE h_greedy_local_search_nl(void)
     if (past_deadline()) { log_warn("time limit exceeded in greedy neighbour-list local search"); return DEADLINE_EXCEEDED; }
     tspgpu_ctx *g = tsp_gpu();
     if (!g) return UNAVAILABLE;
-    struct tspgpu_multi *m = tsp_gpu_multi();
+    struct tspgpu_multi *m = every_start_dont_look ? NULL : tsp_gpu_multi();
     tsp_solution s;
     tsp_init_solution(tsp_inst.nnodes, &s);
     int start = -1;
-    long sweeps = 0, two_opt_moves = 0, or_sweeps = 0, moves = 0, three_sweeps = 0, three_moves = 0;
+    long sweeps = 0, two_opt_moves = 0, or_sweeps = 0, moves = 0, three_sweeps = 0, three_moves = 0, looked = 0, full_sweeps = 0;
     const int w3 = every_start_width3;
     const double t0 = utils_timeelapsed(&tsp_inst.c);
     /* the lists belong to the costs in place: built when the context holds none of that length */
     const int kp = every_start_nl_k < tsp_inst.nnodes - 1 ? every_start_nl_k : tsp_inst.nnodes - 1;
     int rc = m ? tspgpu_multi_neighbours_build(m, every_start_nl_k)
                : tspgpu_info(g, 42) == kp ? 0 : tspgpu_neighbours_build(g, every_start_nl_k);
-    if (rc == 0 && w3)
+    if (rc == 0 && every_start_dont_look)
+        rc = tspgpu_multistart_local_search_nl3_dl(g, w3, batch_dl_closing, NULL, tsp_inst.nnodes, time_left(), s.path, &s.cost, &start, &sweeps,
+                                                   &two_opt_moves, &or_sweeps, &moves, &three_sweeps, &three_moves, &looked, &full_sweeps, NULL);
+    else if (rc == 0 && w3)
         rc = m ? tspgpu_multi_multistart_local_search_nl3(m, w3, NULL, tsp_inst.nnodes, time_left(), s.path, &s.cost, &start, &sweeps,
                                                           &two_opt_moves, &or_sweeps, &moves, &three_sweeps, &three_moves)
                : tspgpu_multistart_local_search_nl3(g, w3, NULL, tsp_inst.nnodes, time_left(), s.path, &s.cost, &start, &sweeps, &two_opt_moves,
@@ -959,6 +970,7 @@ ERROR_CODE h_greedy_local_search_nl(void)
         else log_warn("time limit exceeded in greedy neighbour-list local search");
         log_debug("best start %d, cost %f, %ld 2-opt sweeps (%ld moves), %ld Or-opt sweeps (%ld moves), %ld 3-opt sweeps (%ld moves)", start,
                   s.cost, sweeps, two_opt_moves, or_sweeps, moves, three_sweeps, three_moves);
+        if (every_start_dont_look) log_debug("with don't-look bits: %ld units looked at, %ld full sweeps", looked, full_sweeps);
     }
     free(s.path); free(s.comp);
     return e;
@@ -1036,6 +1048,11 @@ ERROR_CODE tsp_run_algorithm(void)
      * descent with the 3-opt phase over the first W list entries */
     const int es_w3 = env_neighbours("TSP_EVERY_START_3OPT_WIDTH"), vns_w3 = env_neighbours("TSP_VNS_3OPT_WIDTH");
     if (es_w3 < 0 || vns_w3 < 0) return INVALID_ARGUMENT;
+    /* TSP_VNS_DONT_LOOK=1 / TSP_EVERY_START_DONT_LOOK=1 (env_switch): the walks / the multi-start over the lists run with don't-look
+     * bits; TSP_DONT_LOOK_CLOSING=1: their phases close with a full sweep */
+    const int vns_dl = env_switch("TSP_VNS_DONT_LOOK"), es_dl = env_switch("TSP_EVERY_START_DONT_LOOK");
+    const int dl_closing = env_switch("TSP_DONT_LOOK_CLOSING");
+    if (vns_dl < 0 || es_dl < 0 || dl_closing < 0) return INVALID_ARGUMENT;
     /* TSP_GREEDY_EDGE_NEIGHBOURS=K (env_neighbours): -alg GREEDY builds the greedy-edge tour over lists of K nodes */
     const int ge_k = env_neighbours("TSP_GREEDY_EDGE_NEIGHBOURS");
     if (ge_k < 0) return INVALID_ARGUMENT;
@@ -1073,6 +1090,14 @@ ERROR_CODE tsp_run_algorithm(void)
     else if (getenv("TSP_VNS_WALKS")) log_warn("TSP_VNS_WALKS has no effect without TSP_VNS_NEIGHBOURS");
     vns_nl_width3 = vns_nl_k ? vns_w3 : 0;
     if (vns_w3 && !vns_nl_k) log_warn("TSP_VNS_3OPT_WIDTH=%d has no effect without -alg VNS and TSP_VNS_NEIGHBOURS=K", vns_w3);
+    vns_nl_dont_look = vns_nl_k ? vns_dl : 0;
+    if (vns_nl_dont_look) log_warn("TSP_VNS_DONT_LOOK=1: the walks run with don't-look bits; behind a kick only the nodes at changed edges are looked at");
+    else if (vns_dl) log_warn("TSP_VNS_DONT_LOOK=1 has no effect without -alg VNS and TSP_VNS_NEIGHBOURS=K");
+    every_start_dont_look = es_k && tsp_inst.alg == ALG_2OPT_GREEDY ? es_dl : 0;
+    if (every_start_dont_look) log_warn("TSP_EVERY_START_DONT_LOOK=1: every start descends with don't-look bits, on one device");
+    else if (es_dl) log_warn("TSP_EVERY_START_DONT_LOOK=1 has no effect without -alg 2OPT_GREEDY and TSP_EVERY_START_NEIGHBOURS=K");
+    batch_dl_closing = vns_nl_dont_look || every_start_dont_look ? dl_closing : 0;
+    if (dl_closing && !batch_dl_closing) log_warn("TSP_DONT_LOOK_CLOSING=1 has no effect without TSP_VNS_DONT_LOOK=1 or TSP_EVERY_START_DONT_LOOK=1");
     every_start_nl_k = es_k;
     if (es_k && tsp_inst.alg == ALG_2OPT_GREEDY)
         log_warn("TSP_EVERY_START_NEIGHBOURS=%d: every start runs the descent over the neighbour lists; results differ from the reference's trajectory",
