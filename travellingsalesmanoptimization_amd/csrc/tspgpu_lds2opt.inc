@@ -119,6 +119,18 @@ __device__ __forceinline__ unsigned lp_pk_min(unsigned a, unsigned b)
 {
     return __builtin_bit_cast(unsigned, __builtin_elementwise_min(__builtin_bit_cast(s16x2, a), __builtin_bit_cast(s16x2, b)));
 }
+__device__ __forceinline__ unsigned lp_pk_minu(unsigned a, unsigned b)
+{
+    return __builtin_bit_cast(unsigned, __builtin_elementwise_min(__builtin_bit_cast(u16x2, a), __builtin_bit_cast(u16x2, b)));
+}
+// lds_tmat::pk_bias of the low half of a wt word (w | label << 16) in ONE instruction: a packed subtraction whose second operand
+// is the word's low half for both halves of the result
+__device__ __forceinline__ unsigned lp_pk_bias(unsigned wtword)
+{
+    unsigned b;
+    asm("v_pk_sub_u16 %0, %1, %2 op_sel_hi:[1,0]" : "=v"(b) : "v"(lds_tmat::PK_BIAS), "v"(wtword));
+    return b;
+}
 // TABU: tabu_best_move instead of ref_2opt_once -- the best pair none of whose four nodes is tabu, whatever the sign of its
 // delta (metaheuristic.c:188-245), applied every iteration; the nodes' ages (iterations since they were last moved) live
 // in LDS beside the labels.  Pairs of adjacent edges must now lose for real (a delta of 0 can be the minimum): the cells
@@ -541,7 +553,10 @@ __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
                         for (int q = 0; q < RC; q++) wkw[q] = wp[q];
                     }
                 }
-                unsigned acc[4] = {0x7fff7fffu, 0x7fff7fffu, 0x7fff7fffu, 0x7fff7fffu};
+                // The deltas are carried with a bias of 0x8000 a half: acc = min(X + Y + (0x8000 - w[k])), one three-operand 32-bit
+                // add a register.  Every cost <= 16383 (the poison included): a half of the sum lies in [16385, 65534], so no
+                // carry crosses the halves and the UNSIGNED packed minimum orders the halves as the signed one orders the deltas.
+                unsigned acc[4] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
                 v4u32 X = *reinterpret_cast<const v4u32 *>(rchunk);
                 v4u32 Xn = *reinterpret_cast<const v4u32 *>(rchunk + NLC);
                 unsigned exn = rex[NLC];
@@ -556,17 +571,18 @@ __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
                     const unsigned Y[4] = {__builtin_amdgcn_alignbit(Xc.y, Xc.x, 16), __builtin_amdgcn_alignbit(Xc.z, Xc.y, 16),
                                            __builtin_amdgcn_alignbit(Xc.w, Xc.z, 16), __builtin_amdgcn_alignbit(exc, Xc.w, 16)};
                     const unsigned Xa[4] = {X.x, X.y, X.z, X.w};
-                    const unsigned wk2 = __builtin_amdgcn_perm(wkw[r], wkw[r], 0x01000100u);     // w[k] in both halves
+                    const unsigned bk = lp_pk_bias(wkw[r]);       // 0x8000 - w[k] in both halves (lds_tmat::pk_bias)
 #pragma unroll
-                    for (int j = 0; j < 4; j++) acc[j] = lp_pk_min(acc[j], lp_pk_sub(lp_pk_add(Xa[j], Y[j]), wk2));
+                    for (int j = 0; j < 4; j++) acc[j] = lp_pk_minu(acc[j], lds_tmat::pk_biased(Xa[j], Y[j], bk));
                     X = Xc;
                 }
-                // - w[m], still packed (|delta| <= 2 * 16383: no 16-bit overflow); unpacked only where the minimum turns out to be
+                // - w[m], still packed (a half stays in [2, 65534]: no borrow), and the bias taken off: the signed packed deltas
+                // (|delta| <= 2 * 16383: no 16-bit overflow); unpacked only where the minimum turns out to be
                 const v4u32 wa = *reinterpret_cast<const v4u32 *>(wt + me0), wb = *reinterpret_cast<const v4u32 *>(wt + me0 + 4);
-                pacc[0] = lp_pk_sub(acc[0], __builtin_amdgcn_perm(wa.y, wa.x, 0x05040100u));
-                pacc[1] = lp_pk_sub(acc[1], __builtin_amdgcn_perm(wa.w, wa.z, 0x05040100u));
-                pacc[2] = lp_pk_sub(acc[2], __builtin_amdgcn_perm(wb.y, wb.x, 0x05040100u));
-                pacc[3] = lp_pk_sub(acc[3], __builtin_amdgcn_perm(wb.w, wb.z, 0x05040100u));
+                pacc[0] = lp_pk_sub(acc[0], __builtin_amdgcn_perm(wa.y, wa.x, 0x05040100u)) ^ lds_tmat::PK_BIAS;
+                pacc[1] = lp_pk_sub(acc[1], __builtin_amdgcn_perm(wa.w, wa.z, 0x05040100u)) ^ lds_tmat::PK_BIAS;
+                pacc[2] = lp_pk_sub(acc[2], __builtin_amdgcn_perm(wb.y, wb.x, 0x05040100u)) ^ lds_tmat::PK_BIAS;
+                pacc[3] = lp_pk_sub(acc[3], __builtin_amdgcn_perm(wb.w, wb.z, 0x05040100u)) ^ lds_tmat::PK_BIAS;
                 const unsigned pm = lp_pk_min(lp_pk_min(pacc[0], pacc[1]), lp_pk_min(pacc[2], pacc[3]));
                 tmin = min((int)(short)(pm & 0xffffu), (int)pm >> 16);
             }

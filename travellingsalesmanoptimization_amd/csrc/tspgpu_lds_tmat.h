@@ -55,4 +55,12 @@ TMAT_HD inline void cellwise_chunks(int lo, int M, int n, int c[3])
 TMAT_HD inline int wb_first(int lo) { return lo >> 3; }
 TMAT_HD inline int wb_count(int lo, int M) { return ((lo & 7) + M + 7) >> 3; }
 
+// The packed evaluation of the shaped kernels: two 16-bit deltas a register, carried with a bias of 0x8000 a half so that
+// x + y - w[k] is ONE 32-bit three-operand add.  With every operand <= 16383 a half of x + y + pk_bias(wk) lies in
+// [16385, 65534] -- no carry into the upper half -- and, w[m] taken off half by half, in [2, 65534]; the unsigned order of
+// the biased halves is the signed order of the deltas, and XOR PK_BIAS gives the deltas themselves.
+constexpr unsigned PK_BIAS = 0x80008000u;
+TMAT_HD inline unsigned pk_bias(unsigned wk) { return PK_BIAS - (wk | wk << 16); }                   // wk <= 16383
+TMAT_HD inline unsigned pk_biased(unsigned x, unsigned y, unsigned b) { return x + y + b; }          // packed x, y; b = pk_bias(wk)
+
 }   // namespace lds_tmat
