@@ -140,7 +140,13 @@ int tspgpu_set_points(tspgpu_ctx *ctx, const double *xy, int n, int edge_weight_
 int tspgpu_build_costs(tspgpu_ctx *ctx, double *host_out);
 
 /* Caller-supplied matrix, the h_Greedy_2opt_mod_costs case
- * (src/algorithms/heuristics.c:118-149): row-major n x n doubles. */
+ * (src/algorithms/heuristics.c:118-149): row-major n x n doubles.
+ * A matrix that is not symmetric is recorded (tspgpu_info 7 reads 0) and taken by the NN constructions, the plain 2-opt
+ * sweeps, the tabu move and walk, tspgpu_vns_search, tspgpu_multistart_nn_2opt, the farthest pair and Extra Mileage, which then
+ * evaluate only the reference's orientation b > a and read every cost from the row the reference reads it from.  The fused
+ * sweep and the one-launch descents and walks never run on it (TSPGPU_OPT_PERSIST = 2 and TSPGPU_OPT_STREAM_PERSIST = 2
+ * answer 8; both Extra Mileage forms do run) and the extensions refuse it with 9;
+ * tests/test_asymmetric.py pins all of it against the CPU oracle. */
 int tspgpu_set_costs(tspgpu_ctx *ctx, const double *host_costs, int n);
 
 /* Read the device matrix back (row-major n x n doubles). */
