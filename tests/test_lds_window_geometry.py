@@ -12,7 +12,7 @@ POISON = 65535
 
 
 def geometry(n, edges=0):
-    """persist_fits_w of csrc/tspgpu.hip"""
+    """plan::window_fits of csrc/tspgpu_plan.h"""
     if n < 64 or n > 8191:
         return None
     e = max(-(-n // CUS), edges)

@@ -52,6 +52,7 @@
 #include "tspgpu.h"
 #include "tspgpu_relaunch.h"    // LP_ST_*, and the host's protocol over them (run_persist, run_pstream)
 #include "tspgpu_looks.h"       // rounds of launches between looks at a control block (m2_run, or_run, the batched descents)
+#include "tspgpu_plan.h"        // the launch plans: which kernel, what geometry (make_plan, run_persist, run_pstream, or_plan, m2_plan)
 #include "tspgpu_nlphase.h"     // NlbCtl and the phase machine of a tour of a batched neighbour-list descent (tspgpu_nlbatch.inc)
 #include "tspgpu_lds_tmat.h"    // index arithmetic of the tour-ordered matrix copy (k_lds2opt's TM instantiations)
 
@@ -68,12 +69,14 @@ enum { E_OK = 0, E_INVALID = 3, E_DEADLINE = 4, E_EXHAUSTED = 8, E_PRECOND = 9,
 typedef unsigned long long u64;
 
 static constexpr u64 KEY_NONE = ~0ull;
-static constexpr int MAX_WGS_PER_TOUR = 1024;
+using plan::MAX_WGS_PER_TOUR;
 
 struct Partial {
     double d;
     u64 key; // (lo << 32) | hi, KEY_NONE when the workgroup found nothing
 };
+static_assert(sizeof(Partial) == plan::PARTIAL_BYTES, "the plans count a Partial's bytes");
+static_assert(TSPGPU_ELEM_F64 == plan::ELEM_F64 && TSPGPU_ELEM_I32 == plan::ELEM_I32 && TSPGPU_ELEM_U16 == plan::ELEM_U16, "the plans' element kinds are the ABI's");
 
 // ---------------------------------------------------------------------------
 // element traits: the matrix is held either as doubles (any caller matrix) or
@@ -2570,9 +2573,8 @@ __global__ void __launch_bounds__(256) k_gather_ispts(Tours S, int n, int slot0,
 // per pair ONE 32-bit min on (w1 + w2 - c[b][sb]) << 2 | v keeps the reference's tie order.
 // Per pair that leaves the two weights and three integer instructions.
 // ---------------------------------------------------------------------------
-constexpr int OTF8_RUN = 16;        // tour edges per workgroup: the per-b arrays (36 bytes per b) are streamed once per RUN pairs
-constexpr int OTF8_RUN_INT = 64;    // ... with integer points (KIND_CEIL_INT): behind the early-out the sweep is bound by streaming the per-b
-                                    // arrays through the CU's load path (20 bytes per b and workgroup: 1.5 ms of a 1.7 ms sweep with runs of 16)
+using plan::OTF8_RUN;       // tour edges per workgroup, and with integer points behind the early-out (tspgpu_plan.h)
+using plan::OTF8_RUN_INT;
 template <int KIND, bool TABU, bool EARLY = false>
 __global__ void __launch_bounds__(256) k_sweep_otf8(SweepArgs A)
 {
@@ -3301,15 +3303,10 @@ struct tspgpu_ctx : ContextMem, InstanceMem, CostMem, SlotMem {
     std::vector<unsigned char> look_all;     // [tcap] host side
     hipEvent_t ev_ord = nullptr; bool ord_pending = false;   // guards the reuse of h_ord
 
-    // launch plan
-    int plan_kernel = 0, plan_G = 0, plan_P = 0, plan_BT = 0, plan_NCH = 0, plan_D = 0, plan_T = 0;
+    // launch plan (tspgpu_plan.h): kernel 0 = none; make_plan assigns it whole, drop_plan forgets it
+    plan::Sweep plan;
     int opt_depth = 0, opt_ablate = 0, opt_stamps = 0;
-    bool plan_tabu_fits = true;   // the tabu variants' extra n + 32 LDS bytes fit beside the rows
-    size_t plan_lds = 0;
-    size_t plan_lds_fused = 0;  // dynamic LDS of the one-launch-per-sweep kernel (four row buffers in its two-edge streaming form)
-    bool plan_pipe2 = false;    // the fused pipelined kernel streams two tour edges per barrier interval (pipe_stream2)
-    bool plan_pipe2_sweep = false;   // ... and so does the plain pipelined sweep (batches; symmetric, not tabu)
-    int opt_pipe2 = 1;          // 1 = use that form where four rows fit LDS, 0 = never
+    int opt_pipe2 = 1;          // 1 = the two-edge streaming form (pipe_stream2) where four rows fit LDS, 0 = never
 
     // LDS-resident descent (k_lds2opt): exchange slots + control words, allocated on first use
     int opt_persist = 1;       // 0 never, 1 where it applies (uint16 cells, one tour, n <= 4096, a whole idle chip), 2 or fail
@@ -3334,7 +3331,6 @@ struct tspgpu_ctx : ContextMem, InstanceMem, CostMem, SlotMem {
     bool sp_used = false;      // the last descent ran in k_str2opt
     int opt_sp_nch = 0;        // probe hook 93
     int opt_otf_early = 0;         // hook 91: 0 automatic, 1 the early-out kernel for every matrix-free sweep, 2 never
-    bool plan_otf_early = false;   // the matrix-free plan is the early-out kernel's (runs of 64 edges: plain 2-opt over integer points)
     bool lp_shaped = false;    // the last LDS-resident descent ran in a shaped instantiation of k_lds2opt
     int opt_lp_generic = 0;    // undocumented (option 89): 1 = never a shaped instantiation
     bool lp_tmat = false;      // ... and it fetched moved rows from the tour-ordered copy (a TM instantiation)
@@ -3409,6 +3405,23 @@ static void drop_graphs(tspgpu_ctx *ctx)
 {
     for (auto &g : ctx->graphs) hipGraphExecDestroy(g.exec);
     ctx->graphs.clear();
+}
+
+// no plan, and no captured launches of one (the other fields keep the last plan's values: tspgpu_info shows them until the next)
+static void drop_plan(tspgpu_ctx *ctx) { ctx->plan.kernel = 0; drop_graphs(ctx); }
+
+// what the plans read of the context (tspgpu_plan.h)
+static plan::In plan_in(const tspgpu_ctx *ctx)
+{
+    plan::In in;
+    in.cus = ctx->cus; in.lds_max = ctx->lds_max;
+    in.n = ctx->n; in.ld = ctx->ld; in.elem = ctx->elem;
+    in.otf = ctx->otf; in.symmetric = ctx->symmetric; in.has_matrix = ctx->d_mat.p != nullptr;
+    in.int_points = ctx->ceil_int() && ctx->d_ipts.p != nullptr; in.cost_bound = ctx->cost_bound;
+    in.opt_kernel = ctx->opt_kernel; in.opt_block = ctx->opt_block; in.opt_wgs = ctx->opt_wgs; in.opt_depth = ctx->opt_depth;
+    in.opt_pipe2 = ctx->opt_pipe2; in.opt_ablate = ctx->opt_ablate; in.opt_otf_early = ctx->opt_otf_early;
+    in.opt_persist_edges = ctx->opt_persist_edges; in.opt_persist_window = ctx->opt_persist_window; in.opt_sp_nch = ctx->opt_sp_nch;
+    return in;
 }
 
 static void free_matrix(tspgpu_ctx *ctx)
@@ -3506,10 +3519,8 @@ static int new_instance(tspgpu_ctx *ctx, int n)
     return E_OK;
 }
 
-// the matrix sweeps pack a pair as min(a,b) << 16 | max(a,b): labels 0..65535
-static const int MATRIX_MAX_N = 64 * 1024;
-
-static size_t elem_size(int elem) { return elem == TSPGPU_ELEM_F64 ? 8 : elem == TSPGPU_ELEM_I32 ? 4 : 2; }
+using plan::MATRIX_MAX_N;
+using plan::elem_size;
 
 // run `...` with T bound to the storage type of `elem`
 #define ELEM_SWITCH(elem, T, ...)                                             \
@@ -3623,55 +3634,26 @@ template <typename W, typename B> static int time_launches(tspgpu_ctx *ctx, int 
     return rc;
 }
 
-// geometry of a candidate sweep: threads, 16-byte vectors per thread and row, tour positions per workgroup, workgroups, the
-// workgroups a CU holds, dynamic LDS bytes, and the kernel (the caller's to fill in)
-struct SweepGeom { int BT, NCH, R, W, occ; size_t lds; const void *fn; };
-
-// ... for a kernel that keeps `rows` matrix rows and `extra` more bytes in LDS: R is one wave of workgroups over the chip,
-// clamped to [rmin, rmax]; NCH is the first of `nchs` (ascending) that covers a row.  Matrix-free mode: BT = 256, NCH = 0,
-// R = otf_run, no dynamic LDS
-static SweepGeom sweep_geom(const tspgpu_ctx *ctx, int rows, size_t extra, int rmin, int rmax, std::initializer_list<int> nchs, int otf_run)
-{
-    SweepGeom P{};
-    const int n = ctx->n;
-    if (ctx->otf) {
-        P.BT = 256; P.R = otf_run; P.W = (n + P.R - 1) / P.R;
-        return P;
-    }
-    const size_t esz = elem_size(ctx->elem);
-    const int nvec = ctx->ld / (int)(16 / esz);
-    P.BT = nvec <= 256 ? 256 : nvec <= 1024 ? 512 : 1024;
-    for (int c : nchs) { P.NCH = c; if (c * P.BT >= nvec) break; }
-    P.lds = rows * (size_t)ctx->ld * esz + extra;
-    P.occ = (int)std::max<size_t>(1, std::min<size_t>(ctx->lds_max / P.lds, (size_t)(2048 / P.BT)));
-    const int target = ctx->cus * P.occ;
-    P.R = std::min(std::max((n + target - 1) / target, rmin), rmax);
-    P.W = (n + P.R - 1) / P.R;
-    return P;
-}
+using plan::SweepGeom;     // geometry of a candidate sweep (plan::sweep_geom: or_plan, m2_plan)
 
 // --------------------------------------------------------------- launch plan
 template <typename T, int NCH, int D, bool TABU> static const void *pipe_fn() { return (const void *)k_sweep_pipe<T, NCH, D, TABU>; }
 
-// register-prefetch depth per chunk count: D * NCH 16-byte vectors stay in flight per thread
-static int pipe_depth(int nch, int want) {
-    const int dmax = nch <= 1 ? 8 : nch <= 2 ? 4 : 2; // deeper sets would spill under the 128-VGPR cap
-    int d = want > 0 ? want : 2; // measured: deeper sets do not pay (the step is latency-, not bandwidth-bound)
-    d = d >= 8 ? 8 : d >= 4 ? 4 : 2;
-    return std::min(d, dmax);
-}
-
+// The selectors below name the kernels; WHICH (elem, nch) exist is plan::has_pipe2 / has_pipe / has_res / has_fused
+// (tspgpu_plan.h), which every selector asks first and which the plan asks too.
 // depth 9 = the two-edge form (pipe_stream2, four LDS row buffers): symmetric matrices, plain 2-opt, nch <= 3
 static const void *pipe2_kernel(int elem, int nch)
 {
+    if (!plan::has_pipe2(elem, nch)) return nullptr;
     const void *fn = nullptr;
-    ELEM_SWITCH(elem, T, fn = nch == 1 ? pipe_fn<T, 1, 9, false>() : nch == 2 ? pipe_fn<T, 2, 9, false>() : nullptr);
-    if (elem == TSPGPU_ELEM_U16 && nch == 3) fn = pipe_fn<u16, 3, 9, false>();
+    ELEM_SWITCH(elem, T, fn = nch == 1 ? pipe_fn<T, 1, 9, false>() : pipe_fn<T, 2, 9, false>());
+    if (nch == 3) fn = pipe_fn<u16, 3, 9, false>();
     return fn;
 }
 
 static const void *pipe_kernel(int elem, int nch, int depth, bool tabu)
 {
+    if (!plan::has_pipe(elem, nch)) return nullptr;
 #define PK(T, N, DD) (tabu ? pipe_fn<T, N, DD, true>() : pipe_fn<T, N, DD, false>())
     if (elem == TSPGPU_ELEM_F64) {
         switch (nch) {
@@ -3700,6 +3682,7 @@ static const void *pipe_kernel(int elem, int nch, int depth, bool tabu)
 template <typename T, int NCH, bool TABU> static const void *res_fn() { return (const void *)k_sweep_res<T, NCH, 8, TABU>; }
 static const void *res_kernel(int elem, int nch, bool tabu)
 {
+    if (!plan::has_res(elem, nch)) return nullptr;
     const void *fn = nullptr;
     ELEM_SWITCH(elem, T, fn = nch == 1 ? (tabu ? res_fn<T, 1, true>() : res_fn<T, 1, false>())
                                        : (tabu ? res_fn<T, 2, true>() : res_fn<T, 2, false>()));
@@ -3711,17 +3694,18 @@ template <typename T, int NCH, int D> static const void *fused_fn() { return (co
 // LDS row buffers (pipe_stream2) when `pipe2`, else one edge per barrier over three (pipe_stream, register depth 2)
 static const void *fused_kernel(int elem, int nch, int kernel, bool pipe2)
 {
+    if (!plan::has_fused(elem, nch, kernel)) return nullptr;
     const void *fn = nullptr;
-    if (kernel == 3) ELEM_SWITCH(elem, T, fn = nch == 1 ? fused_fn<T, 1, 0>() : nch == 2 ? fused_fn<T, 2, 0>() : nullptr);
-    else if (kernel == 2) {
+    if (kernel == 3) ELEM_SWITCH(elem, T, fn = nch == 1 ? fused_fn<T, 1, 0>() : fused_fn<T, 2, 0>());
+    else {
         // (three uint16 chunks per thread, n > 16 384: the fused prologue no longer fits the register
         // budget next to the per-b state -- measured 1.7x slower than sweep + apply on d18512)
         // rows in flight (4 = one pair, 5 = two): measured at n=4096 -- f64 30.9 us with one pair, 33.0 with two (already at
         // 5.6 TB/s of the ~6.1 TB/s a CU's load path sustains; more requests only queue); int32 20.9 / 20.5
-        if (pipe2 && elem == TSPGPU_ELEM_U16) fn = nch == 1 ? fused_fn<u16, 1, 5>() : nch == 2 ? fused_fn<u16, 2, 4>() : nullptr;
-        else if (pipe2 && elem == TSPGPU_ELEM_F64) fn = nch == 1 ? fused_fn<double, 1, 4>() : nch == 2 ? fused_fn<double, 2, 4>() : nullptr;
-        else if (pipe2) fn = nch == 1 ? fused_fn<int, 1, 5>() : nch == 2 ? fused_fn<int, 2, 5>() : nullptr;
-        else ELEM_SWITCH(elem, T, fn = nch == 1 ? fused_fn<T, 1, 2>() : nch == 2 ? fused_fn<T, 2, 2>() : nullptr);
+        if (pipe2 && elem == TSPGPU_ELEM_U16) fn = nch == 1 ? fused_fn<u16, 1, 5>() : fused_fn<u16, 2, 4>();
+        else if (pipe2 && elem == TSPGPU_ELEM_F64) fn = nch == 1 ? fused_fn<double, 1, 4>() : fused_fn<double, 2, 4>();
+        else if (pipe2) fn = nch == 1 ? fused_fn<int, 1, 5>() : fused_fn<int, 2, 5>();
+        else ELEM_SWITCH(elem, T, fn = nch == 1 ? fused_fn<T, 1, 2>() : fused_fn<T, 2, 2>());
     }
     return fn;
 }
@@ -3733,166 +3717,50 @@ static const void *simple_kernel(int elem, bool tabu)
     return fn;
 }
 
-static int pow2_ceil(int x) { int p = 1; while (p < x) p <<= 1; return p; }
+using plan::pow2_ceil;
 
-// Decide kernel variant, block size, workgroups per tour for `ntours` tours in flight.
-static int make_plan(tspgpu_ctx *ctx, int ntours)
+// The plan for `ntours` tours in flight (plan::decide: kernel variant, block size, workgroups per tour), with the dynamic-LDS
+// caps of its kernels raised.  `early`: plan::otf_early's answer.  A refusal leaves the plan the context had
+static int make_plan(tspgpu_ctx *ctx, int ntours, bool early)
 {
-    const int n = ctx->n, ld = ctx->ld;
-    const size_t esz = elem_size(ctx->elem);
-    const int V = 16 / (int)esz;
-    const int nvec = ld / V;
-    const size_t row = (size_t)ld * esz;
-    const size_t slack = 1024; // nodes[] + reduction scratch
-
-    int BT = ctx->opt_block;
-    if (BT <= 0) BT = std::min(1024, std::max(64, (nvec + 63) & ~63)); // one 16-byte vector per thread, whole waves
-    BT = std::min(1024, std::max(64, (BT + 63) & ~63));
-
-    int kernel = ctx->opt_kernel;
-    int nch = 0;
-    auto pipe_fits = [&](int bt, int P) {
-        return 3 * row + (size_t)(P + 4) * 4 + slack <= ctx->lds_max;
-    };
-    // provisional G / P
-    auto plan_GP = [&](size_t lds, int bt, int &G, int &P, const void *fn) {
-        int occ = (int)std::min<size_t>(ctx->lds_max / std::max<size_t>(lds, 1), (size_t)(2048 / bt));
+    const int n = ctx->n;
+    const size_t row = (size_t)ctx->ld * elem_size(ctx->elem);
+    if (const int rc = ctx->otf ? ensure_spts(ctx, (size_t)ntours * n) : (int)E_OK) return rc;    // matrix-free: every tour's gathered points
+    const plan::Sweep s = plan::decide(plan_in(ctx), ntours, early, [&](plan::Kernel k, int bt, size_t lds) {
+        const void *fn = k.kernel == 2 ? pipe_kernel(ctx->elem, k.nch, k.depth, false) : simple_kernel(ctx->elem, false);
         int api = 0; // registers count too: ask the runtime for this very kernel
         if (fn && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) == hipSuccess &&
             hipOccupancyMaxActiveBlocksPerMultiprocessor(&api, fn, bt, lds) == hipSuccess && api > 0)
-            occ = std::min(occ, api);
-        occ = std::max(1, std::min(occ, 8));
-        if (bt >= 1024) occ = 1; // measured: one 16-wave workgroup per CU beats two (tools/tune_sweep.py)
-        G = ctx->opt_wgs > 0 ? ctx->opt_wgs : std::max(1, (ctx->cus * occ + ntours - 1) / ntours);
-        G = std::min(G, MAX_WGS_PER_TOUR);
-        G = std::min(G, std::max(1, n / 2));
-        P = (n + G - 1) / G;
-        G = (n + P - 1) / P;
-    };
-    int G = 1, P = n;
+            return api;
+        return 0;
+    });
+    switch (s.refused) {
+    case plan::Refusal::NONE: break;
+    case plan::Refusal::RES_ROWS: return fail(ctx, E_EXHAUSTED, "resident sweep: rows of %zu B do not fit", row);
+    case plan::Refusal::PIPE_ROWS: return fail(ctx, E_EXHAUSTED, "pipelined sweep: 3 rows of %zu B do not fit %zu B of LDS", row, ctx->lds_max);
+    case plan::Refusal::WGS: return fail(ctx, E_EXHAUSTED, "resident sweep: %d workgroups per tour exceed %d", s.G, MAX_WGS_PER_TOUR);
+    case plan::Refusal::ROW: return fail(ctx, E_EXHAUSTED, "matrix mode needs one %zu-byte row in LDS (max %zu): n=%d too large", row, ctx->lds_max, n);
+    case plan::Refusal::MATRIX_N: return fail(ctx, E_EXHAUSTED, "n=%d exceeds the matrix-mode limit", n);
+    }
     if (ctx->otf) {
-        // matrix-free: 8 tour edges per workgroup, the whole b range per workgroup
-        if (const int rc = ensure_spts(ctx, (size_t)ntours * n)) return rc;
-        P = (ctx->cost_bound < 33554432.0 && n < 131072) ? (ctx->plan_otf_early ? OTF8_RUN_INT : OTF8_RUN) : 8;     // (k_sweep_otf8 / k_sweep_otf: see launch_sweep)
-        G = (n + P - 1) / P;
-        if (G > ctx->S.pstride) return fail(ctx, E_INTERNAL, "partial stride %d < %d workgroups", ctx->S.pstride, G);
-        ctx->plan_kernel = 4; ctx->plan_G = G; ctx->plan_P = P; ctx->plan_BT = 256; ctx->plan_NCH = 0; ctx->plan_D = 0;
-        ctx->plan_T = ntours; ctx->plan_lds = 0;
-        ctx->plan_pipe2 = ctx->plan_pipe2_sweep = false; ctx->plan_lds_fused = 0;   // (a matrix plan's, if the context had one before)
+        if (s.G > ctx->S.pstride) return fail(ctx, E_INTERNAL, "partial stride %d < %d workgroups", ctx->S.pstride, s.G);
+        ctx->plan = s;
         return E_OK;
     }
-    // resident sweep: all P+1 (<= 9) rows of a run in LDS at once.  One chunk per thread for
-    // uint16 (two would spill), at most two otherwise.
-    const int res_bt = std::min(1024, std::max(64, (nvec + 63) & ~63));
-    const int res_nch = (nvec + res_bt - 1) / res_bt;
-    auto res_P = [&]() { // rows that fit: prefer two workgroups per CU when that still gives P = 8
-        const size_t extra = slack + 64;
-        if (9 * row + extra <= ctx->lds_max / 2) return 8;
-        const long fit = (long)((ctx->lds_max - extra) / row) - 1;
-        return (int)std::min<long>(8, fit);
-    };
-    const bool res_ok = res_nch <= (ctx->elem == TSPGPU_ELEM_U16 ? 1 : 2) && res_P() >= 2 && n >= 8;
-    const bool batch_streams = ntours > 1 && n >= 256 && (size_t)n * row <= ((size_t)256 << 20) && ctx->opt_wgs <= 0;
-    if (kernel == 3 && !res_ok) return fail(ctx, E_EXHAUSTED, "resident sweep: rows of %zu B do not fit", row);
-    if (kernel == 0) {
-        // uint16: resident whenever it fits.  int32 / f64: resident only while 9 rows leave room
-        // for two workgroups per CU (small n, multi-start batches); else pipelined; else simple.
-        // A single tour whose resident runs would not all be on the chip at once (more than two
-        // workgroups per CU's worth: a second, mostly empty round) streams instead.
-        const bool res_one_round = ntours > 1 || (n + res_P() - 1) / std::max(1, res_P()) <= 2 * ctx->cus;
-        // A batch of tours (multi-start) over a matrix the last-level cache holds: the streamed kernel with runs of 16 .. 64
-        // edges (below) beats the resident one's 8-edge runs at every size from n = 512 up -- a run's fixed cost (the tour
-        // state derived, the first rows landed: ~4 us) is paid once per 16 .. 64 rows instead of once per 8:
-        // tools/tune_multistart.py, profiles/r03_multistart_plan.txt (pr1002 all starts 94.7 -> 59 ms, n=4096 x 64 330 -> 181 ms,
-        // n=8192 x 32 1579 -> 718 ms; f64 pr1002 x 256 82 -> 45 ms)
-        if (batch_streams && pipe_fits(BT, 64)) kernel = 2;
-        else if (res_ok && (res_one_round || !pipe_fits(BT, 64)) && (ctx->elem == TSPGPU_ELEM_U16 || 9 * row + slack <= ctx->lds_max / 2)) kernel = 3;
-        else kernel = pipe_fits(BT, 64) ? 2 : 1;
-    }
-    if (kernel == 3) {
-        BT = ctx->opt_block > 0 ? BT : res_bt;
-        nch = (nvec + BT - 1) / BT;
-        if (nch > (ctx->elem == TSPGPU_ELEM_U16 ? 1 : 2)) { BT = res_bt; nch = res_nch; }
-        P = res_P();
-        if (ctx->opt_wgs > 0) P = std::max(2, std::min(P, (n + ctx->opt_wgs - 1) / ctx->opt_wgs));
-        // a single small tour is latency-bound: shorter runs on more workgroups (up to two per CU)
-        // cut the step chain; the extra row per run costs nothing at these sizes (measured:
-        // n=1024 11.1 -> 8.7 us per sweep, n=2048 11.9 -> 10.5)
-        else if (ntours == 1) P = std::max(2, std::min(P, (n + 2 * ctx->cus - 1) / (2 * ctx->cus)));
-        G = (n + P - 1) / P;
-        if (G > MAX_WGS_PER_TOUR) return fail(ctx, E_EXHAUSTED, "resident sweep: %d workgroups per tour exceed %d", G, MAX_WGS_PER_TOUR);
-        ctx->plan_D = 0;
-        ctx->plan_lds = (size_t)(P + 1) * row + (size_t)((P + 2 + 3) & ~3) * 4 + 16 * sizeof(Partial) + 64;
-    }
-    if (kernel == 2) {
-        // a single uint16 tour past the resident kernel's size: two 16-byte vectors per thread on half as many threads
-        // (tools/tune_n4461.py: fnl4461 24.6 -> 18.2 us per sweep -- 9-wave workgroups fill the SIMDs unevenly --, n = 5000 /
-        // 6000 / 8192: 3-5 % faster; n = 16384 takes this shape anyway)
-        if (ctx->opt_block <= 0 && ctx->elem == TSPGPU_ELEM_U16 && ntours == 1 && nvec > 512)
-            BT = std::min(1024, std::max(256, ((nvec + 1) / 2 + 63) & ~63));
-        nch = (nvec + BT - 1) / BT;
-        while (nch > 4 && BT < 1024) { BT *= 2; nch = (nvec + BT - 1) / BT; }
-        int inst = nch <= 1 ? 1 : nch <= 2 ? 2 : (nch == 3 && ctx->elem == TSPGPU_ELEM_U16) ? 3 : 4;
-        if (nch > 4 || !pipe_fits(BT, 64)) {
-            if (ctx->opt_kernel == 2) return fail(ctx, E_EXHAUSTED, "pipelined sweep: 3 rows of %zu B do not fit %zu B of LDS", row, ctx->lds_max);
-            kernel = 1;
-        } else {
-            nch = inst;
-            ctx->plan_D = pipe_depth(nch, ctx->opt_depth);
-            plan_GP(3 * row + slack, BT, G, P, pipe_kernel(ctx->elem, nch, ctx->plan_D, false));
-            if (ctx->opt_wgs <= 0 && ntours == 1) {
-                // a whole number of workgroups per CU (an uneven last round costs a full one), the
-                // most that keeps runs of >= 8 edges (each run fetches P+1 rows: extra row <= 12 %)
-                int k = std::max(1, G / ctx->cus);
-                // (at most two workgroups per CU: a third one -- 320 .. 448-thread workgroups of uint16 tours around n = 6000
-                // fit three -- costs more in row traffic (P + 1 rows per P edges) and skew than it hides: n=6144 30.3 us per
-                // sweep with G = 768, 23.2 with G = 512; tools/tune_mid.py)
-                k = std::min(k, 2);
-                while (k > 1 && (n + ctx->cus * k - 1) / (ctx->cus * k) < 8) k--;
-                if ((n + ctx->cus * k - 1) / (ctx->cus * k) >= 8) { P = (n + ctx->cus * k - 1) / (ctx->cus * k); G = (n + P - 1) / P; }
-            }
-            if (batch_streams) {
-                // runs of n/64 edges, 16 .. 64 (f64 rows: n/16, 32 .. 256), shorter while the batch has fewer than four
-                // workgroups per CU (the optimum is flat: +-50 % of the run length costs 1-3 %)
-                P = ctx->elem == TSPGPU_ELEM_F64 ? std::min(256, std::max(32, n / 16)) : std::min(64, std::max(16, n / 64));
-                while (P > 8 && (long)ntours * ((n + P - 1) / P) < 4L * ctx->cus) P /= 2;
-                G = (n + P - 1) / P;
-            }
-            if (ctx->opt_wgs <= 0 && P < 8) {
-                P = std::min(n, 8); G = (n + P - 1) / P;
-            }
-            while (!pipe_fits(BT, P) && G < MAX_WGS_PER_TOUR) { G *= 2; P = (n + G - 1) / G; G = (n + P - 1) / P; }
-            ctx->plan_lds = 3 * row + (size_t)((P + 2 + 3) & ~3) * 4 + 16 + 16 * sizeof(Partial) + 64;
-            ctx->plan_pipe2 = ctx->opt_pipe2 && nch <= 2 && P >= 2 && ctx->plan_lds + row <= ctx->lds_max;
-            ctx->plan_pipe2_sweep = ctx->opt_pipe2 && pipe2_kernel(ctx->elem, nch) && P >= 2 && ctx->plan_lds + row <= ctx->lds_max;
-        }
-    }
-    if (kernel == 1) {
-        if (row + slack > ctx->lds_max)
-            return fail(ctx, E_EXHAUSTED, "matrix mode needs one %zu-byte row in LDS (max %zu): n=%d too large", row, ctx->lds_max, n);
-        if (ctx->opt_block <= 0) BT = std::min(1024, std::max(64, pow2_ceil(nvec / 4)));
-        plan_GP(row + slack, BT, G, P, simple_kernel(ctx->elem, false));
-        ctx->plan_lds = row + 16 * sizeof(Partial) + 64;
-        nch = 0;
-    }
-    if (n > MATRIX_MAX_N) return fail(ctx, E_EXHAUSTED, "n=%d exceeds the matrix-mode limit", n);
-    ctx->plan_kernel = kernel; ctx->plan_G = G; ctx->plan_P = P; ctx->plan_BT = BT; ctx->plan_NCH = nch; ctx->plan_T = ntours;
-    if (kernel != 2) ctx->plan_pipe2 = ctx->plan_pipe2_sweep = false;
-    ctx->plan_lds_fused = ctx->plan_lds + (ctx->plan_pipe2 ? row : 0);
-    if (ctx->plan_pipe2_sweep)
-        HIP_TRY(hipFuncSetAttribute(pipe2_kernel(ctx->elem, nch), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(ctx->plan_lds + row)));
+    if (s.pipe2_sweep)
+        HIP_TRY(hipFuncSetAttribute(pipe2_kernel(ctx->elem, s.NCH), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(s.lds + row)));
     // raise the dynamic-LDS cap of the kernels we are going to launch
-    if (const void *ff = fused_kernel(ctx->elem, nch, kernel, ctx->plan_pipe2))
-        HIP_TRY(hipFuncSetAttribute(ff, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ctx->plan_lds_fused));
+    if (const void *ff = fused_kernel(ctx->elem, s.NCH, s.kernel, s.pipe2))
+        HIP_TRY(hipFuncSetAttribute(ff, hipFuncAttributeMaxDynamicSharedMemorySize, (int)s.lds_fused));
     for (int tabu = 0; tabu < 2; tabu++) {
-        const void *fn = kernel == 3 ? res_kernel(ctx->elem, nch, tabu)
-                       : kernel == 2 ? pipe_kernel(ctx->elem, nch, ctx->plan_D, tabu) : simple_kernel(ctx->elem, tabu);
-        if (!fn) return fail(ctx, E_INTERNAL, "no kernel instance for nch=%d", nch);
-        const size_t need = tabu && kernel != 1 ? ((ctx->plan_lds + 15) & ~(size_t)15) + n + 32 : ctx->plan_lds;
-        if (tabu) ctx->plan_tabu_fits = need <= ctx->lds_max;      // plain 2-opt must not fail for the tabu variant's sake
-        if (need > ctx->lds_max) continue;
+        const void *fn = s.kernel == 3 ? res_kernel(ctx->elem, s.NCH, tabu)
+                       : s.kernel == 2 ? pipe_kernel(ctx->elem, s.NCH, s.D, tabu) : simple_kernel(ctx->elem, tabu);
+        if (!fn) return fail(ctx, E_INTERNAL, "no kernel instance for nch=%d", s.NCH);
+        const size_t need = tabu ? plan::tabu_lds(s, n) : s.lds;
+        if (need > ctx->lds_max) continue;      // (tabu only, s.tabu_fits: plain 2-opt must not fail for the tabu variant's sake)
         HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)need));
     }
+    ctx->plan = s;
     return E_OK;
 }
 
@@ -3903,17 +3771,17 @@ static int launch_sweep(tspgpu_ctx *ctx, int slot0, int ntours, bool tabu, int g
     memset(&A, 0, sizeof A);
     A.S = ctx->S;
     A.mat = ctx->d_mat;
-    A.n = ctx->n; A.ld = ctx->ld; A.slot0 = slot0; A.P = ctx->plan_P;
+    A.n = ctx->n; A.ld = ctx->ld; A.slot0 = slot0; A.P = ctx->plan.P;
     A.g0 = g0;
-    const int G = gcount < 0 ? ctx->plan_G : gcount;
+    const int G = gcount < 0 ? ctx->plan.G : gcount;
     A.symmetric = ctx->symmetric ? 1 : 0;
     A.ablate = ctx->opt_ablate;
     A.stamps = ctx->opt_stamps ? ctx->d_stamps : nullptr;
     A.pts = ctx->d_pts; A.spts = ctx->d_spts; A.kind = ctx->kind;
     A.tabu_list = ctx->d_tabu_list; A.tabu = ctx->d_tabu;
-    if (ctx->plan_kernel == 4) {
+    if (ctx->plan.kernel == 4) {
         const int n = ctx->n;
-        const bool otf8 = ctx->cost_bound < 33554432.0 && n < 131072;
+        const bool otf8 = plan::otf8(ctx->cost_bound, n);
         if (otf8 && ctx->ceil_int() && ctx->d_ipts) {      // (the int2 successors' points take the front half of the double2 buffer)
             A.ipts = ctx->d_ipts; A.ispts = reinterpret_cast<const int2 *>(ctx->d_spts.p);
             hipLaunchKernelGGL(k_gather_ispts, dim3((n + 255) / 256, ntours), dim3(256), 0, ctx->stream, ctx->S, n, slot0, ctx->d_ipts, reinterpret_cast<int2 *>(ctx->d_spts.p));
@@ -3921,9 +3789,9 @@ static int launch_sweep(tspgpu_ctx *ctx, int slot0, int ntours, bool tabu, int g
             hipLaunchKernelGGL(k_gather_spts, dim3((n + 255) / 256, ntours), dim3(256), 0, ctx->stream, ctx->S, n, slot0, ctx->d_pts, ctx->d_spts);
         HIP_TRY(hipGetLastError());
         const void *fo = tabu ? (const void *)k_sweep_otf<true> : (const void *)k_sweep_otf<false>;
-        if (ctx->cost_bound < 33554432.0 && n < 131072) {     // 2^25, 17-bit labels
+        if (otf8) {
             const int kind = ctx->ceil_int() ? KIND_CEIL_INT : ctx->kind;
-#define OTF8(K) (tabu ? (const void *)k_sweep_otf8<K, true> : ctx->plan_otf_early ? (const void *)k_sweep_otf8<K, false, true> : (const void *)k_sweep_otf8<K, false>)
+#define OTF8(K) (tabu ? (const void *)k_sweep_otf8<K, true> : ctx->plan.otf_early ? (const void *)k_sweep_otf8<K, false, true> : (const void *)k_sweep_otf8<K, false>)
             // plain 2-opt: with the exact early-out and runs of 64 edges (option 99 = 3: without it, the full evaluation of every
             // pair -- diagnostics, tools/otf_rate.py)
             fo = kind == TSPGPU_EUC_2D ? OTF8(TSPGPU_EUC_2D) : kind == TSPGPU_ATT ? OTF8(TSPGPU_ATT)
@@ -3934,20 +3802,20 @@ static int launch_sweep(tspgpu_ctx *ctx, int slot0, int ntours, bool tabu, int g
         HIP_TRY(hipLaunchKernel(fo, dim3(G, ntours), dim3(256), ao, 0, ctx->stream));
         return E_OK;
     }
-    const void *fn = ctx->plan_kernel == 3 ? res_kernel(ctx->elem, ctx->plan_NCH, tabu)
-                   : ctx->plan_kernel == 2 ? pipe_kernel(ctx->elem, ctx->plan_NCH, ctx->plan_D, tabu) : simple_kernel(ctx->elem, tabu);
+    const void *fn = ctx->plan.kernel == 3 ? res_kernel(ctx->elem, ctx->plan.NCH, tabu)
+                   : ctx->plan.kernel == 2 ? pipe_kernel(ctx->elem, ctx->plan.NCH, ctx->plan.D, tabu) : simple_kernel(ctx->elem, tabu);
     // (the two-edge streaming form replaces the pipelined kernel below when it applies)
     // tabu: n + 32 verdict bytes behind everything else in the dynamic LDS
-    if (tabu && ctx->plan_kernel != 1 && !ctx->plan_tabu_fits)
+    if (tabu && ctx->plan.kernel != 1 && !ctx->plan.tabu_fits)
         return fail(ctx, E_EXHAUSTED, "tabu sweep: the rows leave no room for %d verdict bytes in LDS (use TSPGPU_OPT_KERNEL=1 or the matrix-free mode)", ctx->n + 32);
-    A.tabu_lds = (int)((ctx->plan_lds + 15) & ~(size_t)15);
-    size_t lds = tabu && ctx->plan_kernel != 1 ? (size_t)A.tabu_lds + ctx->n + 32 : ctx->plan_lds;
-    if (ctx->plan_kernel == 2 && ctx->plan_pipe2_sweep && !tabu && ctx->symmetric) {
-        fn = pipe2_kernel(ctx->elem, ctx->plan_NCH);
-        lds = ctx->plan_lds + (size_t)ctx->ld * elem_size(ctx->elem);
+    A.tabu_lds = (int)((ctx->plan.lds + 15) & ~(size_t)15);
+    size_t lds = tabu && ctx->plan.kernel != 1 ? (size_t)A.tabu_lds + ctx->n + 32 : ctx->plan.lds;
+    if (ctx->plan.kernel == 2 && ctx->plan.pipe2_sweep && !tabu && ctx->symmetric) {
+        fn = pipe2_kernel(ctx->elem, ctx->plan.NCH);
+        lds = ctx->plan.lds + (size_t)ctx->ld * elem_size(ctx->elem);
     }
     void *args[] = {&A};
-    HIP_TRY(hipLaunchKernel(fn, dim3(G, ntours), dim3(ctx->plan_BT), args, lds, ctx->stream));
+    HIP_TRY(hipLaunchKernel(fn, dim3(G, ntours), dim3(ctx->plan.BT), args, lds, ctx->stream));
     return E_OK;
 }
 
@@ -3967,7 +3835,7 @@ static int launch_apply(tspgpu_ctx *ctx, int slot0, int ntours, bool tabu, bool 
     ApplyArgs A;
     A.S = ctx->S;
     A.mat = ctx->d_mat;
-    A.n = ctx->n; A.ld = ctx->ld; A.slot0 = slot0; A.G = ctx->plan_G;
+    A.n = ctx->n; A.ld = ctx->ld; A.slot0 = slot0; A.G = ctx->plan.G;
     A.symmetric = ctx->symmetric ? 1 : 0;
     A.pts = ctx->d_pts; A.kind = ctx->kind;
     A.tabu_list = ctx->d_tabu_list; A.tabu = ctx->d_tabu;
@@ -4004,16 +3872,16 @@ static int launch_fused(tspgpu_ctx *ctx, int slot0, int ntours, int parity)
     memset(&A, 0, sizeof A);
     A.S = ctx->S;
     A.mat = ctx->d_mat;
-    A.n = ctx->n; A.ld = ctx->ld; A.slot0 = slot0; A.P = ctx->plan_P;
+    A.n = ctx->n; A.ld = ctx->ld; A.slot0 = slot0; A.P = ctx->plan.P;
     A.symmetric = 1;
     A.ablate = ctx->opt_ablate;
     A.stamps = ctx->opt_stamps ? ctx->d_stamps : nullptr;
     A.pts = ctx->d_pts; A.spts = nullptr; A.kind = ctx->kind;
     A.F = ctx->F; A.parity = parity; A.hist = ctx->hist;
-    const void *fn = fused_kernel(ctx->elem, ctx->plan_NCH, ctx->plan_kernel, ctx->plan_pipe2);
-    if (!fn) return fail(ctx, E_INTERNAL, "no one-launch-per-sweep instance for kernel %d, %d chunks", ctx->plan_kernel, ctx->plan_NCH);
+    const void *fn = fused_kernel(ctx->elem, ctx->plan.NCH, ctx->plan.kernel, ctx->plan.pipe2);
+    if (!fn) return fail(ctx, E_INTERNAL, "no one-launch-per-sweep instance for kernel %d, %d chunks", ctx->plan.kernel, ctx->plan.NCH);
     void *args[] = {&A};
-    HIP_TRY(hipLaunchKernel(fn, dim3(ctx->plan_G, ntours), dim3(ctx->plan_BT), args, ctx->plan_lds_fused, ctx->stream));
+    HIP_TRY(hipLaunchKernel(fn, dim3(ctx->plan.G, ntours), dim3(ctx->plan.BT), args, ctx->plan.lds_fused, ctx->stream));
     return E_OK;
 }
 
@@ -4155,42 +4023,6 @@ static int run_fused(tspgpu_ctx *ctx, int slot0, int ntours, double time_left_s,
     return E_OK;
 }
 
-// The LDS-resident descent (k_lds2opt) where it applies: uint16 cells, one tour, a whole chip whose LDS holds the matrix.
-static bool persist_fits(const tspgpu_ctx *ctx, int &E, int &W, size_t &lds, bool tabu = false)
-{
-    const int n = ctx->n;
-    if (ctx->elem != TSPGPU_ELEM_U16 || ctx->otf || !ctx->symmetric || !ctx->d_mat || n < 64 || n > 4096) return false;
-    int e = (n + ctx->cus - 1) / ctx->cus;
-    if (ctx->opt_persist_edges > e) e = ctx->opt_persist_edges;
-    if (e > LP_EMAX || e > n / 4) return false;
-    const size_t nl = (size_t)((n + 7) & ~7);
-    lds = (size_t)(e + 1) * nl * 2 + nl * 4 + std::max<size_t>(nl * 2, 256) + (tabu ? nl * 2 : 0);   // (+ the nodes' ages)
-    if (lds > ctx->lds_max) return false;
-    E = e; W = (n + e - 1) / e;
-    return W <= ctx->cus && W <= 256;        // (the exchange keeps two candidate sets of 4 polling waves: 256 slots)
-}
-
-// The half-window form (k_lds2opt_w): every row kept as the window of E + n/2 + 16.. cells ahead of the workgroup's first own
-// cell, so that instances a little past n = 4096 (fnl4461, BASELINE config 3) stay LDS-resident.  Plain 2-opt only.
-static bool persist_fits_w(const tspgpu_ctx *ctx, int &E, int &W, size_t &lds, int &Ws, int &nstage, bool tabu = false)
-{
-    const int n = ctx->n;
-    if (ctx->elem != TSPGPU_ELEM_U16 || ctx->otf || !ctx->symmetric || !ctx->d_mat || n < 64 || n > 8191) return false;
-    int e = (n + std::min(ctx->cus, 256) - 1) / std::min(ctx->cus, 256);
-    if (ctx->opt_persist_edges > e) e = ctx->opt_persist_edges;
-    if (e > LW_EMAX) return false;
-    const int ws = (e + n / 2 + 23) & ~7;             // window cells per row (see k_lds2opt_w)
-    if (ws > n || (ws >> 3) - 1 > LW_BT) return false;
-    const size_t nl = (size_t)((n + 7) & ~7);
-    if ((nl >> 3) > (size_t)LW_BT) return false;
-    const size_t fixed = (size_t)(e + 1) * ws * 2 + (nl + 8) * 4 + 512 + (tabu ? (nl + 16) * 2 : 0);   // (+ the nodes' ages)
-    int ns = 2;
-    if (fixed + 2 * nl * 2 > ctx->lds_max) ns = 1;
-    if (fixed + (size_t)ns * nl * 2 > ctx->lds_max) return false;
-    E = e; W = (n + e - 1) / e; Ws = ws; nstage = ns; lds = fixed + (size_t)ns * nl * 2;
-    return W <= ctx->cus && W <= 256;
-}
-
 // The shaped instantiations of k_lds2opt (plain packed descent, n == nl): the one place that lists them.
 // tmat: the form that fetches moved rows from the tour-ordered copy (PersistArgs::tmat, n * n cells)
 static const void *lp_shaped_fn(int n, int E, bool tmat)
@@ -4290,14 +4122,11 @@ static int run_persist(tspgpu_ctx *ctx, int slot, double *time_left_io, bool *de
 {
     *ran = false;
     const double time_left_s = time_left_io ? *time_left_io : -1.0;
-    int E = 0, W = 0, Ws = 0, nstage = 0;
-    size_t lds = 0;
-    bool win = false;
-    if (ctx->opt_persist_window == 1 && persist_fits_w(ctx, E, W, lds, Ws, nstage, tabu != nullptr)) win = true;
-    else if (!persist_fits(ctx, E, W, lds, tabu != nullptr)) {
-        if (ctx->opt_persist_window == 2 || !persist_fits_w(ctx, E, W, lds, Ws, nstage, tabu != nullptr)) return E_OK;
-        win = true;
-    }
+    const plan::Resident R = plan::resident(plan_in(ctx), tabu != nullptr);
+    if (R.form == plan::Form::NONE) return E_OK;
+    const int E = R.E, W = R.W, Ws = R.Ws, nstage = R.nstage;
+    const size_t lds = R.lds;
+    const bool win = R.form == plan::Form::WINDOW;
     if (ctx->lp_gate.skip_this()) return E_OK;
     HIP_TRY(ctx->d_lp_slots.reserve(((size_t)2 * LP_BT * 64 + 64) / 8));   // exchange slots, then the control words
     HIP_TRY(ctx->h_lp.reserve(16));
@@ -4396,32 +4225,15 @@ static int run_persist(tspgpu_ctx *ctx, int slot, double *time_left_io, bool *de
     return E_OK;
 }
 
-// The streamed persistent descent (k_str2opt) where it applies: uint16 cells, one tour, a symmetric matrix too large for the
-// LDS-resident kernels, four rows + the node-per-cell array in one workgroup's LDS, a whole idle chip.
-static bool stream_fits(const tspgpu_ctx *ctx, int &P, int &W, int &BT, int &NCH, size_t &lds)
-{
-    const int n = ctx->n, ld = ctx->ld;
-    if (ctx->elem != TSPGPU_ELEM_U16 || ctx->otf || !ctx->symmetric || !ctx->d_mat || n < 1024 || n >= 16384) return false;
-    const int cus = std::min(ctx->cus, 256);
-    P = (n + cus - 1) / cus;
-    W = (n + P - 1) / P;
-    NCH = ld / 8 <= 1024 ? 1 : 2;
-    if (ctx->opt_sp_nch > 0) NCH = ctx->opt_sp_nch;    // undocumented (option 93): force one / two 16-byte vectors per thread
-    BT = std::max(256, ((ld / 8 + NCH - 1) / NCH + 63) & ~63);     // (at least the 256 lanes that poll the exchange slots)
-    if (BT > 1024 || P < 2 || P > 64) return false;
-    lds = sp_lds_rows(ld) + sp_lds_ord(n) + sp_lds_nodes(P) + SP_LDS_SCRATCH;
-    lds = std::max<size_t>(lds, 84 * 1024);           // more than half a CU's LDS: one workgroup per CU, every CU one
-    return lds <= ctx->lds_max && W <= 256;
-}
-
 // *ran, *time_left_io and the deadline as run_persist.
 static int run_pstream(tspgpu_ctx *ctx, int slot, double *time_left_io, bool *deadline_hit, bool *ran)
 {
     *ran = false;
     const double time_left_s = time_left_io ? *time_left_io : -1.0;
-    int P = 0, W = 0, BT = 0, NCH = 0;
-    size_t lds = 0;
-    if (!stream_fits(ctx, P, W, BT, NCH, lds)) return E_OK;
+    const plan::Stream SP = plan::stream(plan_in(ctx));
+    if (!SP.fits) return E_OK;
+    const int P = SP.P, W = SP.W, BT = SP.BT, NCH = SP.NCH;
+    const size_t lds = SP.lds;
     if (ctx->lp_gate.skip_this()) return E_OK;
     HIP_TRY(ctx->d_lp_slots.reserve(((size_t)2 * LP_BT * 64 + 64) / 8));
     HIP_TRY(ctx->h_lp.reserve(16));
@@ -4454,25 +4266,13 @@ __global__ void k_rebase(Tours S, int slot, int delta)     // sweep counter and 
 
 static int run_sweeps_plain(tspgpu_ctx *ctx, int slot0, int ntours, bool tabu, long max_iters, double time_left_s, bool *deadline_hit);
 
-// the launch plan for `ntours` tours in flight, plain 2-opt or tabu: the matrix-free sweep over integer points runs two
-// instantiations with different run lengths (early-out: 64 edges per workgroup; full evaluation: 16), so the number of
-// partials a sweep leaves -- what k_apply reduces -- follows the variant
-static bool otf_early(const tspgpu_ctx *ctx, bool tabu)
-{
-    if (!ctx->otf || tabu || ctx->opt_ablate == 3 || ctx->opt_otf_early == 2 || !(ctx->cost_bound < 33554432.0 && ctx->n < 131072)) return false;
-    if (ctx->opt_otf_early == 1) return true;          // (hook 91: every weight kind, every size -- tests)
-    // automatic: integer points (the tests are integer subtractions and f32 products) and enough 64-edge runs for two workgroups
-    // per CU.  Measured (tools/otf_rate.py): pla85900 3.94 -> 0.93 ms per sweep, 85 900 uniform-random integer points (no
-    // locality in the node order: only the pair tests reject) 4.01 -> 2.94; but n = 20 000 305 -> 360 us (313 workgroups), and
-    // with double points (f64 subtractions in every test) d18512 296 -> 322 us, n = 16 384 uniform 210 -> 345 us
-    return ctx->ceil_int() && ctx->d_ipts && ctx->n >= 128 * ctx->cus;
-}
+// the launch plan for `ntours` tours in flight, plain 2-opt or tabu (the matrix-free sweep's run length follows the variant:
+// plan::otf_early)
 static int ensure_plan(tspgpu_ctx *ctx, int ntours, bool tabu)
 {
-    const bool early = otf_early(ctx, tabu);
-    if (ctx->plan_T != ntours || ctx->plan_kernel == 0 || (ctx->otf && ctx->plan_otf_early != early)) {
-        ctx->plan_otf_early = early;
-        int rc = make_plan(ctx, ntours);
+    const bool early = plan::otf_early(plan_in(ctx), tabu);
+    if (ctx->plan.T != ntours || ctx->plan.kernel == 0 || (ctx->otf && ctx->plan.otf_early != early)) {
+        int rc = make_plan(ctx, ntours, early);
         if (rc) return rc;
         drop_graphs(ctx);
     }
@@ -4526,11 +4326,9 @@ static int run_sweeps(tspgpu_ctx *ctx, int slot0, int ntours, bool tabu, long ma
     bool stream = !tabu && ntours == 1 && ctx->opt_stream == 2;
     if (!tabu && ntours == 1 && ctx->opt_stream == 1 && resident_wanted(ctx)) {      // (PERSIST = 2 does not get here)
         // automatic: where the LDS-resident kernels do not take the instance
-        int e_, w_, ws_, ns_;
-        size_t l_;
         // (one 16-byte vector per thread: n <= 8192; with two the kernel is at the register limit and the one-launch-per-sweep
         // kernel is faster: n = 12288 65.6 vs 56.5 us per sweep)
-        stream = ctx->ld / 8 <= 1024 && !persist_fits(ctx, e_, w_, l_) && (ctx->opt_persist_window == 2 || !persist_fits_w(ctx, e_, w_, l_, ws_, ns_));
+        stream = ctx->ld / 8 <= 1024 && plan::resident(plan_in(ctx), false).form == plan::Form::NONE;
     }
     if (stream) {
         ctx->lp_handed = false;
@@ -4546,7 +4344,7 @@ static int run_sweeps(tspgpu_ctx *ctx, int slot0, int ntours, bool tabu, long ma
 
 static int run_sweeps_plain(tspgpu_ctx *ctx, int slot0, int ntours, bool tabu, long max_iters, double time_left_s, bool *deadline_hit)
 {
-    if (!tabu && ctx->symmetric && fused_kernel(ctx->elem, ctx->plan_NCH, ctx->plan_kernel, ctx->plan_pipe2) &&
+    if (!tabu && ctx->symmetric && fused_kernel(ctx->elem, ctx->plan.NCH, ctx->plan.kernel, ctx->plan.pipe2) &&
         (ctx->opt_fused == 2 || (ctx->opt_fused == 1 && ntours <= 4)))
         return run_fused(ctx, slot0, ntours, time_left_s, deadline_hit);
     const double t_end = deadline_of(time_left_s);
@@ -5000,9 +4798,9 @@ int tspgpu_set_option(tspgpu_ctx *ctx, int option, long value)
     hipSetDevice(ctx->device);
     switch (option) {
     case TSPGPU_OPT_ELEM: if (value < 0 || value > 3) return fail(ctx, E_INVALID, "bad element kind"); ctx->opt_elem = (int)value; break;
-    case TSPGPU_OPT_KERNEL: if (value < 0 || value > 3) return fail(ctx, E_INVALID, "bad kernel id"); ctx->opt_kernel = (int)value; ctx->plan_kernel = 0; break;
+    case TSPGPU_OPT_KERNEL: if (value < 0 || value > 3) return fail(ctx, E_INVALID, "bad kernel id"); ctx->opt_kernel = (int)value; drop_plan(ctx); break;
     case TSPGPU_OPT_BATCH: if (value < 1 || value > 4096) return fail(ctx, E_INVALID, "bad batch"); ctx->opt_batch = (int)value; drop_graphs(ctx); break;
-    case TSPGPU_OPT_WGS_PER_TOUR: if (value < 0 || value > MAX_WGS_PER_TOUR) return fail(ctx, E_INVALID, "bad wgs"); ctx->opt_wgs = (int)value; ctx->plan_kernel = 0; break;
+    case TSPGPU_OPT_WGS_PER_TOUR: if (value < 0 || value > MAX_WGS_PER_TOUR) return fail(ctx, E_INVALID, "bad wgs"); ctx->opt_wgs = (int)value; drop_plan(ctx); break;
     case TSPGPU_OPT_HISTORY: {
         if (value < 0 || value > (1 << 22)) return fail(ctx, E_INVALID, "bad history size");
         drop_graphs(ctx);       // (captured launches hold the old arrays: they go first, so a failure below leaves "no history")
@@ -5017,13 +4815,13 @@ int tspgpu_set_option(tspgpu_ctx *ctx, int option, long value)
     }
     case TSPGPU_OPT_GRAPH: ctx->opt_graph = value ? 1 : 0; break;
     case TSPGPU_OPT_TIMING: ctx->opt_timing = value ? 1 : 0; break;
-    case TSPGPU_OPT_BLOCK: if (value < 0 || value > 1024) return fail(ctx, E_INVALID, "bad block"); ctx->opt_block = (int)value; ctx->plan_kernel = 0; break;
-    case TSPGPU_OPT_DEPTH: if (value < 0 || value > 8) return fail(ctx, E_INVALID, "bad depth"); ctx->opt_depth = (int)value; ctx->plan_kernel = 0; break;
+    case TSPGPU_OPT_BLOCK: if (value < 0 || value > 1024) return fail(ctx, E_INVALID, "bad block"); ctx->opt_block = (int)value; drop_plan(ctx); break;
+    case TSPGPU_OPT_DEPTH: if (value < 0 || value > 8) return fail(ctx, E_INVALID, "bad depth"); ctx->opt_depth = (int)value; drop_plan(ctx); break;
     case 99: ctx->opt_ablate = (int)value; drop_graphs(ctx); break; // undocumented: kernel ablation for profiling
     case 88: ctx->opt_lp_no_tmat = value ? 1 : 0; break; // undocumented: the shaped k_lds2opt that reloads moved rows from the matrix, not from the tour-ordered copy (tests)
     case 89: ctx->opt_lp_generic = value ? 1 : 0; break; // undocumented: the generic k_lds2opt where a shaped instantiation exists (tests)
     case 90: ctx->opt_or_otf_early = value == 1 || value == 2 ? (int)value : 0; break; // undocumented: see or_otf_early()
-    case 91: ctx->opt_otf_early = value == 1 || value == 2 ? (int)value : 0; ctx->plan_kernel = 0; drop_graphs(ctx); break; // undocumented: see otf_early()
+    case 91: ctx->opt_otf_early = value == 1 || value == 2 ? (int)value : 0; drop_plan(ctx); break; // undocumented: see plan::otf_early()
     case 92: ctx->opt_build_tile = (int)value; break; // undocumented: tile of the triangle build (tools/build_probe.py)
     case 93: ctx->opt_sp_nch = value == 1 || value == 2 ? (int)value : 0; break; // undocumented: vectors per thread of k_str2opt (tools/stream_probe.py)
     case 94: ctx->opt_vns_launch_k = value > 0 ? (int)std::min<long>(value, 65536) : 65536; break; // undocumented: VNS iterations per launch (tests)
@@ -5043,7 +4841,7 @@ int tspgpu_set_option(tspgpu_ctx *ctx, int option, long value)
     case TSPGPU_OPT_PERSIST_EDGES: if (value < 0 || value > LW_EMAX) return fail(ctx, E_INVALID, "edges per workgroup: 0 (auto) .. %d", LW_EMAX); ctx->opt_persist_edges = (int)value; break;
     case TSPGPU_OPT_BUILD_KERNEL: if (value < 0 || value > 1) return fail(ctx, E_INVALID, "bad build kernel"); ctx->opt_build = (int)value; break;
     case TSPGPU_OPT_PERSIST_WINDOW: if (value < 0 || value > 2) return fail(ctx, E_INVALID, "bad window mode"); ctx->opt_persist_window = (int)value; break;
-    case TSPGPU_OPT_PIPE2: if (value < 0 || value > 1) return fail(ctx, E_INVALID, "bad pipe2 mode"); ctx->opt_pipe2 = (int)value; ctx->plan_kernel = 0; drop_graphs(ctx); break;
+    case TSPGPU_OPT_PIPE2: if (value < 0 || value > 1) return fail(ctx, E_INVALID, "bad pipe2 mode"); ctx->opt_pipe2 = (int)value; drop_plan(ctx); break;
     case TSPGPU_OPT_NN_KERNEL: if (value < 0 || value > 3) return fail(ctx, E_INVALID, "bad NN kernel id"); ctx->opt_nn = (int)value; break;
     case TSPGPU_OPT_EM_FORM: if (value < 0 || value > 2) return fail(ctx, E_INVALID, "bad Extra Mileage form"); ctx->opt_em_form = (int)value; break;
     case TSPGPU_OPT_OR_MATRIX_FREE: if (value < 0 || value > 1) return fail(ctx, E_INVALID, "bad matrix-free Or-opt mode"); ctx->opt_or_otf = (int)value; break;
@@ -5064,25 +4862,20 @@ long tspgpu_info(const tspgpu_ctx *ctx, int what)
     case 0: return ctx->n;
     case 1: return ctx->ld;
     case 2: return ctx->elem;
-    case 3: return ctx->plan_kernel;
-    case 4: return ctx->plan_G;
-    case 5: return (long)ctx->plan_lds;
-    case 6: return ctx->plan_BT;
+    case 3: return ctx->plan.kernel;
+    case 4: return ctx->plan.G;
+    case 5: return (long)ctx->plan.lds;
+    case 6: return ctx->plan.BT;
     case 7: return ctx->symmetric ? 1 : 0;
     case 8: return ctx->cus;
-    case 9: return ctx->plan_D;
+    case 9: return ctx->plan.D;
     case 10: return ctx->otf ? 1 : 0;
-    case 11: return (ctx->symmetric && ctx->opt_fused && fused_kernel(ctx->elem, ctx->plan_NCH, ctx->plan_kernel, ctx->plan_pipe2)) ? 1 : 0;
-    case 14: return (ctx->plan_pipe2 || ctx->plan_pipe2_sweep) ? 1 : 0;
+    case 11: return (ctx->symmetric && ctx->opt_fused && fused_kernel(ctx->elem, ctx->plan.NCH, ctx->plan.kernel, ctx->plan.pipe2)) ? 1 : 0;
+    case 14: return (ctx->plan.pipe2 || ctx->plan.pipe2_sweep) ? 1 : 0;
     case 15: return ctx->lp_used ? 1 : 0;
     case 16: case 17: case 18: case 19: {    // geometry of the LDS-resident descent (0: it does not apply to the instance)
-        int E = 0, W = 0, Ws = 0, ns = 0; size_t lds = 0;
-        const bool full = ctx->opt_persist_window != 1 && persist_fits(ctx, E, W, lds);
-        if (!full && (ctx->opt_persist_window == 2 || !persist_fits_w(ctx, E, W, lds, Ws, ns))) {
-            if (!persist_fits(ctx, E, W, lds)) return 0;
-            Ws = 0;
-        }
-        return what == 16 ? W : what == 17 ? E : what == 18 ? (long)lds : Ws;
+        const plan::Resident R = plan::resident(plan_in(ctx), false);
+        return what == 16 ? R.W : what == 17 ? R.E : what == 18 ? (long)R.lds : R.Ws;
     }
     case 20: return ctx->lp_used && ctx->lp_window ? 1 : 0;
     case 21: return ctx->lp_handed ? 1 : 0;
@@ -5090,8 +4883,8 @@ long tspgpu_info(const tspgpu_ctx *ctx, int what)
     case 23: return ctx->vns_mode;
     case 24: return ctx->sp_used ? 1 : 0;
     case 25:   // the matrix-free sweep kernel of the current plan (see launch_sweep)
-        if (!ctx->otf || ctx->plan_kernel != 4) return 0;
-        return !(ctx->cost_bound < 33554432.0 && ctx->n < 131072) ? 1 : ctx->plan_otf_early ? 3 : 2;
+        if (!ctx->otf || ctx->plan.kernel != 4) return 0;
+        return !plan::otf8(ctx->cost_bound, ctx->n) ? 1 : ctx->plan.otf_early ? 3 : 2;
     case 26: return ctx->have_points && ctx->ceil_int() ? 1 : 0;   // CEIL_2D weights by the integer ceil-sqrt (edge_w<KIND_CEIL_INT>)
     case 27: return ctx->em_form;
     case 28: return ctx->em_stale;
@@ -5250,7 +5043,7 @@ int tspgpu_build_costs(tspgpu_ctx *ctx, double *host_out)
         ctx->symmetric = true;
         ctx->have_costs = true;
         ctx->built = true;
-        ctx->plan_kernel = 0;
+        drop_plan(ctx);
         return E_OK;
     }
     if (!row_fits) return fail(ctx, E_EXHAUSTED, "n = %d: a matrix row does not fit LDS and matrix-free mode is disabled", ctx->n);
@@ -5263,7 +5056,7 @@ int tspgpu_build_costs(tspgpu_ctx *ctx, double *host_out)
     ctx->max8k = ctx->cost_bound <= 8190.0;
     ctx->have_costs = true;
     ctx->built = true;
-    ctx->plan_kernel = 0;
+    drop_plan(ctx);
     HIP_TRY(hipStreamSynchronize(ctx->stream));
     if (host_out) return tspgpu_get_costs(ctx, host_out);
     return E_OK;
@@ -5315,7 +5108,7 @@ int tspgpu_set_costs(tspgpu_ctx *ctx, const double *host_costs, int n)
         HIP_TRY(hipStreamSynchronize(ctx->stream));
     }
     ctx->have_costs = true;
-    ctx->plan_kernel = 0;
+    drop_plan(ctx);
     return E_OK;
 }
 
@@ -5726,7 +5519,7 @@ int tspgpu_tour_sweep_part(tspgpu_ctx *ctx, int slot, int part, int nparts, doub
     if ((rc = need_slot(ctx, slot))) return rc;
     if (!ctx->symmetric) return fail(ctx, E_PRECOND, "a sharded sweep needs a symmetric matrix (both orientations of a pair live in different parts otherwise)");
     if ((rc = ensure_plan(ctx, 1, false))) return rc;
-    const int G = ctx->plan_G;
+    const int G = ctx->plan.G;
     const int g_lo = (int)((long)part * G / nparts), g_hi = (int)((long)(part + 1) * G / nparts);
     *delta = 0.0; *a = 0; *b = 0;
     if (g_hi <= g_lo) return E_OK;
@@ -5755,7 +5548,7 @@ int tspgpu_tour_apply_move(tspgpu_ctx *ctx, int slot, int a, int b, double delta
     if ((rc = need_slot(ctx, slot))) return rc;
     wake_slots(ctx, slot, 1);
     if ((rc = ensure_plan(ctx, 1, false))) return rc;
-    const int G = ctx->plan_G;
+    const int G = ctx->plan.G;
     const u64 key = delta < TWO_OPT_EPS ? (a < b ? ((u64)(unsigned)a << 32) | (unsigned)b : ((u64)(unsigned)b << 32) | (unsigned)a) : 0;
     hipLaunchKernelGGL(k_reopen, dim3(1), dim3(1), 0, ctx->stream, ctx->S, slot);     // (k_apply leaves a finished slot alone)
     hipLaunchKernelGGL(k_set_move, dim3((G + 255) / 256), dim3(256), 0, ctx->stream, ctx->S, slot, G, delta < TWO_OPT_EPS ? delta : 0.0, key);
@@ -6019,7 +5812,7 @@ static bool or_otf_early(const tspgpu_ctx *ctx) { return ctx->opt_or_otf_early =
 static SweepGeom or_plan(const tspgpu_ctx *ctx)
 {
     const int rmin = std::max(2, (ctx->n + MAX_WGS_PER_TOUR - 1) / MAX_WGS_PER_TOUR);
-    SweepGeom P = sweep_geom(ctx, 4, OR_EXTRA, rmin, OR_RMAX, {1, 2, 3}, OR_OTF_RUN);
+    SweepGeom P = plan::sweep_geom(plan_in(ctx), 4, OR_EXTRA, rmin, OR_RMAX, {1, 2, 3}, OR_OTF_RUN);
     if (!ctx->otf) ELEM_SWITCH(ctx->elem, T, P.fn = or_sweep_fn<T>(P.NCH));
     return P;
 }
@@ -6378,7 +6171,7 @@ template <typename T> static const void *m2_sweep_fn(int nch)
 // vectors at most)
 static SweepGeom m2_plan(const tspgpu_ctx *ctx)
 {
-    SweepGeom P = sweep_geom(ctx, 1, M2_EXTRA, M2_RMIN, M2_RMAX, {1, 2, 4, 10}, M2_OTF_RUN);
+    SweepGeom P = plan::sweep_geom(plan_in(ctx), 1, M2_EXTRA, M2_RMIN, M2_RMAX, {1, 2, 4, 10}, M2_OTF_RUN);
     if (!ctx->otf) ELEM_SWITCH(ctx->elem, T, P.fn = m2_sweep_fn<T>(P.NCH));
     return P;
 }

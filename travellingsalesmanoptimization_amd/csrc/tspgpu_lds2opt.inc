@@ -77,7 +77,8 @@ struct PersistArgs {
     u16 *tmat;
 };
 
-static constexpr int LP_EMAX = 16, LP_BT = 512;
+using plan::LP_EMAX;      // tour edges per workgroup at most, threads (tspgpu_plan.h)
+using plan::LP_BT;
 static constexpr u64 LP_KEYMASK = (1ull << 60) - 1;
 static constexpr u64 LP_NONE = 0xFFFFFFFFFull << 24;     // "no improving pair": delta field all ones, labels 0
 static constexpr int LP_DBIAS = 131072;

@@ -24,7 +24,9 @@
 //     Rows whose own cell lies inside R change node: swapped with their mirror row or reloaded, as in k_lds2opt.
 //   * a whole row is (re)loaded coalesced in node order into a staging row and gathered into the window by the labels.
 // ---------------------------------------------------------------------------
-static constexpr int LW_EMAX = 24, LW_BT = 768, LW_RB = 10, LW_FIX = 128;   // (768 threads: 170 registers each, ten rows in flight)
+using plan::LW_EMAX;      // tour edges per workgroup at most, threads (tspgpu_plan.h: 768 threads, 170 registers each)
+using plan::LW_BT;
+static constexpr int LW_RB = 10, LW_FIX = 128;   // (ten rows in flight)
 typedef v4u32 v4u32_a4 __attribute__((aligned(4)));       // 16 bytes of LDS at a 4-byte boundary
 static constexpr u64 LW_NONE = 0x3FFFFull << 26;         // "no improving pair": delta field (18 bits) all ones, labels 0
 

@@ -41,10 +41,10 @@ static constexpr int SP_DBIAS = 131072;                  // |delta| < 2 * 65535
 static constexpr u64 SP_NONE = 0x3FFFFull << 28;         // "no improving pair": delta field all ones, labels 0
 
 // LDS bytes of k_str2opt for (n, ld, P) -- the host asks for at least 82 KB so that one workgroup owns a CU
-__host__ __device__ static inline size_t sp_lds_rows(int ld) { return (size_t)4 * ld * 2; }
-__host__ __device__ static inline size_t sp_lds_ord(int n) { return (size_t)((n + 15) & ~7) * 2; }
-__host__ __device__ static inline size_t sp_lds_nodes(int P) { return (size_t)((P + 2 + 3) & ~3) * 4 + 16; }
-static constexpr size_t SP_LDS_SCRATCH = 32 * sizeof(Partial) + 64 + 16 * 8 * 2;
+using plan::sp_lds_rows;       // (tspgpu_plan.h: the host sizes the launch with the same functions)
+using plan::sp_lds_ord;
+using plan::sp_lds_nodes;
+using plan::SP_LDS_SCRATCH;
 
 template <int NCH, int MAXBT>
 __global__ void __launch_bounds__(MAXBT) k_str2opt(StreamArgs A)
