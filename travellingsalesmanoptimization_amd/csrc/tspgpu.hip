@@ -4025,10 +4025,16 @@ static int run_fused(tspgpu_ctx *ctx, int slot0, int ntours, double time_left_s,
 
 // The shaped instantiations of k_lds2opt (plain packed descent, n == nl): the one place that lists them.
 // tmat: the form that fetches moved rows from the tour-ordered copy (PersistArgs::tmat, n * n cells)
-static const void *lp_shaped_fn(int n, int E, bool tmat)
+// clocked: the instantiation that carries the phase clocks (option 98); production runs the one without
+template <int NLC, int EC> static const void *lp_shaped_of(bool tmat, bool clocked)
 {
-    if (n == 4096 && E == 16) return tmat ? (const void *)k_lds2opt<true, false, false, 4096, 16, true> : (const void *)k_lds2opt<true, false, false, 4096, 16>;
-    if (n == 1024 && E == 4) return tmat ? (const void *)k_lds2opt<true, false, false, 1024, 4, true> : (const void *)k_lds2opt<true, false, false, 1024, 4>;
+    if (clocked) return tmat ? (const void *)k_lds2opt<true, false, false, NLC, EC, true, true> : (const void *)k_lds2opt<true, false, false, NLC, EC, false, true>;
+    return tmat ? (const void *)k_lds2opt<true, false, false, NLC, EC, true> : (const void *)k_lds2opt<true, false, false, NLC, EC>;
+}
+static const void *lp_shaped_fn(int n, int E, bool tmat, bool clocked)
+{
+    if (n == 4096 && E == 16) return lp_shaped_of<4096, 16>(tmat, clocked);
+    if (n == 1024 && E == 4) return lp_shaped_of<1024, 4>(tmat, clocked);
     return nullptr;
 }
 
@@ -4137,11 +4143,11 @@ static int run_persist(tspgpu_ctx *ctx, int slot, double *time_left_io, bool *de
         {{k_lds2opt_w<false, false>, k_lds2opt_w<true, false>}, {k_lds2opt_w<false, true>, k_lds2opt_w<true, true>}, {k_lds2opt_w<false, false, true>, k_lds2opt_w<true, false, true>}}};
     // (E comes from the device's compute units: 16 / 4 on a whole MI355X; with fewer CUs E is larger, no shape is listed and
     // the generic kernel runs -- tspgpu_info 61 tells)
-    const bool shaped = !win && !tabu && !vns && pk && !ctx->opt_lp_generic && lp_shaped_fn(ctx->n, E, false);
+    const bool shaped = !win && !tabu && !vns && pk && !ctx->opt_lp_generic && lp_shaped_fn(ctx->n, E, false, false);
     // the tour-ordered copy where a shaped form runs; without the memory for it the shaped form that needs none
     bool tm = shaped && !ctx->opt_lp_no_tmat;
     if (tm && ctx->d_lp_tmat.reserve((size_t)ctx->n * ctx->n) != hipSuccess) { (void)hipGetLastError(); tm = false; }
-    const void *const sfn = shaped ? lp_shaped_fn(ctx->n, E, tm) : nullptr;
+    const void *const sfn = shaped ? lp_shaped_fn(ctx->n, E, tm, ctx->opt_stamps != 0) : nullptr;
     const void *const fn = sfn ? sfn : (const void *)fns[win][tabu ? 1 : vns ? 2 : 0][pk];
     if (const int rc = ensure_max_lds(ctx, fn)) return rc;
     const double t_end = deadline_of(time_left_s);

@@ -161,12 +161,16 @@ __device__ __forceinline__ unsigned lp_pk_bias(unsigned wtword)
 //     tmat[x] in this very sweep;
 //   * every thread waits for its stores (vmcnt(0)) in front of the last barrier before the exchange: a published record implies
 //     that the workgroup's tmat is up to date, and a row is read only behind the exchange of the sweep that moves it.
-template <bool PK16, bool TABU, bool VNS = false, int NLC = 0, int EC = 0, bool TM = false>
+// CLK: the shaped form with the phase clocks (TSPGPU_OPT_STAMPS).  Their counters live in every thread across the whole sweep
+// loop, so the shaped form that production runs (CLK false) has none of them; the other forms keep theirs whatever CLK says.
+template <bool PK16, bool TABU, bool VNS = false, int NLC = 0, int EC = 0, bool TM = false, bool CLK = false>
 __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     constexpr int EMAX = LP_EMAX, BT = LP_BT;
     constexpr bool SH = NLC > 0;
+    constexpr bool CLOCKS = !SH || CLK;
+    static_assert(SH || !CLK, "the clocked instantiation is a shaped one: the other forms always carry their clocks");
     constexpr int WC = NLC / (EC > 0 ? EC : 1);             // workgroups of the shaped form
     typedef __attribute__((address_space(4))) const PersistArgs c_PersistArgs;      // (the kernel arguments where they lie)
     static_assert(!SH || (PK16 && !TABU && !VNS), "the shaped form is the plain packed descent");
@@ -478,11 +482,12 @@ __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
         return (int)age16[q] < tenure || (int)age16[q1] < tenure;    // is_tabu, metaheuristic.c:416-418 (age = iter - tabu_list[node])
     };
     // phase clocks (TSPGPU_OPT_STAMPS): thread 0 of every workgroup sums wall-clock ticks per phase
-    unsigned long long ph[6] = {0, 0, 0, 0, 0, 0}, nreload = 0, nrows = 0, ph2[4] = {0, 0, 0, 0};
-    const bool clk = A.stamps != nullptr && tid == 0;
-    unsigned long long tc = clk ? wall_clock64() : 0ull;
-#define LP_PHASE2(i) do { if (clk) { const unsigned long long now_ = wall_clock64(); ph2[i] += now_ - tc; tc = now_; } } while (0)
-#define LP_PHASE(i) do { if (clk) { const unsigned long long now_ = wall_clock64(); ph[i] += now_ - tc; tc = now_; } } while (0)
+    [[maybe_unused]] unsigned long long ph[6] = {0, 0, 0, 0, 0, 0}, nreload = 0, nrows = 0, ph2[4] = {0, 0, 0, 0};
+    bool clk = false;
+    if constexpr (CLOCKS) clk = A.stamps != nullptr && tid == 0;
+    [[maybe_unused]] unsigned long long tc = clk ? wall_clock64() : 0ull;
+#define LP_PHASE2(i) do { if constexpr (CLOCKS) if (clk) { const unsigned long long now_ = wall_clock64(); ph2[i] += now_ - tc; tc = now_; } } while (0)
+#define LP_PHASE(i) do { if constexpr (CLOCKS) if (clk) { const unsigned long long now_ = wall_clock64(); ph[i] += now_ - tc; tc = now_; } } while (0)
     // Evaluation geometry (the same every sweep).  A pair of tour edges {k, m} has two owners; with n a multiple of 16 it is
     // evaluated by ONE of them -- the owner of k takes the m at most n/2 cells ahead of k -- which halves the arithmetic:
     // the thread owns one 8-cell chunk out of the n/16 chunks ahead of its half of the own edges (threads [0, n/16): the
@@ -962,11 +967,11 @@ __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
         LP_PHASE(3);                                  // reversal
         if (need) {
             if constexpr (TM) fetch_tm(need, lo, M, LP_TID); else reload(need);
-            nreload++; nrows += __builtin_popcount(need);
+            if constexpr (CLOCKS) { nreload++; nrows += __builtin_popcount(need); }
         }
         LP_PHASE(4);                                  // rows fetched
         if constexpr (TM) { write_back_tm(lo, M, LP_TID); LP_PHASE2(3); }
-        if (clk && wg == 0 && sdone < 4000) A.stamps[8192 + sdone] = ((unsigned long long)M << 48) | (wall_clock64() & 0xFFFFFFFFFFFFull);
+        if constexpr (CLOCKS) if (clk && wg == 0 && sdone < 4000) A.stamps[8192 + sdone] = ((unsigned long long)M << 48) | (wall_clock64() & 0xFFFFFFFFFFFFull);
         }   // (!nomove)
         if constexpr (TABU) {
             // mh_TabuSearch's loop body behind the move (metaheuristic.c:126-143): incumbent, trace, the linear tenure policy
@@ -996,7 +1001,7 @@ __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
 #undef LP_WRAP_EQ
 #undef LP_TID
 #undef LP_LM0
-    if (clk) {
+    if constexpr (CLOCKS) if (clk) {
         unsigned long long *o = A.stamps + (size_t)wg * 16;
         for (int i = 0; i < 6; i++) o[i] = ph[i];
         o[6] = nreload; o[7] = nrows; o[8] = (unsigned long long)sdone;
@@ -1030,7 +1035,7 @@ __global__ void __launch_bounds__(LP_BT) k_lds2opt(PersistArgs A)
     }
     if constexpr (SH) {
         // (the kernel-argument segment begins with the explicit arguments: PersistArgs, the only one, lies at offset 0)
-        static_assert(std::is_same_v<decltype(&k_lds2opt<PK16, TABU, VNS, NLC, EC, TM>), void (*)(PersistArgs)>, "PersistArgs must stay the kernel's only argument");
+        static_assert(std::is_same_v<decltype(&k_lds2opt<PK16, TABU, VNS, NLC, EC, TM, CLK>), void (*)(PersistArgs)>, "PersistArgs must stay the kernel's only argument");
         c_PersistArgs *Ak = (c_PersistArgs *)__builtin_amdgcn_kernarg_segment_ptr();
         asm volatile("" : "+s"(Ak));
         const int tk = Ak->slot;
