@@ -126,7 +126,7 @@ int  tspgpu_set_option(tspgpu_ctx *ctx, int option, long value);
  * packed 16-bit costs, (n, edges per workgroup) = (4096, 16) or (1024, 4); 0: the generic kernel); 62 .. 67 in
  * "Neighbour-list 3-opt" below; 68 with tspgpu_debug_tmat below; 69 the last LDS-resident descent, tabu walk or VNS walk (whole rows or
  * half-window rows) ran the loop over packed 16-bit deltas (every cost <= 16383; the tabu walk: <= 8190), 0: 32-bit deltas; 70 .. 77 in
- * the sections below; 78 .. 81 in "Batched neighbour-list 3-opt" below */
+ * the sections below; 78 .. 81 in "Batched neighbour-list 3-opt" below; 86 .. 90 in "Held-Karp lower bound" below */
 long tspgpu_info(const tspgpu_ctx *ctx, int what);
 
 /* ---- instance / cost matrix ------------------------------------------- */
@@ -928,6 +928,54 @@ int tspgpu_vns_walks_nl3_dl(tspgpu_ctx *ctx, int width, int closing, int walks, 
                             int *best_paths /* [walks][n] in/out */, double *best_costs /* [walks] in/out */,
                             double *trace /* [walks][k] or NULL; only the iterations this call completes are written */,
                             long *totals /* [walks][11] or NULL: the nine of tspgpu_vns_walks_nl3, then looked, full sweeps */);
+
+/* ---- Held-Karp lower bound (an extension: 1-trees in Boruvka rounds and the subgradient ascent over them, on the device) ----
+ * What none of the sections above gives: a distance to a bound instead of tour against tour.  Opt-in: no other entry point
+ * changes.
+ * Preconditions: costs or points in place; an integral cost source (uint16 or int32 cells, or matrix-free mode; f64 cells
+ * answer 12); a symmetric matrix; n >= 5.  No row-in-LDS limit, and the neighbour lists play no part.
+ * Scale: S = 128.  The multipliers pi[v] are 64-bit integers in units of 1/S of a cost unit, at most 2^45 in magnitude.  All
+ * arithmetic is exact, in 64-bit integers.
+ *   1. Weights and keys.  w(a, b) = S c[a][b] + pi[a] + pi[b].  An edge is an unordered pair {a, b}, a < b; its key is
+ *      (w(a, b), a, b), compared lexicographically.  Keys are distinct, so the order is total and every minimum below is unique.
+ *   2. 1-tree T(pi).  The minimum spanning tree, under the key order, of the complete graph on the nodes 1 .. n - 1, and the two
+ *      edges {0, u} with the smallest keys.  deg[v] is v's degree in T (deg[0] = 2), and
+ *      L(pi) = sum of w(e) over T - 2 sum of pi[v].  ceil(L(pi) / S) is a lower bound on every tour of an integer instance, for
+ *      any pi: a tour is a 1-tree, and its w-weight is S times its cost plus 2 sum pi.
+ *   3. Ascent.  Inputs: an upper bound UB, integral, 0 <= UB, S UB < 2^40; iters >= 1; patience >= 1; starting multipliers
+ *      (default all 0).  State h = 0, bad = 0, best = -infinity.  For it = 0 .. iters - 1:
+ *        compute L and deg of T(pi);
+ *        if L > best: best = L, pi* = pi, bad = 0; else bad += 1, and if bad >= patience: h += 1, bad = 0;
+ *        g[v] = deg[v] - 2, q = sum g[v]^2; if q = 0 stop with reason 1 (T is a tour, and it is optimal);
+ *        gap = S UB - L; if gap <= 0 stop with reason 2 (the bound has met the caller's upper bound);
+ *        t = floor(((2 gap) >> h) / q); if t = 0 stop with reason 3;
+ *        if some |pi[v] + t g[v]| > 2^45 stop with reason 5, nothing applied;
+ *        pi[v] += t g[v].
+ *      When the iterations run out the reason is 0.  A passed deadline is reason 4 and code 4, with the bound so far -- a
+ *      success, as everywhere in this ABI; the clock is read every TSPGPU_OPT_BATCH iterations, and at least that many run.
+ *      Results: bound = ceil(best / S); pi*; the iterations evaluated (the one that stopped included); the reason; on reason 1
+ *      the tour T is, as a successor array: it starts at node 0 and the successor of 0 is the smaller-numbered of its two
+ *      neighbours (rule 5 of "Greedy-edge construction").
+ *   4. Rounds.  The device computes the tree of rule 2 without sorting, in Boruvka rounds: every node v >= 1 finds the smallest
+ *      key among its edges to nodes u >= 1 of another component; every component takes the smallest of its nodes' keys; those
+ *      edges are accepted; the components are merged and relabelled.  This is the tree of rule 2: the smallest key leaving a
+ *      component is the smallest key of a cut, and under a total order the minimum spanning tree is unique and holds the
+ *      smallest edge of every cut.  No cycle can form: along a chain of components that hook onto one another the keys strictly
+ *      decrease unless two components chose the same edge, so the only cycle is such a mutual pair, which is one edge.  Every
+ *      round at least halves the components: at most ceil(log2(n - 1)) rounds, all of them enqueued; the rounds after the last
+ *      merge return at once.  The ascent has no read-back per iteration and none per round.
+ * Codes: no context 14, every output untouched; a null required argument (weight; bound, iters_done, reason) 3; n < 5 3; no
+ * costs 9; an asymmetric matrix 9; f64 cells 12; UB, iters, patience or a multiplier out of range 3; the state cannot be
+ * allocated 8, all of it or none.
+ * Memory: 68 n bytes per context (and 1.3 KB of slack) at the first 1-tree; dropped with the instance.
+ * tspgpu_info: 86 the Boruvka rounds (those that accepted an edge) of the last 1-tree, 87 / 88 the iterations and the reason
+ * of the last ascent, 89 its final h, 90 the nodes per workgroup of the scan. */
+/* one 1-tree: pi NULL = all zero; edges [2n] (n pairs a < b, ascending by pair), degree [n], each may be NULL */
+int tspgpu_one_tree(tspgpu_ctx *ctx, const long *pi, int *edges, int *degree, long *weight /* L(pi), units of 1/128 */);
+/* the ascent of rule 3 */
+int tspgpu_lower_bound(tspgpu_ctx *ctx, double upper, int iters, int patience, double time_left_s,
+                       const long *pi_in /* NULL = zeros */, double *bound, long *pi_out /* [n] or NULL */,
+                       int *path /* [n] or NULL: the tour on reason 1 */, int *iters_done, int *reason);
 
 #ifdef __cplusplus
 }

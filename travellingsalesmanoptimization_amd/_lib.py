@@ -47,6 +47,8 @@ INFO_GREEDY_ROUNDS1, INFO_GREEDY_ROUNDS2, INFO_GREEDY_EDGES1, INFO_GREEDY_FREE =
 # ... the last batched neighbour-list descent: its 3-opt width in effect (0: two phases), 3-opt sweeps / moves over the tours, and the
 # most moves one tour's 3-opt sweep accepted
 INFO_NL3_BATCH_W, INFO_NL3_BATCH_SWEEPS, INFO_NL3_BATCH_MOVES, INFO_NL3_BATCH_MAX_MOVES = 78, 79, 80, 81
+# ... Boruvka rounds of the last 1-tree, iterations / reason / final h of the last Held-Karp ascent, nodes per workgroup of its scan
+INFO_HK_ROUNDS, INFO_HK_ITERATIONS, INFO_HK_REASON, INFO_HK_H, INFO_HK_NODES = 86, 87, 88, 89, 90
 EM_FORM_AUTO, EM_FORM_RESIDENT, EM_FORM_PER_STEP = 0, 1, 2
 MOPT_EXCHANGE = 1000
 EXCHANGE_AUTO, EXCHANGE_HOST, EXCHANGE_RCCL = 0, 1, 2
@@ -154,6 +156,8 @@ SIGNATURES = {
     "tspgpu_local_search_nl3_dl": (C.c_int, [_ctx, C.c_int, C.c_int, _ip, _pd, C.c_double, _pl, _pl, _pl, _pl, _pi, _pl, _pl, _pi, _pl, _pl]),
     "tspgpu_tour_greedy": (C.c_int, [_ctx, C.c_int]),
     "tspgpu_greedy_tour": (C.c_int, [_ctx, _ip, _pd]),
+    "tspgpu_one_tree": (C.c_int, [_ctx, C.c_void_p, C.c_void_p, C.c_void_p, _pl]),
+    "tspgpu_lower_bound": (C.c_int, [_ctx, C.c_double, C.c_int, C.c_int, C.c_double, C.c_void_p, _pd, C.c_void_p, C.c_void_p, _pi, _pi]),
     "tspgpu_multi_neighbours_build": (C.c_int, [_ctx, C.c_int]),
     "tspgpu_multi_multistart_local_search_nl": (C.c_int, [_ctx, C.c_void_p, C.c_int, C.c_double, _ip, _pd, _pi, _pl, _pl, _pl, _pl]),
     "tspgpu_tours_local_search_nl3": (C.c_int, [_ctx, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,

@@ -3119,6 +3119,7 @@ __global__ void k_cap_now(Tours S, int slot0, int count)
 #include "tspgpu_nlbatch.inc"
 #include "tspgpu_nlbatch_dl.inc"
 #include "tspgpu_nlvns.inc"
+#include "tspgpu_hk.inc"
 
 // ===========================================================================
 // host side
@@ -3189,6 +3190,18 @@ struct MEM_GROUP InstanceMem {            // of one n: new_instance drops it
     }
     void drop_greedy() { tspmem::free_rows<HipMem>(ge_rows(0)); }
 
+    // Held-Karp lower bound (tspgpu_hk.inc): multipliers and pi*, labels, hooks, the nodes' and the components' best keys, degrees,
+    // the tree's edges and the control block, 68 n bytes (+ 1.3 KB of slack behind the arrays the scan reads in vectors): all of
+    // them at the first 1-tree, or none; dropped with the instance
+    HkBuf hk{};
+    Rows hk_rows(size_t n)
+    {
+        const size_t slack = 64;    // the scan reads pi[] and comp[] in vectors up to ld
+        return {{&hk.pi, n * 8, slack * 8, 0}, {&hk.pibest, n * 8, slack * 8, 0}, {&hk.comp, n * 4, slack * 4, 0}, {&hk.up, n * 4}, {&hk.bw, n * 8},
+                {&hk.be, n * 8}, {&hk.cw, n * 8}, {&hk.ce, n * 8}, {&hk.deg, n * 4}, {&hk.edges, n * 8}, {&hk.ctl, sizeof(HkCtl), 0, 0}};
+    }
+    void drop_hk() { tspmem::free_rows<HipMem>(hk_rows(0)); }
+
     Rows look_ctx_rows(size_t n) { return {{&d_lq, n * 4}, {&d_look, sizeof(LookCtl), 0, 0}}; }
     void drop_look_ctx() { tspmem::free_rows<HipMem>(look_ctx_rows(0)); }
     static Rows m2_rows(M2Buf &B, size_t n)
@@ -3202,7 +3215,7 @@ struct MEM_GROUP InstanceMem {            // of one n: new_instance drops it
     void drop_nlbq() { tspmem::free_rows<HipMem>(nlbq_rows(0)); nlbq_cap = 0; }
     void drop_nlb() { tspmem::free_rows<HipMem>(nlb_rows(0)); nlb_cap = 0; drop_nlbq(); drop_nlv(); }
     void drop_grid() { tspmem::reset_all(d_gxy, d_gidx, d_gpos, d_cstart, d_gcell, d_knn); grid_G = 0; grid_ok = false; }
-    void reset() { tspmem::free_rows<HipMem>(m2_rows(m2, 0)); drop_look_ctx(); drop_greedy(); drop_nlb(); drop_grid(); }
+    void reset() { tspmem::free_rows<HipMem>(m2_rows(m2, 0)); drop_look_ctx(); drop_greedy(); drop_hk(); drop_nlb(); drop_grid(); }
     ~InstanceMem() { reset(); }
 };
 
@@ -3369,6 +3382,8 @@ struct tspgpu_ctx : ContextMem, InstanceMem, CostMem, SlotMem {
     long nlb_dl_looked = 0, nlb_dl_full = 0, nlb_dl_max_q = 0;  // the last batched descent with looks: sums and the maximum over its tours
     // greedy-edge construction (tspgpu_greedy.inc): the last one's rounds per phase, phase-1 edges, free nodes entering phase 2
     long ge_rounds1 = 0, ge_rounds2 = 0, ge_edges1 = 0, ge_free = 0;
+    // Held-Karp lower bound (tspgpu_hk.inc): Boruvka rounds of the last 1-tree; iterations, reason and final h of the last ascent
+    long hk_rounds = 0, hk_iters = 0, hk_reason = 0, hk_h = 0;
     // batched neighbour-list descent (tspgpu_nlbatch.inc)
     long nlb_tours = 0, nlb_launches = 0, nlb_max_live = 0;     // the last batched descent: tours, sweeps launched, most tours in one
     long nlb_w3 = 0, nlb_three_sweeps = 0, nlb_three_moves = 0, nlb_three_max_k = 0;    // ... its 3-opt width in effect (0: none), 3-opt sweeps and
@@ -4949,6 +4964,11 @@ long tspgpu_info(const tspgpu_ctx *ctx, int what)
     case 82: return ctx->nlb_dl_looked;
     case 83: return ctx->nlb_dl_full;
     case 84: return ctx->nlb_dl_max_q;
+    case 86: return ctx->hk_rounds;
+    case 87: return ctx->hk_iters;
+    case 88: return ctx->hk_reason;
+    case 89: return ctx->hk_h;
+    case 90: return HK_ROWS;
     case 85: return ctx->have_costs && ctx->n >= 8 ? std::min(NLB_QSWEEP_WGS, (ctx->n + ORNL_STARTS - 1) / ORNL_STARTS) : 0;
     case 55: return ctx->have_costs && ctx->symmetric && ctx->n >= 8 ? (ctx->n + ORNL_STARTS - 1) / ORNL_STARTS : 0;
     case 12: return (ctx->built && ctx->grid_ok && ctx->opt_nn != 1 && ctx->cost_bound < 134217728.0) ? ctx->grid_G : 0;
@@ -7287,6 +7307,194 @@ int tspgpu_greedy_tour(tspgpu_ctx *ctx, int *path, double *cost)
     if ((rc = ensure_tours(ctx, 1))) return rc;
     if ((rc = greedy_build(ctx, 0))) return rc;
     return store_path(ctx, 0, path, cost, nullptr);
+}
+
+} // extern "C"
+
+// ---- Held-Karp lower bound (tspgpu_hk.inc) ---------------------------------------------------------------------------------
+
+static int hk_check(tspgpu_ctx *ctx)
+{
+    const int rc = need_costs(ctx);
+    if (rc) return rc;
+    if (ctx->n < 5) return fail(ctx, E_INVALID, "the Held-Karp bound needs at least 5 nodes, got %d", ctx->n);
+    if (!ctx->symmetric) return fail(ctx, E_PRECOND, "the Held-Karp bound needs a symmetric cost matrix");
+    if (!ctx->otf && ctx->elem == TSPGPU_ELEM_F64) return fail(ctx, E_UNIMPL, "the Held-Karp bound needs integer costs (uint16 / int32 cells or matrix-free mode), not f64 cells");
+    return E_OK;
+}
+
+static int hk_pi_check(tspgpu_ctx *ctx, const long *pi)
+{
+    if (pi)
+        for (int v = 0; v < ctx->n; v++)
+            if (pi[v] > HK_PI_MAX || pi[v] < -HK_PI_MAX) return fail(ctx, E_INVALID, "multiplier %d is %ld: at most 2^45 in magnitude", v, pi[v]);
+    return E_OK;
+}
+
+// the state (all or none) and the multipliers in place: pi, or zeros
+static int hk_begin(tspgpu_ctx *ctx, const long *pi)
+{
+    const size_t n = (size_t)ctx->n;
+    if (!ctx->hk.ctl) {
+        const Rows rows = ctx->hk_rows(n);
+        const hipError_t e = tspmem::grow(HipMem{ctx->stream}, rows, 0, 1);
+        if (e != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(ctx, E_EXHAUSTED, "the Held-Karp bound needs %zu bytes of device memory for %d nodes (%s)", tspmem::rows_bytes(rows, 1), ctx->n,
+                        hipGetErrorString(e));
+        }
+    }
+    static_assert(sizeof(long) == sizeof(long long), "the ABI's long is 64 bits");
+    if (pi) HIP_TRY(hipMemcpyAsync(ctx->hk.pi, pi, n * 8, hipMemcpyHostToDevice, ctx->stream));
+    else HIP_TRY(hipMemsetAsync(ctx->hk.pi, 0, n * 8, ctx->stream));
+    return E_OK;
+}
+
+static int hk_rounds_max(int n)
+{
+    int r = 0;
+    while ((1 << r) < n - 1) r++;
+    return std::max(r, 1);
+}
+
+// one 1-tree of the multipliers in place, enqueued: init, node 0's edges, the maximal number of rounds
+static int hk_enqueue_tree(tspgpu_ctx *ctx)
+{
+    const int n = ctx->n, ld = ctx->ld;
+    const HkBuf H = ctx->hk;
+    hipStream_t st = ctx->stream;
+    const dim3 nodes((n + HK_BT - 1) / HK_BT), block(HK_BT), rows((n - 1 + HK_ROWS - 1) / HK_ROWS), wave_rows(HK_ROWS * 64);
+    const bool stage = (size_t)12 * ld <= 65536;
+    const size_t lds = stage ? (size_t)12 * ld : 0;
+    const bool i32 = ctx->elem == TSPGPU_ELEM_I32;
+    hipLaunchKernelGGL(k_hk_init, nodes, block, 0, st, H, n);
+    if (ctx->otf) kind_switch(ctx, [&](auto kind, auto *pts, auto *) { hipLaunchKernelGGL((k_hk_zero_otf<kind()>), dim3(1), block, 0, st, H, pts, n); });
+    else if (i32) hipLaunchKernelGGL((k_hk_zero<int>), dim3(1), block, 0, st, H, (const int *)ctx->d_mat.p, n, ld);
+    else hipLaunchKernelGGL((k_hk_zero<u16>), dim3(1), block, 0, st, H, (const u16 *)ctx->d_mat.p, n, ld);
+    for (int r = 0, R = hk_rounds_max(n); r < R; r++) {
+        if (ctx->otf)
+            kind_switch(ctx, [&](auto kind, auto *pts, auto *) {
+                if (stage) hipLaunchKernelGGL((k_hk_scan_otf<kind(), true>), rows, wave_rows, lds, st, H, pts, n, ld);
+                else hipLaunchKernelGGL((k_hk_scan_otf<kind(), false>), rows, wave_rows, 0, st, H, pts, n, ld);
+            });
+        else if (i32) {
+            if (stage) hipLaunchKernelGGL((k_hk_scan<int, true>), rows, wave_rows, lds, st, H, (const int *)ctx->d_mat.p, n, ld);
+            else hipLaunchKernelGGL((k_hk_scan<int, false>), rows, wave_rows, 0, st, H, (const int *)ctx->d_mat.p, n, ld);
+        } else {
+            if (stage) hipLaunchKernelGGL((k_hk_scan<u16, true>), rows, wave_rows, lds, st, H, (const u16 *)ctx->d_mat.p, n, ld);
+            else hipLaunchKernelGGL((k_hk_scan<u16, false>), rows, wave_rows, 0, st, H, (const u16 *)ctx->d_mat.p, n, ld);
+        }
+        hipLaunchKernelGGL(k_hk_cmin, nodes, block, 0, st, H, n);
+        hipLaunchKernelGGL(k_hk_hook, nodes, block, 0, st, H, n);
+        hipLaunchKernelGGL(k_hk_flat, nodes, block, 0, st, H, n);
+    }
+    HIP_TRY(hipGetLastError());
+    return E_OK;
+}
+
+static long long hk_ceil_div(long long x) { return x >= 0 ? (x + HK_S - 1) / HK_S : -((-x) / HK_S); }
+
+// the tree's edges from the device, ascending by pair
+static int hk_fetch_edges(tspgpu_ctx *ctx, std::vector<u64> &e)
+{
+    e.resize((size_t)ctx->n);
+    HIP_TRY(hipMemcpyAsync(e.data(), ctx->hk.edges, e.size() * 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream));
+    std::sort(e.begin(), e.end());
+    for (const u64 x : e)
+        if ((unsigned)(x >> 32) >= (unsigned)x || (unsigned)x >= (unsigned)ctx->n) return fail(ctx, E_INTERNAL, "the 1-tree holds an edge that is none");
+    return E_OK;
+}
+
+extern "C" {
+
+int tspgpu_one_tree(tspgpu_ctx *ctx, const long *pi, int *edges, int *degree, long *weight)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    if (!weight) return fail(ctx, E_INVALID, "null argument");
+    hipSetDevice(ctx->device);
+    int rc = hk_check(ctx);
+    if (rc || (rc = hk_pi_check(ctx, pi)) || (rc = hk_begin(ctx, pi))) return rc;
+    const int n = ctx->n;
+    HkCtl C;
+    memset(&C, 0, sizeof C);
+    HIP_TRY(hipMemcpyAsync(ctx->hk.ctl, &C, sizeof C, hipMemcpyHostToDevice, ctx->stream));
+    if ((rc = hk_enqueue_tree(ctx)) || (rc = ctl_get(ctx, &C, (const HkCtl *)ctx->hk.ctl))) return rc;
+    if (!C.done || C.err || C.nedges != (unsigned)(n - 2))
+        return fail(ctx, E_INTERNAL, "the 1-tree ended with %u tree edges of %d (%d rounds)", C.nedges, n - 2, C.rounds);
+    ctx->hk_rounds = C.rounds;
+    long long spi = 0;
+    if (pi) for (int v = 0; v < n; v++) spi += pi[v];
+    if (edges) {
+        std::vector<u64> e;
+        if ((rc = hk_fetch_edges(ctx, e))) return rc;
+        for (int k = 0; k < n; k++) { edges[2 * k] = (int)(e[k] >> 32); edges[2 * k + 1] = (int)(unsigned)e[k]; }
+    }
+    if (degree) HIP_TRY(hipMemcpy(degree, ctx->hk.deg, (size_t)n * 4, hipMemcpyDeviceToHost));
+    *weight = (long)(C.wsum - 2 * spi);
+    return E_OK;
+}
+
+int tspgpu_lower_bound(tspgpu_ctx *ctx, double upper, int iters, int patience, double time_left_s, const long *pi_in, double *bound,
+                       long *pi_out, int *path, int *iters_done, int *reason)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    if (!bound || !iters_done || !reason) return fail(ctx, E_INVALID, "null argument");
+    hipSetDevice(ctx->device);
+    int rc = hk_check(ctx);
+    if (rc) return rc;
+    if (!(upper >= 0) || upper != std::floor(upper) || !(upper * (double)HK_S < 1099511627776.0))
+        return fail(ctx, E_INVALID, "the upper bound %g is not an integer in [0, 2^40 / 128)", upper);
+    if (iters < 1 || patience < 1) return fail(ctx, E_INVALID, "iters = %d, patience = %d: both at least 1", iters, patience);
+    if ((rc = hk_pi_check(ctx, pi_in)) || (rc = hk_begin(ctx, pi_in))) return rc;
+    const int n = ctx->n;
+    const double t_end = deadline_of(time_left_s);
+    HkCtl C;
+    memset(&C, 0, sizeof C);
+    C.ubs = HK_S * (long long)upper; C.patience = patience;
+    HIP_TRY(hipMemcpyAsync(ctx->hk.ctl, &C, sizeof C, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->hk.pibest, ctx->hk.pi, (size_t)n * 8, hipMemcpyDeviceToDevice, ctx->stream));
+    // batches of TSPGPU_OPT_BATCH iterations behind one another on the stream; the host looks at the control block per batch
+    const int batch = std::max(1, ctx->opt_batch);
+    bool late = false;
+    for (int queued = 0; queued < iters && !C.stop && !late;) {
+        const int k = std::min(batch, iters - queued);
+        for (int i = 0; i < k; i++) {
+            if ((rc = hk_enqueue_tree(ctx))) return rc;
+            hipLaunchKernelGGL(k_hk_step, dim3(1), dim3(HK_STEP_BT), 0, ctx->stream, ctx->hk, n);
+        }
+        HIP_TRY(hipGetLastError());
+        queued += k;
+        if ((rc = ctl_get(ctx, &C, (const HkCtl *)ctx->hk.ctl))) return rc;
+        late = t_end >= 0 && queued < iters && !C.stop && now_s() >= t_end;
+    }
+    if (C.stop == 7 || !C.have_best) return fail(ctx, E_INTERNAL, "a 1-tree of the ascent did not complete (iteration %d, %u tree edges of %d)", C.iters, C.nedges, n - 2);
+    const int why = C.stop ? C.stop - 1 : late ? 4 : 0;
+    ctx->hk_rounds = C.rounds; ctx->hk_iters = C.iters; ctx->hk_reason = why; ctx->hk_h = C.h;
+    if (why == 1 && path) {                 // the tree in hand is a tour: from node 0 towards its smaller neighbour
+        std::vector<u64> e;
+        if ((rc = hk_fetch_edges(ctx, e))) return rc;
+        std::vector<int> adj(2 * (size_t)n, -1), cnt((size_t)n, 0);
+        for (const u64 x : e) {
+            const int a = (int)(x >> 32), b = (int)(unsigned)x;
+            if (cnt[a] >= 2 || cnt[b] >= 2) return fail(ctx, E_INTERNAL, "the 1-tree of reason 1 is no tour");
+            adj[2 * a + cnt[a]++] = b; adj[2 * b + cnt[b]++] = a;
+        }
+        std::vector<int> succ((size_t)n, -1);
+        int prev = 0, v = std::min(adj[0], adj[1]);
+        succ[0] = v;
+        for (int k = 1; k < n; k++) {
+            const int next = adj[2 * v] == prev ? adj[2 * v + 1] : adj[2 * v];
+            if ((unsigned)next >= (unsigned)n || succ[v] >= 0) return fail(ctx, E_INTERNAL, "the 1-tree of reason 1 is no tour");
+            succ[v] = next; prev = v; v = next;
+        }
+        if (v != 0) return fail(ctx, E_INTERNAL, "the 1-tree of reason 1 is no tour");
+        memcpy(path, succ.data(), (size_t)n * sizeof(int));
+    }
+    if (pi_out) HIP_TRY(hipMemcpy(pi_out, ctx->hk.pibest, (size_t)n * 8, hipMemcpyDeviceToHost));
+    *bound = (double)hk_ceil_div(C.best);
+    *iters_done = C.iters; *reason = why;
+    return done_code(why == 4);
 }
 
 } // extern "C"

@@ -17,6 +17,22 @@ class TspGpuError(RuntimeError):
         self.code = code
 
 
+class LowerBound:
+    """what Engine.lower_bound returns: the bound (ceil(best L / 128)), pi* [n] int64 in units of 1/128, the iterations evaluated,
+    the stop reason (0 iterations ran out, 1 the 1-tree is a tour -- `path` holds it --, 2 the bound met `upper`, 3 the step
+    reached 0, 4 deadline, 5 a multiplier would pass 2^45), the upper bound used and the return code (0, or 4 on a deadline)."""
+
+    def __init__(self, bound, pi, iters, reason, path, upper, rc):
+        self.bound, self.pi, self.iters, self.reason, self.path, self.upper, self.rc = bound, pi, iters, reason, path, upper, rc
+
+    def gap(self, cost):
+        """(cost - bound) / bound"""
+        return (cost - self.bound) / self.bound
+
+    def __repr__(self):
+        return f"LowerBound(bound={self.bound:.0f}, iters={self.iters}, reason={self.reason})"
+
+
 class Engine:
     def __init__(self, device=0):
         self.L = _lib.load()
@@ -63,7 +79,8 @@ class Engine:
                  "dl_looked", "dl_full_sweeps", "dl_max_queue", "dl_max_wgs",
                  "greedy_rounds1", "greedy_rounds2", "greedy_edges1", "greedy_free",
                  "nl3_batch_w", "nl3_batch_sweeps", "nl3_batch_moves", "nl3_batch_max_moves",
-                 "nlb_dl_looked", "nlb_dl_full_sweeps", "nlb_dl_max_queue", "nlb_dl_qsweep_wgs"]
+                 "nlb_dl_looked", "nlb_dl_full_sweeps", "nlb_dl_max_queue", "nlb_dl_qsweep_wgs",
+                 "hk_rounds", "hk_iterations", "hk_reason", "hk_h", "hk_nodes"]
         return {k: int(self.L.tspgpu_info(self.ctx, i)) for i, k in enumerate(names)}
 
     # ---- instance
@@ -626,6 +643,33 @@ class Engine:
         path, c = np.empty(self.n, dtype=np.int32), C.c_double()
         self._ck(self.L.tspgpu_greedy_tour(self.ctx, path, C.byref(c)))
         return path, c.value
+
+    # ---- Held-Karp lower bound (include/tspgpu.h "Held-Karp lower bound")
+    def _pi_arg(self, pi):
+        if pi is None:
+            return None, None
+        pi = np.ascontiguousarray(pi, dtype=np.int64)
+        if pi.shape != (self.n,):
+            raise ValueError("pi must hold n multipliers")
+        return pi, pi.ctypes.data
+
+    def one_tree(self, pi=None):
+        """the 1-tree T(pi) -> (L in units of 1/128, edges [n][2] ascending by pair, degree [n])."""
+        keep, pp = self._pi_arg(pi)
+        edges, deg, w = np.empty((self.n, 2), dtype=np.int32), np.empty(self.n, dtype=np.int32), C.c_long()
+        self._ck(self.L.tspgpu_one_tree(self.ctx, pp, edges.ctypes.data, deg.ctypes.data, C.byref(w)))
+        return w.value, edges, deg
+
+    def lower_bound(self, upper=None, iters=300, patience=10, pi=None, time_left_s=-1.0):
+        """the subgradient ascent over 1-trees -> LowerBound; upper=None takes the cost of nn_tour(0)."""
+        if upper is None:
+            upper = self.nn_tour(0)[1]
+        keep, pp = self._pi_arg(pi)
+        out, path = np.zeros(self.n, dtype=np.int64), np.full(self.n, -1, dtype=np.int32)
+        bound, it, why = C.c_double(), C.c_int(), C.c_int()
+        rc = self._ck(self.L.tspgpu_lower_bound(self.ctx, float(upper), int(iters), int(patience), float(time_left_s), pp, C.byref(bound),
+                                                out.ctypes.data, path.ctypes.data, C.byref(it), C.byref(why)), ok=(T_OK, DEADLINE_EXCEEDED))
+        return LowerBound(bound.value, out, it.value, why.value, path if why.value == 1 else None, float(upper), rc)
 
     def time_three_nl_sweep(self, slot, width, reps):
         ms = C.c_float()

@@ -1004,8 +1004,51 @@ static int env_neighbours(const char *name)
     return -1;
 }
 
+/* TSP_LOWER_BOUND=<iters>: after the algorithm has finished, the Held-Karp ascent (tspgpu_lower_bound, an extension) runs that many
+ * iterations with the incumbent's cost as the upper bound, on the process-wide context (device 0's when several are configured).
+ * Unset or 0 = off, 1..100000 = the iterations; anything else is an error (-1) */
+static int env_lower_bound(void)
+{
+    const char *v = getenv("TSP_LOWER_BOUND");
+    if (!v) return 0;
+    char *end = NULL;
+    const long k = strtol(v, &end, 10);
+    if (*v && !*end && k >= 0 && k <= 100000) return (int)k;
+    fprintf(stderr, "tsp: TSP_LOWER_BOUND=\"%s\": expected an iteration count from 1 to 100000 (or 0: off)\n", v);
+    return -1;
+}
+
+/* one line on stderr (and one more under TSP_GPU_STATS=1); the solution, the exit code and every other output stay as they are */
+static void lower_bound_report(int iters)
+{
+    tspgpu_ctx *g = tsp_gpu();
+    if (!g) { fprintf(stderr, "tsp: TSP_LOWER_BOUND: no device context\n"); return; }
+    const double cost = tsp_inst.best_solution.cost, t0 = utils_timeelapsed(&tsp_inst.c);
+    double bound = 0;
+    int done = 0, reason = 0;
+    const int rc = tspgpu_lower_bound(g, cost, iters, 10, -1.0, NULL, &bound, NULL, NULL, &done, &reason);
+    if (rc != 0 && rc != 4) { fprintf(stderr, "tsp: TSP_LOWER_BOUND: the bound was not computed (code %d: %s)\n", rc, tspgpu_last_error(g)); return; }
+    const double gap = bound > 0 ? (cost - bound) / bound : 0.0, secs = utils_timeelapsed(&tsp_inst.c) - t0;
+    fprintf(stderr, "tsp: lower bound %.0f after %d iterations (reason %d), gap %.4f %%\n", bound, done, reason, 100.0 * gap);
+    const char *on = getenv("TSP_GPU_STATS");
+    if (on && atoi(on))
+        fprintf(stderr, "tspgpu-stats: {\"call\": \"lower_bound\", \"bound\": %.0f, \"iterations\": %d, \"reason\": %d, \"gap\": %.6f, "
+                        "\"seconds\": %.6f, \"best_cost\": %.2f}\n", bound, done, reason, gap, secs, cost);
+}
+
+static ERROR_CODE run_algorithm(void);
+
 /* ===================================================================== main.c:4-87 */
 ERROR_CODE tsp_run_algorithm(void)
+{
+    const int lb_iters = env_lower_bound();
+    if (lb_iters < 0) return INVALID_ARGUMENT;
+    const ERROR_CODE e = run_algorithm();
+    if (lb_iters && (e == T_OK || e == DEADLINE_EXCEEDED)) lower_bound_report(lb_iters);
+    return e;
+}
+
+static ERROR_CODE run_algorithm(void)
 {
     const int polish = env_switch("TSP_OR_OPT"), every_start = env_switch("TSP_OR_OPT_EVERY_START");
     const int polish_mf = env_switch("TSP_OR_OPT_MATRIX_FREE");
