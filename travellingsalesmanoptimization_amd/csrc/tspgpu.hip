@@ -52,6 +52,7 @@
 #include "tspgpu.h"
 #include "tspgpu_relaunch.h"    // LP_ST_*, and the host's protocol over them (run_persist, run_pstream)
 #include "tspgpu_looks.h"       // rounds of launches between looks at a control block (m2_run, or_run, the batched descents)
+#include "tspgpu_descent.h"     // Descent, descent_out, and the descent over the neighbour lists on one tour (nl_descent)
 #include "tspgpu_plan.h"        // the launch plans: which kernel, what geometry (make_plan, run_persist, run_pstream, or_plan, m2_plan)
 #include "tspgpu_nlphase.h"     // NlbCtl and the phase machine of a tour of a batched neighbour-list descent (tspgpu_nlbatch.inc)
 #include "tspgpu_lds_tmat.h"    // index arithmetic of the tour-ordered matrix copy (k_lds2opt's TM instantiations)
@@ -4657,30 +4658,7 @@ static int launch_nn(tspgpu_ctx *ctx, int slot0, const int *h_starts, int count)
 
 // ---- what the entry points of every move family share ------------------------------------------------------------------
 
-// what a descent did on one tour: 2-opt sweeps and moves, Or-opt sweeps and moves, rounds (a family without one leaves it 0)
-struct Descent {
-    long tw = 0, tm = 0, os = 0, om = 0;
-    int nr = 0;
-    long hs = 0, hm = 0;    // 3-opt sweeps and moves, 3-opt phases: the batched descent with a 3-opt phase alone fills them
-    int np = 0;
-    long lk = 0, lf = 0;    // looked units and full sweeps: the batched descent with looks alone fills them
-    void operator+=(const Descent &d)
-    {
-        tw += d.tw; tm += d.tm; os += d.os; om += d.om; nr += d.nr; hs += d.hs; hm += d.hm; np += d.np; lk += d.lk; lf += d.lf;
-    }
-};
-
-// D[0 .. count) to the caller's arrays, each of them optional
-static void descent_out(const Descent *D, int count, long *tw, long *tm, long *os, long *om, int *nr)
-{
-    for (int i = 0; i < count; i++) {
-        if (tw) tw[i] = D[i].tw;
-        if (tm) tm[i] = D[i].tm;
-        if (os) os[i] = D[i].os;
-        if (om) om[i] = D[i].om;
-        if (nr) nr[i] = D[i].nr;
-    }
-}
+// (what a descent did on one tour, and its way to the caller's arrays: Descent, DescentOut, descent_out of tspgpu_descent.h)
 
 // Host tour in, host tour out, for an entry point that has checked its arguments: the family's check, the tour into slot 0
 // (load_path recomputes its cost, refinment.c:6-9; keep_cost: the caller's running cost instead, as ref_2opt_once),
@@ -6081,7 +6059,7 @@ int tspgpu_tours_local_search(tspgpu_ctx *ctx, int slot0, int count, double time
     std::vector<Descent> D(count);
     bool late = false;
     if ((rc = or_descent_batch(ctx, slot0, count, time_left_s, D.data(), &late))) return rc;
-    descent_out(D.data(), count, two_opt_sweeps, nullptr, nullptr, or_moves, rounds);
+    descent_out(D.data(), count, DescentOut{two_opt_sweeps, nullptr, nullptr, or_moves, rounds});
     return done_code(late);
 }
 
@@ -6099,7 +6077,7 @@ int tspgpu_multistart_local_search(tspgpu_ctx *ctx, const int *starts, int nstar
     rc = multistart(ctx, starts, nstarts, time_left_s, -1, best_path, best_cost, best_start, costs_out, &ms,
                     [&](int m, double left, bool *late, Descent *D) { return or_descent_batch(ctx, 0, m, left, D, late); });
     if (rc && rc != E_DEADLINE) return rc;
-    descent_out(&ms.total, 1, total_two_opt_sweeps, nullptr, nullptr, total_or_moves, nullptr);
+    descent_out(&ms.total, 1, DescentOut{total_two_opt_sweeps, nullptr, nullptr, total_or_moves});
     return rc;
 }
 
@@ -6115,7 +6093,7 @@ int tspgpu_tour_local_search(tspgpu_ctx *ctx, int slot, double time_left_s, long
     return with_slot(ctx, slot, or_check, [&](bool *late) {
         Descent D;
         const int rc = or_descent(ctx, slot, time_left_s, &D, late);
-        descent_out(&D, 1, two_opt_sweeps, nullptr, nullptr, or_moves, rounds);
+        descent_out(&D, 1, DescentOut{two_opt_sweeps, nullptr, nullptr, or_moves, rounds});
         return rc;
     });
 }
@@ -6161,7 +6139,7 @@ int tspgpu_local_search(tspgpu_ctx *ctx, int *path, double *cost, double time_le
     return with_host_tour(ctx, path, cost, false, or_check, [&](bool *late) {
         Descent D;
         const int rc = or_descent(ctx, 0, time_left_s, &D, late);
-        descent_out(&D, 1, two_opt_sweeps, nullptr, nullptr, or_moves, rounds);
+        descent_out(&D, 1, DescentOut{two_opt_sweeps, nullptr, nullptr, or_moves, rounds});
         return rc;
     });
 }
@@ -6274,10 +6252,11 @@ static void m2_put_pair(int *out, const M2Moves &L, int x) { out[0] = L.a[x]; ou
 
 static const M2Family M2_FULL = {m2_check, m2_sweep_full, m2_compact_pairs, m2_apply_pairs, 2, nullptr, m2_put_pair, &tspgpu_ctx::m2_count, nullptr};
 
-// the candidate sweep and the selection of one sweep
-static int m2_launch_select(tspgpu_ctx *ctx, int slot, const SweepGeom &P, bool gather, const M2Family &F)
+// the candidate sweep and the selection of one sweep; K: the queue pass over the family's window and the queued sweep instead
+static int m2_launch_select(tspgpu_ctx *ctx, int slot, const SweepGeom &P, bool gather, const M2Family &F, const LookBuf *K = nullptr,
+                            int closing = 0)
 {
-    const int rc = F.sweep(ctx, slot, P, gather);
+    const int rc = K ? F.qsweep(ctx, slot, *K, closing) : F.sweep(ctx, slot, P, gather);
     if (rc) return rc;
     HIP_TRY(hipGetLastError());
     F.compact(ctx, slot);
@@ -6306,29 +6285,68 @@ static void m2_record(tspgpu_ctx *ctx, const M2Ctl &C, const M2Family &F)
     if (F.voids) ctx->*F.voids = 0;
 }
 
+// what a phase with looks ("Don't-look bits") counts beyond its sweeps and moves; a phase with looks is m2_run with an M2Looks
+struct DlCount {
+    long looked = 0, full = 0, max_q = 0;
+    void operator+=(const DlCount &d) { looked += d.looked; full += d.full; max_q = std::max(max_q, d.max_q); }
+};
+struct M2Looks { int closing; DlCount *dl; };
+static int look_buf(tspgpu_ctx *ctx, int slot, bool sets, LookBuf *K);
+
 // sweeps on `slot` until one accepts nothing, max_sweeps (< 0: no cap) have run or t_end (< 0: none) passes; per sweep the
-// launches of m2_launch_select and the family's apply, four sweeps between looks at the control block (looks::drive)
-static int m2_run(tspgpu_ctx *ctx, int slot, long max_sweeps, double t_end, long *sweeps, long *moves, bool *late, const M2Family &F)
+// launches of m2_launch_select and the family's apply, four sweeps between looks at the control block (looks::drive).
+// lk: the phase with looks of the family: the queue pass in front of the sweep and the wake pass in front of the apply, and
+// the host decides at its look what a stopped phase does next (looks::after_stop); *lk->dl: totals over the phase
+static int m2_run(tspgpu_ctx *ctx, int slot, long max_sweeps, double t_end, long *sweeps, long *moves, bool *late, const M2Family &F,
+                  const M2Looks *lk = nullptr)
 {
     M2Ctl C;
+    LookCtl LC;
     memset(&C, 0, sizeof C);
+    memset(&LC, 0, sizeof LC);
     *late = false;
+    if (lk) *lk->dl = DlCount{};
     if (sweeps) *sweeps = 0;
     if (moves) *moves = 0;
     m2_record(ctx, C, F);
     if (max_sweeps == 0) return E_OK;
-    int rc = m2_arm(ctx, slot, max_sweeps);
-    if (rc) return rc;
+    LookBuf K{};
+    int rc;
+    if (lk) {
+        if ((rc = look_buf(ctx, slot, true, &K))) return rc;
+        HIP_TRY(hipMemsetAsync(ctx->d_look, 0, sizeof(LookCtl), ctx->stream));
+    }
+    if ((rc = m2_arm(ctx, slot, max_sweeps))) return rc;
     const SweepGeom P = m2_plan(ctx);
+    const int n = ctx->n;
     const looks::Result r = looks::drive(
         now_s, t_end, 4,
-        [&] { const int e = m2_launch_select(ctx, slot, P, true, F); return e ? e : F.apply(ctx, slot); },
-        [&] { const int e = ctl_get(ctx, &C, ctx->d_m2.p); return e ? e : C.stop ? (int)looks::STOP : (int)looks::GO_ON; });
+        [&]() -> int {
+            int e = m2_launch_select(ctx, slot, P, true, F, lk ? &K : nullptr, lk ? lk->closing : 0);
+            if (e) return e;
+            if (lk && (e = F.wake(ctx, slot, K))) return e;
+            return F.apply(ctx, slot);
+        },
+        [&]() -> int {
+            int e = ctl_get(ctx, &C, ctx->d_m2.p);
+            if (e) return e;
+            if (!C.stop) return (int)looks::GO_ON;
+            if (!lk) return (int)looks::STOP;
+            if ((e = ctl_get(ctx, &LC, (const LookCtl *)ctx->d_look))) return e;
+            const looks::AfterStop next = looks::after_stop(lk->closing != 0, C.sweeps, C.last_k, LC.last_q, n, C.budget);
+            if (next == looks::AfterStop::END) return (int)looks::STOP;
+            HIP_TRY(hipMemsetAsync(K.awake + (size_t)F.look_set * n, 1, (size_t)n, ctx->stream));
+            if (next == looks::AfterStop::WAKE_END) return (int)looks::STOP;
+            HIP_TRY(hipMemsetAsync(&ctx->d_m2.p->stop, 0, sizeof(int), ctx->stream));
+            return (int)looks::GO_ON;
+        });
     if (r.code) return r.code;
     *late = r.late;
     if (r.late && (rc = ctl_get(ctx, &C, ctx->d_m2.p))) return rc;
+    if (lk && (rc = ctl_get(ctx, &LC, (const LookCtl *)ctx->d_look))) return rc;
     if (sweeps) *sweeps = (long)C.sweeps;
     if (moves) *moves = (long)C.moves;
+    if (lk) *lk->dl = DlCount{(long)LC.looked, (long)LC.full, (long)LC.max_q};
     m2_record(ctx, C, F);
     return E_OK;
 }
@@ -6636,30 +6654,6 @@ static void ornl_put(int *out, const M2Moves &L, int x)
 static const M2Family M2_ORNL = {ornl_check, ornl_launch_sweep, ornl_launch_compact, ornl_launch_apply, 4, nullptr, ornl_put, &tspgpu_ctx::ornl_count,
                                  nullptr, 1, ornl_launch_qsweep, look_launch_wake<1>};
 
-// the descent of tspgpu_local_search_nl on a slot: { neighbour-list 2-opt to its end; neighbour-list Or-opt until a sweep accepts
-// nothing } until an Or-opt phase applies nothing
-static int ornl_descent(tspgpu_ctx *ctx, int slot, double time_left_s, Descent *out, bool *late)
-{
-    const double t_end = deadline_of(time_left_s);
-    Descent D;
-    long mk = 0;
-    int rc = E_OK;
-    *late = false;
-    ctx->ornl_count = M2Counters{};
-    for (;;) {
-        long s = 0, m = 0;
-        if ((rc = m2_run(ctx, slot, -1, t_end, &s, &m, late, M2_NL))) break;
-        D.tw += s; D.tm += m; D.nr++;
-        if (*late) break;
-        if ((rc = m2_run(ctx, slot, -1, t_end, &s, &m, late, M2_ORNL))) break;
-        D.os += s; D.om += m; mk = std::max(mk, ctx->ornl_count.max_k);
-        if (*late || m == 0) break;
-    }
-    ctx->ornl_count = M2Counters{D.os, D.om, mk}; ctx->ornl_rounds = D.nr;
-    *out = D;
-    return rc;
-}
-
 extern "C" {
 
 int tspgpu_or_opt_nl_once(tspgpu_ctx *ctx, int *path, double *cost, int *nmoves, int *moves, double *deltas, int cap)
@@ -6680,31 +6674,6 @@ int tspgpu_tour_or_opt_nl(tspgpu_ctx *ctx, int slot, long max_sweeps, double tim
     if (!ctx) return E_UNAVAILABLE;
     return with_slot(ctx, slot, ornl_check,
                      [&](bool *late) { return m2_run(ctx, slot, max_sweeps, deadline_of(time_left_s), sweeps, moves, late, M2_ORNL); });
-}
-
-int tspgpu_local_search_nl(tspgpu_ctx *ctx, int *path, double *cost, double time_left_s, long *two_opt_sweeps, long *two_opt_moves,
-                           long *or_sweeps, long *or_moves, int *rounds)
-{
-    if (!ctx) return E_UNAVAILABLE;
-    if (!path || !cost) return fail(ctx, E_INVALID, "null argument");
-    return with_host_tour(ctx, path, cost, false, ornl_check, [&](bool *late) {
-        Descent D;
-        const int rc = ornl_descent(ctx, 0, time_left_s, &D, late);
-        descent_out(&D, 1, two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds);
-        return rc;
-    });
-}
-
-int tspgpu_tour_local_search_nl(tspgpu_ctx *ctx, int slot, double time_left_s, long *two_opt_sweeps, long *two_opt_moves,
-                                long *or_sweeps, long *or_moves, int *rounds)
-{
-    if (!ctx) return E_UNAVAILABLE;
-    return with_slot(ctx, slot, ornl_check, [&](bool *late) {
-        Descent D;
-        const int rc = ornl_descent(ctx, slot, time_left_s, &D, late);
-        descent_out(&D, 1, two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds);
-        return rc;
-    });
 }
 
 int tspgpu_time_or_nl_sweep(tspgpu_ctx *ctx, int slot, int reps, float *ms_mean)
@@ -6779,42 +6748,6 @@ static void nl3_put(int *out, const M2Moves &L, int x)
 static const M2Family M2_NL3 = {nl3_check, nl3_launch_sweep, nl3_launch_compact, nl3_launch_apply, 4, nl3_describe, nl3_put, &tspgpu_ctx::nl3_count,
                                 nullptr, 2, nl3_launch_qsweep, look_launch_wake<2>};
 
-struct Descent3 { long ts = 0, tm = 0; int np = 0; };
-
-// the descent of tspgpu_local_search_nl3 on a slot: { the alternation of ornl_descent to its end; neighbour-list 3-opt until a
-// sweep accepts nothing } until a 3-opt phase applies nothing.  The counters of "Neighbour-list Or-opt" hold the totals
-static int nl3_descent(tspgpu_ctx *ctx, int slot, double time_left_s, Descent *out, Descent3 *out3, bool *late)
-{
-    const double t_end = deadline_of(time_left_s);
-    Descent D;
-    Descent3 D3;
-    long mk = 0, omk = 0;
-    int rc = E_OK;
-    *late = false;
-    ctx->nl3_count = M2Counters{};
-    for (;;) {
-        Descent d;
-        rc = ornl_descent(ctx, slot, t_end >= 0 ? std::max(0.0, t_end - now_s()) : -1.0, &d, late);
-        D += d; omk = std::max(omk, ctx->ornl_count.max_k);
-        if (rc || *late) break;
-        long s = 0, m = 0;
-        if ((rc = m2_run(ctx, slot, -1, t_end, &s, &m, late, M2_NL3))) break;
-        D3.ts += s; D3.tm += m; D3.np++; mk = std::max(mk, ctx->nl3_count.max_k);
-        if (*late || m == 0) break;
-    }
-    ctx->ornl_count = M2Counters{D.os, D.om, omk}; ctx->ornl_rounds = D.nr;
-    ctx->nl3_count = M2Counters{D3.ts, D3.tm, mk}; ctx->nl3_phases = D3.np;
-    *out = D; *out3 = D3;
-    return rc;
-}
-
-static void descent3_out(const Descent3 &D3, long *three_sweeps, long *three_moves, int *three_phases)
-{
-    if (three_sweeps) *three_sweeps = D3.ts;
-    if (three_moves) *three_moves = D3.tm;
-    if (three_phases) *three_phases = D3.np;
-}
-
 extern "C" {
 
 int tspgpu_three_opt_nl_once(tspgpu_ctx *ctx, int width, int *path, double *cost, int *nmoves, int *moves, double *deltas, int cap)
@@ -6839,37 +6772,6 @@ int tspgpu_tour_three_opt_nl(tspgpu_ctx *ctx, int slot, int width, long max_swee
     ctx->nl3_width = width;
     return with_slot(ctx, slot, nl3_check,
                      [&](bool *late) { return m2_run(ctx, slot, max_sweeps, deadline_of(time_left_s), sweeps, moves, late, M2_NL3); });
-}
-
-int tspgpu_local_search_nl3(tspgpu_ctx *ctx, int width, int *path, double *cost, double time_left_s, long *two_opt_sweeps, long *two_opt_moves,
-                            long *or_sweeps, long *or_moves, int *rounds, long *three_sweeps, long *three_moves, int *three_phases)
-{
-    if (!ctx) return E_UNAVAILABLE;
-    if (!path || !cost) return fail(ctx, E_INVALID, "null argument");
-    ctx->nl3_width = width;
-    return with_host_tour(ctx, path, cost, false, nl3_check, [&](bool *late) {
-        Descent D;
-        Descent3 D3;
-        const int rc = nl3_descent(ctx, 0, time_left_s, &D, &D3, late);
-        descent_out(&D, 1, two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds);
-        descent3_out(D3, three_sweeps, three_moves, three_phases);
-        return rc;
-    });
-}
-
-int tspgpu_tour_local_search_nl3(tspgpu_ctx *ctx, int slot, int width, double time_left_s, long *two_opt_sweeps, long *two_opt_moves,
-                                 long *or_sweeps, long *or_moves, int *rounds, long *three_sweeps, long *three_moves, int *three_phases)
-{
-    if (!ctx) return E_UNAVAILABLE;
-    ctx->nl3_width = width;
-    return with_slot(ctx, slot, nl3_check, [&](bool *late) {
-        Descent D;
-        Descent3 D3;
-        const int rc = nl3_descent(ctx, slot, time_left_s, &D, &D3, late);
-        descent_out(&D, 1, two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds);
-        descent3_out(D3, three_sweeps, three_moves, three_phases);
-        return rc;
-    });
 }
 
 int tspgpu_time_three_nl_sweep(tspgpu_ctx *ctx, int slot, int width, int reps, float *ms_mean)
@@ -6916,68 +6818,6 @@ static int look_buf(tspgpu_ctx *ctx, int slot, bool sets, LookBuf *K)
     return E_OK;
 }
 
-struct DlCount {
-    long looked = 0, full = 0, max_q = 0;
-    void operator+=(const DlCount &d) { looked += d.looked; full += d.full; max_q = std::max(max_q, d.max_q); }
-};
-
-// The phase with looks of family F on `slot`: m2_run with the queue pass in front of the sweep and the wake pass in front of
-// the apply.  The host decides at its look what a stopped phase does next (looks::after_stop); the counters are totals over
-// the phase, the deadline is m2_run's
-static int dl_run(tspgpu_ctx *ctx, int slot, int closing, long max_sweeps, double t_end, long *sweeps, long *moves, DlCount *dl, bool *late,
-                  const M2Family &F)
-{
-    M2Ctl C;
-    LookCtl LC;
-    memset(&C, 0, sizeof C);
-    memset(&LC, 0, sizeof LC);
-    *late = false;
-    *dl = DlCount{};
-    if (sweeps) *sweeps = 0;
-    if (moves) *moves = 0;
-    m2_record(ctx, C, F);
-    if (max_sweeps == 0) return E_OK;
-    LookBuf K;
-    int rc = look_buf(ctx, slot, true, &K);
-    if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(ctx->d_look, 0, sizeof(LookCtl), ctx->stream));
-    if ((rc = m2_arm(ctx, slot, max_sweeps))) return rc;
-    const int n = ctx->n;
-    const looks::Result r = looks::drive(
-        now_s, t_end, 4,
-        [&]() -> int {
-            int e = F.qsweep(ctx, slot, K, closing);
-            if (e) return e;
-            F.compact(ctx, slot);
-            HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(k_m2_select, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, ctx->m2, (const M2Ctl *)ctx->d_m2);
-            HIP_TRY(hipGetLastError());
-            if ((e = F.wake(ctx, slot, K))) return e;
-            return F.apply(ctx, slot);
-        },
-        [&]() -> int {
-            int e = ctl_get(ctx, &C, ctx->d_m2.p);
-            if (e) return e;
-            if (!C.stop) return (int)looks::GO_ON;
-            if ((e = ctl_get(ctx, &LC, (const LookCtl *)ctx->d_look))) return e;
-            const looks::AfterStop next = looks::after_stop(closing != 0, C.sweeps, C.last_k, LC.last_q, n, C.budget);
-            if (next == looks::AfterStop::END) return (int)looks::STOP;
-            HIP_TRY(hipMemsetAsync(K.awake + (size_t)F.look_set * n, 1, (size_t)n, ctx->stream));
-            if (next == looks::AfterStop::WAKE_END) return (int)looks::STOP;
-            HIP_TRY(hipMemsetAsync(&ctx->d_m2.p->stop, 0, sizeof(int), ctx->stream));
-            return (int)looks::GO_ON;
-        });
-    if (r.code) return r.code;
-    *late = r.late;
-    if (r.late && (rc = ctl_get(ctx, &C, ctx->d_m2.p))) return rc;
-    if ((rc = ctl_get(ctx, &LC, (const LookCtl *)ctx->d_look))) return rc;
-    if (sweeps) *sweeps = (long)C.sweeps;
-    if (moves) *moves = (long)C.moves;
-    *dl = DlCount{(long)LC.looked, (long)LC.full, (long)LC.max_q};
-    m2_record(ctx, C, F);
-    return E_OK;
-}
-
 static void dl_record(tspgpu_ctx *ctx, const DlCount &dl) { ctx->dl_looked = dl.looked; ctx->dl_full = dl.full; ctx->dl_max_q = dl.max_q; }
 
 // a single phase with looks on a slot (tspgpu_tour_two_opt_nl_dl, _or_opt_nl_dl, _three_opt_nl_dl)
@@ -6986,7 +6826,8 @@ static int dl_phase(tspgpu_ctx *ctx, int slot, int closing, long max_sweeps, dou
 {
     return with_slot(ctx, slot, F.check, [&](bool *late) {
         DlCount dl;
-        const int rc = dl_run(ctx, slot, closing, max_sweeps, deadline_of(time_left_s), sweeps, moves, &dl, late, F);
+        const M2Looks lk{closing, &dl};
+        const int rc = m2_run(ctx, slot, max_sweeps, deadline_of(time_left_s), sweeps, moves, late, F, &lk);
         if (rc) return rc;
         dl_record(ctx, dl);
         if (looked) *looked = dl.looked;
@@ -6994,46 +6835,86 @@ static int dl_phase(tspgpu_ctx *ctx, int slot, int closing, long max_sweeps, dou
     }, true);
 }
 
-// the descent of tspgpu_local_search_nl3_dl on a slot: nl3_descent with every phase a phase with looks; width == 0: no 3-opt
-// phase, which is ornl_descent.  The plain families' counters hold what the plain descents leave
-static int dl_descent(tspgpu_ctx *ctx, int slot, int width, int closing, double time_left_s, Descent *out, Descent3 *out3, DlCount *dl, bool *late)
-{
-    const double t_end = deadline_of(time_left_s);
-    Descent D;
-    Descent3 D3;
-    DlCount total, d;
-    long mk = 0, omk = 0;
-    int rc = E_OK;
-    *late = false;
-    ctx->ornl_count = M2Counters{};
-    ctx->nl3_count = M2Counters{};
-    for (bool more = true; more && !rc && !*late;) {
-        for (;;) {                          // rule 8 of "Neighbour-list Or-opt"
-            long s = 0, m = 0;
-            if ((rc = dl_run(ctx, slot, closing, -1, t_end, &s, &m, &d, late, M2_NL))) break;
-            D.tw += s; D.tm += m; D.nr++; total += d;
-            if (*late) break;
-            if ((rc = dl_run(ctx, slot, closing, -1, t_end, &s, &m, &d, late, M2_ORNL))) break;
-            D.os += s; D.om += m; total += d; omk = std::max(omk, ctx->ornl_count.max_k);
-            if (*late || m == 0) break;
-        }
-        if (rc || *late || width == 0) break;
-        long s = 0, m = 0;
-        if ((rc = dl_run(ctx, slot, closing, -1, t_end, &s, &m, &d, late, M2_NL3))) break;
-        D3.ts += s; D3.tm += m; D3.np++; total += d; mk = std::max(mk, ctx->nl3_count.max_k);
-        more = m != 0;
-    }
-    ctx->ornl_count = M2Counters{D.os, D.om, omk}; ctx->ornl_rounds = D.nr;
-    if (width) { ctx->nl3_count = M2Counters{D3.ts, D3.tm, mk}; ctx->nl3_phases = D3.np; }
-    *out = D; *out3 = D3; *dl = total;
-    return rc;
-}
-
 // a width of 0 .. 16; 0: the checks of the descent without a 3-opt phase
 static int dl_descent_check(tspgpu_ctx *ctx)
 {
     if (ctx->nl3_width == 0) return ornl_check(ctx);
     return nl3_check(ctx);
+}
+
+// ---- the descent over the neighbour lists behind its entry points: plain, with a 3-opt phase, with looks --------------------
+
+// the looks mode of a batched descent: off, or "Batched don't-look bits" with its `closing`
+struct NlbMode { bool looks = false; int closing = 0; };
+
+// which descent an entry point asks for: tspgpu_*_nl (nl_plain), tspgpu_*_nl3 (nl_three), tspgpu_*_nl3_dl (nl_looks)
+struct NlSpec {
+    int (*check)(tspgpu_ctx *);
+    int width;              // the caller's
+    bool keep;              // ... goes into ctx->nl3_width; the plain forms leave that as it is
+    bool looks;             // every phase is a phase with looks
+    int closing;
+    // the width of the 3-opt phase once `check` has passed, 0: the descent has none
+    int w3(const tspgpu_ctx *ctx) const { return looks ? (width ? ctx->nl3_w : 0) : keep ? ctx->nl3_w : 0; }
+    NlbMode mode() const { return NlbMode{looks, closing}; }
+};
+static NlSpec nl_plain() { return NlSpec{ornl_check, 0, false, false, 0}; }
+static NlSpec nl_three(int width) { return NlSpec{nl3_check, width, true, false, 0}; }
+static NlSpec nl_looks(int width, int closing) { return NlSpec{dl_descent_check, width, true, true, closing}; }
+
+// what stands in front of the device and the family's check: the forms with looks refuse a width out of range; the width is kept
+static int nl_admit(tspgpu_ctx *ctx, const NlSpec &S)
+{
+    if (S.looks && (S.width < 0 || S.width > NL_KMAX))
+        return fail(ctx, E_INVALID, "the descent with looks takes a width of 0 to %d list entries, got %d", NL_KMAX, S.width);
+    if (S.keep) ctx->nl3_width = S.width;
+    return E_OK;
+}
+
+// The descent on a slot: descent::alternate over m2_run, every phase without a cap.  The counters of "Neighbour-list Or-opt"
+// hold the totals; those of "Neighbour-list 3-opt" too where the descent has the phase (with looks and no phase the sweep
+// counters are 0 and the phase count stands).  Counters and `out` are written whatever the answer
+static int nl_descent(tspgpu_ctx *ctx, int slot, const NlSpec &S, double time_left_s, const DescentOut &out, bool *late)
+{
+    static const M2Family *const family[3] = {&M2_NL, &M2_ORNL, &M2_NL3};
+    const double t_end = deadline_of(time_left_s);
+    const int w3 = S.w3(ctx);
+    Descent D;
+    descent::Peaks P;
+    DlCount total;
+    if (S.looks) ctx->nl3_count = M2Counters{};
+    const int rc = descent::alternate(
+        w3,
+        [&](descent::Family f, long *sweeps, long *moves, bool *phase_late) {
+            DlCount dl;
+            const M2Looks lk{S.closing, &dl};
+            const int e = m2_run(ctx, slot, -1, t_end, sweeps, moves, phase_late, *family[f], S.looks ? &lk : nullptr);
+            if (!e) total += dl;
+            return e;
+        },
+        [&](descent::Family f) { return (ctx->*family[f]->count).max_k; }, &D, &P, late);
+    ctx->ornl_count = M2Counters{D.os, D.om, P.k[descent::OR_OPT]}; ctx->ornl_rounds = D.nr;
+    if (w3) { ctx->nl3_count = M2Counters{D.hs, D.hm, P.k[descent::THREE_OPT]}; ctx->nl3_phases = D.np; }
+    if (S.looks) { D.lk = total.looked; D.lf = total.full; dl_record(ctx, total); }
+    descent_out(&D, 1, out);
+    return rc;
+}
+
+// ... of a host tour
+static int nl_search_host(tspgpu_ctx *ctx, const NlSpec &S, int *path, double *cost, double time_left_s, const DescentOut &out)
+{
+    if (!path || !cost) return fail(ctx, E_INVALID, "null argument");
+    const int rc = nl_admit(ctx, S);
+    if (rc) return rc;
+    return with_host_tour(ctx, path, cost, false, S.check, [&](bool *late) { return nl_descent(ctx, 0, S, time_left_s, out, late); });
+}
+
+// ... of the tour in a slot; with looks from the slot's awake sets as they stand
+static int nl_search_slot(tspgpu_ctx *ctx, const NlSpec &S, int slot, double time_left_s, const DescentOut &out)
+{
+    const int rc = nl_admit(ctx, S);
+    if (rc) return rc;
+    return with_slot(ctx, slot, S.check, [&](bool *late) { return nl_descent(ctx, slot, S, time_left_s, out, late); }, S.looks);
 }
 
 static int kick_check(tspgpu_ctx *ctx)
@@ -7148,20 +7029,9 @@ int tspgpu_tour_local_search_nl3_dl(tspgpu_ctx *ctx, int slot, int width, int cl
                                     long *looked, long *full_sweeps)
 {
     if (!ctx) return E_UNAVAILABLE;
-    if (width < 0 || width > NL_KMAX) return fail(ctx, E_INVALID, "the descent with looks takes a width of 0 to %d list entries, got %d", NL_KMAX, width);
-    ctx->nl3_width = width;
-    return with_slot(ctx, slot, dl_descent_check, [&](bool *late) {
-        Descent D;
-        Descent3 D3;
-        DlCount dl;
-        const int rc = dl_descent(ctx, slot, width, closing, time_left_s, &D, &D3, &dl, late);
-        descent_out(&D, 1, two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds);
-        descent3_out(D3, three_sweeps, three_moves, three_phases);
-        dl_record(ctx, dl);
-        if (looked) *looked = dl.looked;
-        if (full_sweeps) *full_sweeps = dl.full;
-        return rc;
-    }, true);
+    return nl_search_slot(ctx, nl_looks(width, closing), slot, time_left_s,
+                          DescentOut{two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds, three_sweeps, three_moves, three_phases, looked,
+                                     full_sweeps});
 }
 
 int tspgpu_local_search_nl3_dl(tspgpu_ctx *ctx, int width, int closing, int *path, double *cost, double time_left_s, long *two_opt_sweeps,
@@ -7169,21 +7039,39 @@ int tspgpu_local_search_nl3_dl(tspgpu_ctx *ctx, int width, int closing, int *pat
                                int *three_phases, long *looked, long *full_sweeps)
 {
     if (!ctx) return E_UNAVAILABLE;
-    if (!path || !cost) return fail(ctx, E_INVALID, "null argument");
-    if (width < 0 || width > NL_KMAX) return fail(ctx, E_INVALID, "the descent with looks takes a width of 0 to %d list entries, got %d", NL_KMAX, width);
-    ctx->nl3_width = width;
-    return with_host_tour(ctx, path, cost, false, dl_descent_check, [&](bool *late) {
-        Descent D;
-        Descent3 D3;
-        DlCount dl;
-        const int rc = dl_descent(ctx, 0, width, closing, time_left_s, &D, &D3, &dl, late);
-        descent_out(&D, 1, two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds);
-        descent3_out(D3, three_sweeps, three_moves, three_phases);
-        dl_record(ctx, dl);
-        if (looked) *looked = dl.looked;
-        if (full_sweeps) *full_sweeps = dl.full;
-        return rc;
-    });
+    return nl_search_host(ctx, nl_looks(width, closing), path, cost, time_left_s,
+                          DescentOut{two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds, three_sweeps, three_moves, three_phases, looked,
+                                     full_sweeps});
+}
+
+int tspgpu_local_search_nl(tspgpu_ctx *ctx, int *path, double *cost, double time_left_s, long *two_opt_sweeps, long *two_opt_moves,
+                           long *or_sweeps, long *or_moves, int *rounds)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    return nl_search_host(ctx, nl_plain(), path, cost, time_left_s, DescentOut{two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds});
+}
+
+int tspgpu_tour_local_search_nl(tspgpu_ctx *ctx, int slot, double time_left_s, long *two_opt_sweeps, long *two_opt_moves,
+                                long *or_sweeps, long *or_moves, int *rounds)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    return nl_search_slot(ctx, nl_plain(), slot, time_left_s, DescentOut{two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds});
+}
+
+int tspgpu_local_search_nl3(tspgpu_ctx *ctx, int width, int *path, double *cost, double time_left_s, long *two_opt_sweeps, long *two_opt_moves,
+                            long *or_sweeps, long *or_moves, int *rounds, long *three_sweeps, long *three_moves, int *three_phases)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    return nl_search_host(ctx, nl_three(width), path, cost, time_left_s,
+                          DescentOut{two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds, three_sweeps, three_moves, three_phases});
+}
+
+int tspgpu_tour_local_search_nl3(tspgpu_ctx *ctx, int slot, int width, double time_left_s, long *two_opt_sweeps, long *two_opt_moves,
+                                 long *or_sweeps, long *or_moves, int *rounds, long *three_sweeps, long *three_moves, int *three_phases)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    return nl_search_slot(ctx, nl_three(width), slot, time_left_s,
+                          DescentOut{two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds, three_sweeps, three_moves, three_phases});
 }
 
 } // extern "C"
@@ -7518,10 +7406,7 @@ static int nlb_ensure(tspgpu_ctx *ctx, int count)
     return E_OK;
 }
 
-// the looks mode of a batched descent: off, or "Batched don't-look bits" with its `closing`
-struct NlbMode { bool looks = false; int closing = 0; };
-
-// ... its memory beyond nlb_ensure's: the slots' sets (ensure_looks), and a queue of n nodes and a look block per slot of the range
+// the memory of a batched descent with looks (NlbMode) beyond nlb_ensure's: the slots' sets (ensure_looks), and a queue of n nodes and a look block per slot of the range
 static int nlbq_ensure(tspgpu_ctx *ctx, int count)
 {
     int rc = ensure_looks(ctx);
@@ -7638,7 +7523,7 @@ static int nlb_looks_out(tspgpu_ctx *ctx, int count, Descent *D)
     return E_OK;
 }
 
-// ornl_descent (w3 > 0: nl3_descent at that width) on the slots slot0 .. slot0 + count - 1 at once.  The control blocks are
+// nl_descent's rule (w3 > 0: with the 3-opt phase at that width) on the slots slot0 .. slot0 + count - 1 at once.  The control blocks are
 // armed (2-opt phase, round 1) and the slots re-armed as m2_arm does; then sweeps of all live tours -- four between looks at
 // the control blocks, one under a deadline, as m2_run -- and the tours whose descent has ended leave the list.  D: per-slot
 // counters, [count]
@@ -7699,42 +7584,65 @@ static int nlb_no_cap(tspgpu_ctx *ctx)
     return E_OK;
 }
 
+// the batched descent on the slots slot0 .. slot0 + count - 1 (tspgpu_tours_local_search_nl, _nl3, _nl3_dl)
+static int nl_search_tours(tspgpu_ctx *ctx, const NlSpec &S, int slot0, int count, double time_left_s, const DescentOut &out)
+{
+    int rc = nl_admit(ctx, S);
+    if (rc) return rc;
+    hipSetDevice(ctx->device);
+    if ((rc = S.check(ctx))) return rc;
+    if ((rc = nlb_range(ctx, slot0, count, !S.looks))) return rc;
+    std::vector<Descent> D(count);
+    bool late = false;
+    if ((rc = nlb_descent(ctx, slot0, count, S.w3(ctx), time_left_s, D.data(), &late, S.mode()))) return rc;
+    descent_out(D.data(), count, out);
+    return done_code(late);
+}
+
+// the multi-start with it (tspgpu_multistart_local_search_nl, _nl3, _nl3_dl); total: sums over every start processed
+static int nl_multistart(tspgpu_ctx *ctx, const NlSpec &S, const int *starts, int nstarts, double time_left_s, int *best_path, double *best_cost,
+                         int *best_start, const DescentOut &total, double *costs_out)
+{
+    if (!best_path || !best_cost || !best_start || nstarts <= 0) return fail(ctx, E_INVALID, "bad argument");
+    int rc = nl_admit(ctx, S);
+    if (rc) return rc;
+    hipSetDevice(ctx->device);
+    if ((rc = S.check(ctx))) return rc;
+    if ((rc = nlb_no_cap(ctx))) return rc;
+    const int w3 = S.w3(ctx);
+    MultiStart ms;
+    rc = multistart(ctx, starts, nstarts, time_left_s, -1, best_path, best_cost, best_start, costs_out, &ms,
+                    [&](int m, double left, bool *late, Descent *D) { return nlb_descent(ctx, 0, m, w3, left, D, late, S.mode()); });
+    if (rc && rc != E_DEADLINE) return rc;
+    descent_out(&ms.total, 1, total);
+    return rc;
+}
+
 extern "C" {
 
 int tspgpu_tours_local_search_nl(tspgpu_ctx *ctx, int slot0, int count, double time_left_s, long *two_opt_sweeps, long *two_opt_moves,
                                  long *or_sweeps, long *or_moves, int *rounds)
 {
     if (!ctx) return E_UNAVAILABLE;
-    hipSetDevice(ctx->device);
-    int rc = ornl_check(ctx);
-    if (rc) return rc;
-    if ((rc = nlb_range(ctx, slot0, count))) return rc;
-    std::vector<Descent> D(count);
-    bool late = false;
-    if ((rc = nlb_descent(ctx, slot0, count, 0, time_left_s, D.data(), &late))) return rc;
-    descent_out(D.data(), count, two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds);
-    return done_code(late);
+    return nl_search_tours(ctx, nl_plain(), slot0, count, time_left_s, DescentOut{two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds});
 }
 
 int tspgpu_tours_local_search_nl3(tspgpu_ctx *ctx, int slot0, int count, int width, double time_left_s, long *two_opt_sweeps, long *two_opt_moves,
                                   long *or_sweeps, long *or_moves, int *rounds, long *three_sweeps, long *three_moves, int *three_phases)
 {
     if (!ctx) return E_UNAVAILABLE;
-    hipSetDevice(ctx->device);
-    ctx->nl3_width = width;
-    int rc = nl3_check(ctx);
-    if (rc) return rc;
-    if ((rc = nlb_range(ctx, slot0, count))) return rc;
-    std::vector<Descent> D(count);
-    bool late = false;
-    if ((rc = nlb_descent(ctx, slot0, count, ctx->nl3_w, time_left_s, D.data(), &late))) return rc;
-    descent_out(D.data(), count, two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds);
-    for (int i = 0; i < count; i++) {
-        if (three_sweeps) three_sweeps[i] = D[i].hs;
-        if (three_moves) three_moves[i] = D[i].hm;
-        if (three_phases) three_phases[i] = D[i].np;
-    }
-    return done_code(late);
+    return nl_search_tours(ctx, nl_three(width), slot0, count, time_left_s,
+                           DescentOut{two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds, three_sweeps, three_moves, three_phases});
+}
+
+int tspgpu_tours_local_search_nl3_dl(tspgpu_ctx *ctx, int slot0, int count, int width, int closing, double time_left_s, long *two_opt_sweeps,
+                                     long *two_opt_moves, long *or_sweeps, long *or_moves, int *rounds, long *three_sweeps, long *three_moves,
+                                     int *three_phases, long *looked, long *full_sweeps)
+{
+    if (!ctx) return E_UNAVAILABLE;
+    return nl_search_tours(ctx, nl_looks(width, closing), slot0, count, time_left_s,
+                           DescentOut{two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds, three_sweeps, three_moves, three_phases, looked,
+                                      full_sweeps});
 }
 
 int tspgpu_multistart_local_search_nl(tspgpu_ctx *ctx, const int *starts, int nstarts, double time_left_s, int *best_path, double *best_cost,
@@ -7742,17 +7650,8 @@ int tspgpu_multistart_local_search_nl(tspgpu_ctx *ctx, const int *starts, int ns
                                       long *total_or_moves, double *costs_out)
 {
     if (!ctx) return E_UNAVAILABLE;
-    if (!best_path || !best_cost || !best_start || nstarts <= 0) return fail(ctx, E_INVALID, "bad argument");
-    hipSetDevice(ctx->device);
-    int rc = ornl_check(ctx);
-    if (rc) return rc;
-    if ((rc = nlb_no_cap(ctx))) return rc;
-    MultiStart ms;
-    rc = multistart(ctx, starts, nstarts, time_left_s, -1, best_path, best_cost, best_start, costs_out, &ms,
-                    [&](int m, double left, bool *late, Descent *D) { return nlb_descent(ctx, 0, m, 0, left, D, late); });
-    if (rc && rc != E_DEADLINE) return rc;
-    descent_out(&ms.total, 1, total_two_opt_sweeps, total_two_opt_moves, total_or_sweeps, total_or_moves, nullptr);
-    return rc;
+    return nl_multistart(ctx, nl_plain(), starts, nstarts, time_left_s, best_path, best_cost, best_start,
+                         DescentOut{total_two_opt_sweeps, total_two_opt_moves, total_or_sweeps, total_or_moves}, costs_out);
 }
 
 int tspgpu_multistart_local_search_nl3(tspgpu_ctx *ctx, int width, const int *starts, int nstarts, double time_left_s, int *best_path,
@@ -7761,46 +7660,10 @@ int tspgpu_multistart_local_search_nl3(tspgpu_ctx *ctx, int width, const int *st
                                        double *costs_out)
 {
     if (!ctx) return E_UNAVAILABLE;
-    if (!best_path || !best_cost || !best_start || nstarts <= 0) return fail(ctx, E_INVALID, "bad argument");
-    hipSetDevice(ctx->device);
-    ctx->nl3_width = width;
-    int rc = nl3_check(ctx);
-    if (rc) return rc;
-    if ((rc = nlb_no_cap(ctx))) return rc;
-    const int w3 = ctx->nl3_w;
-    MultiStart ms;
-    rc = multistart(ctx, starts, nstarts, time_left_s, -1, best_path, best_cost, best_start, costs_out, &ms,
-                    [&](int m, double left, bool *late, Descent *D) { return nlb_descent(ctx, 0, m, w3, left, D, late); });
-    if (rc && rc != E_DEADLINE) return rc;
-    descent_out(&ms.total, 1, total_two_opt_sweeps, total_two_opt_moves, total_or_sweeps, total_or_moves, nullptr);
-    if (total_three_sweeps) *total_three_sweeps = ms.total.hs;
-    if (total_three_moves) *total_three_moves = ms.total.hm;
-    return rc;
-}
-
-int tspgpu_tours_local_search_nl3_dl(tspgpu_ctx *ctx, int slot0, int count, int width, int closing, double time_left_s, long *two_opt_sweeps,
-                                     long *two_opt_moves, long *or_sweeps, long *or_moves, int *rounds, long *three_sweeps, long *three_moves,
-                                     int *three_phases, long *looked, long *full_sweeps)
-{
-    if (!ctx) return E_UNAVAILABLE;
-    if (width < 0 || width > NL_KMAX) return fail(ctx, E_INVALID, "the descent with looks takes a width of 0 to %d list entries, got %d", NL_KMAX, width);
-    hipSetDevice(ctx->device);
-    ctx->nl3_width = width;
-    int rc = dl_descent_check(ctx);
-    if (rc) return rc;
-    if ((rc = nlb_range(ctx, slot0, count, false))) return rc;
-    std::vector<Descent> D(count);
-    bool late = false;
-    if ((rc = nlb_descent(ctx, slot0, count, width ? ctx->nl3_w : 0, time_left_s, D.data(), &late, NlbMode{true, closing}))) return rc;
-    descent_out(D.data(), count, two_opt_sweeps, two_opt_moves, or_sweeps, or_moves, rounds);
-    for (int i = 0; i < count; i++) {
-        if (three_sweeps) three_sweeps[i] = D[i].hs;
-        if (three_moves) three_moves[i] = D[i].hm;
-        if (three_phases) three_phases[i] = D[i].np;
-        if (looked) looked[i] = D[i].lk;
-        if (full_sweeps) full_sweeps[i] = D[i].lf;
-    }
-    return done_code(late);
+    return nl_multistart(ctx, nl_three(width), starts, nstarts, time_left_s, best_path, best_cost, best_start,
+                         DescentOut{total_two_opt_sweeps, total_two_opt_moves, total_or_sweeps, total_or_moves, nullptr, total_three_sweeps,
+                                    total_three_moves},
+                         costs_out);
 }
 
 int tspgpu_multistart_local_search_nl3_dl(tspgpu_ctx *ctx, int width, int closing, const int *starts, int nstarts, double time_left_s,
@@ -7809,24 +7672,10 @@ int tspgpu_multistart_local_search_nl3_dl(tspgpu_ctx *ctx, int width, int closin
                                           long *total_three_moves, long *total_looked, long *total_full_sweeps, double *costs_out)
 {
     if (!ctx) return E_UNAVAILABLE;
-    if (!best_path || !best_cost || !best_start || nstarts <= 0) return fail(ctx, E_INVALID, "bad argument");
-    if (width < 0 || width > NL_KMAX) return fail(ctx, E_INVALID, "the descent with looks takes a width of 0 to %d list entries, got %d", NL_KMAX, width);
-    hipSetDevice(ctx->device);
-    ctx->nl3_width = width;
-    int rc = dl_descent_check(ctx);
-    if (rc) return rc;
-    if ((rc = nlb_no_cap(ctx))) return rc;
-    const int w3 = width ? ctx->nl3_w : 0;
-    MultiStart ms;
-    rc = multistart(ctx, starts, nstarts, time_left_s, -1, best_path, best_cost, best_start, costs_out, &ms,
-                    [&](int m, double left, bool *late, Descent *D) { return nlb_descent(ctx, 0, m, w3, left, D, late, NlbMode{true, closing}); });
-    if (rc && rc != E_DEADLINE) return rc;
-    descent_out(&ms.total, 1, total_two_opt_sweeps, total_two_opt_moves, total_or_sweeps, total_or_moves, nullptr);
-    if (total_three_sweeps) *total_three_sweeps = ms.total.hs;
-    if (total_three_moves) *total_three_moves = ms.total.hm;
-    if (total_looked) *total_looked = ms.total.lk;
-    if (total_full_sweeps) *total_full_sweeps = ms.total.lf;
-    return rc;
+    return nl_multistart(ctx, nl_looks(width, closing), starts, nstarts, time_left_s, best_path, best_cost, best_start,
+                         DescentOut{total_two_opt_sweeps, total_two_opt_moves, total_or_sweeps, total_or_moves, nullptr, total_three_sweeps,
+                                    total_three_moves, nullptr, total_looked, total_full_sweeps},
+                         costs_out);
 }
 
 } // extern "C"
@@ -7967,22 +7816,32 @@ static int nlv_walks(tspgpu_ctx *ctx, int w3, int walks, int k, double time_left
     return E_OK;
 }
 
+// the walks behind their argument checks (tspgpu_vns_walks_nl, _nl3, _nl3_dl)
+static int nl_walks(tspgpu_ctx *ctx, const NlSpec &S, int walks, int k, double time_left_s, int *paths, double *costs, const int *rand_values,
+                    long nrand, long *consumed, int *iterations, int *kick_pending, int *best_paths, double *best_costs, double *trace,
+                    long *totals)
+{
+    if (walks <= 0 || k < 0 || nrand < 0 || !paths || !costs || !consumed || !iterations || !kick_pending || !best_paths || !best_costs ||
+        (nrand > 0 && !rand_values))
+        return fail(ctx, E_INVALID, "bad argument");
+    int rc = nl_admit(ctx, S);
+    if (rc) return rc;
+    hipSetDevice(ctx->device);
+    if ((rc = S.check(ctx))) return rc;
+    for (int w = 0; w < walks; w++)
+        if (iterations[w] < 0 || iterations[w] > k) return fail(ctx, E_INVALID, "iterations[%d] = %d is outside [0, %d]", w, iterations[w], k);
+    return nlv_walks(ctx, S.w3(ctx), walks, k, time_left_s, paths, costs, rand_values, nrand, consumed, iterations, kick_pending, best_paths,
+                     best_costs, trace, totals, S.mode());
+}
+
 extern "C" {
 
 int tspgpu_vns_walks_nl(tspgpu_ctx *ctx, int walks, int k, double time_left_s, int *paths, double *costs, const int *rand_values, long nrand,
                         long *consumed, int *iterations, int *kick_pending, int *best_paths, double *best_costs, double *trace, long *totals)
 {
     if (!ctx) return E_UNAVAILABLE;
-    if (walks <= 0 || k < 0 || nrand < 0 || !paths || !costs || !consumed || !iterations || !kick_pending || !best_paths || !best_costs ||
-        (nrand > 0 && !rand_values))
-        return fail(ctx, E_INVALID, "bad argument");
-    hipSetDevice(ctx->device);
-    const int rc = ornl_check(ctx);
-    if (rc) return rc;
-    for (int w = 0; w < walks; w++)
-        if (iterations[w] < 0 || iterations[w] > k) return fail(ctx, E_INVALID, "iterations[%d] = %d is outside [0, %d]", w, iterations[w], k);
-    return nlv_walks(ctx, 0, walks, k, time_left_s, paths, costs, rand_values, nrand, consumed, iterations, kick_pending, best_paths, best_costs,
-                     trace, totals);
+    return nl_walks(ctx, nl_plain(), walks, k, time_left_s, paths, costs, rand_values, nrand, consumed, iterations, kick_pending, best_paths,
+                    best_costs, trace, totals);
 }
 
 int tspgpu_vns_walks_nl3(tspgpu_ctx *ctx, int width, int walks, int k, double time_left_s, int *paths, double *costs, const int *rand_values,
@@ -7990,17 +7849,8 @@ int tspgpu_vns_walks_nl3(tspgpu_ctx *ctx, int width, int walks, int k, double ti
                          long *totals)
 {
     if (!ctx) return E_UNAVAILABLE;
-    if (walks <= 0 || k < 0 || nrand < 0 || !paths || !costs || !consumed || !iterations || !kick_pending || !best_paths || !best_costs ||
-        (nrand > 0 && !rand_values))
-        return fail(ctx, E_INVALID, "bad argument");
-    hipSetDevice(ctx->device);
-    ctx->nl3_width = width;
-    const int rc = nl3_check(ctx);
-    if (rc) return rc;
-    for (int w = 0; w < walks; w++)
-        if (iterations[w] < 0 || iterations[w] > k) return fail(ctx, E_INVALID, "iterations[%d] = %d is outside [0, %d]", w, iterations[w], k);
-    return nlv_walks(ctx, ctx->nl3_w, walks, k, time_left_s, paths, costs, rand_values, nrand, consumed, iterations, kick_pending, best_paths,
-                     best_costs, trace, totals);
+    return nl_walks(ctx, nl_three(width), walks, k, time_left_s, paths, costs, rand_values, nrand, consumed, iterations, kick_pending, best_paths,
+                    best_costs, trace, totals);
 }
 
 int tspgpu_vns_walks_nl3_dl(tspgpu_ctx *ctx, int width, int closing, int walks, int k, double time_left_s, int *paths, double *costs,
@@ -8008,18 +7858,8 @@ int tspgpu_vns_walks_nl3_dl(tspgpu_ctx *ctx, int width, int closing, int walks, 
                             double *best_costs, double *trace, long *totals)
 {
     if (!ctx) return E_UNAVAILABLE;
-    if (walks <= 0 || k < 0 || nrand < 0 || !paths || !costs || !consumed || !iterations || !kick_pending || !best_paths || !best_costs ||
-        (nrand > 0 && !rand_values))
-        return fail(ctx, E_INVALID, "bad argument");
-    if (width < 0 || width > NL_KMAX) return fail(ctx, E_INVALID, "the descent with looks takes a width of 0 to %d list entries, got %d", NL_KMAX, width);
-    hipSetDevice(ctx->device);
-    ctx->nl3_width = width;
-    const int rc = dl_descent_check(ctx);
-    if (rc) return rc;
-    for (int w = 0; w < walks; w++)
-        if (iterations[w] < 0 || iterations[w] > k) return fail(ctx, E_INVALID, "iterations[%d] = %d is outside [0, %d]", w, iterations[w], k);
-    return nlv_walks(ctx, width ? ctx->nl3_w : 0, walks, k, time_left_s, paths, costs, rand_values, nrand, consumed, iterations, kick_pending,
-                     best_paths, best_costs, trace, totals, NlbMode{true, closing});
+    return nl_walks(ctx, nl_looks(width, closing), walks, k, time_left_s, paths, costs, rand_values, nrand, consumed, iterations, kick_pending,
+                    best_paths, best_costs, trace, totals);
 }
 
 } // extern "C"

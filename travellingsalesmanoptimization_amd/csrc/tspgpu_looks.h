@@ -1,5 +1,6 @@
-// The look loop of the drivers that launch rounds on a stream and now and then read a control block back: m2_run, or_run,
-// the Or-opt phase of or_descent_batch, nlb_descent and the sweep loop of nlv_walks.  Host-only and free of HIP headers, as
+// The look loop of the drivers that launch rounds on a stream and now and then read a control block back: m2_run (plain and,
+// with an M2Looks, the phase with looks, which asks after_stop below), or_run, the Or-opt phase of or_descent_batch,
+// nlb_descent, the sweep loop of nlv_walks and the rounds of greedy_phase.  Host-only and free of HIP headers, as
 // tspgpu_relaunch.h: templated on a clock and on the callables of its user (tests/looks_main.cpp scripts them).
 //
 // A GROUP is: the deadline check, the group hook, the rounds, one look.  Before each group, t_end >= 0 and now() >= t_end make

@@ -353,6 +353,26 @@ int sharded(tspgpu_multi *m, const int *starts, int nstarts, int *best_path, dou
     return late ? E_DEADLINE : E_OK;
 }
 
+// The sharded multi-start with the batched descent over the neighbour lists: call is the single-device entry
+// (tspgpu_multistart_local_search_nl or _nl3 at its width); the totals are optional, hs and hm those of the 3-opt phase
+template <typename F>
+int sharded_nl(tspgpu_multi *m, const int *starts, int nstarts, int *best_path, double *best_cost, int *best_start, long *tw, long *tm, long *os,
+               long *om, long *hs, long *hm, F call)
+{
+    if (!m) return E_UNAVAILABLE;
+    if (!best_path || !best_cost || !best_start || nstarts <= 0) return mfail(m, E_INVALID, "bad argument");
+    Local T;
+    const int rc = sharded(m, starts, nstarts, best_path, best_cost, best_start, &T, call);
+    if (rc && rc != E_DEADLINE) return rc;
+    if (tw) *tw = T.tw;
+    if (tm) *tm = T.tm;
+    if (os) *os = T.os;
+    if (om) *om = T.om;
+    if (hs) *hs = T.hs;
+    if (hm) *hm = T.hm;
+    return rc;
+}
+
 } // namespace
 
 extern "C" {
@@ -520,19 +540,11 @@ int tspgpu_multi_multistart_local_search_nl(tspgpu_multi *m, const int *starts, 
                                             double *best_cost, int *best_start, long *total_two_opt_sweeps, long *total_two_opt_moves,
                                             long *total_or_sweeps, long *total_or_moves)
 {
-    if (!m) return E_UNAVAILABLE;
-    if (!best_path || !best_cost || !best_start || nstarts <= 0) return mfail(m, E_INVALID, "bad argument");
-    Local T;
-    const int rc = sharded(m, starts, nstarts, best_path, best_cost, best_start, &T, [&](tspgpu_ctx *ctx, const int *list, int count, Local &l) {
-        return tspgpu_multistart_local_search_nl(ctx, list, count, time_left_s, l.path.data(), &l.cost, &l.start, &l.tw, &l.tm, &l.os, &l.om,
-                                                 nullptr);
-    });
-    if (rc && rc != E_DEADLINE) return rc;
-    if (total_two_opt_sweeps) *total_two_opt_sweeps = T.tw;
-    if (total_two_opt_moves) *total_two_opt_moves = T.tm;
-    if (total_or_sweeps) *total_or_sweeps = T.os;
-    if (total_or_moves) *total_or_moves = T.om;
-    return rc;
+    return sharded_nl(m, starts, nstarts, best_path, best_cost, best_start, total_two_opt_sweeps, total_two_opt_moves, total_or_sweeps,
+                      total_or_moves, nullptr, nullptr, [&](tspgpu_ctx *ctx, const int *list, int count, Local &l) {
+                          return tspgpu_multistart_local_search_nl(ctx, list, count, time_left_s, l.path.data(), &l.cost, &l.start, &l.tw, &l.tm,
+                                                                   &l.os, &l.om, nullptr);
+                      });
 }
 
 // ... and with the 3-opt phase at `width` (tspgpu_multistart_local_search_nl3 per device)
@@ -540,21 +552,11 @@ int tspgpu_multi_multistart_local_search_nl3(tspgpu_multi *m, int width, const i
                                              double *best_cost, int *best_start, long *total_two_opt_sweeps, long *total_two_opt_moves,
                                              long *total_or_sweeps, long *total_or_moves, long *total_three_sweeps, long *total_three_moves)
 {
-    if (!m) return E_UNAVAILABLE;
-    if (!best_path || !best_cost || !best_start || nstarts <= 0) return mfail(m, E_INVALID, "bad argument");
-    Local T;
-    const int rc = sharded(m, starts, nstarts, best_path, best_cost, best_start, &T, [&](tspgpu_ctx *ctx, const int *list, int count, Local &l) {
-        return tspgpu_multistart_local_search_nl3(ctx, width, list, count, time_left_s, l.path.data(), &l.cost, &l.start, &l.tw, &l.tm, &l.os,
-                                                  &l.om, &l.hs, &l.hm, nullptr);
-    });
-    if (rc && rc != E_DEADLINE) return rc;
-    if (total_two_opt_sweeps) *total_two_opt_sweeps = T.tw;
-    if (total_two_opt_moves) *total_two_opt_moves = T.tm;
-    if (total_or_sweeps) *total_or_sweeps = T.os;
-    if (total_or_moves) *total_or_moves = T.om;
-    if (total_three_sweeps) *total_three_sweeps = T.hs;
-    if (total_three_moves) *total_three_moves = T.hm;
-    return rc;
+    return sharded_nl(m, starts, nstarts, best_path, best_cost, best_start, total_two_opt_sweeps, total_two_opt_moves, total_or_sweeps,
+                      total_or_moves, total_three_sweeps, total_three_moves, [&](tspgpu_ctx *ctx, const int *list, int count, Local &l) {
+                          return tspgpu_multistart_local_search_nl3(ctx, width, list, count, time_left_s, l.path.data(), &l.cost, &l.start, &l.tw,
+                                                                    &l.tm, &l.os, &l.om, &l.hs, &l.hm, nullptr);
+                      });
 }
 
 int tspgpu_multi_nn_all(tspgpu_multi *m, const int *starts, int nstarts, double time_left_s, int *best_path, double *best_cost,
