@@ -126,7 +126,7 @@ int  tspgpu_set_option(tspgpu_ctx *ctx, int option, long value);
  * packed 16-bit costs, (n, edges per workgroup) = (4096, 16) or (1024, 4); 0: the generic kernel); 62 .. 67 in
  * "Neighbour-list 3-opt" below; 68 with tspgpu_debug_tmat below; 69 the last LDS-resident descent, tabu walk or VNS walk (whole rows or
  * half-window rows) ran the loop over packed 16-bit deltas (every cost <= 16383; the tabu walk: <= 8190), 0: 32-bit deltas; 70 .. 77 in
- * the sections below; 78 .. 81 in "Batched neighbour-list 3-opt" below; 86 .. 90 in "Held-Karp lower bound" below */
+ * the sections below; 78 .. 81 in "Batched neighbour-list 3-opt" below; 86 .. 91 in "Held-Karp lower bound" below */
 long tspgpu_info(const tspgpu_ctx *ctx, int what);
 
 /* ---- instance / cost matrix ------------------------------------------- */
@@ -969,7 +969,9 @@ int tspgpu_vns_walks_nl3_dl(tspgpu_ctx *ctx, int width, int closing, int walks, 
  * allocated 8, all of it or none.
  * Memory: 68 n bytes per context (and 1.3 KB of slack) at the first 1-tree; dropped with the instance.
  * tspgpu_info: 86 the Boruvka rounds (those that accepted an edge) of the last 1-tree, 87 / 88 the iterations and the reason
- * of the last ascent, 89 its final h, 90 the nodes per workgroup of the scan. */
+ * of the last ascent, 89 its final h, 90 the nodes per workgroup of the scan, 91 the LDS bytes per workgroup of the scan of the
+ * last 1-tree (of one_tree or of an ascent): 12 ld where the labels and the multipliers of all nodes are staged there (12 ld <=
+ * 65536: n <= 5440), 0 where the scan reads them through L2, and 0 before any 1-tree. */
 /* one 1-tree: pi NULL = all zero; edges [2n] (n pairs a < b, ascending by pair), degree [n], each may be NULL */
 int tspgpu_one_tree(tspgpu_ctx *ctx, const long *pi, int *edges, int *degree, long *weight /* L(pi), units of 1/128 */);
 /* the ascent of rule 3 */

@@ -7,7 +7,9 @@ berlin52 and kroA100, the golden against the optima and against L(0), berlin52's
 the null-handle code.
 GPU: one_tree bit-equal with the model in every integral cell type and weight form at the sizes around a wave, a workgroup's
 rows and a vector, the tie cases, the ascent against the golden, continuation, fnl4461 / pla85900 trees against the golden,
-refusals, reasons 2 and 5, the deadline, memory across instances, the host binary's TSP_LOWER_BOUND."""
+refusals, reasons 2 and 5, the deadline, memory across instances, the host binary's TSP_LOWER_BOUND.
+tests/test_held_karp_limits.py goes on from here with the helpers of this file: the scans that read comp[] and pi[] through L2
+(n > 5440), weights that need 64 bits, one hook chain of n - 3, reason 3, other batch sizes."""
 import json
 import math
 import os

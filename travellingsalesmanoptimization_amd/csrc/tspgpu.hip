@@ -3383,8 +3383,9 @@ struct tspgpu_ctx : ContextMem, InstanceMem, CostMem, SlotMem {
     long nlb_dl_looked = 0, nlb_dl_full = 0, nlb_dl_max_q = 0;  // the last batched descent with looks: sums and the maximum over its tours
     // greedy-edge construction (tspgpu_greedy.inc): the last one's rounds per phase, phase-1 edges, free nodes entering phase 2
     long ge_rounds1 = 0, ge_rounds2 = 0, ge_edges1 = 0, ge_free = 0;
-    // Held-Karp lower bound (tspgpu_hk.inc): Boruvka rounds of the last 1-tree; iterations, reason and final h of the last ascent
-    long hk_rounds = 0, hk_iters = 0, hk_reason = 0, hk_h = 0;
+    // Held-Karp lower bound (tspgpu_hk.inc): Boruvka rounds of the last 1-tree; iterations, reason and final h of the last ascent;
+    // the LDS bytes per workgroup of the last 1-tree's scan (0: comp[] and pi[] came through L2)
+    long hk_rounds = 0, hk_iters = 0, hk_reason = 0, hk_h = 0, hk_lds = 0;
     // batched neighbour-list descent (tspgpu_nlbatch.inc)
     long nlb_tours = 0, nlb_launches = 0, nlb_max_live = 0;     // the last batched descent: tours, sweeps launched, most tours in one
     long nlb_w3 = 0, nlb_three_sweeps = 0, nlb_three_moves = 0, nlb_three_max_k = 0;    // ... its 3-opt width in effect (0: none), 3-opt sweeps and
@@ -4947,6 +4948,7 @@ long tspgpu_info(const tspgpu_ctx *ctx, int what)
     case 88: return ctx->hk_reason;
     case 89: return ctx->hk_h;
     case 90: return HK_ROWS;
+    case 91: return ctx->hk_lds;
     case 85: return ctx->have_costs && ctx->n >= 8 ? std::min(NLB_QSWEEP_WGS, (ctx->n + ORNL_STARTS - 1) / ORNL_STARTS) : 0;
     case 55: return ctx->have_costs && ctx->symmetric && ctx->n >= 8 ? (ctx->n + ORNL_STARTS - 1) / ORNL_STARTS : 0;
     case 12: return (ctx->built && ctx->grid_ok && ctx->opt_nn != 1 && ctx->cost_bound < 134217728.0) ? ctx->grid_G : 0;
@@ -7255,6 +7257,7 @@ static int hk_enqueue_tree(tspgpu_ctx *ctx)
     const bool stage = (size_t)12 * ld <= 65536;
     const size_t lds = stage ? (size_t)12 * ld : 0;
     const bool i32 = ctx->elem == TSPGPU_ELEM_I32;
+    ctx->hk_lds = (long)lds;
     hipLaunchKernelGGL(k_hk_init, nodes, block, 0, st, H, n);
     if (ctx->otf) kind_switch(ctx, [&](auto kind, auto *pts, auto *) { hipLaunchKernelGGL((k_hk_zero_otf<kind()>), dim3(1), block, 0, st, H, pts, n); });
     else if (i32) hipLaunchKernelGGL((k_hk_zero<int>), dim3(1), block, 0, st, H, (const int *)ctx->d_mat.p, n, ld);

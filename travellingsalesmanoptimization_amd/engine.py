@@ -80,7 +80,7 @@ class Engine:
                  "greedy_rounds1", "greedy_rounds2", "greedy_edges1", "greedy_free",
                  "nl3_batch_w", "nl3_batch_sweeps", "nl3_batch_moves", "nl3_batch_max_moves",
                  "nlb_dl_looked", "nlb_dl_full_sweeps", "nlb_dl_max_queue", "nlb_dl_qsweep_wgs",
-                 "hk_rounds", "hk_iterations", "hk_reason", "hk_h", "hk_nodes"]
+                 "hk_rounds", "hk_iterations", "hk_reason", "hk_h", "hk_nodes", "hk_lds"]
         return {k: int(self.L.tspgpu_info(self.ctx, i)) for i, k in enumerate(names)}
 
     # ---- instance
