@@ -40,7 +40,11 @@ enum { TSPGPU_EUC_2D = 0, TSPGPU_ATT = 1, TSPGPU_CEIL_2D = 2 };
 /* storage of the device-resident cost matrix.  AUTO keeps the narrowest EXACT copy:
  * uint16 when every entry is an integer in [0, 65534] (diagonal -1), int32 when every
  * entry is an integer in [-1, 2^27) (true for every EUC_2D / ATT / CEIL_2D matrix),
- * else doubles, the reference's own format. */
+ * else doubles, the reference's own format.  The lower end is for every cell, not the diagonal alone: a caller matrix
+ * (tspgpu_set_costs) with an off-diagonal -1 is admitted in int32 cells and taken as the cost -1 by the sweeps, the
+ * neighbour lists and the greedy-edge construction; a matrix with a value below -1 or a non-integer is held in doubles,
+ * negative values and -0.0 (which compares equal to +0.0) included.  Extra Mileage alone refuses a negative
+ * off-diagonal cost, with FAILED_PRECONDITION (9): its packed keys hold costs in [0, 2^27). */
 enum { TSPGPU_ELEM_AUTO = 0, TSPGPU_ELEM_F64 = 1, TSPGPU_ELEM_I32 = 2, TSPGPU_ELEM_U16 = 3 };
 
 /* tunables (tspgpu_set_option) */

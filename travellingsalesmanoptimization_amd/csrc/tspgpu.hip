@@ -106,7 +106,9 @@ template <> struct Elem<int> {
     typedef int acc;
     static constexpr int V = 4;
     __device__ static int lim() { return INT_MAX; }
-    __device__ static int big() { return 1 << 29; }      // poison; real costs < 2^27 so |delta| < 2^28
+    // poison; real costs lie in [-1, 2^27): a 2-opt delta (two weights against two) stays below 2^28 in magnitude, a
+    // three-edge delta (Or-opt, 3-opt: three weights against three) below 3 * 2^27 -- both under the 2^29 poison and inside int32
+    __device__ static int big() { return 1 << 29; }
     __device__ static double widen(int x) { return (double)x; }
 };
 template <> struct Elem<u16> {
